@@ -1,6 +1,12 @@
 """bench.py — frames/s of HARP's render + loss + backward + Adam inner step on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]          (N>1: launched by torch.distributed.run, one rank per GPU)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]   (N>1: launched by torch.distributed.run, one rank per GPU)
+
+A plain run sets up, warms up, times the K steps and prints the headline.  --full also measures everything else: per-kernel roofline
+(HIP events + rocprofv3 children), the keep_image rate, the other configurations (`extras`), the CPU oracle and, for N > 1, the all-reduce
+alone and the ranks' parameter consistency.  --dump-outputs DIR writes the last timed step's loss terms, parameters and gradients as
+DIR/<name>.npy (float32), before anything else runs on the engine.  With it, that last step starts from the fitting state every run
+begins with (main() says why), so two runs, and two builds, can be compared output for output.
 
 Workload (BASELINE.json configs[2]/[3], SURVEY.md §8d "C3/C4"): 256-frame synthetic sequence, 512x512, subdivided MANO
 hand mesh (3093 v / 6152 f / 3327 uv), self-shadow on, per-vertex displacement + texture/normal-map optimisation stage
@@ -25,7 +31,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 from harp_amd import synth  # noqa: E402
-from harp_amd.engine import FitEngine  # noqa: E402
+from harp_amd.engine import LOSS_NAMES, FitEngine  # noqa: E402
 
 T_FRAMES, S, B_PER_GPU = 256, 512, 32
 HBM_PEAK_GBS = 8000.0        # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
@@ -502,6 +508,32 @@ def cpu_baseline(seed=0, frames_per_step=4):
                    "sample": "config C1 in full: one 256x256 frame, raw MANO mesh 778v/1538f, silhouette L1 only, Adam; median of 5 steps after 1 warm-up"}}
 
 
+# what a step reads and carries into the next one (FitEngine.step saves and restores the same counters around its capture)
+_FIT_STATE = ("p_buf", "m_buf", "v_buf", "hyper", "draw_counter", "schedule_row", "loss_total")
+
+
+def fit_state(eng):
+    return {k: getattr(eng, k).clone() for k in _FIT_STATE}
+
+
+def restore_fit_state(eng, state):
+    for k, t in state.items():
+        getattr(eng, k).copy_(t)
+
+
+def dump_outputs(eng, out_dir):
+    """What a caller of FitEngine.step holds after the last timed step: the unweighted loss terms (LOSS_NAMES order), every parameter
+    table and its gradient, as float32 .npy files (~13 MB for the headline workload)."""
+    os.makedirs(out_dir, exist_ok=True)
+    lv = eng.losses()
+    arrays = {"losses": torch.tensor([lv[k] for k in LOSS_NAMES])}
+    for k in eng.params:
+        arrays["param_" + k] = eng.params[k]
+        arrays["grad_" + k] = eng.grads[k]
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().to(torch.float32).cpu().numpy())
+
+
 class _StdoutToStderr:
     """RCCL prints a version banner on fd 1 when the communicator is created; keep stdout for the ONE JSON line"""
     def __enter__(self):
@@ -524,6 +556,9 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's loss terms, parameters and gradients as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true", help="measure more than the headline: roofline, keep_image rate, extras, CPU baseline, N > 1 "
+                    "all-reduce and rank consistency (the --no-* options and --vgg-weights below select among them)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip the rates of the other configurations (keep_image, B=18, C5 arm 1024)")
@@ -533,6 +568,8 @@ def main():
     ap.add_argument("--vgg-weights", default="random", help="filters of the perceptual-term entry of `extras`: 'random' (default, timing only), "
                     "'none' (skip the entry) or the path of torchvision's vgg16 state dict (vgg16-397923af.pth)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -587,6 +624,10 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
+    # --dump-outputs: the fit does not retrace its path from run to run — the step's float atomics are unordered (~1e-7 after one step) and
+    # Adam carries that into the next step's rasterisation, growing it ~2x per step — so the LAST timed step starts again from the fitting
+    # state every run begins with: its inputs are identical from run to run and its outputs agree to rounding (one 19 MB copy, timed)
+    start = fit_state(eng) if args.dump_outputs else None
     use_graph = not args.no_graph
     graph_fallback = None
     try:
@@ -616,6 +657,8 @@ def main():
     sync()
     t0 = time.perf_counter()
     for i in range(args.steps):
+        if start is not None and i == args.steps - 1:
+            restore_fit_state(eng, start)
         eng.step(None, True, True, use_graph=use_graph)
     sync()
     dt = time.perf_counter() - t0
@@ -624,12 +667,15 @@ def main():
         tmax = torch.tensor([dt], device=device, dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, args.dump_outputs)          # first: the all-reduce timing below overwrites the gradient bucket
     per_rank_ms, allreduce = None, None
     if world > 1 or force_dist:
         tmax = torch.tensor([dt_local], device=device, dtype=torch.float64)
         allt = [torch.zeros_like(tmax) for _ in range(world)]
         dist.all_gather(allt, tmax)
         per_rank_ms = [float(t.item()) / args.steps * 1e3 for t in allt]
+    if args.full and (world > 1 or force_dist):
         # the collective on its own (outside the timed region): the flat gradient bucket, K back-to-back all-reduces on one stream
         bucket = eng.g_buf[eng.opt_span[0]:eng.opt_span[0] + eng.opt_span[1]]
         K = 20
@@ -655,7 +701,7 @@ def main():
     losses = eng.losses()
     finite = all(np.isfinite(v) for v in losses.values())
     consistent = None
-    if world > 1 or force_dist:
+    if args.full and (world > 1 or force_dist):
         # data-parallel invariant (outside the timed region): every rank holds the same parameters after the same all-reduced updates
         cs = eng.p_buf[:eng.opt_span[0] + eng.opt_span[1]].double().abs().sum().reshape(1)
         hi, lo = cs.clone(), cs.clone()
@@ -684,10 +730,11 @@ def main():
         out["ranks_consistent"] = consistent
     if per_rank_ms is not None:
         out["per_rank_ms_per_step"] = per_rank_ms
+    if allreduce is not None:
         out["allreduce"] = allreduce
     if shared_gpu or backend != "nccl":
         out["invalid_timing"] = f"development run: backend={backend}, all ranks on one GPU={shared_gpu}"
-    if rank == 0 and world == 1 and not args.no_roofline:
+    if rank == 0 and world == 1 and args.full and not args.no_roofline:
         a_frame, a_step, parts = algorithmic_bytes(eng)
         kt = kernel_roofline(eng, 4)                    # stand-alone: one stream, the group runs alone (HIP events)
         kt_situ = kernel_roofline(eng, 4, overlap=True)   # eager two-stream re-run, events around the C-ABI call

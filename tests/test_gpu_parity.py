@@ -6,6 +6,8 @@ evaluated in FLOAT64 with the float32-undecidable pixels out of the photometric 
 printed and bounded per case) — the stand-alone silhouette op, compared with the float32 oracle, keeps 2e-3 —, parameters after
 Adam steps abs 1e-3 (one Adam step moves a parameter by ~lr)."""
 GRAD_TOL = 1e-3
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -14,6 +16,7 @@ from tests._scene import check_removed, make_scene, mask_scene_targets, oracle_p
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
+ARM_CORR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "harp_amd", "assets", "arm_corr.npz")
 
 
 @pytest.fixture(scope="module")
@@ -343,7 +346,7 @@ def test_smplx_arm_lbs_vs_oracle():
     from harp_amd.hand_models_harp.body_models import SMPLXARM
     from oracle import harp_ref as H
     m = synth.make_smplx_arm_model(seed=0)
-    corr = np.load("harp_amd/assets/arm_corr.npz")
+    corr = np.load(ARM_CORR)
     layer = SMPLXARM(m, m["faces"], corr["mano_vert_from_arm"], device=DEV)
     mt = {k: torch.from_numpy(v) for k, v in m.items()}
     g = torch.Generator().manual_seed(0)
@@ -382,7 +385,7 @@ def test_tree_lbs_workspace_reused_across_batch_sizes():
     from harp_amd import _lib, synth
     from harp_amd.hand_models_harp.body_models import SMPLXARM
     m = synth.make_smplx_arm_model(seed=0)
-    corr = np.load("harp_amd/assets/arm_corr.npz")
+    corr = np.load(ARM_CORR)
     dm = SMPLXARM(m, m["faces"], corr["mano_vert_from_arm"], device=DEV).device_model
     L = _lib.lib()
     g = torch.Generator().manual_seed(1)

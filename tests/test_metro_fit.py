@@ -1,6 +1,8 @@
 """MANO-to-METRO preprocessing fits (harp_amd/metro_modifications/hand_utils.py) against the oracle restatement (oracle/metro_fit.py).
 CPU: loss classes, spike filter, pickle helpers.  GPU: the native two-stage vertex fit (hipGraph replay vs eager vs oracle's
 torch.optim.Adam), its full-length convergence, the arm variant and the sequence smoothing."""
+import os
+
 import numpy as np
 import pytest
 import torch
@@ -8,6 +10,7 @@ import torch
 from tests._scene import make_scene
 
 DEV = "cuda"
+ARM_CORR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "harp_amd", "assets", "arm_corr.npz")
 
 
 def test_loss_terms_and_spike_filter():
@@ -117,7 +120,7 @@ def test_arm_vertex_fit_runs(monkeypatch, capsys):
     from harp_amd.metro_modifications import hand_utils as hu
     from harp_amd import synth
     model = synth.make_smplx_arm_model(seed=0)
-    corr = np.load("harp_amd/assets/arm_corr.npz")
+    corr = np.load(ARM_CORR)
     layer = SMPLXARM(model, model["faces"], corr["mano_vert_from_arm"], device=DEV)
     g = torch.Generator().manual_seed(4)
     with torch.no_grad():

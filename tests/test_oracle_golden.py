@@ -85,6 +85,11 @@ def test_smooth_losses_golden(golden_dir):
     assert abs(lp.item() - float(d["smooth_pose"])) <= 1e-5 * abs(float(d["smooth_pose"]))
     assert abs(lr.item() - float(d["smooth_root"])) <= 1e-5 * abs(float(d["smooth_root"]))
     (lp + 1e4 * lr).backward()
-    for k in ("rot", "pose", "shape", "trans", "cam"):
+    for k in ("rot", "pose", "shape", "cam"):
         g, want = P[k].grad, torch.from_numpy(d["g_" + k])
         assert (g - want).norm() <= 2e-4 * want.norm() + 1e-6, k
+    # trans leaves both terms exactly (root-aligned joints; detached root joint): its gradient is 0 (4e-11 in float64).  The reference's
+    # float32 value, 7e-7 of the largest gradient, is the rounding of that cancellation, which differs between CPU kernels (SSE / AVX2 /
+    # AVX-512 paths of MKL): both are held to float32 noise of the gradient scale instead of to each other
+    scale = max(float(np.linalg.norm(d["g_" + k])) for k in ("rot", "pose", "shape", "cam"))
+    assert P["trans"].grad.norm() <= 1e-5 * scale and np.linalg.norm(d["g_trans"]) <= 1e-5 * scale, (P["trans"].grad.norm(), scale)

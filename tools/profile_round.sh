@@ -8,7 +8,7 @@ tag=${1:-rXX}
 out=gpurun_out
 mkdir -p $out
 export TMPDIR=/tmp
-python bench.py > $out/${tag}_bench.json 2> $out/${tag}_bench.err
+python bench.py --full > $out/${tag}_bench.json 2> $out/${tag}_bench.err
 timeout 900 rocprofv3 --kernel-trace --stats -d $out/prof_$tag -o run -- python bench.py --steps 40 --warmup 8 --no-cpu-baseline --no-extras --no-roofline \
     > $out/${tag}_bench_under_rocprof.json 2> $out/${tag}_prof.err
 db=$(find $out/prof_$tag -name "*.db" | head -1)
