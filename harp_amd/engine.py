@@ -485,7 +485,7 @@ class FitEngine:
     def _texel_record_buffers(self):
         if self._trec is None:
             nb = _lib.lib().harp_texel_bins(self.Ht, self.Wt)
-            cap = max(int(self.trec_cap_min), self.B * self.S * self.S // max(1, int(self.trec_cap_div)))
+            cap = ops.texel_record_capacity(self.B * self.S * self.S, self.trec_cap_div, self.trec_cap_min)
             self._trec = (torch.empty(nb * 9 * cap, dtype=torch.float32, device=self.dev),
                           torch.zeros(nb * 16 + 16, dtype=torch.int32, device=self.dev), cap)
         if self._tacc is None:                           # double accumulators of the two maps: all-zero between steps (harp_texel_finish clears what it consumes)
@@ -949,6 +949,8 @@ class FitEngine:
           * else the four tap maps (126 MB per frame): one full forward + backward over the B rendered images per step;
           * else nothing: every step also recomputes the target features of its B frames."""
         from .model.vgg_hip import Vgg16Hip, activation_shapes, active_tiles, tap_shapes
+        if vgg is not None and self.S % 8:               # (refused here, before any state changes: the kernels tile the image by 8)
+            raise ValueError(f"perceptual term: image size {self.S} is not a multiple of 8")
         self._vgg_module = vgg
         self._vgg_cache_bytes = int(cache_bytes)         # the caller's budget (set_targets re-invokes with it)
         self._vgg_precision = int(precision)

@@ -98,23 +98,53 @@ class Vgg16Features(torch.nn.Module):
         scale = (lambda t, f: t if f is None else f * t)
         feats = [] if skip_input else [scale(x.flatten(start_dim=1), w[0])]
         h = x
+        moved = self._filters_on(x.device) if next(self.parameters()).device != x.device else None
         for n in range(1, 5):
-            h = getattr(self, f"slice{n}")(h)
+            for ix, layer in getattr(self, f"slice{n}").named_children():
+                if moved is not None and int(ix) in moved:
+                    h = torch.nn.functional.conv2d(h, *moved[int(ix)], padding=1)
+                else:
+                    h = layer(h)
             feats.append(scale(h.flatten(start_dim=1), w[n]))
         return feats
 
     hip_precision = 0                # 0: float32 MFMA (parity anchor), 1: three-term bf16 split (model/conv_hip.py)
 
+    def _weight_cache(self):
+        """copies of the filters made for another device: dropped whenever a parameter was replaced or written in place since
+        (load_state_dict, .to(), an optimiser step) — the cache is keyed on every parameter's storage and version counter"""
+        weights = tuple((p.data_ptr(), p._version) for p in self.parameters())
+        if self.__dict__.get("_hip_weights") != weights:
+            self.__dict__["_hip_cache"], self.__dict__["_hip_weights"] = {}, weights
+        return self.__dict__["_hip_cache"]
+
+    def _filters_on(self, device):
+        """{layer index: (weight, bias)} on `device` for the torch layers of a module whose parameters live elsewhere (frozen filters,
+        as on the HIP path)"""
+        cache = self._weight_cache()
+        key = ("torch", str(device))
+        if key not in cache:
+            convs = {int(ix): m for n in range(1, 5) for ix, m in getattr(self, f"slice{n}").named_children() if int(ix) in _CONVS}
+            cache[key] = {ix: (m.weight.detach().to(device), m.bias.detach().to(device)) for ix, m in convs.items()}
+        return cache[key]
+
     def _hip(self, device):
+        """the filters packed for csrc/conv.hip, per (device, precision) (see _weight_cache)"""
         from .vgg_hip import Vgg16Hip
         key = (str(device), int(self.hip_precision))
-        cache = self.__dict__.setdefault("_hip_cache", {})
+        cache = self._weight_cache()
         if key not in cache:
             cache[key] = Vgg16Hip(self, device, self.hip_precision)
         return cache[key]
 
+    def _apply(self, fn, *args, **kwargs):
+        self.__dict__.pop("_hip_weights", None)          # new storage may reuse a freed pointer at version 0: repack regardless
+        return super()._apply(fn, *args, **kwargs)
+
     def forward(self, x):
-        if x.is_cuda:
+        # the HIP kernels tile the image by 8 (three 2x2 pools); any other size goes through the torch layers declared here, as the
+        # reference module does (the engine's perceptual term, FitEngine.set_perceptual, refuses such sizes instead)
+        if x.is_cuda and x.shape[-2] % 8 == 0 and x.shape[-1] % 8 == 0:
             from .vgg_hip import Vgg16Rows
             return Vgg16Rows.apply(x, self._hip(x.device))
         return torch.cat(self.features(x), 1)

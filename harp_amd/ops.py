@@ -274,6 +274,13 @@ TEXEL_RECORDS = True
 _trec_cache = {}
 
 
+def texel_record_capacity(n_pixels, div, floor):
+    """capacity of one texel tile's record list (harp_shade_args.trec_cap): max(floor, n_pixels // div), rounded UP to a multiple of 4 —
+    harp_shade_bwd and harp_texel_reduce refuse any other value"""
+    cap = max(int(floor), int(n_pixels) // max(1, int(div)))
+    return (cap + 3) & ~3
+
+
 def texel_record_buffers(device, Ht, Wt, cap):
     """(records, counters, cap, double accumulators of both maps) for harp_shade_args.trec / trec_cnt / trec_cap and harp_texel_reduce /
     harp_texel_finish; None when the map has more tiles than the reduce handles"""
@@ -323,7 +330,7 @@ class _Shade(torch.autograd.Function):
                      ("g_zl", g_zl), ("g_light_pos", g_lp), ("g_colors", g_col), ("g_light_R", g_lR), ("g_light_T", g_lT)):
             setattr(a, k, _lib.ptr(t))
         B = verts.shape[0]
-        bufs = texel_record_buffers(verts.device, a.Ht, a.Wt, max(4096, B * S * S // 8)) if TEXEL_RECORDS else None
+        bufs = texel_record_buffers(verts.device, a.Ht, a.Wt, texel_record_capacity(B * S * S, 8, 4096)) if TEXEL_RECORDS else None
         if bufs is not None:
             a.trec, a.trec_cnt, a.trec_cap = _lib.ptr(bufs[0]), _lib.ptr(bufs[1]), bufs[2]
             a.trec_acc_tex, a.trec_acc_nmap = _lib.ptr(bufs[3][0]), _lib.ptr(bufs[3][1])

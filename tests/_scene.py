@@ -44,6 +44,8 @@ def scene_f64(sc, targets):
 # removes is bounded, not ignored.
 AMBIGUOUS_FRACTION = {
     "api_loop_body_128": 0.0535,
+    "api_loop_body_300": 0.0596,
+    "api_loop_body_301": 0.0519,
     "app_only_hand_256_b2": 0.0618,
     "c2_hand_128_b18": 0.0436,
     "c2_hand_512_b18": 0.0466,
@@ -52,6 +54,11 @@ AMBIGUOUS_FRACTION = {
     "c5_arm_1024_b1": 0.0262,
     "c5_arm_1024_b32": 0.0311,
     "c5_arm_1024_b8": 0.0266,
+    "offgrid_arm_520_b1": 0.0261,
+    "offgrid_hand_200_b3": 0.0570,
+    "offgrid_hand_300_b2": 0.0686,
+    "offgrid_hand_301_b1": 0.0681,
+    "offgrid_hand_448_b2": 0.0573,
     "parity_arm_128": 0.0245,
     "parity_empty_supertiles_256": 0.0421,
     "parity_full_step_128": 0.0841,

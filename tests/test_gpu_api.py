@@ -11,6 +11,18 @@ DEV = "cuda"
 
 
 def test_loop_body_through_reference_api():
+    _loop_body_through_reference_api(128)
+
+
+@pytest.mark.parametrize("S,fid", [(300, [1]), (301, [2])])
+def test_loop_body_through_reference_api_off_the_tile_grid(S, fid):
+    """the same loop body, one frame at sizes off the 16-px tile grid (301: odd, a pixel centre sits on NDC 0), where the shader backward's
+    texel-record capacity S * S / 8 is no multiple of 4.  (At 301 frame 2: frame 1's cam / trans gradient is not decided at float32
+    precision against these noise targets — the float32 oracle itself is 2.6e-3 from the float64 one there, 1.8e-4 on frame 2.)"""
+    _loop_body_through_reference_api(S, fid)
+
+
+def _loop_body_through_reference_api(S, fid=(1, 2)):
     from harp_amd.loss.arap import arap_loss, mesh_laplacian_smoothing, mesh_normal_consistency
     from harp_amd.loss.kps_loss import kps_loss
     from harp_amd.loss.texture_reg import albedo_reg, normal_reg
@@ -20,8 +32,8 @@ def test_loop_body_through_reference_api():
     from harp_amd.structures import Meshes
     from harp_amd.utils.visualize import prepare_materials, prepare_mesh, render_image, render_image_with_RT
     from oracle import harp_ref as H
-    sc = make_scene(T=3, S=128, seed=1)
-    S, focal, tg = sc["S"], sc["focal"], sc["targets"]
+    sc = make_scene(T=3, S=S, seed=1)
+    focal, tg = sc["focal"], sc["targets"]
     configs = dict(model_type="harp", img_size=S, focal_length=focal, use_arm=False, self_shadow=True, share_light_position=True)
     layer = ManoLayer(mano_root="unused", flat_hand_mean=False, use_pca=False, model=sc["model_np"], device=DEV)
     sub = get_mesh_subdivider(layer, use_arm=False, device=DEV)
@@ -31,11 +43,11 @@ def test_loop_body_through_reference_api():
         params["verts_disps"].copy_(torch.randn(3093, 1) * 0.001)
         params["texture"].copy_(torch.rand(1, 512, 512, 3) * 0.5 + 0.3)
         params["trans"].copy_(torch.randn(3, 3) * 0.01)      # all-zero trans takes the reference's no-translation branch (manolayer.py:281)
-    fid = torch.tensor([1, 2])
-    B = 2
+    fid = torch.tensor(fid)
+    B = len(fid)
     # pixels whose colour is not decided at float32 precision (tests/_scene.mask_ambiguous_pixels) leave the photometric mask of both paths
     tg, removed = mask_scene_targets(sc, params, fid)
-    check_removed("api_loop_body_128", removed)
+    check_removed(f"api_loop_body_{S}", removed)
     P = oracle_params(sc, params)
     # ---- the loop body, reference call for call (optimize_sequence.py:453-553)
     with torch.no_grad():
@@ -77,8 +89,11 @@ def test_loop_body_through_reference_api():
     for k, v in oloss.items():
         assert abs(loss[k].item() - v.item()) <= 2e-5 * abs(v.item()) + 1e-8, (k, loss[k].item(), v.item())
     assert ((y_pred.detach().cpu() - aux["y_pred"]).abs().max(-1).values > 1e-4).float().mean() < 1e-3
-    for k in ("pose", "cam", "verts_disps", "shape", "light_positions", "amb_ratio", "texture", "normal_map", "rot", "trans"):
-        assert rel(params[k].grad.cpu(), P[k].grad) < 2e-3, (k, rel(params[k].grad.cpu(), P[k].grad))
+    worst = {k: rel(params[k].grad.cpu(), P[k].grad) for k in ("pose", "cam", "verts_disps", "shape", "light_positions", "amb_ratio",
+                                                                "texture", "normal_map", "rot", "trans")}
+    print(f"[gradient rel-L2 vs fp64 oracle] reference API {S} frames {fid.tolist()}: " + ", ".join(f"{k} {v:.1e}" for k, v in worst.items()))
+    for k, v in worst.items():
+        assert v < 2e-3, (k, v)
 
 
 def test_unshadowed_phong_renderer():

@@ -8,6 +8,7 @@ same inputs (so the comparison is against the mathematically exact result, not a
          striding kernels, all gradients; B = 32 against the plain grid
   C1     single 256x256 frame, RAW 778-vertex / 1538-face MANO mesh, silhouette loss only — through the engine and through the
          reference API (prepare_mesh(mesh_subdivider=None) -> silhouette renderer)
+  off the tile grid: S = 300 / 301 / 448 / 200 (hand) and 520 (arm), where the last 16-px tile and 64-px super-tile are partial
   10 Adam steps vs torch.optim.Adam on the oracle; the appearance-only stage's geometry gradients (barycentric path of the shader backward)
 
 Tolerances are SURVEY.md §8(d)'s: images |d| <= 1e-4 on >= 99.9 % of the pixels, nearest-face ids identical except <= 1e-4 of the pixels,
@@ -91,6 +92,79 @@ def test_c2_c3_hand_512_b2_unmasked_companion():
         if keep:
             _check_images(eng, aux, 2)
         _check_grads(eng, P, keys, tol=5e-3, tag=f"512 hand UNMASKED keep_image={keep}")
+
+
+# Image sizes off the tile grid: the last 16-px tile and 64-px super-tile of every row / column are partial (the in-image guards, clamped
+# shadow taps, window flushes near S - 1 and per-tile flag indexing of every kernel of the step).  (kind, S, B, seed, stages, variants):
+# every stage (coarse, app) is one oracle evaluation that all engine variants (keep_image, light-view tile flags, HARP_RASTER_LOOP) meet.
+_FULL, _GEOM, _APP = (True, True), (True, False), (False, True)
+OFF_GRID = {
+    "hand_300_b2": ("hand", 300, 2, 0, (_FULL,), [(k, f, l) for l in (0, 16) for f in (False, True) for k in (True, False) if not (f and l)]),
+    "hand_301_b1": ("hand", 301, 1, 1, (_FULL,), [(True, False, 0), (False, False, 0)]),        # odd: a pixel centre on NDC 0
+    "hand_448_b2": ("hand", 448, 2, 2, (_FULL,), [(True, False, 0), (False, False, 0)]),        # the reference's img_size (optimize_sequence.py:352)
+    "hand_200_b3": ("hand", 200, 3, 3, (_GEOM, _APP), [(True, False, 0), (False, False, 0)]),
+    "arm_520_b1": ("arm", 520, 1, 0, (_FULL,), [(True, False, 0), (False, False, 0)]),
+}
+
+
+@pytest.mark.parametrize("name", list(OFF_GRID))
+def test_step_off_the_tile_grid_vs_fp64_oracle(name, monkeypatch):
+    """The whole step at image sizes that are no multiple of 16 or 64 (S = 300, 301, 448, 200, 520) against the float64 oracle: every loss
+    term (rel 1e-5), the image (SURVEY.md §8d criterion) and every gradient (rel-L2 <= 1e-3), float32-undecidable pixels out of the mask as
+    everywhere.  Variants (keep_image, zl_tile_flags, raster loop): zl_tile_flags = True puts the light-view tile flags ((S + 15) >> 4 a
+    side; on by default only at S >= 1024) on partial tiles; HARP_RASTER_LOOP=16 runs the striding raster / depth-backward kernels over
+    ragged super-tiles."""
+    kind, S, B, seed, stages, variants = OFF_GRID[name]
+    case = make_fit_case(kind, T=B, S=S, B=B, seed=seed, device=DEV)
+    eng = case["eng"]
+    if S % 8:      # the engine's HIP perceptual term tiles the image by 8: refused at the call, before it changes anything
+        from harp_amd.model.vgg import Vgg16Features
+        with pytest.raises(ValueError, match=f"image size {S} "):
+            eng.set_perceptual(Vgg16Features(weights="random"))
+        assert eng.perceptual is None
+    check_removed(f"offgrid_{name}", mask_ambiguous_pixels(case))
+    eng.draw_texture_offsets()
+    fid = torch.arange(B).flip(0)
+    keys = [k for k in ORACLE_KEYS if kind == "arm" or k != "wrist_pose"]
+    for coarse, app in stages:
+        P, loss, total, aux, _ = oracle_step(case, fid, coarse=coarse, app=app)
+        for keep, zl_flags, loop in variants:
+            eng.keep_image, eng.zl_tile_flags = keep, zl_flags
+            if loop:
+                monkeypatch.setenv("HARP_RASTER_LOOP", str(loop))
+            else:
+                monkeypatch.delenv("HARP_RASTER_LOOP", raising=False)
+            lv = engine_eval(case, fid, coarse=coarse, app=app)
+            _check_losses(lv, loss)
+            if keep and coarse and app:
+                _check_images(eng, aux, B)
+            elif keep and coarse:            # (the geometry-only stage shades nothing)
+                a = eng.s["alpha"][:B].cpu().double()
+                assert ((a - aux["y_sil_pred"]).abs() > 1e-4).float().mean() < 1e-3
+            elif keep:
+                rgb = eng.s["rgb"][:B].cpu().double()
+                assert ((rgb - aux["y_pred"]).abs().max(-1).values > 1e-4).float().mean() < 1e-3
+            _check_grads(eng, P, keys, tag=f"{name} coarse={coarse} app={app} keep_image={keep} zl_tile_flags={zl_flags} raster_loop={loop}")
+    monkeypatch.delenv("HARP_RASTER_LOOP", raising=False)
+
+
+def test_step_off_the_tile_grid_unmasked_companion():
+    """test_step_off_the_tile_grid_vs_fp64_oracle[hand_300_b2] with NO pixel taken out of the photometric mask, at the tolerances of
+    test_c2_c3_hand_512_b2_unmasked_companion (losses rel 1e-4, gradients rel-L2 <= 5e-3): the mask bounds the edge pixels of the partial
+    tiles, it does not hide them."""
+    case = make_fit_case("hand", T=2, S=300, B=2, seed=0, device=DEV)
+    eng = case["eng"]
+    eng.draw_texture_offsets()
+    fid = torch.tensor([1, 0])
+    P, loss, total, aux, _ = oracle_step(case, fid)
+    keys = [k for k in ORACLE_KEYS if k != "wrist_pose"]
+    for keep in (True, False):
+        eng.keep_image = keep
+        lv = engine_eval(case, fid)
+        _check_losses(lv, loss, tol=1e-4)
+        if keep:
+            _check_images(eng, aux, 2)
+        _check_grads(eng, P, keys, tol=5e-3, tag=f"300 hand UNMASKED keep_image={keep}")
 
 
 def test_c2_reference_batch_18():

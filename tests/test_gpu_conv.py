@@ -435,3 +435,54 @@ def test_whole_term_full_and_bounded_against_the_reference_pair(golden_dir, prec
         torch.cuda.synchronize()
         rel = ((g_rgb.double().cpu() - g_want).norm() / g_want.norm()).item()
         assert abs(loss.item() - float(ref["pair_loss"])) < 2e-5 * float(ref["pair_loss"]) and rel < (2e-3, 6e-2)[precision], (bd is None, loss.item(), rel)
+
+
+@pytest.mark.parametrize("shape,seed", [((2, 3, 60, 44), 10), ((1, 3, 100, 100), 11)])
+def test_module_call_off_the_8_grid_against_torch_float64(golden_dir, shape, seed):
+    """`Vgg16Features.forward` on a HIP tensor whose H or W is no multiple of 8 (the pools floor: 60 x 44 -> 7 x 5 at relu4_3, 100 -> 12): the
+    HIP kernels tile the image by 8, so the module runs its own torch layers, as the reference module does, instead of refusing the input.
+    Row and input gradient of a linear functional against the same module's CPU path in float64 (the bound of
+    test_module_call_backward_on_hip_against_torch_float64).  The input gradient is piecewise: where a ReLU input or a max-pool pair sits
+    within float32 rounding of its switch, one flipped gate moves it by ~1e-3 on the HIP kernels and torch's layers alike (measured on
+    uniform-noise inputs: 100 x 100 seed 10, 104 x 104 seeds 11 / 12 / 14).  The seeds here are decided by float32 under both of torch's
+    GPU convolution back ends (row 7e-7, gradient 6e-7)."""
+    import numpy as np, os
+    from harp_amd.model.vgg import Vgg16Features
+    ref = np.load(os.path.join(golden_dir, "vgg_ref.npz"))
+    LW = [float(v) for v in ref["layers_weights_fit"]]
+    vgg = _ref_filters_module(golden_dir, LW)
+    vgg64 = Vgg16Features(layers_weights=LW, weights=vgg.state_dict()).double()
+    g = torch.Generator().manual_seed(seed)
+    x = torch.rand(shape, generator=g, dtype=torch.float64).requires_grad_(True)
+    row64 = vgg64(x)
+    R = torch.randn(row64.shape, generator=g, dtype=torch.float64)
+    (want,) = torch.autograd.grad((row64 * R).sum(), x)
+    xd = x.detach().float().to(DEV).requires_grad_(True)
+    row = vgg(xd)
+    assert row.shape == row64.shape
+    (got,) = torch.autograd.grad((row * R.float().to(DEV)).sum(), xd)
+    torch.cuda.synchronize()
+    rel_row = ((row.detach().double().cpu() - row64.detach()).norm() / row64.detach().norm()).item()
+    rel = ((got.double().cpu() - want).norm() / want.norm()).item()
+    print(f"[module call off the 8-grid {tuple(shape)}] row rel-L2 {rel_row:.1e}, input gradient rel-L2 {rel:.1e}")
+    assert rel_row < 2e-6 and rel < 2e-6, (rel_row, rel)
+
+
+def test_module_call_after_load_state_dict_uses_the_new_filters():
+    """the filters packed for the HIP kernels are cached per module: loading other weights after a HIP forward must repack them (a stale
+    pack would silently evaluate the old filters)"""
+    from harp_amd.model.vgg import Vgg16Features
+    vgg = Vgg16Features(weights="random", seed=1)
+    g = torch.Generator().manual_seed(11)
+    x = torch.rand(1, 3, 64, 48, generator=g)
+    first = vgg(x.to(DEV)).double().cpu()
+    new = Vgg16Features(weights="random", seed=2)
+    vgg.load_state_dict(new.state_dict())
+    second = vgg(x.to(DEV)).double().cpu()
+    with torch.no_grad():
+        want_old = Vgg16Features(weights="random", seed=1).double()(x.double())
+        want_new = new.double()(x.double())
+    r = lambda a, b: ((a - b).norm() / b.norm()).item()
+    print(f"[reloaded filters] first vs old filters {r(first, want_old):.1e}, second vs new filters {r(second, want_new):.1e}")
+    assert r(first, want_old) < 1e-5 and r(second, want_new) < 1e-5, (r(first, want_old), r(second, want_new))
+    assert r(want_old, want_new) > 1e-2                              # (the two sets of filters give different rows)

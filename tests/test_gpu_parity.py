@@ -1818,12 +1818,13 @@ def test_wide_mesh_chain_raw_abi_equals_the_one_workgroup_chain(sc, kind):
 
 
 @pytest.mark.parametrize("stage", [(True, True, False), (False, True, False), (False, True, True)])
-@pytest.mark.parametrize("cap", [1 << 16, 48])
+@pytest.mark.parametrize("cap", [1 << 16, 48, 50, 65538])
 def test_texel_records_match_the_table_form(sc, cap, stage):
     """harp_shade_args.trec: one record per shaded pixel + harp_texel_reduce instead of the shader backward's own texel scatter (the
     backward of TexturesUV.sample_textures, renderer/pbr_materials.py:82-124).  Same texture / normal-map gradient as the table form
     (float-atomic order apart), every other gradient untouched, counters handed back zeroed; a list that is full (cap = 48: nearly every
-    record of this scene) falls back to memory atomics and changes nothing."""
+    record of this scene) falls back to memory atomics and changes nothing.  A requested capacity that is no multiple of 4 (50, 65538 =
+    2 mod 4; the kernels refuse such a list) is rounded up by ops.texel_record_capacity."""
     from tests._scene import make_fit_case
     case = make_fit_case("hand", T=3, S=128, B=3, seed=5, device=DEV)
     eng = case["eng"]
@@ -1844,7 +1845,7 @@ def test_texel_records_match_the_table_form(sc, cap, stage):
     eng.texel_records, eng.trec_cap_min, eng.trec_cap_div, eng._trec = True, cap, 1 << 30, None
     for graph in (False, True):
         g, l = run(graph)
-        assert eng._trec[2] == cap
+        assert eng._trec[2] == (cap + 3) // 4 * 4
         assert int(eng._trec[1].abs().max().item()) == 0, "harp_texel_reduce hands the list counters back zeroed"
         for k in ("texture", "normal_map"):
             a, b = eng.arena.view(g, k), eng.arena.view(ref[graph][0], k)
@@ -1897,24 +1898,27 @@ def test_texture_terms_by_tile_owners_edge_cases():
             assert (a - b).abs().max().item() <= 4e-7 * a.abs().max().item(), (H, W)
 
 
-@pytest.mark.parametrize("shrink,loop", [(1.0, 0), (0.25, 0), (0.1, 0), (1.0, 16)])
-def test_silhouette_backward_fused_into_the_raster_launch(sc, shrink, loop, monkeypatch):
+@pytest.mark.parametrize("shrink,loop,S", [pytest.param(sh, lp, 128, id=f"{sh}-{lp}") for sh, lp in ((1.0, 0), (0.25, 0), (0.1, 0), (1.0, 16))]
+                         + [(1.0, 0, 300), (1.0, 16, 300)])
+def test_silhouette_backward_fused_into_the_raster_launch(sc, shrink, loop, S, monkeypatch):
     """harp_rasterize_l1_fwd_bwd (the camera-view raster with every tile's silhouette backward fused in: the rim pixels walk the tile's
     faces while these are still staged in LDS) against harp_rasterize_l1_fwd + harp_silhouette_bwd on the same workspace: same alpha, loss
     and gradient image, same d loss / d ndc up to the order of float sums (the fused form accumulates a face's sums in float, the
     stand-alone one in double).  shrink < 1: the whole hand in a handful of tiles — hundreds to thousands of faces per tile against 256
-    staging slots, i.e. the tiles that stage their rounds a second time for the backward; loop: the striding grid."""
+    staging slots, i.e. the tiles that stage their rounds a second time for the backward; loop: the striding grid.  S = 300: the last
+    16-px tile and 64-px super-tile of each row and column are partial (the scene's focal length scaled with S: the same view)."""
     from harp_amd import _lib, ops
     from oracle import harp_ref as H, p3d_like as P
     if loop:
         monkeypatch.setenv("HARP_RASTER_LOOP", str(loop))
-    S, focal, topo = 128, sc["focal"] * shrink, sc["topo"]
+    f_S = sc["focal"] * S / sc["S"]
+    focal, topo = f_S * shrink, sc["topo"]
     params = dict(pose=sc["seq"]["pose"], rot=sc["seq"]["rot"], trans=sc["seq"]["trans"], shape=sc["seq"]["shape"].mean(0),
                   verts_disps=torch.zeros(3093, 1))
     fid = torch.arange(3)
     with torch.no_grad():
         _, v = H.prepare_mesh(params, fid, sc["model"], topo)
-        R, T = H.camera_RT(sc["seq"]["cam"][fid], S, sc["focal"])
+        R, T = H.camera_RT(sc["seq"]["cam"][fid], S, f_S)
         _, ndc = P.world_to_ndc(v, R, T, focal, (S / 2, S / 2), S)
     B, V, F = 3, ndc.shape[1], topo["faces"].shape[0]
     ndc_d, faces_d = ndc.float().to(DEV).contiguous(), topo["faces"].int().to(DEV).contiguous()
