@@ -13,8 +13,12 @@
 //                   pixel as a 64-bit LDS min over (depth bits, face id) (K=1 semantics, ties -> lower face id like PyTorch3D), flagging the
 //                   pixels a face saturates; the soft pass pairs the remaining pixels with the faces near them and multiplies the silhouette
 //                   product prod_f (1 - sigmoid(-d_f/sigma)) in ascending face order (raster_body.h).
-//   4. sil_bwd      same walk, rim pixels only: dL/dalpha -> dL/d(ndc xy) of the face vertices (atomics).
+//   4. sil_bwd      same walk, rim pixels only: dL/dalpha -> dL/d(ndc xy) of the face vertices (atomics).  With a record buffer bound to
+//                   the workspace (harp_sil_records_bind) the soft pass of 3. stores its (pixel, face) pairs per tile and 4. walks those
+//                   instead: no rim read of empty tiles, no second staging, no pair enumeration (raster_body.h: sil_bwd_records).
 #include <stdlib.h>
+#include <mutex>
+#include <unordered_map>
 #include "raster_body.h"
 
 namespace {
@@ -170,11 +174,12 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE =
                                                      int V, float* __restrict__ g_ndc, const float* __restrict__ l1_target,
                                                      const int32_t* __restrict__ l1_fid, const float* __restrict__ l1_w,
                                                      float* __restrict__ l1_loss, float* __restrict__ l1_grad, float l1_inv, int sparse,
-                                                     const float* __restrict__ l1_bg_sums, int32_t* __restrict__ st_state) {
+                                                     const float* __restrict__ l1_bg_sums, int32_t* __restrict__ st_state,
+                                                     uint32_t* __restrict__ srec, int srec_cap) {
   __shared__ rb::RasterSmem<MODE, BWD> sm;
   if constexpr (!LOOP) {
     rb::raster_tile<MODE, BWD>(sm, blockIdx.x, recs, bbs, bins, bin_count, order, nact, B, F, S, nsx, blur, sigma, face_id, zbuf, alpha, g_alpha, faces, V, g_ndc,
-                          l1_target, l1_fid, l1_w, l1_loss, l1_grad, l1_inv, sparse, l1_bg_sums, st_state);
+                          l1_target, l1_fid, l1_w, l1_loss, l1_grad, l1_inv, sparse, l1_bg_sums, st_state, srec, srec_cap);
     return;
   }
   // LOOP (grids above 64 k workgroups, i.e. 1024^2 and up): the grid is capped at kRasterGrid workgroups (a multiple of 8, so a workgroup's tiles stay on its XCD) and a workgroup strides over
@@ -189,7 +194,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE =
   for (unsigned v = blockIdx.x; v < limit; v += gridDim.x) {
     if (v != blockIdx.x) __syncthreads();                 // LDS of the previous tile
     rb::raster_tile<MODE, BWD>(sm, v, recs, bbs, bins, bin_count, order, nact, B, F, S, nsx, blur, sigma, face_id, zbuf, alpha, g_alpha, faces, V, g_ndc,
-                          l1_target, l1_fid, l1_w, l1_loss, l1_grad, l1_inv, sparse, l1_bg_sums, st_state);
+                          l1_target, l1_fid, l1_w, l1_loss, l1_grad, l1_inv, sparse, l1_bg_sums, st_state, srec, srec_cap);
   }
   if (bg_table) {
     // slots below `limit` (nact rounded up to 8) already went through raster_tile, whose sub == 0 workgroup adds the table value of an
@@ -205,6 +210,18 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MODE =
 }
 
 }  // namespace
+
+extern "C" size_t harp_sil_records_bytes(int B, int S, int cap);
+// Silhouette records bound to a camera-view workspace (harp_sil_records_bind): the soft passes on that workspace store their pairs, its
+// silhouette backward reads them.  Host-side, looked up when a launch is enqueued (a captured graph keeps what was bound at capture).
+struct SilRecBinding { uint32_t* rec; int cap; size_t bytes; };
+static std::mutex g_srec_mu;
+static std::unordered_map<const void*, SilRecBinding> g_srec;
+static SilRecBinding srec_of(const void* ws) {
+  std::lock_guard<std::mutex> lk(g_srec_mu);
+  const auto it = g_srec.find(ws);
+  return it == g_srec.end() ? SilRecBinding{nullptr, 0, 0} : it->second;
+}
 
 static void raster_setup_any(const float* ndc, const int32_t* faces, int B, int V, int F, int S, float r, void* ws, hipStream_t stream) {
   const RasterWs W = raster_ws_split(ws, B, F, S);
@@ -278,19 +295,23 @@ static int rasterize_impl(const float* ndc, const int32_t* faces, int B, int V, 
   if ((soft & 1) && g_ndc) {
     // camera view with the silhouette backward of every tile fused in (harp_rasterize_l1_fwd_bwd)
     if (loop) hipLaunchKernelGGL((raster_kernel<1, true, true>), grid, dim3(256), 0, stream, recs, bbs, bins, cnt, order, W.nact, B, F, S, nsx, blur_radius, sigma, face_id, zbuf,
-                                 alpha, nullptr, faces, V, g_ndc, l1_target, l1_fid, l1_w, l1_loss, l1_grad, l1_inv, sp, l1_bg_sums, nullptr);
+                                 alpha, nullptr, faces, V, g_ndc, l1_target, l1_fid, l1_w, l1_loss, l1_grad, l1_inv, sp, l1_bg_sums, nullptr, nullptr, 0);
     else hipLaunchKernelGGL((raster_kernel<1, false, true>), grid, dim3(256), 0, stream, recs, bbs, bins, cnt, order, W.nact, B, F, S, nsx, blur_radius, sigma, face_id, zbuf,
-                            alpha, nullptr, faces, V, g_ndc, l1_target, l1_fid, l1_w, l1_loss, l1_grad, l1_inv, sp, l1_bg_sums, nullptr);
+                            alpha, nullptr, faces, V, g_ndc, l1_target, l1_fid, l1_w, l1_loss, l1_grad, l1_inv, sp, l1_bg_sums, nullptr, nullptr, 0);
   } else if (soft & 1) {
+    const SilRecBinding sr = srec_of(ws);
+    if (sr.rec && harp_sil_records_bytes(B, S, sr.cap) > sr.bytes) return HARP_ERR_ARG;       // (bound for fewer frames / a smaller image)
+    uint32_t* srec = sr.rec;
+    const int srec_cap = sr.cap;
     if (loop) HARP_RASTER_LAUNCH(1, true, recs, bbs, bins, cnt, order, W.nact, B, F, S, nsx, blur_radius, sigma, face_id, zbuf, alpha, nullptr, nullptr, 0, nullptr,
-                                 l1_target, l1_fid, l1_w, l1_loss, l1_grad, l1_inv, sp, l1_bg_sums, nullptr);
+                                 l1_target, l1_fid, l1_w, l1_loss, l1_grad, l1_inv, sp, l1_bg_sums, nullptr, srec, srec_cap);
     else HARP_RASTER_LAUNCH(1, false, recs, bbs, bins, cnt, order, W.nact, B, F, S, nsx, blur_radius, sigma, face_id, zbuf, alpha, nullptr, nullptr, 0, nullptr,
-                            l1_target, l1_fid, l1_w, l1_loss, l1_grad, l1_inv, sp, l1_bg_sums, nullptr);
+                            l1_target, l1_fid, l1_w, l1_loss, l1_grad, l1_inv, sp, l1_bg_sums, nullptr, srec, srec_cap);
   } else {
     if (loop) HARP_RASTER_LAUNCH(0, true, recs, bbs, bins, cnt, order, W.nact, B, F, S, nsx, 0.f, 1.f, face_id, zbuf, nullptr, nullptr, nullptr, 0, nullptr, nullptr,
-                                 nullptr, nullptr, nullptr, nullptr, 0.f, sp, nullptr, st_state);
+                                 nullptr, nullptr, nullptr, nullptr, 0.f, sp, nullptr, st_state, nullptr, 0);
     else HARP_RASTER_LAUNCH(0, false, recs, bbs, bins, cnt, order, W.nact, B, F, S, nsx, 0.f, 1.f, face_id, zbuf, nullptr, nullptr, nullptr, 0, nullptr, nullptr,
-                            nullptr, nullptr, nullptr, nullptr, 0.f, sp, nullptr, st_state);
+                            nullptr, nullptr, nullptr, nullptr, 0.f, sp, nullptr, st_state, nullptr, 0);
   }
   HARP_CHECK_LAUNCH();
   return HARP_OK;
@@ -355,9 +376,14 @@ int harp_rasterize_fwd_keep(const float* ndc, const int32_t* faces, int B, int V
 
 // Soft-silhouette backward: g_alpha (B,S,S) -> accumulates (atomicAdd) into g_ndc (B,V,3) (x,y components).
 // ws must be the workspace of the matching harp_rasterize_fwd(soft=1); alpha its output.
+// A workspace with silhouette records bound (harp_sil_records_bind) walks the pairs its forward stored.
 int harp_silhouette_bwd(const int32_t* faces, int B, int V, int F, int S, float blur_radius, float sigma, const void* ws,
                         const float* alpha, const float* g_alpha, float* g_ndc, hipStream_t stream) {
   if (!faces || !ws || !alpha || !g_alpha || !g_ndc) return HARP_ERR_ARG;
+  const SilRecBinding sr = srec_of(ws);
+  if (sr.rec && harp_sil_records_bytes(B, S, sr.cap) > sr.bytes) return HARP_ERR_ARG;
+  uint32_t* srec = sr.rec;
+  const int srec_cap = sr.cap;
   const RasterWs W = raster_ws_split((void*)ws, B, F, S);
   FaceRec* recs = W.recs; int32_t *bins = W.bins, *cnt = W.cnt, *order = W.order; float4* bbs = W.bbs;
   const int nsx = W.nsx;
@@ -365,10 +391,26 @@ int harp_silhouette_bwd(const int32_t* faces, int B, int V, int F, int S, float 
   const bool loop = lgrid != 0u;
   const dim3 grid(loop ? lgrid : tile_grid(B, nsx));
   if (loop) HARP_RASTER_LAUNCH(2, true, recs, bbs, bins, cnt, order, W.nact, B, F, S, nsx, blur_radius, sigma, nullptr, nullptr, (float*)alpha, g_alpha, faces, V, g_ndc,
-                               nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0, nullptr, nullptr);
+                               nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0, nullptr, nullptr, srec, srec_cap);
   else HARP_RASTER_LAUNCH(2, false, recs, bbs, bins, cnt, order, W.nact, B, F, S, nsx, blur_radius, sigma, nullptr, nullptr, (float*)alpha, g_alpha, faces, V, g_ndc,
-                          nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0, nullptr, nullptr);
+                          nullptr, nullptr, nullptr, nullptr, nullptr, 0.f, 0, nullptr, nullptr, srec, srec_cap);
   HARP_CHECK_LAUNCH();
+  return HARP_OK;
+}
+
+// Silhouette records (raster_body.h: srec_*): the camera view's soft pass stores its (pixel, face) pairs per tile, the backward walks them.
+size_t harp_sil_records_bytes(int B, int S, int cap) {
+  if (B <= 0 || S <= 0 || cap < 0) return 0;
+  const int nsx = (S + kSuper - 1) / kSuper;
+  return (rb::srec_count_words(B, nsx) + rb::srec_tiles(B, nsx) * (size_t)cap) * sizeof(uint32_t);
+}
+
+int harp_sil_records_bind(const void* ws, void* sil_rec, int rec_cap, int B, int F, int S) {
+  if (!ws || (sil_rec && (rec_cap < 0 || B <= 0 || S <= 0 || F > (1 << 24) || harp_sil_records_bytes(B, S, rec_cap) >= ((size_t)1 << 34))))
+    return HARP_ERR_ARG;                              // (face id << 8 | pixel; 32-bit record offsets)
+  std::lock_guard<std::mutex> lk(g_srec_mu);
+  if (sil_rec) g_srec[ws] = SilRecBinding{(uint32_t*)sil_rec, rec_cap, harp_sil_records_bytes(B, S, rec_cap)};
+  else g_srec.erase(ws);
   return HARP_OK;
 }
 

@@ -101,6 +101,7 @@ struct RasterSmem {
   // into them through an fp32 compare-and-swap loop (11 clk per wave instruction; ds_add_f32 takes 193 on gfx950)
   float s_gf[(MODE == 1 && BWD) ? kCap : 1][6];
   float red[4];
+  int rec_n;                                        // MODE 1 with silhouette records: records of this tile so far
 };
 
 __device__ __forceinline__ void lds_add_f32(float* p, float v) {
@@ -110,6 +111,90 @@ __device__ __forceinline__ void lds_add_f32(float* p, float v) {
     assumed = old;
     old = atomicCAS(u, assumed, __float_as_uint(__uint_as_float(assumed) + v));
   } while (old != assumed);
+}
+
+// ---- silhouette records (harp_sil_records_bind: harp_rasterize_l1_fwd -> harp_silhouette_bwd).  The camera view's soft pass already enumerates every
+//      (candidate pixel, staged face) pair with a soft factor — the pairs the silhouette backward needs, on the rim pixels among them.  With a
+//      record buffer it stores them: per (frame, 16x16 tile of the tile grid) — tile index (b * nst + st) * 16 + sub — a count (ints, first,
+//      256-B padded) and a region of `cap` 32-bit records (face id << 8 | pixel of the tile).  A wave takes its offset from a tile-local LDS
+//      counter; the tile stores its count with a plain store, also when it holds more than `cap` (the backward then walks it as before).
+__host__ __device__ inline size_t srec_tiles(int B, int nsx) { return (size_t)B * nsx * nsx * ((kSuper / kTile) * (kSuper / kTile)); }
+__host__ __device__ inline size_t srec_count_words(int B, int nsx) { return (srec_tiles(B, nsx) + 63) / 64 * 64; }
+
+// PointLineDistanceBackward of ONE record: the same arithmetic as the pair walk of MODE 2 (raster_tile) on a pair read back instead of
+// enumerated.  Per-vertex sums in an LDS table keyed by vertex id (double: see VertexAccum), one memory atomic per (vertex, component) per tile.
+template <int MODE, bool BWD>
+__device__ __forceinline__ void sil_bwd_records(RasterSmem<MODE, BWD>& sm, const uint32_t* __restrict__ rt, int nrec, int b, int tx0, int ty0,
+                                                const FaceRec* __restrict__ rb, const int32_t* __restrict__ faces, int S, int V, float blur,
+                                                float sigma, const float* __restrict__ alpha, const float* __restrict__ g_alpha,
+                                                float* __restrict__ g_ndc) {
+  static_assert(sizeof(VertexAccum<256, 2>) <= sizeof(sm.s_g), "vertex table must fit the face accumulators");
+  auto* acc = reinterpret_cast<VertexAccum<256, 2>*>(&sm.s_g[0][0]);
+  acc->clear();
+  __syncthreads();
+  const float inv_sigma = 1.0f / sigma;
+  float* gb = g_ndc + (size_t)b * V * 3;
+  for (int i = threadIdx.x; i < nrec; i += 256) {
+    const unsigned rw = rt[i];
+    const int c = (int)(rw & 255u), fid = (int)(rw >> 8);
+    const int xi = tx0 + (c & (kTile - 1)), yi = ty0 + (c >> 4);
+    const size_t o = ((size_t)b * S + yi) * S + xi;
+    const float Pq = 1.0f - alpha[o], gq = g_alpha[o];
+    if (Pq == 0.f || Pq == 1.0f || gq == 0.f) continue;          // not a rim pixel (the pass's own `need` test)
+    const FaceRec fr = rb[fid];
+    const int v0 = faces[3 * fid], v1 = faces[3 * fid + 1], v2 = faces[3 * fid + 2];
+    const float qx = pix_to_ndc(xi, S), qy = pix_to_ndc(yi, S);
+    const Tri t = tri_from(fr.a, fr.b, make_float4(0.f, 0.f, 0.f, 0.f));
+    const float e0 = edge_fn(qx, qy, t.x1, t.y1, t.x2, t.y2);
+    const float e1 = edge_fn(qx, qy, t.x2, t.y2, t.x0, t.y0);
+    const float e2 = edge_fn(qx, qy, t.x0, t.y0, t.x1, t.y1);
+    const float area = edge_fn(t.x2, t.y2, t.x0, t.y0, t.x1, t.y1) + kEps;
+    const float sg = (area > 0.f) ? 1.f : ((area < 0.f) ? -1.f : 0.f);
+    const float e0s = e0 * sg, e1s = e1 * sg, e2s = e2 * sg;
+    const bool inside = (e0s > 0.f) && (e1s > 0.f) && (e2s > 0.f);
+    const float l12 = (t.x2 - t.x1) * (t.x2 - t.x1) + (t.y2 - t.y1) * (t.y2 - t.y1);
+    const float l20 = (t.x0 - t.x2) * (t.x0 - t.x2) + (t.y0 - t.y2) * (t.y0 - t.y2);
+    const float l01 = (t.x1 - t.x0) * (t.x1 - t.x0) + (t.y1 - t.y0) * (t.y1 - t.y0);
+    bool soft = true;
+    if (inside) {
+      const float K = 18.0f * sigma;
+      if (e0 * e0 > K * l12 && e1 * e1 > K * l20 && e2 * e2 > K * l01) soft = false;
+    } else {
+      const float Bf = blur * 1.00001f;
+      if ((e0s < 0.f && e0 * e0 >= Bf * l12) || (e1s < 0.f && e1 * e1 >= Bf * l20) || (e2s < 0.f && e2 * e2 >= Bf * l01)) soft = false;
+    }
+    if (!soft) continue;
+    float ta, tb, tc;
+    const float d01 = seg_dist2(qx, qy, t.x0, t.y0, t.x1, t.y1, ta);
+    const float d02 = seg_dist2(qx, qy, t.x0, t.y0, t.x2, t.y2, tb);
+    const float d12 = seg_dist2(qx, qy, t.x1, t.y1, t.x2, t.y2, tc);
+    const float dist = fminf(d01, fminf(d02, d12));
+    if (!(inside || dist < blur)) continue;
+    const float sd = inside ? -dist : dist;
+    const float p = __builtin_amdgcn_rcpf(1.0f + __expf(sd * inv_sigma));
+    const float g_sd = gq * (-Pq * p * inv_sigma);
+    const float gd = inside ? -g_sd : g_sd;
+    int va, vb; float ax, ay, bx, by, tt;
+    if (d01 <= d02 && d01 <= d12) { va = v0; vb = v1; ax = t.x0; ay = t.y0; bx = t.x1; by = t.y1; tt = ta; }
+    else if (d02 <= d12)          { va = v0; vb = v2; ax = t.x0; ay = t.y0; bx = t.x2; by = t.y2; tt = tb; }
+    else                          { va = v1; vb = v2; ax = t.x1; ay = t.y1; bx = t.x2; by = t.y2; tt = tc; }
+    const float hx = ax + tt * (bx - ax), hy = ay + tt * (by - ay);
+    const float cx = gd * 2.f * (hx - qx), cy = gd * 2.f * (hy - qy);
+    const float gax = (1.f - tt) * cx, gay = (1.f - tt) * cy, gbx = tt * cx, gby = tt * cy;
+    int k = acc->find(va);
+    if (k >= 0) { acc->add(k, 0, gax); acc->add(k, 1, gay); }
+    else { atomicAdd(gb + 3 * va, gax); atomicAdd(gb + 3 * va + 1, gay); }          // (table full: straight to memory)
+    k = acc->find(vb);
+    if (k >= 0) { acc->add(k, 0, gbx); acc->add(k, 1, gby); }
+    else { atomicAdd(gb + 3 * vb, gbx); atomicAdd(gb + 3 * vb + 1, gby); }
+  }
+  __syncthreads();
+  const int v = acc->key[threadIdx.x];
+  if (v >= 0) {
+    const float gx = (float)acc->val[threadIdx.x][0], gy = (float)acc->val[threadIdx.x][1];
+    if (gx != 0.f) atomicAdd(gb + 3 * v, gx);
+    if (gy != 0.f) atomicAdd(gb + 3 * v + 1, gy);
+  }
 }
 
 // One 16x16 tile; `vblock` = index in the 1-D heaviest-first tile grid (harp_common.h: tile_decode_v).  A __device__ function so that
@@ -125,7 +210,8 @@ __device__ __forceinline__ void raster_tile(RasterSmem<MODE, BWD>& sm, unsigned 
                                                      int V, float* __restrict__ g_ndc, const float* __restrict__ l1_target,
                                                      const int32_t* __restrict__ l1_fid, const float* __restrict__ l1_w,
                                                      float* __restrict__ l1_loss, float* __restrict__ l1_grad, float l1_inv, int sparse,
-                                                     const float* __restrict__ l1_bg_sums, int32_t* __restrict__ st_state = nullptr) {
+                                                     const float* __restrict__ l1_bg_sums, int32_t* __restrict__ st_state = nullptr,
+                                                     uint32_t* __restrict__ srec = nullptr, int srec_cap = 0) {
   auto& s_a = sm.s_a; auto& s_b = sm.s_b; auto& s_bb = sm.s_bb; auto& s_z2 = sm.s_z2; auto& s_id = sm.s_id;
   auto& s_g = sm.s_g;
   int* lds_cnt = sm.lds_cnt;
@@ -186,6 +272,21 @@ __device__ __forceinline__ void raster_tile(RasterSmem<MODE, BWD>& sm, unsigned 
   }
   const int nst = nsx * nsx;
   if (MODE == 0 && st_state && sub == 0 && threadIdx.x == 0) st_state[b * nst + st] = 0;               // holds depths: to be cleared when it empties
+  // silhouette records: index of this tile's count / record region
+  const unsigned rtile = (unsigned)((b * nst + st) * ((kSuper / kTile) * (kSuper / kTile)) + sub);
+  const unsigned roff = (unsigned)srec_count_words(B, nsx) + rtile * (unsigned)srec_cap;      // this tile's first record
+  if constexpr (MODE == 2) {
+    if (srec != nullptr) {
+      // the camera view's soft pass stored this tile's pairs: walk them, no rim read, no staging (a tile with more than `cap` walks as below)
+      const int nrec = __builtin_amdgcn_readfirstlane(reinterpret_cast<const int32_t*>(srec)[rtile]);
+      if (nrec <= srec_cap) {
+        if (nrec > 0)
+          sil_bwd_records(sm, srec + roff, nrec, b, tx0, ty0, recs + (size_t)b * F, faces, S, V,
+                          blur, sigma, alpha, g_alpha, g_ndc);
+        return;
+      }
+    }
+  }
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int xi = tx0 + (lane & 15), yi = ty0 + w * 4 + (lane >> 4);
   const bool in_img = (xi < S) && (yi < S);
@@ -230,6 +331,7 @@ __device__ __forceinline__ void raster_tile(RasterSmem<MODE, BWD>& sm, unsigned 
   if (kScan) {                                  // (the first barrier of the staging below orders these before their first use)
     sm.zkey[threadIdx.x] = ~0ull;
     if (MODE == 1) { sm.sat[threadIdx.x] = 0; sm.prodl[threadIdx.x] = 1.0f; }
+    if (MODE == 1 && threadIdx.x == 0) sm.rec_n = 0;
     if (threadIdx.x < kTile) sm.ndc_x[threadIdx.x] = pix_to_ndc(tx0 + threadIdx.x, S);
     else if (threadIdx.x < 2 * kTile) sm.ndc_y[threadIdx.x - kTile] = pix_to_ndc(ty0 + threadIdx.x - kTile, S);
   }
@@ -432,6 +534,7 @@ __device__ __forceinline__ void raster_tile(RasterSmem<MODE, BWD>& sm, unsigned 
           auto process = [&](int nvalid) {
             float f = 1.0f;
             int c = -1 - lane;                             // (distinct keys for idle lanes)
+            bool em = false;                               // the pair gets a soft factor: a silhouette record
             if (lane < nvalid) {
               const int pr = wl[(head + lane) & 127], j = pr & 255;
               c = pr >> 8;
@@ -462,7 +565,20 @@ __device__ __forceinline__ void raster_tile(RasterSmem<MODE, BWD>& sm, unsigned 
                   const float sd = inside ? -dist : dist;
                   const float p = __builtin_amdgcn_rcpf(1.0f + __expf(sd * inv_sigma));   // sigmoid(-sd/sigma): fast exp + reciprocal (rel. error ~1e-6 at |x| ~ 18; image tolerance 1e-4)
                   f = 1.0f - p;
+                  em = true;
                 }
+              }
+            }
+            if (srec) {
+              // record the pair: one LDS atomic per wave and batch for the wave's offset in the tile's region
+              // (the pair's staged index is read back from the ring: nothing more stays live across the distance arithmetic)
+              const unsigned long long m = __ballot(em);
+              if (m) {
+                int o0 = 0;
+                if (lane == 0) o0 = atomicAdd(&sm.rec_n, __popcll(m));
+                o0 = __builtin_amdgcn_readfirstlane(o0);
+                const int slot = o0 + __popcll(m & ((1ull << lane) - 1ull));
+                if (em && slot < srec_cap) srec[roff + (unsigned)slot] = ((unsigned)s_id[wl[(head + lane) & 127] & 255] << 8) | (unsigned)c;
               }
             }
             const int cprev = __shfl_up(c, 1);
@@ -607,6 +723,7 @@ __device__ __forceinline__ void raster_tile(RasterSmem<MODE, BWD>& sm, unsigned 
     const unsigned long long key = sm.zkey[threadIdx.x];
     if (key != ~0ull) { best_f = (int)(unsigned)(key & 0xffffffffull); best_z = __uint_as_float((unsigned)(key >> 32)); }
     if (MODE == 1) prod = sm.sat[threadIdx.x] ? 0.f : sm.prodl[threadIdx.x];
+    if (MODE == 1 && srec && threadIdx.x == 0) reinterpret_cast<int32_t*>(srec)[rtile] = sm.rec_n;      // (also when it exceeds the capacity)
   }
   float l1_acc = 0.f;
   if (MODE != 2 && in_img) {

@@ -20,6 +20,7 @@ and scaled by 1/world inside the Adam kernel (SURVEY.md §5 "Data-parallel seman
 """
 import ctypes
 import os
+import weakref
 import math
 
 import numpy as np
@@ -216,6 +217,12 @@ class FitEngine:
         self.vgg_streams = 2             # perceptual term: the batch in this many parts on as many streams (harp_vgg16_term_args.side_streams; 1 - 4)
         self.split_adam = True           # with the texel records: the maps' Adam update on the second stream behind harp_texel_finish, the step's last launch only for the small parameters
         self.fused_sil_bwd = False       # the silhouette backward inside the camera-view raster launch (harp_rasterize_l1_fwd_bwd) instead of a launch of its own beside the shader backward.  Correct (tests) and measured SLOWER: the shader backward gains 32 us without its neighbour (230 -> 198 in the graph), the camera raster pays 56 (198 -> 254: 94 VGPRs / 26 KB of LDS = 5 waves per SIMD instead of 7, and the rim walk is ~25 us of VALU work wherever it runs): step 0.665 vs 0.638 ms (profiles/r06_ab_record.txt)
+        # silhouette records (harp_sil_records_bind): the camera raster's soft pass stores its (pixel, face) pairs per 16x16 tile and the
+        # silhouette backward walks them instead of reading alpha / g_alpha of every tile and staging the tile's faces again; a tile with more
+        # than sil_rec_cap pairs takes the staged walk (512: 2.7x the fullest hand tile at 512^2, ~0.1 % of the arm's tiles at 1024^2 go over).
+        # Step -19 us, geometry-only stage -24 us (profiles/r07_ab_record.txt).  Off with fused_sil_bwd / fused_bwd.
+        self.sil_records = True
+        self.sil_rec_cap = 512
         self.lean_app_stage = False      # appearance-only stage without the geometry gradients nothing reads (set by optimize_hand_sequence; off by default: g_buf then holds what autograd would)
         self._lean_now = False
         self.sil_only_raster = True      # geometry-only steps without a kept image: the camera raster forms no nearest-face ids (harp_rasterize_l1_fwd with face_id == NULL)
@@ -575,6 +582,21 @@ class FitEngine:
         marks = {}
         # the silhouette backward inside the camera-view raster launch (its atomics into g_ndc_c need the slab clear in front of them)
         fsb = bool(self.fused_sil_bwd and coarse and not (self.fused_bwd and app and self.perceptual is None))
+        # silhouette records: written by the camera raster, read by the stand-alone silhouette backward
+        srec = bool(self.sil_records and coarse and not self.fused_sil_bwd and not self.fused_bwd)
+        # (bound to the camera workspace: harp_rasterize_l1_fwd stores the pairs, harp_silhouette_bwd walks them)
+        bind = (max(B, lane["B"]), self.sil_rec_cap) if srec else None
+        if s.get("sil_rec_bound") != bind:
+            if bind is not None and ("sil_rec" not in s or s["sil_rec"].numel() < L.harp_sil_records_bytes(bind[0], S, bind[1])):
+                # (a replaced buffer stays alive: graphs captured with it hold its address)
+                s.setdefault("sil_rec_old", []).append(s.get("sil_rec"))
+                s["sil_rec"] = torch.empty(L.harp_sil_records_bytes(bind[0], S, bind[1]), dtype=torch.uint8, device=self.dev)
+            self._ck(L.harp_sil_records_bind(p(s["ws_c"]), p(s["sil_rec"]) if bind else None, bind[1] if bind else 0, bind[0] if bind else 0, F, S),
+                     "sil_records_bind")
+            s["sil_rec_bound"] = bind
+            if bind is not None and "sil_rec_fin" not in s:
+                # unbound when the workspace goes: a later workspace at the same address must not inherit the binding
+                s["sil_rec_fin"] = weakref.finalize(s["ws_c"], L.harp_sil_records_bind, p(s["ws_c"]), None, 0, 0, 0, 0)
         # ---- terms that depend on the parameters only (normal-map normalisation, texture regularisers, displacement regulariser) go
         #      first on the second stream: they run under the LBS / mesh chain, which is a string of small latency-bound launches
         deferred = []
@@ -757,6 +779,10 @@ class FitEngine:
         fuse_bwd = self.fused_bwd and coarse and app and self.perceptual is None
         side_used = False
         sil_after = None
+        def sil_bwd():
+            # (with `sil_records` the workspace has a record buffer bound: the launch walks the pairs the camera raster stored)
+            self._ck(L.harp_silhouette_bwd(p(tp.faces), B, V, F, S, ops.SIL_BLUR, ops.SIL_SIGMA, p(s["ws_c"]), p(s["alpha"]), p(s["g_alpha"]),
+                                           p(s["g_ndc_c"]), ST()), "silhouette_bwd")
         def launch_sil(ev=None):
             # the silhouette backward only needs g_alpha and the camera-view workspace: it overlaps with shading on the side stream
             if ev is None:
@@ -764,8 +790,7 @@ class FitEngine:
             else:
                 wait_e(side, ev)
             with torch.cuda.stream(side):
-                self._ck(L.harp_silhouette_bwd(p(tp.faces), B, V, F, S, ops.SIL_BLUR, ops.SIL_SIGMA, p(s["ws_c"]), p(s["alpha"]), p(s["g_alpha"]),
-                                               p(s["g_ndc_c"]), ST()), "silhouette_bwd")
+                sil_bwd()
                 if mesh_late:
                     mesh_terms()                # `mesh_terms_late`: beside the (latency-bound) shader backward instead of beside the (VALU-bound) rasterisers
                 marks["sil"] = None if one else side.record_event()
@@ -773,8 +798,7 @@ class FitEngine:
             if not app and self.overlap:
                 # geometry-only stage: there is no shader backward to run next to — the silhouette backward stays on the critical stream
                 # (two cross-stream edges, ~6 us each, off the step)
-                self._ck(L.harp_silhouette_bwd(p(tp.faces), B, V, F, S, ops.SIL_BLUR, ops.SIL_SIGMA, p(s["ws_c"]), p(s["alpha"]), p(s["g_alpha"]),
-                                               p(s["g_ndc_c"]), ST()), "silhouette_bwd")
+                sil_bwd()
             else:
                 side_used = True
                 if go and app:
@@ -1266,7 +1290,7 @@ class FitEngine:
         # every switch the enqueued launch sequence depends on is part of the key: flipping one re-captures instead of replaying a
         # graph recorded for another configuration
         gkey = (coarse, app, scheduled, n, self.keep_image, self.fused_loss, self.self_shadow, tuple(self.frozen), self.overlap, self.early_terms,
-                self.packed_texels, self.fused_keep, self.mesh_third, self.graph_order, fold, self.fused_terms, self.zl_tile_flags, self.accumulate_loss, self.lean_app_stage, self.sil_only_raster, self.auto_draw, self.mesh_terms_late, self.sil_late, self.paired_setup, self.late_texture_terms, self.mesh_terms_first, self.camera_first, self.tail_side, self.fused_bwd, self.fused_chain, self.fused_front, self.wide_front, self.hybrid_front, self.front_auto, self.wide_back, self.fused_back, self.consume_gzl, self.keep_depth, self.texel_records, self.fused_sil_bwd, self.split_adam, self.vert9, self.vgg_streams, dist_on, self.overlap_allreduce,
+                self.packed_texels, self.fused_keep, self.mesh_third, self.graph_order, fold, self.fused_terms, self.zl_tile_flags, self.accumulate_loss, self.lean_app_stage, self.sil_only_raster, self.auto_draw, self.mesh_terms_late, self.sil_late, self.paired_setup, self.late_texture_terms, self.mesh_terms_first, self.camera_first, self.tail_side, self.fused_bwd, self.fused_chain, self.fused_front, self.wide_front, self.hybrid_front, self.front_auto, self.wide_back, self.fused_back, self.consume_gzl, self.keep_depth, self.texel_records, self.fused_sil_bwd, self.sil_records, self.sil_rec_cap, self.split_adam, self.vert9, self.vgg_streams, dist_on, self.overlap_allreduce,
                 self.comm is not None, self.perceptual is not None and app)
         g = self._graphs.get(gkey)
         if g is None:

@@ -70,6 +70,17 @@ int harp_rasterize_l1_fwd_bwd(const float* ndc, const int32_t* faces, int B, int
 /* replaces _C.rasterize_meshes_backward (grad_dists path) + sigmoid_alpha_blend backward; g_ndc (B,V,3) (+=) */
 int harp_silhouette_bwd(const int32_t* faces, int B, int V, int F, int S, float blur_radius, float sigma, const void* ws,
                         const float* alpha, const float* g_alpha, float* g_ndc, hipStream_t stream);
+/* Silhouette records: the soft pass of the camera view (renderer_helper.py:44-58) already pairs every pixel it blends with every face
+ * whose soft factor it forms — the pairs that rasterize_meshes_backward's dists path (with sigmoid_alpha_blend's backward) differentiates.
+ * harp_sil_records_bind(ws, sil_rec, rec_cap, B, F, S) binds a record buffer of harp_sil_records_bytes(B, S, rec_cap) bytes to a
+ * workspace: from then on every soft pass on ws (harp_rasterize_fwd / harp_rasterize_l1_fwd with soft & 1, up to B frames of S^2) also
+ * stores its pairs there — per (frame, 16x16 tile) a count and up to rec_cap records (face id << 8 | pixel of the tile; a tile with more
+ * stores its count only) — and harp_silhouette_bwd on ws walks those pairs instead of finding them again (a tile over the capacity walks
+ * as without records).  Every output of both calls is what it is without records (the gradient up to the order of float sums).  Keep the
+ * binding between a forward and its backward; sil_rec needs no initial contents.  sil_rec == NULL unbinds.  Host-side state, read when a
+ * call is enqueued (a captured graph replays what was bound at capture). */
+size_t harp_sil_records_bytes(int B, int S, int rec_cap);
+int harp_sil_records_bind(const void* ws, void* sil_rec, int rec_cap, int B, int F, int S);
 /* replaces _C.rasterize_meshes_backward (grad_zbuf path) for a K=1 pass: g_z (B,S,S) -> g_ndc (B,V,3) (+=) */
 int harp_depth_bwd(const int32_t* face_id, const void* ws, const int32_t* faces, const float* g_z, int B, int V, int F, int S,
                    float* g_ndc, hipStream_t stream);
