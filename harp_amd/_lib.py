@@ -235,7 +235,8 @@ class Conv3x3Args(ctypes.Structure):
                 [(n, _i) for n in ("N", "H", "W", "Cin", "Cout", "precision", "epilogue", "in_channels")] + [("tap_scale", _f)] +
                 [("tile_list", _vp), ("tile_count", _vp), ("max_tiles", _i), ("in_valid_shift", _i), ("in_valid", _vp), ("in_alt", _vp),
                  ("out_valid", _vp), ("tile_origin", _vp), ("in_valid_origin", _vp), ("out_valid_origin", _vp), ("tile_pitch", _i),
-                 ("in_valid_pitch", _i), ("out_valid_pitch", _i), ("tile_side", _i), ("in_valid_cell", _i), ("out_valid_cell", _i)])
+                 ("in_valid_pitch", _i), ("out_valid_pitch", _i), ("tile_side", _i), ("in_valid_cell", _i), ("out_valid_cell", _i),
+                 ("in_amax", _vp), ("in_exp", _i)])
 
 
 SIGNATURES.update({

@@ -16,6 +16,12 @@
 //      (the dropped lo.lo is 2^-18 relative), float32 accumulate: ~16 mantissa bits per product (the reference's stack — torch 1.11 + cuDNN,
 //      requirements.txt:81 — runs these convolutions with TF32 allowed, 10 bits), 3/16 of the float32 MFMA time.  The split of the
 //      activations happens while the patch is staged; the filters are split once (harp_conv3x3_pack_filters).
+//   2  single-pass f16 on v_mfma_f32_32x32x16_f16: one product per MAC of two 11-bit significands, float32 accumulate — the precision class
+//      of the reference's TF32 convolutions, 1/3 of mode 1's MFMA work, half its LDS.  Mode 1 with the lo planes removed and the hi planes
+//      in _Float16 (the same lane maps and fragment reads).  f16's range (6.1e-5 ... 65504) is shifted per launch: the activations are
+//      staged as f16(in * 2^e) and the accumulator is multiplied by 2^-e before the epilogue — a power of two, so no rounding changes
+//      except that values stay in the normal range.  e = in_exp - floor(log2(*in_amax)) (or in_exp alone), harp_conv3x3_args; the
+//      conversion saturates at +-65504.
 #include "harp_common.h"
 #include "harp_hip.h"
 
@@ -24,6 +30,8 @@ namespace {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kCT = 16;                   // output tile: 16 x 16 pixels
 constexpr int kCK = 16;                   // input channels per staged chunk
@@ -39,6 +47,10 @@ constexpr int kInF4 = 4 * kPlane;
 constexpr int kWF4 = 9 * 4 * kCN;         // filter slab of one (64 output channels, 16 input channels) pair: [tap][plane][co][16 B] = 36 864 B
 constexpr int kLdsBytes = (kInF4 + kWF4) * 16;
 constexpr int kUnits = (kPatch * kPatch * 4 + 255) / 256;   // 16-byte staging units per thread (6; the last one is mostly idle)
+// f16 mode: the two hi planes only — patch [2][18][24][16 B] (same pitch, same fragment addresses as bf16's hi reads) and slab
+// [tap][2][co][16 B] = 18 432 B: 32 320 B of LDS in all
+constexpr int kWF4h = 9 * 2 * kCN;
+constexpr int kLdsBytesH = (2 * kPlane + kWF4h) * 16;
 // SUB8 form (bounded mode at the coarse levels, harp_conv3x3_args.tile_side == 8): the workgroup's four waves own four INDEPENDENT 8x8-pixel
 // tiles of the frame's list (x 64 channels, the same filter slab); a wave stages its own 10x10 patch and its two MFMA row blocks are the
 // upper and the lower 8x4 half of its tile.  Two waves share a set of planes [10 rows][24 pixels], 12 pixels apart: the same row pitch, hence
@@ -48,6 +60,8 @@ constexpr int kPlane8 = kPatch8 * kRow + 2;
 constexpr int kInF4_8 = 2 * 4 * kPlane8;
 constexpr int kUnits8 = (kPatch8 * kPatch8 * 4 + 63) / 64;   // 16-byte staging units per LANE (7)
 constexpr int kLdsBytes8 = (kInF4_8 + kWF4) * 16;
+constexpr int kInF4_8h = 2 * 2 * kPlane8;
+constexpr int kLdsBytes8h = (kInF4_8h + kWF4h) * 16;
 
 // experiment switches (tools/dev/build_variant.sh): CONV_PIPE 0 = the compiler's own placement of the fragment reads, 1 = reads of step s + 1
 // issued before the MFMAs of step s, pinned by sched_barrier, 2 = the same without the pins.  Measured on one box, 256 -> 256 channels at
@@ -68,6 +82,25 @@ constexpr int kLdsBytes8 = (kInF4_8 + kWF4) * 16;
 enum { EPI_RELU = 0, EPI_RELU_TAP = 1, EPI_GATE = 2, EPI_UNPOOL = 3 };
 
 __device__ __forceinline__ float sgn(float d) { return (float)((d > 0.f) - (d < 0.f)); }
+// float32 -> f16, saturating at +-65504 (never inf)
+__device__ __forceinline__ _Float16 f16_sat(float v) { return (_Float16)fminf(fmaxf(v, -65504.f), 65504.f); }
+// f16 mode: the launch's exponent shift e (harp_conv3x3_args.in_exp / in_amax; wave-uniform, one scalar load) -> 2^(sign * e)
+__device__ __forceinline__ float f16_shift(const harp_conv3x3_args& a, int sign) {
+  int e = a.in_exp;
+  if (a.in_amax) {
+    const unsigned mb = __float_as_uint(*a.in_amax) & 0x7fffffffu;
+    if (mb != 0u && mb < 0x7f800000u) e -= (int)(mb >> 23) - 127;               // floor(log2) of a normal float (-127 for a subnormal one)
+  }
+  e = sign * min(max(e, -126), 126);
+  return __uint_as_float((unsigned)(127 + e) << 23);
+}
+// fold v >= 0 into *word (max; the bits of non-negative floats are ordered as unsigned integers): a wave max, then one atomic per wave
+// unless the word already holds as much
+__device__ __forceinline__ void fold_max(float* word, float v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+  if ((threadIdx.x & 63) == 0 && v > *(volatile float*)word) atomicMax((unsigned*)word, __float_as_uint(v));
+}
 
 // ---- filter packing ---------------------------------------------------------------------------------------------------------------
 // w (Cout_src, Cin_src, 3, 3) in torch's layout -> slabs [Cout/64][Cin/16] of kWF4 float4 each, zero-padded to the multiples.
@@ -91,6 +124,9 @@ __global__ void pack_filters_kernel(const float* __restrict__ w, int Cout_src, i
   }
   if (precision == 0) {
     packed[slab * (kWF4 * 4) + ((size_t)(tap * 4 + (c >> 2)) * kCN + co_l) * 4 + (c & 3)] = v;
+  } else if (precision == 2) {
+    _Float16* p = (_Float16*)packed + slab * (kWF4h * 8);
+    p[((size_t)(tap * 2 + (c >> 3)) * kCN + co_l) * 8 + (c & 7)] = f16_sat(v);
   } else {
     const __bf16 hi = (__bf16)v;
     const __bf16 lo = (__bf16)(v - (float)hi);
@@ -105,9 +141,11 @@ template <int PREC, int EPI, bool SUB8 = false>
 __global__ __launch_bounds__(256, CONV_WAVES) void conv3x3_kernel(const harp_conv3x3_args a, const int tiles_x, const int tiles_y) {
   extern __shared__ float4 smem[];          // ONE LDS object (a second one makes hipcc drain vmcnt before every ds_read, cdna_hip_programming.md §5)
   float4* s_in = smem;
-  float4* s_w = smem + (SUB8 ? kInF4_8 : kInF4);
+  float4* s_w = smem + (PREC == 2 ? (SUB8 ? kInF4_8h : 2 * kPlane) : (SUB8 ? kInF4_8 : kInF4));
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6, half = lane >> 5, m = lane & 31;
   constexpr int kT = SUB8 ? 8 : kCT, kP = SUB8 ? kPatch8 : kPatch, kPl = SUB8 ? kPlane8 : kPlane, kU = SUB8 ? kUnits8 : kUnits;
+  constexpr int kWF = PREC == 2 ? kWF4h : kWF4;       // float4 per filter slab
+  constexpr int kNPl = PREC == 2 ? 2 : 4;             // patch planes
 
   const int ncb = a.Cout / kCN, nchunk = a.Cin / kCK;
   int id = blockIdx.x;
@@ -149,7 +187,7 @@ __global__ __launch_bounds__(256, CONV_WAVES) void conv3x3_kernel(const harp_con
   const int Cin = a.in_channels > 0 ? a.in_channels : a.Cin;     // channels per pixel in memory (the rest of a.Cin reads as zero)
   const float* __restrict__ in_n = a.in + (size_t)n * H * W * Cin;
   const float* __restrict__ alt_n = a.in_alt ? a.in_alt + row * H * W * Cin : nullptr;
-  const float4* __restrict__ wslab = (const float4*)a.filters + (size_t)cb * nchunk * kWF4;
+  const float4* __restrict__ wslab = (const float4*)a.filters + (size_t)cb * nchunk * kWF;
 
   // bounded mode: which cells (8 << shift input pixels square) under the patch hold values of THIS pass; the patch spans at most 4 x 4 cells.
   // Wave-uniform: 16 scalar loads, one bit each.
@@ -174,7 +212,7 @@ __global__ __launch_bounds__(256, CONV_WAVES) void conv3x3_kernel(const harp_con
 
   // staging units of this thread: unit u = (patch pixel u >> 2, channel quad u & 3): four consecutive lanes fetch one pixel's 64 bytes
   // (SUB8: the units of this WAVE's own patch, lane by lane; its planes start at sbase, its columns at 12 * (wv & 1))
-  const int sbase = SUB8 ? (wv >> 1) * 4 * kPlane8 + 12 * (wv & 1) : 0;
+  const int sbase = SUB8 ? (wv >> 1) * kNPl * kPlane8 + 12 * (wv & 1) : 0;
   int goff[kU], lidx[kU];
   unsigned use_alt = 0;                    // bit j: unit j lies in a cell this pass did not write -> read in_alt (or zero)
 #pragma unroll
@@ -185,7 +223,7 @@ __global__ __launch_bounds__(256, CONV_WAVES) void conv3x3_kernel(const harp_con
       const int py = pix / kP, px = pix - py * kP;
       const int gy = y0 + py - 1, gx = x0 + px - 1;
       if (PREC == 0) lidx[j] = sbase + q * kPl + py * kRow + px;                       // float4 index
-      else lidx[j] = ((sbase + (q >> 1) * kPl + py * kRow + px) << 1) | (q & 1);      // 8-byte index of the hi half; lo is 2 planes further
+      else lidx[j] = ((sbase + (q >> 1) * kPl + py * kRow + px) << 1) | (q & 1);      // 8-byte index of the hi half; lo is 2 planes further (bf16)
       if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
         goff[j] = (gy * W + gx) * Cin + 4 * q;
         const int c = ((((gy + poy) >> csh) - cy0) << 2) | (((gx + pox) >> csh) - cx0);
@@ -210,17 +248,26 @@ __global__ __launch_bounds__(256, CONV_WAVES) void conv3x3_kernel(const harp_con
       const float* __restrict__ src = ((use_alt >> j) & 1u) ? alt_n : in_n;
       rin[j] = *(const float4*)(src + (unit_ok(j, cc) ? goff[j] + cc * kCK : 0));
     }
-#define HARP_RW_LOAD(j, r) r = wslab[(size_t)cc * kWF4 + j * 256 + t];
-    HARP_RW_EACH(HARP_RW_LOAD)
+#define HARP_RW_LOAD(j, r) r = wslab[(size_t)cc * kWF + j * 256 + t];
+    if (PREC == 2) {                       // (4.5 float4 per thread: the fifth in waves 0 and 1)
+      HARP_RW_LOAD(0, rw0) HARP_RW_LOAD(1, rw1) HARP_RW_LOAD(2, rw2) HARP_RW_LOAD(3, rw3)
+      if (t < kWF4h - 4 * 256) HARP_RW_LOAD(4, rw4)
+    } else {
+      HARP_RW_EACH(HARP_RW_LOAD)
+    }
 #undef HARP_RW_LOAD
   };
+  const float in_scale = PREC == 2 ? f16_shift(a, 1) : 1.f;
   auto stage = [&](int cc) {
 #pragma unroll
     for (int j = 0; j < kU; ++j) {
       if (lidx[j] < 0) continue;
       const float4 v = unit_ok(j, cc) ? rin[j] : make_float4(0.f, 0.f, 0.f, 0.f);
-      if (PREC == 0) {
+      if constexpr (PREC == 0) {
         s_in[lidx[j]] = v;
+      } else if constexpr (PREC == 2) {
+        const f16x4 h = {f16_sat(v.x * in_scale), f16_sat(v.y * in_scale), f16_sat(v.z * in_scale), f16_sat(v.w * in_scale)};
+        ((uint2*)s_in)[lidx[j]] = __builtin_bit_cast(uint2, h);
       } else {
         bf16x4 hi = {(__bf16)v.x, (__bf16)v.y, (__bf16)v.z, (__bf16)v.w};
         bf16x4 lo = {(__bf16)(v.x - (float)hi[0]), (__bf16)(v.y - (float)hi[1]), (__bf16)(v.z - (float)hi[2]), (__bf16)(v.w - (float)hi[3])};
@@ -230,7 +277,12 @@ __global__ __launch_bounds__(256, CONV_WAVES) void conv3x3_kernel(const harp_con
       }
     }
 #define HARP_RW_STORE(j, r) s_w[j * 256 + t] = r;
-    HARP_RW_EACH(HARP_RW_STORE)
+    if (PREC == 2) {
+      HARP_RW_STORE(0, rw0) HARP_RW_STORE(1, rw1) HARP_RW_STORE(2, rw2) HARP_RW_STORE(3, rw3)
+      if (t < kWF4h - 4 * 256) HARP_RW_STORE(4, rw4)
+    } else {
+      HARP_RW_EACH(HARP_RW_STORE)
+    }
 #undef HARP_RW_STORE
   };
 
@@ -265,7 +317,7 @@ __global__ __launch_bounds__(256, CONV_WAVES) void conv3x3_kernel(const harp_con
     // fragments of step s + 1 are read from LDS before the MFMAs of step s issue, so one wave alone covers its LDS latency (the compiler's
     // own schedule read each step's fragments right in front of its MFMAs: MFMA pipe 78 % / 37 % busy, profiles/r05_a_pmc_sq_conv_*).
     constexpr int kSteps = PREC == 0 ? 18 : 9;
-    constexpr int kFrag = PREC == 0 ? 4 : 8;
+    constexpr int kFrag = PREC == 1 ? 8 : 4;
     float4 fr[2][kFrag];
     auto read_frags = [&](float4* f, int step) {
       if (PREC == 0) {
@@ -273,6 +325,10 @@ __global__ __launch_bounds__(256, CONV_WAVES) void conv3x3_kernel(const harp_con
         const int plane = 2 * g + half, toff = (tap / 3) * kRow + (tap % 3);
         f[0] = s_in[plane * kPl + pixA + toff]; f[1] = s_in[plane * kPl + pixA + toff + kBlk1];
         f[2] = s_w[(tap * 4 + plane) * kCN + m]; f[3] = s_w[(tap * 4 + plane) * kCN + 32 + m];
+      } else if (PREC == 2) {
+        const int tap = step, toff = (tap / 3) * kRow + (tap % 3);
+        f[0] = s_in[half * kPl + pixA + toff]; f[1] = s_in[half * kPl + pixA + toff + kBlk1];
+        f[2] = s_w[(tap * 2 + half) * kCN + m]; f[3] = s_w[(tap * 2 + half) * kCN + 32 + m];
       } else {
         const int tap = step, toff = (tap / 3) * kRow + (tap % 3);
         f[0] = s_in[half * kPl + pixA + toff]; f[1] = s_in[half * kPl + pixA + toff + kBlk1];                       // A hi
@@ -335,6 +391,13 @@ __global__ __launch_bounds__(256, CONV_WAVES) void conv3x3_kernel(const harp_con
 #pragma unroll
         for (int e = 0; e < 4; ++e) acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[e], b1[e], acc[1][1], 0, 0, 0);
 #endif
+      } else if (PREC == 2) {
+        const f16x8 A0 = __builtin_bit_cast(f16x8, f[0]), A1 = __builtin_bit_cast(f16x8, f[1]);
+        const f16x8 B0 = __builtin_bit_cast(f16x8, f[2]), B1 = __builtin_bit_cast(f16x8, f[3]);
+        acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A0, B0, acc[0][0], 0, 0, 0);
+        acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A0, B1, acc[0][1], 0, 0, 0);
+        acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A1, B0, acc[1][0], 0, 0, 0);
+        acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x16_f16(A1, B1, acc[1][1], 0, 0, 0);
       } else {
         const bf16x8 Ah0 = __builtin_bit_cast(bf16x8, f[0]), Ah1 = __builtin_bit_cast(bf16x8, f[1]);
         const bf16x8 Al0 = __builtin_bit_cast(bf16x8, f[2]), Al1 = __builtin_bit_cast(bf16x8, f[3]);
@@ -395,6 +458,15 @@ __global__ __launch_bounds__(256, CONV_WAVES) void conv3x3_kernel(const harp_con
   // pixel = square 2 (r >> 2) + half of the row block (4 across, 2 down), corner (dy, dx) = ((r >> 1) & 1, r & 1).
   const int Cout = a.Cout;
   float lsum = 0.f;
+  if (PREC == 2) {
+    const float out_scale = f16_shift(a, -1);
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[i][j][r] *= out_scale;
+  }
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const int co = cb * kCN + 32 * j + m;
@@ -470,7 +542,7 @@ template <int PREC, int EPI, bool SUB8>
 int launch_conv(const harp_conv3x3_args& a, hipStream_t stream) {
   static bool ready = false;               // per instantiation: raise the dynamic-LDS limit once, not per launch (and never inside a capture)
   auto kern = conv3x3_kernel<PREC, EPI, SUB8>;
-  constexpr int lds = SUB8 ? kLdsBytes8 : kLdsBytes;
+  constexpr int lds = PREC == 2 ? (SUB8 ? kLdsBytes8h : kLdsBytesH) : (SUB8 ? kLdsBytes8 : kLdsBytes);
   if (!ready) {
     if (hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) return HARP_ERR_LAUNCH;
     ready = true;
@@ -508,22 +580,24 @@ int launch_conv_prec(const harp_conv3x3_args& a, hipStream_t stream) {
 __global__ __launch_bounds__(256) void vgg_prep_kernel(const float* __restrict__ image, const int32_t* __restrict__ image_rows,
                                                        const float* __restrict__ mask, const int32_t* __restrict__ mask_rows,
                                                        const float* __restrict__ y_true, int S, float scale0, float4* __restrict__ x0,
-                                                       double* __restrict__ loss) {
+                                                       double* __restrict__ loss, float* __restrict__ amax) {
   __shared__ float red[4];
   const int n = blockIdx.y;
   const size_t ir = image_rows ? (size_t)image_rows[n] : (size_t)n, mr = mask_rows ? (size_t)mask_rows[n] : (size_t)n;
   const int p = blockIdx.x * 256 + threadIdx.x;
-  float l = 0.f;
+  float l = 0.f, mx = 0.f;
   if (p < S * S) {
     const float m = mask[mr * S * S + p];
     const float* px = image + (ir * S * S + p) * 3;
     const float r = px[0] * m, g = px[1] * m, b = px[2] * m;
     x0[(size_t)n * S * S + p] = make_float4(r, g, b, 0.f);
+    mx = fmaxf(fmaxf(fabsf(r), fabsf(g)), fabsf(b));
     if (y_true) {
       const float* t = y_true + (mr * S * S + p) * 3;
       l = fabsf(r - t[0] * m) + fabsf(g - t[1] * m) + fabsf(b - t[2] * m);
     }
   }
+  if (amax) fold_max(amax, mx);                 // f16 mode: max|x0|, from which the forward convolutions take their exponent shift
   if (y_true) {
     const float s = block_sum_256(l, red);
     if (threadIdx.x == 0 && s != 0.f) atomicAdd(loss, (double)s * (double)scale0);
@@ -608,6 +682,11 @@ __global__ __launch_bounds__(256) void vgg_grad_image_kernel(const float* __rest
   g_rgb[o + 2] += weight * m * (o2 + scale0 * sgn(d2));
 }
 
+// f16 mode: the max|x0| word starts every pass at zero (vgg_prep_kernel folds into it; a captured memset would not replay, App. A)
+__global__ void vgg_amax_clear_kernel(float* __restrict__ amax) {
+  if (threadIdx.x == 0) amax[0] = 0.f;
+}
+
 __global__ void vgg_loss_finish_kernel(double* __restrict__ loss_acc, float* __restrict__ loss_out) {
   if (loss_out) loss_out[0] = (float)loss_acc[0];
   loss_acc[0] = 0.0;
@@ -627,6 +706,7 @@ struct VggWs {
   float* g_tap[4];
   float* gbuf[2];
   double* loss;
+  float* amax;                             // f16 mode: max|x0| (in the loss accumulator's 256 bytes)
   size_t bytes;
 };
 inline VggWs vgg_ws_split(void* ws, int N, int S, int with_gradient) {
@@ -635,6 +715,7 @@ inline VggWs vgg_ws_split(void* ws, int N, int S, int with_gradient) {
   auto take = [&](size_t floats) { char* r = p; p += (floats * 4 + 255) / 256 * 256; return (float*)r; };
   const size_t NS2 = (size_t)N * S * S;
   w.loss = (double*)take(64);
+  w.amax = (float*)w.loss + 32;
   w.x0 = (float4*)take(NS2 * 4);
   for (int k = 0; k < 10; ++k) w.act[k] = take(NS2 / (kVggDiv[k] * kVggDiv[k]) * kVggCout[k]);
   for (int k = 0; k < 3; ++k) w.pool[k] = take(NS2 / (4 << (2 * k)) * kVggCout[kVggTap[k]]);
@@ -669,6 +750,7 @@ int vgg_forward(const harp_vgg16* net, const VggWs& w, int N, int S, float* cons
     a.N = N; a.H = s; a.W = s; a.Cin = (kVggCin[k] + kCK - 1) / kCK * kCK; a.Cout = kVggCout[k];
     a.in_channels = k == 0 ? 4 : 0;
     a.precision = net->precision;
+    if (a.precision == HARP_CONV_F16) a.in_amax = w.amax;     // every layer shifted by x0's exponent: its max staged in [1, 2)
     a.out = (out && out[k]) ? out[k] : w.act[k];
     a.epilogue = HARP_CONV_RELU;
     float* pooled = nullptr;
@@ -708,7 +790,7 @@ void vgg_scales(const harp_vgg16* net, int N, int S, float scale[5]) {
 }
 
 bool vgg_net_ok(const harp_vgg16* net, bool gradient) {
-  if (!net || (net->precision != 0 && net->precision != 1)) return false;
+  if (!net || net->precision < HARP_CONV_F32 || net->precision > HARP_CONV_F16) return false;
   for (int k = 0; k < 10; ++k) {
     if (!net->filters[k] || !net->bias[k]) return false;
     if (gradient && k > 0 && !net->filters_t[k]) return false;
@@ -726,7 +808,7 @@ size_t harp_conv3x3_filter_bytes(int Cout, int Cin) {
 }
 
 int harp_conv3x3_pack_filters(const float* w, int Cout, int Cin, int transpose, int precision, void* packed, hipStream_t stream) {
-  if (!w || !packed || Cout <= 0 || Cin <= 0 || (precision != 0 && precision != 1)) return HARP_ERR_ARG;
+  if (!w || !packed || Cout <= 0 || Cin <= 0 || precision < HARP_CONV_F32 || precision > HARP_CONV_F16) return HARP_ERR_ARG;
   const int co_src = Cout, ci_src = Cin;
   const int out_c = transpose ? Cin : Cout, in_c = transpose ? Cout : Cin;          // channels of the packed convolution
   const int Cout_p = (out_c + kCN - 1) / kCN * kCN, Cin_p = (in_c + kCK - 1) / kCK * kCK;
@@ -757,6 +839,7 @@ int harp_conv3x3(const harp_conv3x3_args* a, hipStream_t stream) {
       (a->out_valid_cell != 0 && a->out_valid_cell != 8 && a->out_valid_cell != 16)) return HARP_ERR_ARG;
   if (a->precision == 0) return launch_conv_prec<0>(*a, stream);
   if (a->precision == 1) return launch_conv_prec<1>(*a, stream);
+  if (a->precision == 2) return launch_conv_prec<2>(*a, stream);
   return HARP_ERR_ARG;
 }
 
@@ -778,8 +861,13 @@ int harp_vgg16_features(const harp_vgg16* net, const float* image, const float* 
   for (int k = 0; k < 4; ++k)
     if (!out[kVggTap[k]]) return HARP_ERR_ARG;
   const VggWs w = vgg_ws_split(ws, N, S, 0);
+  const bool f16 = net->precision == HARP_CONV_F16;
+  if (f16) {
+    hipLaunchKernelGGL(vgg_amax_clear_kernel, dim3(1), dim3(64), 0, stream, w.amax);
+    HARP_CHECK_LAUNCH();
+  }
   hipLaunchKernelGGL(vgg_prep_kernel, dim3((S * S + 255) / 256, N), dim3(256), 0, stream, image, rows, mask, rows, (const float*)nullptr, S, 0.f, w.x0,
-                     w.loss);
+                     w.loss, f16 ? w.amax : (float*)nullptr);
   HARP_CHECK_LAUNCH();
   return vgg_forward(net, w, N, S, out, nullptr, nullptr, nullptr, nullptr, stream);
 }
@@ -792,6 +880,16 @@ int harp_vgg16_term(const harp_vgg16* net, const harp_vgg16_term_args* t, hipStr
   const int N = t->N, S = t->S;
   float scale[5];
   vgg_scales(net, N, S, scale);
+  // f16 mode: the backward is linear in the tap seeds (+-scale[1..4]); its launches are shifted by the exponent that stages the largest
+  // seed in [1, 2) — fixed on the host: the bounded pass and the full pass shift alike, and layer weights x 2^k shift every gradient bit for bit
+  const bool f16 = net->precision == HARP_CONV_F16;
+  int e_bwd = 0;
+  const float smax = fmaxf(fmaxf(scale[1], scale[2]), fmaxf(scale[3], scale[4]));
+  if (f16 && smax > 0.f) {
+    int ex;
+    frexpf(smax, &ex);
+    e_bwd = 1 - ex;
+  }
   // every argument is checked before the first launch: vgg_prep_kernel adds into the workspace's loss accumulator, which only the LAST
   // launch of the term hands back zeroed — an error return between the two would leave it dirty for the next call
   VggBound bd = {};
@@ -818,8 +916,12 @@ int harp_vgg16_term(const harp_vgg16* net, const harp_vgg16_term_args* t, hipStr
     const int32_t* rows = t->rows ? t->rows + n0 : nullptr;
     VggBound b = bd;
     b.rows = rows;
+    if (f16) {
+      hipLaunchKernelGGL(vgg_amax_clear_kernel, dim3(1), dim3(64), 0, st, w.amax);
+      HARP_CHECK_LAUNCH();
+    }
     hipLaunchKernelGGL(vgg_prep_kernel, dim3((S * S + 255) / 256, Nh), dim3(256), 0, st, t->rgb + px * 3, (const int32_t*)nullptr, t->mask, rows, t->y_true, S,
-                       scale[0], w.x0, w.loss);
+                       scale[0], w.x0, w.loss, f16 ? w.amax : (float*)nullptr);
     HARP_CHECK_LAUNCH();
     int rc = vgg_forward(net, w, Nh, S, nullptr, t->target, t->target_by_row ? rows : nullptr, scale, bounded ? &b : nullptr, st);
     if (rc != HARP_OK) return rc;
@@ -832,6 +934,7 @@ int harp_vgg16_term(const harp_vgg16* net, const harp_vgg16_term_args* t, hipStr
       a.in = g; a.filters = net->filters_t[k];
       a.N = Nh; a.H = s; a.W = s; a.Cin = kVggCout[k]; a.Cout = kVggCin[k];
       a.precision = net->precision;
+      a.in_exp = f16 ? e_bwd : 0;
       int tap = -1;
       for (int j = 0; j < 3; ++j)
         if (kVggTap[j] == k - 1) tap = j;                 // the layer below is a tap layer followed by the pool: route through it

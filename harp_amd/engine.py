@@ -964,7 +964,8 @@ class FitEngine:
         (the filters; None removes the term).  The ten convolutions, their data gradients and everything between them run on the HIP
         kernels of csrc/conv.hip (harp_vgg16_term: 21 launches, captured into the step's hipGraph like every other launch).  precision:
         0 = float32 MFMA (a float32 fma chain, what the parity tests anchor on), 1 = three-term bf16 split with float32 accumulation
-        (~16 mantissa bits per product; the reference's own stack runs these convolutions in TF32).
+        (~16 mantissa bits per product), 2 = single-pass f16 with float32 accumulation (11-bit significands: the TF32 class the
+        reference's own stack runs these convolutions in, at a third of mode 1's matrix-core work; include/harp_hip.h).
         The target frames' features do not change during a fit; what is kept in HBM depends on `cache_bytes`:
           * ALL 13 activation maps of every resident frame (300 floats per pixel, 307 MB per 512x512 frame — 256 frames are 79 GB of the
             288 GB) -> `bounded` mode: y_pred * mask and y_true * mask are identical outside the mask's support, so the stack runs only in
@@ -975,6 +976,8 @@ class FitEngine:
         from .model.vgg_hip import Vgg16Hip, activation_shapes, active_tiles, tap_shapes
         if vgg is not None and self.S % 8:               # (refused here, before any state changes: the kernels tile the image by 8)
             raise ValueError(f"perceptual term: image size {self.S} is not a multiple of 8")
+        if int(precision) != precision or int(precision) not in (0, 1, 2):
+            raise ValueError(f"perceptual term: precision must be 0, 1 or 2, got {precision!r}")
         self._vgg_module = vgg
         self._vgg_cache_bytes = int(cache_bytes)         # the caller's budget (set_targets re-invokes with it)
         self._vgg_precision = int(precision)

@@ -108,7 +108,7 @@ class Vgg16Features(torch.nn.Module):
             feats.append(scale(h.flatten(start_dim=1), w[n]))
         return feats
 
-    hip_precision = 0                # 0: float32 MFMA (parity anchor), 1: three-term bf16 split (model/conv_hip.py)
+    hip_precision = 0                # 0: float32 MFMA (parity anchor), 1: three-term bf16 split, 2: single-pass f16 (model/conv_hip.py)
 
     def _weight_cache(self):
         """copies of the filters made for another device: dropped whenever a parameter was replaced or written in place since

@@ -605,9 +605,18 @@ int harp_schedule_next_rows(const int32_t* schedule, const int32_t* tschedule, i
  *   HARP_CONV_GATE      data gradient through the ReLU in front of this convolution's input: out = conv * [gate > 0], gate (N,H,W,Cout)
  *   HARP_CONV_UNPOOL    data gradient through max pool + ReLU: the convolution runs at the pooled size (H,W); out and gate are (N,2H,2W,Cout);
  *                       out (+=) the result routed to the first maximum of each 2x2 window of gate where that maximum is positive
- * precision 0: v_mfma_f32_32x32x2_f32 (float32 fma chain); 1: three-term bf16 split, float32 accumulate (~16 mantissa bits per product).
+ * precision HARP_CONV_F32 (0): v_mfma_f32_32x32x2_f32 (float32 fma chain); HARP_CONV_BF16X3 (1): three-term bf16 split, float32 accumulate
+ * (~16 mantissa bits per product); HARP_CONV_F16 (2): one v_mfma_f32_32x32x16_f16 product per MAC, float32 accumulate — both operands
+ * rounded to f16 (11-bit significand, round to nearest even), the precision class of TF32.  f16's range is moved per launch: the input is
+ * staged as f16(in * 2^e) and the float32 accumulator is multiplied by 2^-e before the epilogue (a power of two: no rounding changes,
+ * values are only kept in f16's normal range), with e = in_exp - floor(log2(*in_amax)) when in_amax != NULL (an upper bound of |in| on the
+ * device: in_exp = 14 stages the largest value in [2^14, 2^15)), else e = in_exp; e is clamped to [-126, 126].  Every f32 -> f16
+ * conversion (activations and filters) saturates at +-65504, never inf.  Filters of magnitude below 6.1e-5 keep an absolute error of 3e-8.
  * filters: harp_conv3x3_pack_filters output for the same precision (transpose = 1 packs the data-gradient filters of a forward (Cout,Cin,3,3)
  * weight: channels swap roles, taps are mirrored). */
+#define HARP_CONV_F32 0
+#define HARP_CONV_BF16X3 1
+#define HARP_CONV_F16 2
 #define HARP_CONV_RELU 0
 #define HARP_CONV_RELU_TAP 1
 #define HARP_CONV_GATE 2
@@ -649,6 +658,9 @@ typedef struct harp_conv3x3_args {
    * in_valid_cell: side of in_valid's cells in INPUT pixels when the producer's tiles are not 16 pixels (4 — only with tile_side 8 —, 8, 16;
    * 0 = 8 << in_valid_shift; in_valid_shift still says whether the producer sits behind a pool).  out_valid_cell: side of `out`'s tiles (8 or 16; 0 = 16). */
   int tile_side, in_valid_cell, out_valid_cell;
+  /* HARP_CONV_F16 only (ignored otherwise): the exponent shift e of the staged input, see above.  NULL / 0 = unscaled */
+  const float* in_amax;
+  int in_exp;
 } harp_conv3x3_args;
 size_t harp_conv3x3_filter_bytes(int Cout, int Cin);
 int harp_conv3x3_pack_filters(const float* w, int Cout, int Cin, int transpose, int precision, void* packed, hipStream_t stream);
@@ -674,7 +686,10 @@ int harp_conv3x3(const harp_conv3x3_args* a, hipStream_t stream);
  *   convolution k (k = 1..9: out[0], out[10], out[2], out[11], out[4], out[5], out[12], out[7], out[8] of harp_vgg16_features).  Same
  *   loss and gradient as the full pass, bit for bit in the tiles it computes.
  * harp_vgg16_term: forward over rgb * mask[rows[n]] with the L1 against target[k] fused into the tap layers, backward to the image:
- *   *loss = the term (unweighted);  g_rgb (N,S,S,3) = covered < 0 ? 0 : g_rgb + weight * d loss / d rgb   (covered NULL: everywhere). */
+ *   *loss = the term (unweighted);  g_rgb (N,S,S,3) = covered < 0 ? 0 : g_rgb + weight * d loss / d rgb   (covered NULL: everywhere).
+ * precision HARP_CONV_F16: the two entry points choose the exponent shifts themselves — the forward convolutions from max|image * mask| of
+ *   the pass (folded on the device: its largest value staged in [1, 2)), the backward ones from the largest tap seed layer_w[k] / n (on the
+ *   host: staged in [1, 2)).  Layer weights scaled by 2^k scale the loss and gradient by exactly 2^k. */
 typedef struct harp_vgg16 {
   const void* filters[10];
   const void* filters_t[10];

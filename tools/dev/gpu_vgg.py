@@ -1,5 +1,5 @@
 """Cost of the optional perceptual term at the bench configuration (B=32, 512^2): ms/step of the full stage with the term off /
-on (float32 MFMA, cached target features) / on (float32, uncached) / on (bf16 split, cached / uncached).  Random filters (timing only)."""
+on (float32 MFMA, cached target features) / on (float32, uncached) / on (bf16 split, cached / uncached) / on (single-pass f16, cached / uncached).  Random filters (timing only)."""
 import sys, time
 import torch
 sys.path.insert(0, ".")
@@ -24,7 +24,8 @@ eng.set_schedule(torch.arange(T).reshape(-1, eng.B))
 print("term off            %8.2f ms/step" % time_steps(eng, 20), flush=True)
 vgg = Vgg16Features(layers_weights=[1, 1 / 16, 1 / 8, 1 / 4, 1], weights="random")
 for name, kw in (("f32 bounded", dict()), ("f32 full, taps cached", dict(bounded=False)), ("f32 uncached", dict(cache_bytes=0)),
-                 ("bf16x3 bounded", dict(precision=1)), ("bf16x3 full, taps cached", dict(precision=1, bounded=False))):
+                 ("bf16x3 bounded", dict(precision=1)), ("bf16x3 full, taps cached", dict(precision=1, bounded=False)),
+                 ("f16 bounded", dict(precision=2)), ("f16 full, taps cached", dict(precision=2, bounded=False))):
     t0 = time.perf_counter()
     eng.set_perceptual(vgg, **kw)
     torch.cuda.synchronize()
