@@ -511,10 +511,19 @@ class FitEngine:
         return bool(self.fold_step and self.fused_front and self.fused_chain and self.fused_back and self.overlap and self.early_terms
                     and self.schedule is not None and self._lane.get("owns_shared"))
 
-    def forward_backward(self, coarse=True, app=True, B=None, shared_terms=True, tick=False, sched=False):
+    def forward_backward(self, coarse=True, app=True, B=None, shared_terms=True, tick=False, sched=False, *, _defer_maps_join=False):
         """Enqueue forward + losses + backward for the first B (default: the lane's size) frames of the active lane; gradients land
         in self.g_buf, loss terms in loss_vec[:9] (unweighted, order LOSS_NAMES).  shared_terms=False skips everything that does not
-        depend on the frames (gradient-arena zeroing, offset draw, normal-map normalisation, displacement / texture regularisers)."""
+        depend on the frames (gradient-arena zeroing, offset draw, normal-map normalisation, displacement / texture regularisers).
+        On return every gradient is final on the current stream: the branch of the map gradients (texel reduce -> finish on the second
+        stream) is joined before this returns.  _defer_maps_join=True (step() only) leaves that branch open for adam() to join behind
+        the maps' own update (`split_adam`)."""
+        self._join_maps()                                # (no-op unless a deferred branch is still open: it writes the record buffers / _tacc this step reuses)
+        self._fb(coarse, app, B, shared_terms, tick, sched)
+        if not _defer_maps_join:
+            self._join_maps()
+
+    def _fb(self, coarse, app, B, shared_terms, tick, sched):
         lane = self._lane
         if getattr(self, "_shadow_state_stale", False) and not torch.cuda.is_current_stream_capturing():
             self._reset_shadow_state()
@@ -1278,7 +1287,7 @@ class FitEngine:
             self.set_stage(coarse, app)
             self._stage = key
         fold = scheduled and self._can_fold()
-        fb0 = lambda: self.forward_backward(coarse, app, B=n, tick=True, sched=fold)
+        fb0 = lambda: self.forward_backward(coarse, app, B=n, tick=True, sched=fold, _defer_maps_join=True)      # adam() joins the maps' branch
         fb = (lambda: (self._schedule_next(), fb0())) if (scheduled and not fold) else fb0
         dist_on = self._dist_on()
         graph_ok = (not dist_on) or self.comm is not None or self.graph_collectives
@@ -1305,6 +1314,7 @@ class FitEngine:
             with torch.cuda.stream(side):
                 fb()
                 self.allreduce()                         # completes (and clears) the early all-reduce the warm-up pass started
+                self._join_maps()                        # ... and the maps' branch: the capture must not start with a wait on it
             torch.cuda.current_stream().wait_stream(side)
             self.hyper.copy_(hyper)                      # the warm-up pass must not advance the optimiser's step count ...
             self.draw_counter.copy_(draws)               # ... nor the texture-offset generator (same draws as an eager run with this seed)

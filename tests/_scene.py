@@ -284,3 +284,37 @@ def mask_ambiguous_pixels(case):
     case["targets"]["y_sil_col"] = y_col
     eng.set_targets(case["targets"]["y_true"], case["targets"]["y_sil"], y_col)
     return amb.sum().item() / max(cov, 1)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Per-segment comparison of two gradient arenas.  Texture and normal map hold 99.99 % of the arena's elements and dominate its norm:
+# a bound on the whole arena does not see a wrong cam / light_positions / amb_ratio block.
+# ----------------------------------------------------------------------------------------------------------------------
+# Spread of each segment over undelayed steps from the same state (lr = 0, one-row schedule), MEASURED on MI355X: the worst rel-L2 of a
+# step's gradients against the first step's, over 20 graph replays and 8 eager steps of the hand (S = 128, B = 3) and arm cases of
+# tests/test_gpu_stream_order.py, 10 replays each of five switch settings and of the perceptual term, and the 120 replays of
+# test_graph_replays_see_the_same_state (hand, S = 256, B = 4), which stayed below these figures.  The spread is the order of the float
+# atomics; a segment that measured 0 (wrist_pose: one add per element onto the cleared arena, zero for the hand) must come out bit for bit.
+REPLAY_SPREAD = {"pose": 1.95e-7, "cam": 2.02e-8, "verts_disps": 5.92e-8, "shape": 3.80e-7, "rot": 5.59e-7, "wrist_pose": 0.0,
+                 "light_positions": 4.96e-6, "amb_ratio": 2.40e-6, "texture": 1.23e-8, "normal_map": 6.34e-9, "trans": 5.71e-8}
+
+
+def block_bound(k):
+    """per-segment bound: 10 x the measured replay spread, never looser than 1e-4 rel-L2 (the per-block bound of the schedule tests)"""
+    return min(1e-4, 10.0 * REPLAY_SPREAD[k])
+
+
+def block_errors(eng, g, ref):
+    """{segment: rel-L2 of g against ref} over every key of eng.grads (a one-element segment: |d| / |ref|)"""
+    out = {}
+    for k in eng.grads:
+        a, b = eng.arena.view(g, k).double(), eng.arena.view(ref, k).double()
+        out[k] = ((a - b).norm() / (b.norm() + 1e-30)).item() if b.norm() > 0 else float((a - b).norm() > 0) * 1e30
+    return out
+
+
+def assert_blocks(eng, g, ref, tag=""):
+    errs = block_errors(eng, g, ref)
+    bad = {k: (e, block_bound(k)) for k, e in errs.items() if e > block_bound(k)}
+    assert not bad, (tag, bad, errs)
+    return errs

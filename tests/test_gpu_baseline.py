@@ -592,7 +592,8 @@ def test_ten_free_running_adam_steps_against_the_oracle(sigma, monkeypatch):
     """SURVEY.md §8(d) "parameters after 10 Adam steps rel 1e-3" (the loop optimize_sequence.py:567-573), FREE-RUNNING: the engine (eager
     step, then the replayed hipGraph) and torch.optim.Adam on the fp64 oracle each walk their own 10 steps from the same start, all terms on.
       sigma = 1e-5 — a silhouette rim ~1 px wide at this size instead of the production 0.1 px: the comparison is well-posed, and the
-        parameters agree to rel-L2 1e-3 after EVERY one of the 10 steps (the 9 light-position values: 3e-3, see below);
+        parameters agree to rel-L2 1e-3 after EVERY one of the 10 steps (the 9 light-position values: 3e-3, see below), and a second
+        engine run from the same start stays within the same 3e-3 of the first one's light positions;
       sigma = 1e-7 (optimize_sequence.py:426, production) — the silhouette gradient lives on a 0.2-px rim, the two trajectories separate
         geometrically in parameter space (test_ten_adam_steps_kernel_vs_torch_adam) — but they descend the same objective: the weighted total
         loss of the two runs stays within 1e-2 relative at every step (measured: <= 1e-4 for the first steps, 5e-3 at step 6 — the rim
@@ -613,10 +614,13 @@ def test_ten_free_running_adam_steps_against_the_oracle(sigma, monkeypatch):
     opt_c = torch.optim.Adam([{"params": [P["pose"], P["cam"]], "lr": 1e-3}, {"params": [P["verts_disps"], P["shape"]], "lr": 1e-3}])
     opt_a = torch.optim.Adam([P[k] for k in keys_a], lr=1e-2)
     worst_p, worst_l, trace = 0.0, 0.0, []
+    start = [t.clone() for t in (eng.p_buf, eng.m_buf, eng.v_buf, eng.hyper, eng.draw_counter)]
+    lp_run, lp_oracle = [], []
     for it in range(10):
         fid = torch.tensor([it % 3, (it + 1) % 3])
         eng.step(fid, True, True, use_graph=(it > 0))
         torch.cuda.synchronize()
+        lp_run.append(eng.params["light_positions"].cpu().double().clone())
         lv = eng.losses()                                        # the terms at the parameters this step started from
         opt_c.zero_grad(); opt_a.zero_grad()
         _, loss, total, _, _ = oracle_step(case, fid, P=P, model=model, targets=targets)      # same batches, same texture-regulariser offsets
@@ -636,9 +640,27 @@ def test_ten_free_running_adam_steps_against_the_oracle(sigma, monkeypatch):
                 worst_p = max(worst_p, r if k != "verts_disps" else 0.0)
                 # (verts_disps: |values| ~ 6e-4 but every Adam step moves an element by ~lr = 1e-3, so its norm IS the updates.
                 #  light_positions: 9 values that move by lr = 1e-2 per step on a gradient that reaches them through the shadow test of a few
-                #  hundred pixels — the order of the GPU's float atomics decides the last bits of it, and Adam turns a small component's noise
-                #  into a full step: 2e-4 ... 5e-4 in most runs, 1.2e-3 at step 7 in one run of four on the same box; 3e-3 = 0.3 % of the value,
-                #  2 % of the distance it has moved by then)
+                #  hundred pixels, and Adam turns a small component's difference into a full step.  The gap to the oracle has two parts
+                #  (the second run below measures them): a reproducible 1.4e-4 ... 1.5e-4 after 10 steps — float32 against float64, two engine
+                #  runs from the same start then stay within 1.1e-5 of each other (4 pairs of 5 on MI355X) — and, in some runs, a different
+                #  order of the GPU's float atomics that Adam turns into a whole step from step 7 on: 4.0e-4 between two engine runs and
+                #  4.0e-4 to the oracle in the 5th pair; 1.2e-3 to the oracle at step 7 in one run of four earlier.  3e-3 = 0.3 % of the
+                #  value, 2 % of the distance it has moved by then)
                 bound = {"verts_disps": 1e-2, "light_positions": 3e-3}.get(k, 1e-3)
                 assert r < bound, (sigma, it, k, r)
+                if k == "light_positions":
+                    lp_oracle.append(r)
     print(f"[10 free-running steps, sigma {sigma:g}] worst parameter rel-L2 {worst_p:.1e}, total-loss rel per step {trace}")
+    if sigma > 1e-6:
+        # the same 10 engine steps again from the same start (no oracle): how far apart two runs' light positions are.  The order of the
+        # float atomics is all that differs between them; the light_positions note above says what they measured
+        for t, t0 in zip((eng.p_buf, eng.m_buf, eng.v_buf, eng.hyper, eng.draw_counter), start):
+            t.copy_(t0)
+        spread = []
+        for it in range(10):
+            eng.step(torch.tensor([it % 3, (it + 1) % 3]), True, True, use_graph=(it > 0))
+            torch.cuda.synchronize()
+            spread.append(rel(eng.params["light_positions"].cpu().double(), lp_run[it]))
+        print("[10 free-running steps] light_positions rel-L2 per step: run vs run", [float("%.1e" % r) for r in spread],
+              "engine vs oracle", [float("%.1e" % r) for r in lp_oracle])
+        assert max(spread) < 3e-3, spread

@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests._scene import check_removed, make_scene, mask_scene_targets, oracle_params, rel, scene_f64
+from tests._scene import block_bound, block_errors, check_removed, make_scene, mask_scene_targets, oracle_params, rel, scene_f64
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -1115,13 +1115,19 @@ def test_graph_replays_see_the_same_state(keep):
     assert len(eng._graphs) == 1
     g0, l0 = eng.g_buf.double().clone(), eng.loss_vec.double().clone()
     worst_g = worst_l = 0.0
+    worst_k = {k: 0.0 for k in eng.grads}
     for i in range(120):
         eng.step(None, True, True)
         if i % 4 == 3:
             torch.cuda.synchronize()
             worst_g = max(worst_g, rel(eng.g_buf.double(), g0))
             worst_l = max(worst_l, ((eng.loss_vec.double() - l0).abs() / l0.abs().clamp_min(1e-12)).max().item())
+            for k, e in block_errors(eng, eng.g_buf, g0).items():
+                worst_k[k] = max(worst_k[k], e)
+    print(f"[graph replays, keep_image={keep}] worst per-segment rel-L2", {k: float("%.1e" % e) for k, e in worst_k.items()})
     assert worst_g < 1e-5 and worst_l < 1e-4, (worst_g, worst_l)
+    # (the whole arena's norm is the maps': a wrong cam / light_positions / amb_ratio block would pass the bound above)
+    assert all(e <= block_bound(k) for k, e in worst_k.items()), {k: (e, block_bound(k)) for k, e in worst_k.items()}
 
 
 def test_arm_engine_loss_only_mode():
@@ -1291,7 +1297,7 @@ def test_schedule_switches_give_the_default_schedules_result(switches):
             g, l = run(graph)
             assert rel(g, ref[graph][0]) < tol_g, (switches, graph, rel(g, ref[graph][0]))
             assert ((l - ref[graph][1]).abs() <= 1e-5 * ref[graph][1].abs() + 1e-9).all(), (switches, graph, l, ref[graph][1])
-            for k in ("pose", "cam", "verts_disps", "shape", "light_positions", "texture", "normal_map"):
+            for k in eng.grads:
                 a, b = eng.arena.view(g, k), eng.arena.view(ref[graph][0], k)
                 assert rel(a, b) < tol_k, (switches, graph, k, rel(a, b))
     finally:
