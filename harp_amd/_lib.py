@@ -263,3 +263,10 @@ SIGNATURES.update({
     "harp_vgg16_features": (_i, [ctypes.POINTER(Vgg16), _vp, _vp, _vp, _i, _i, _vp, ctypes.POINTER(_vp), _vp]),
     "harp_vgg16_term": (_i, [ctypes.POINTER(Vgg16), ctypes.POINTER(Vgg16TermArgs), _vp]),
 })
+
+# post-fit evaluation metrics (csrc/metrics.hip)
+_ll = ctypes.c_longlong
+SIGNATURES.update({
+    "harp_image_metrics_ws_bytes": (_sz, [_i, _i, _i]),
+    "harp_image_metrics": (_i, [_vp, _vp, _vp, _vp, _ll, _ll, _ll, _ll, _i, _i, _i, _i, _f, ctypes.POINTER(_f), _i, _f, _f, _f, _vp, _vp, _vp]),
+})

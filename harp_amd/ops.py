@@ -400,3 +400,74 @@ def rasterize_fragments(ndc, faces, S, blur_radius=0.0, faces_per_pixel=1, packe
         off = (torch.arange(ndc.shape[0], device=ndc.device) * faces.shape[0]).view(-1, 1, 1, 1)
         p2f = torch.where(p2f >= 0, p2f + off, p2f)
     return p2f, zbuf, bary, dists
+
+
+# ------------------------------------------------------------------------------------------------------
+# post-fit evaluation metrics (csrc/metrics.hip): MS-SSIM, silhouette IoU, L1
+# ------------------------------------------------------------------------------------------------------
+MS_SSIM_WEIGHTS = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)   # pytorch_msssim 0.2.1 ms_ssim default
+MS_SSIM_MIN_SIDE = (11 - 1) * 2 ** 4                          # its assertion: min(H, W) > 160
+
+
+def check_forward_only(*ts):
+    """the metrics have no backward: refuse to be part of an autograd graph rather than silently detach (nobody should take MS-SSIM
+    for a loss here)"""
+    if torch.is_grad_enabled() and any(t.requires_grad for t in ts):
+        raise RuntimeError("image_metrics is forward-only (no MS-SSIM gradient): evaluate under torch.no_grad() or detach the inputs")
+
+
+def image_metrics(ref, pred, ref_mask=None, pred_mask=None, channels_last=True, data_range=1.0, weights=None, win_sigma=1.5, K=(0.01, 0.03)):
+    """Per-image evaluation metrics of utils/eval_util.py (image_eval :10-26) in one launch chain, forward only.
+
+    ref / pred: float32 HIP tensors (N,H,W,C) (channels_last, the reference's render layout) or (N,C,H,W), C <= 3, read in place.
+    ref_mask / pred_mask: optional (N,H,W[,1]) silhouettes (IoU of the >= 0.5 masks, :41-49).  MS-SSIM: pytorch_msssim 0.2.1
+    ms_ssim(..., size_average=False) with an 11-tap window of `win_sigma` and len(weights) levels.  Returns a dict of per-image tensors:
+    iou, l1 (mean |ref - pred|), l1_sum, inter, union, ms_ssim (N,), ssim and cs (N, levels, C) (means over each level's valid map)."""
+    if not (torch.is_tensor(ref) and torch.is_tensor(pred)):
+        raise TypeError("image_metrics takes tensors")
+    check_forward_only(ref, pred)
+    if not (ref.is_cuda and pred.is_cuda):
+        raise RuntimeError("harp_amd ops need HIP device tensors (no CPU path)")
+    if ref.dtype != torch.float32 or pred.dtype != torch.float32:
+        raise TypeError(f"image_metrics takes float32 images, got {ref.dtype} / {pred.dtype}")
+    if ref.dim() != 4 or ref.shape != pred.shape:
+        raise ValueError(f"image_metrics takes two images of the same 4-D shape, got {tuple(ref.shape)} and {tuple(pred.shape)}")
+    if ref.device != pred.device:
+        raise ValueError("ref and pred live on different devices")
+    if channels_last:
+        N, H, W, C = ref.shape
+    else:
+        N, C, H, W = ref.shape
+    weights = list(MS_SSIM_WEIGHTS if weights is None else [float(w) for w in weights])
+    if not 1 <= len(weights) <= 5:
+        raise ValueError(f"1 to 5 level weights, got {len(weights)}")
+    if not 1 <= C <= 3:
+        raise ValueError(f"1 to 3 channels, got {C}")
+    if min(H, W) <= MS_SSIM_MIN_SIDE:
+        raise ValueError(f"MS-SSIM needs both image sides > {MS_SSIM_MIN_SIDE} (pytorch_msssim's assertion), got {H} x {W}")
+    if N > 65535:
+        raise ValueError("at most 65535 images per call")
+    if ref.stride() != pred.stride() or min(ref.stride()) < 0:
+        ref, pred = ref.contiguous(), pred.contiguous()
+    s = ref.stride()
+    sn, sy, sx, sc = (s[0], s[1], s[2], s[3]) if channels_last else (s[0], s[2], s[3], s[1])
+    masks = (ref_mask, pred_mask)
+    if (ref_mask is None) != (pred_mask is None):
+        raise ValueError("pass both masks or neither")
+    if ref_mask is not None:
+        masks = tuple(m.detach().reshape(N, H, W).to(device=ref.device, dtype=torch.float32).contiguous() for m in masks)
+    dev = ref.device
+    L = _lib.lib()
+    ws = torch.empty(L.harp_image_metrics_ws_bytes(N, H, W), dtype=torch.uint8, device=dev)
+    nl = len(weights)
+    out = torch.empty(N, 4 + 2 * nl * C, dtype=torch.float32, device=dev)
+    w = (ctypes.c_float * nl)(*weights)
+    with torch.cuda.device(dev):
+        rc = L.harp_image_metrics(ref.data_ptr(), pred.data_ptr(), _lib.ptr(masks[0]), _lib.ptr(masks[1]), sn, sc, sy, sx, N, C, H, W,
+                                  float(data_range), w, nl, float(K[0]), float(K[1]), float(win_sigma), _lib.ptr(ws), _lib.ptr(out),
+                                  _lib.stream())
+    _lib.check(rc, "harp_image_metrics")
+    inter, union = out[:, 0], out[:, 1]
+    return {"iou": inter / union if ref_mask is not None else None, "l1": out[:, 2] / float(H * W * C), "l1_sum": out[:, 2],
+            "inter": inter, "union": union, "ms_ssim": out[:, 3],
+            "ssim": out[:, 4:4 + nl * C].reshape(N, nl, C), "cs": out[:, 4 + nl * C:].reshape(N, nl, C)}

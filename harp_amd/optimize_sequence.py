@@ -86,8 +86,10 @@ def stage_flags(epoch_id, training_stage):
 
 def optimize_hand_sequence(configs, input_params, images_dataset, val_params, val_images_dataset, hand_layer,
                            VERTS_UVS=None, FACES_UVS=None, VERTS_COLOR=None, device="cuda", uv_mask=None, batch_size=18, log_fn=None,
-                           seed=0, vgg=None, rank=None, world_size=None, shards=None, plateau_patience=40, plateau_threshold=1e-4, device_schedule=True):
-    """Fit the sequence (optimize_sequence.py:313-596).  Returns the parameter dict in the reference's checkpoint layout.
+                           seed=0, vgg=None, rank=None, world_size=None, shards=None, plateau_patience=40, plateau_threshold=1e-4, device_schedule=True,
+                           evaluate=False):
+    """Fit the sequence (optimize_sequence.py:313-596).  Returns the parameter dict in the reference's checkpoint layout; evaluate=True
+    then runs the post-fit evaluation `evaluate_sequence` (:595-816) on rank 0 (off by default).
     `images_dataset[i]` -> (fid, y_true (S,S,3), y_sil (S,S,1), y_sil_eroded (S,S,1)) like utils/data_util.ImagesDataset.
 
     Data-parallel (the reference is single-device): launched under `torch.distributed.run` (or with rank / world_size given)
@@ -216,7 +218,119 @@ def optimize_hand_sequence(configs, input_params, images_dataset, val_params, va
         if comm is not None:
             torch.cuda.synchronize(eng.dev)
             comm.destroy()                                           # drops the step graphs that captured it
+    if evaluate and rank == 0:
+        evaluate_sequence(configs, params, images_dataset, hand_layer, device=device, uv_mask=uv_mask)
     return params
+
+
+EVAL_CHUNK = 64                  # optimize_sequence.py:716: image_eval runs on every 64 frames; the final stats are means of the chunk means
+
+
+def evaluate_sequence(configs, params, images_dataset, hand_layer, device="cuda", batch_size=32, uv_mask=None):
+    """The post-fit evaluation of optimize_sequence.py:595-816: re-render every dataset item in order with the fitted `params` through the
+    reference-API mirror (silhouette: get_renderers(silh_sigma=1e-7, silh_faces_per_pixel=50)[1]; image: render_image_with_RT through
+    get_shadow_renderers with self_shadow, else render_image with the phong renderer), `batch_size` frames per render call; per-frame
+    Silhouette IoU, L1 and MS-SSIM from ops.image_metrics (csrc/metrics.hip); the reference's averaging — the mean over 64-frame chunks
+    (the last partial chunk included) of each chunk's mean; with configs["eval_mesh"] the Procrustes-aligned vertex error against
+    `<gt_mesh_dir>/<500 + fid + 1>_manov.xyz` (:760-774, also written to eval_vert_mm[_test].txt).  Writes eval_results[_test].txt
+    (" %s: %.5f" lines, :808-816) and uv_out/texture.png, uv_out/normal_map.png (:627-654) under configs["base_output_dir"] and returns
+    the stats dict.  Left out: LPIPS (no pretrained weights), and MS_SSIM with a warning when the image side is <= 160 px (the reference
+    would fail pytorch_msssim's assertion there); the rendered_after_opt panels and the turntables."""
+    import os
+    import warnings
+    import torch.nn.functional as F
+    from PIL import Image
+    from . import ops
+    from .renderer import renderer_helper
+    from .structures import Meshes
+    from .utils.eval_util import align_w_scale, load_gt_vert, sil_iou
+    from .utils.visualize import prepare_materials, prepare_mesh, render_image, render_image_with_RT
+    S, focal = int(configs["img_size"]), configs["focal_length"]
+    base = configs["base_output_dir"]
+    test_name = "_test" if configs["known_appearance"] else ""
+    use_arm = bool(configs["use_arm"])
+    P = {k: (v.detach().to(device) if torch.is_tensor(v) else v) for k, v in params.items()}
+    # ---- texture and normal map (:627-654)
+    uv_out_dir = os.path.join(base, "uv_out")
+    os.makedirs(uv_out_dir, exist_ok=True)
+    uvm = params.get("uv_mask") if uv_mask is None else uv_mask
+    tex = P["texture"].cpu().numpy()[0]
+    uvm = np.ones(tex.shape[:2]) if uvm is None else np.asarray(torch.as_tensor(uvm).detach().cpu(), dtype=np.float64)
+    Image.fromarray(np.uint8(tex.clip(0, 1) * np.expand_dims(uvm, 2) * 255)).save(os.path.join(uv_out_dir, "texture.png"))
+    if "normal_map" in P:
+        nm = F.normalize(P["normal_map"], dim=-1).cpu().numpy()
+        nm = (nm / 2.0 + 0.5) * np.expand_dims(uvm, 2)
+        Image.fromarray(np.uint8(nm[0].clip(0, 1) * 255)).save(os.path.join(uv_out_dir, "normal_map.png"))
+    # ---- renders and per-frame metrics
+    sub = get_mesh_subdivider(hand_layer, use_arm=use_arm, device=device)
+    with_ms = S > ops.MS_SSIM_MIN_SIDE
+    if not with_ms:
+        warnings.warn(f"MS_SSIM left out of the evaluation: {S} px images (pytorch_msssim needs a side > {ops.MS_SSIM_MIN_SIDE})")
+    iou, l1, ms, vert_err = [], [], [], []
+    n = len(images_dataset)
+    with torch.no_grad():
+        for lo in range(0, n, batch_size):
+            items = [images_dataset[i] for i in range(lo, min(n, lo + batch_size))]
+            fid = torch.as_tensor([int(it[0]) for it in items], dtype=torch.long)
+            y_true = torch.stack([torch.as_tensor(it[1]) for it in items]).to(device=device, dtype=torch.float32)
+            y_sil_true = torch.stack([torch.as_tensor(it[2]) for it in items]).reshape(len(items), S, S).to(device=device, dtype=torch.float32)
+            B = fid.shape[0]
+            fd = fid.to(device)
+            if configs["share_light_position"]:
+                light_positions = P["light_positions"][0].repeat(B, 1)
+            else:
+                light_positions = P["light_positions"][fd]
+            phong_renderer, silhouette_renderer, _ = renderer_helper.get_renderers(
+                image_size=S, light_posi=light_positions, silh_sigma=1e-7, silh_gamma=1e-1, silh_faces_per_pixel=50, device=device)
+            _, hand_verts, faces, textures = prepare_mesh(P, fid, hand_layer, False, sub, False, configs, device=device, use_arm=use_arm)
+            materials_properties = prepare_materials(P, B, device=device)
+            meshes = Meshes(hand_verts, faces, textures)
+            cam = P["cam"][fd]
+            y_sil_pred = render_image(meshes, cam, B, silhouette_renderer, S, focal, silhouette=True, device=device)
+            if configs["self_shadow"]:
+                light_R, light_T, cam_R, cam_T = renderer_helper.process_info_for_shadow(cam, light_positions, hand_verts.mean(1), image_size=S,
+                                                                                         focal_length=focal, device=device)
+                shadow_renderer = renderer_helper.get_shadow_renderers(image_size=S, light_posi=light_positions, silh_sigma=1e-7, silh_gamma=1e-1,
+                                                                       silh_faces_per_pixel=50, amb_ratio=torch.sigmoid(P["amb_ratio"]), device=device)
+                y_pred = render_image_with_RT(meshes, light_T, light_R, cam_T, cam_R, B, shadow_renderer, S, focal, silhouette=False,
+                                              materials_properties=materials_properties, device=device)
+            else:
+                y_pred = render_image(meshes, cam, B, phong_renderer, S, focal, silhouette=False, materials_properties=materials_properties,
+                                      device=device)
+            y_pred = y_pred.float()
+            if with_ms:
+                m = ops.image_metrics(y_true, y_pred, y_sil_true, y_sil_pred)
+                iou.append(m["iou"].cpu())
+                l1.append(m["l1_sum"].double().cpu())
+                ms.append(m["ms_ssim"].double().cpu())
+            else:                                     # no MS-SSIM at this size, so no metrics kernel: sil_iou / l1_diff per frame
+                iou.append(torch.stack([torch.as_tensor(sil_iou(y_sil_true[b:b + 1], y_sil_pred[b:b + 1])) for b in range(B)]).cpu())
+                l1.append((y_true - y_pred).abs().double().sum((1, 2, 3)).cpu())
+            if configs["eval_mesh"]:                 # :760-774
+                for b in range(B):
+                    gt = load_gt_vert(fid[b:b + 1], configs["gt_mesh_dir"], dataset="synthetic", start_from_one=True, idx_offset=500)
+                    pred = hand_verts[b, hand_layer.right_mano_idx] if use_arm else hand_verts[b, :778]
+                    err = gt - align_w_scale(gt, pred.detach().cpu().numpy())
+                    vert_err.append(float(np.linalg.norm(err, axis=1).mean()) * 1000.0)
+    # ---- the reference's averaging: image_eval per 64-frame chunk (:713-731), then np.mean over the chunks (:733-738)
+    iou, l1 = torch.cat(iou).double(), torch.cat(l1)
+    chunks = [slice(c, min(n, c + EVAL_CHUNK)) for c in range(0, n, EVAL_CHUNK)]
+    per_pixel = float(S * S * 3)
+    stats = {"Silhouette IoU": float(np.mean([iou[c].mean().item() for c in chunks])),
+             "L1": float(np.mean([l1[c].sum().item() / ((c.stop - c.start) * per_pixel) for c in chunks]))}
+    if with_ms:
+        ms = torch.cat(ms)
+        stats["MS_SSIM"] = float(np.mean([ms[c].mean().item() for c in chunks]))
+    if vert_err:
+        stats["Procrustes-aligned vertex error (mm)"] = float(np.mean(vert_err))
+        np.savetxt(os.path.join(base, "eval_vert_mm" + test_name + ".txt"), vert_err)
+    print("  -- Evaluation --")
+    for k, v in stats.items():
+        print(" %s: %.5f" % (k, v))
+    with open(os.path.join(base, "eval_results" + test_name + ".txt"), "w") as f_out:
+        for k, v in stats.items():
+            f_out.write(" %s: %.5f\n" % (k, v))
+    return stats
 
 
 def main(argv=None):
@@ -235,6 +349,7 @@ def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", required=True, help="yaml with the keys of utils/config_utils.get_config")
     ap.add_argument("--batch-size", type=int, default=18)
+    ap.add_argument("--eval", action="store_true", help="after the fit, the evaluation of optimize_sequence.py:595-816 (evaluate_sequence)")
     args = ap.parse_args(argv)
     with open(args.config) as f:
         configs = get_config(write_yaml=False, **yaml.safe_load(f))
@@ -256,7 +371,7 @@ def main(argv=None):
         configs["metro_output_dir"], configs["image_dir"], train_list=configs["train_list"], val_list=configs["val_list"],
         average_cam_sequence=configs["average_cam_sequence"], use_smooth_seq=configs["use_smooth_seq"], model_type=configs["model_type"])
     params = optimize_hand_sequence(configs, mano_params, images_dataset, val_mano_params, val_images_dataset, hand_layer, VERTS_UVS, FACES_UVS,
-                                    VERTS_COLOR, device=device, batch_size=args.batch_size)
+                                    VERTS_COLOR, device=device, batch_size=args.batch_size, evaluate=args.eval)
     if world > 1:
         tdist.barrier()
         tdist.destroy_process_group()

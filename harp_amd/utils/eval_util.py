@@ -1,8 +1,13 @@
-"""Evaluation metrics of the reference's utils/eval_util.py that do not need absent third-party packages:
-silhouette IoU, masked-free L1, white-background fill, Procrustes alignment.  LPIPS / MS-SSIM need `lpips` / `pytorch_msssim`
-(not installed, no network): `image_eval` reports them as None.  All metrics run on whatever device the tensors live on."""
+"""Evaluation metrics of the reference's utils/eval_util.py: silhouette IoU, masked-free L1, white-background
+fill, Procrustes alignment, MS-SSIM (harp_amd.pytorch_msssim: the HIP kernels of csrc/metrics.hip, so it needs a HIP device) and the
+ground-truth vertex loader.  LPIPS needs pretrained AlexNet + LPIPS head weights that cannot be shipped: `image_eval` reports it as None.
+IoU and L1 run on whatever device the tensors live on."""
+import warnings
+
 import numpy as np
 import torch
+
+from .. import ops
 
 
 def fill_bg(img, mask):
@@ -24,12 +29,40 @@ def sil_iou(ref_masks, pred_masks):
     return torch.mean(inter / union).detach().cpu().numpy()
 
 
-def image_eval(images_for_eval):
-    """utils/eval_util.py:10-26: dict of lists of (n,H,W[,3]) tensors -> {"Silhouette IoU", "L1", "LPIPS", "MS_SSIM"}"""
+def ms_ssim_diff(ref_images, pred_images):
+    """utils/eval_util.py:56-60: MS_SSIM(data_range=1, size_average=True, channel=3) of (N,H,W,3) images (HIP tensors; the permuted
+    views are read in place)"""
+    from ..pytorch_msssim import MS_SSIM
+    with torch.no_grad():
+        diff = MS_SSIM(data_range=1, size_average=True, channel=3)(ref_images.permute(0, 3, 1, 2), pred_images.permute(0, 3, 1, 2))
+    return torch.mean(diff).cpu().numpy()
+
+
+def image_eval(images_for_eval, device=None):
+    """utils/eval_util.py:10-26: dict of lists of (n,H,W[,3]) tensors -> {"Silhouette IoU", "L1", "LPIPS", "MS_SSIM"}.
+    MS_SSIM is computed when the images are HIP tensors or `device` names a HIP device (they are copied there); on CPU tensors without
+    a device it is None, as is LPIPS.  Images whose smaller side is <= 160 px (pytorch_msssim asserts there) also give None, with a warning."""
     ev = {k: torch.vstack(v) for k, v in images_for_eval.items()}
-    return {"Silhouette IoU": sil_iou(ev["ref_mask"], ev["pred_mask"]),
+    stat = {"Silhouette IoU": sil_iou(ev["ref_mask"], ev["pred_mask"]),
             "L1": l1_diff(ev["ref_image"], ev["ref_mask"], ev["pred_image"], ev["pred_mask"]),
             "LPIPS": None, "MS_SSIM": None}
+    ref, pred = ev["ref_image"], ev["pred_image"]
+    dev = torch.device(device) if device is not None else (ref.device if ref.is_cuda else None)
+    if dev is not None and dev.type == "cuda":
+        if min(ref.shape[1:3]) <= ops.MS_SSIM_MIN_SIDE:
+            warnings.warn(f"MS_SSIM left out: images of {ref.shape[1]} x {ref.shape[2]} px (pytorch_msssim needs both sides > {ops.MS_SSIM_MIN_SIDE})")
+        else:
+            stat["MS_SSIM"] = ms_ssim_diff(ref.to(dev, torch.float32), pred.to(dev, torch.float32))
+    return stat
+
+
+def load_gt_vert(fid, gt_mesh_dir, dataset="synthetic", start_from_one=False, idx_offset=0):
+    """utils/eval_util.py:63-70: the ground-truth MANO vertices (mm, `<num>_manov.xyz`) of frame fid[0], in metres"""
+    if dataset != "synthetic":
+        raise NotImplementedError("only the 'synthetic' ground-truth layout (as in the reference)")
+    num = idx_offset + int(fid[0]) + (1 if start_from_one else 0)
+    mano_verts = np.loadtxt("{:s}/{:d}_manov.xyz".format(gt_mesh_dir, num))
+    return mano_verts / 1000.0
 
 
 def align_w_scale(mtx1, mtx2, return_trafo=False):

@@ -745,6 +745,27 @@ int harp_comm_create(const void* id, int rank, int world, void** comm_out);
 int harp_comm_destroy(void* comm);
 int harp_allreduce_flat(void* comm, float* buf, size_t n, hipStream_t stream);
 
+/* ---- post-fit evaluation metrics (csrc/metrics.hip) ------------------------------------------------------------------------------
+ * replaces utils/eval_util.py:10-60 as called per 64-frame chunk at optimize_sequence.py:713-722: MS_SSIM(data_range=1,
+ * size_average=True, channel=3) of pytorch_msssim 0.2.1 (eval_util.py:8, 56-60; ms_ssim / _ssim / gaussian_filter of that package),
+ * sil_iou's >= 0.5 mask counts (:41-49) and l1_diff's |ref - pred| sum (:34-38), for N images of C <= 3 channels and H x W pixels.
+ * ref / pred: float32 images read in place through element strides (sn, sc, sy, sx) shared by both: the reference's (N,H,W,3) render
+ * layout is (H*W*3, 1, W*3, 3), pytorch_msssim's NCHW is (C*H*W, H*W, W, 1).  ref_mask / pred_mask: (N,H,W) contiguous float32, both
+ * or neither (NULL: inter = union = 0).  weights: n_levels (1..5) host floats (the package's default [0.0448, 0.2856, 0.3001, 0.2363,
+ * 0.1333]); window: 11 taps of a float32 Gaussian of `sigma`; C1 = (K1 * data_range)^2, C2 = (K2 * data_range)^2.
+ * out: per image 4 + 2 * n_levels * C floats: inter, union (pixel counts over the full image), l1_sum (over the full image and all
+ * channels), ms_ssim (relu, weight powers, channel mean), then ssim[level][channel], then cs[level][channel] (means over each level's
+ * valid map).  ws: harp_image_metrics_ws_bytes(N, H, W) bytes, 16-B aligned, no initial contents.  Deterministic: no atomics, fixed
+ * reduction order.  Returns HARP_ERR_ARG without launching for NULL images / ws / out / weights, one mask without the other,
+ * min(H, W) <= 160 (the package's own assertion (11 - 1) * 2^4), C outside 1..3, n_levels outside 1..5, N outside 1..65535.
+ * harp_image_metrics_ws_bytes: pure host arithmetic, 0 for those sizes — with h_0 = H, h_{l+1} = (h_l + 1) / 2 (w likewise),
+ * tiles_l = ceil((h_l - 10) / 32) * ceil((w_l - 10) / 32) and A(b) = b rounded up to 256:
+ *   sum_{l=1..4} 2 * A(12 * N * h_l * w_l)  +  sum_{l=0..4} A(64 * N * tiles_l). */
+size_t harp_image_metrics_ws_bytes(int N, int H, int W);
+int harp_image_metrics(const float* ref, const float* pred, const float* ref_mask, const float* pred_mask, long long sn, long long sc,
+                       long long sy, long long sx, int N, int C, int H, int W, float data_range, const float* weights, int n_levels,
+                       float K1, float K2, float sigma, void* ws, float* out, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
