@@ -270,3 +270,11 @@ SIGNATURES.update({
     "harp_image_metrics_ws_bytes": (_sz, [_i, _i, _i]),
     "harp_image_metrics": (_i, [_vp, _vp, _vp, _vp, _ll, _ll, _ll, _ll, _i, _i, _i, _i, _f, ctypes.POINTER(_f), _i, _f, _f, _f, _vp, _vp, _vp]),
 })
+
+# LPIPS v0.1 / AlexNet of the post-fit evaluation (csrc/lpips.hip)
+SIGNATURES.update({
+    "harp_lpips_alex_net_bytes": (_sz, []),
+    "harp_lpips_alex_pack": (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_vp), ctypes.POINTER(_vp), _vp, _vp]),
+    "harp_lpips_alex_ws_bytes": (_sz, [_i, _i, _i]),
+    "harp_lpips_alex": (_i, [_vp, _vp, _vp, _ll, _ll, _ll, _ll, _i, _i, _i, _i, _vp, _vp, _vp]),
+})

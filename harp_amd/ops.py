@@ -471,3 +471,77 @@ def image_metrics(ref, pred, ref_mask=None, pred_mask=None, channels_last=True, 
     return {"iou": inter / union if ref_mask is not None else None, "l1": out[:, 2] / float(H * W * C), "l1_sum": out[:, 2],
             "inter": inter, "union": union, "ms_ssim": out[:, 3],
             "ssim": out[:, 4:4 + nl * C].reshape(N, nl, C), "cs": out[:, 4 + nl * C:].reshape(N, nl, C)}
+
+
+# ------------------------------------------------------------------------------------------------------
+# LPIPS v0.1 / AlexNet of the post-fit evaluation (csrc/lpips.hip)
+# ------------------------------------------------------------------------------------------------------
+LPIPS_MIN_SIDE = 31                       # below it the second 3x3 / stride-2 pool has no window (torch's layers fail there too)
+LPIPS_ALEX_CONVS = ((64, 3, 11), (192, 64, 5), (384, 192, 3), (256, 384, 3), (256, 256, 3))    # (Cout, Cin, kernel) of features 0, 3, 6, 8, 10
+
+
+def lpips_alex_pack(convs, lins, device):
+    """Pack the LPIPS / AlexNet weights for csrc/lpips.hip: convs = five (weight (Cout,Cin,k,k), bias (Cout,)) pairs in torch's layout,
+    lins = the five head weights ((1,C,1,1) or (C,)).  Returns the opaque net buffer (uint8 tensor on `device`)."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("harp_amd ops need HIP device tensors (no CPU path)")
+    ws, bs, ls = [], [], []
+    for k, ((w, b), lin) in enumerate(zip(convs, lins)):
+        co, ci, ks = LPIPS_ALEX_CONVS[k]
+        if tuple(w.shape) != (co, ci, ks, ks) or tuple(b.shape) != (co,) or lin.numel() != co:
+            raise ValueError(f"LPIPS layer {k}: weight {tuple(w.shape)}, bias {tuple(b.shape)}, lin {tuple(lin.shape)}; "
+                             f"want ({co}, {ci}, {ks}, {ks}), ({co},), (1, {co}, 1, 1)")
+        ws.append(w.detach().to(device, torch.float32).contiguous())
+        bs.append(b.detach().to(device, torch.float32).contiguous())
+        ls.append(lin.detach().reshape(-1).to(device, torch.float32).contiguous())
+    L = _lib.lib()
+    net = torch.empty(L.harp_lpips_alex_net_bytes(), dtype=torch.uint8, device=device)
+    arr = lambda ts: (ctypes.c_void_p * 5)(*[t.data_ptr() for t in ts])      # noqa: E731
+    with torch.cuda.device(device):
+        rc = L.harp_lpips_alex_pack(arr(ws), arr(bs), arr(ls), net.data_ptr(), _lib.stream())
+        _lib.check(rc, "harp_lpips_alex_pack")
+        torch.cuda.current_stream().synchronize()      # (the float32 copies above are freed on return)
+    return net
+
+
+def lpips_alex(ref, pred, net, channels_last=True, normalize=False):
+    """Per-image LPIPS v0.1 (net='alex', spatial=False) of utils/eval_util.py:51-53, forward only, in one launch chain.
+
+    ref / pred: float32 HIP tensors (N,H,W,3) (channels_last, the reference's render layout) or (N,3,H,W), read in place; both sides
+    >= 31 px.  net: lpips_alex_pack(...).  normalize=False (the reference's call) feeds the values as they are, i.e. as if in [-1, 1];
+    normalize=True maps [0, 1] -> [-1, 1] first.  Returns (N, 6) float32: LPIPS, then the five taps' spatial means (relu1 .. relu5)."""
+    if not (torch.is_tensor(ref) and torch.is_tensor(pred)):
+        raise TypeError("lpips_alex takes tensors")
+    check_forward_only(ref, pred)
+    if not (ref.is_cuda and pred.is_cuda):
+        raise RuntimeError("harp_amd ops need HIP device tensors (no CPU path)")
+    if ref.dtype != torch.float32 or pred.dtype != torch.float32:
+        raise TypeError(f"lpips_alex takes float32 images, got {ref.dtype} / {pred.dtype}")
+    if ref.dim() != 4 or ref.shape != pred.shape:
+        raise ValueError(f"lpips_alex takes two images of the same 4-D shape, got {tuple(ref.shape)} and {tuple(pred.shape)}")
+    if ref.device != pred.device or not (torch.is_tensor(net) and net.device == ref.device):
+        raise ValueError("ref, pred and the packed net must live on the same device")
+    if channels_last:
+        N, H, W, C = ref.shape
+    else:
+        N, C, H, W = ref.shape
+    if C != 3:
+        raise ValueError(f"LPIPS takes 3-channel images, got {C}")
+    if min(H, W) < LPIPS_MIN_SIDE:
+        raise ValueError(f"LPIPS / AlexNet needs both image sides >= {LPIPS_MIN_SIDE}, got {H} x {W}")
+    if N > 65535:
+        raise ValueError("at most 65535 images per call")
+    if ref.stride() != pred.stride() or min(ref.stride()) < 0:
+        ref, pred = ref.contiguous(), pred.contiguous()
+    s = ref.stride()
+    sn, sy, sx, sc = (s[0], s[1], s[2], s[3]) if channels_last else (s[0], s[2], s[3], s[1])
+    dev = ref.device
+    L = _lib.lib()
+    ws = torch.empty(L.harp_lpips_alex_ws_bytes(N, H, W), dtype=torch.uint8, device=dev)
+    out = torch.empty(N, 6, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.harp_lpips_alex(net.data_ptr(), ref.data_ptr(), pred.data_ptr(), sn, sc, sy, sx, N, H, W, int(bool(normalize)), _lib.ptr(ws),
+                               _lib.ptr(out), _lib.stream())
+    _lib.check(rc, "harp_lpips_alex")
+    return out

@@ -226,7 +226,7 @@ def optimize_hand_sequence(configs, input_params, images_dataset, val_params, va
 EVAL_CHUNK = 64                  # optimize_sequence.py:716: image_eval runs on every 64 frames; the final stats are means of the chunk means
 
 
-def evaluate_sequence(configs, params, images_dataset, hand_layer, device="cuda", batch_size=32, uv_mask=None):
+def evaluate_sequence(configs, params, images_dataset, hand_layer, device="cuda", batch_size=32, uv_mask=None, lpips_fn=None):
     """The post-fit evaluation of optimize_sequence.py:595-816: re-render every dataset item in order with the fitted `params` through the
     reference-API mirror (silhouette: get_renderers(silh_sigma=1e-7, silh_faces_per_pixel=50)[1]; image: render_image_with_RT through
     get_shadow_renderers with self_shadow, else render_image with the phong renderer), `batch_size` frames per render call; per-frame
@@ -234,8 +234,12 @@ def evaluate_sequence(configs, params, images_dataset, hand_layer, device="cuda"
     (the last partial chunk included) of each chunk's mean; with configs["eval_mesh"] the Procrustes-aligned vertex error against
     `<gt_mesh_dir>/<500 + fid + 1>_manov.xyz` (:760-774, also written to eval_vert_mm[_test].txt).  Writes eval_results[_test].txt
     (" %s: %.5f" lines, :808-816) and uv_out/texture.png, uv_out/normal_map.png (:627-654) under configs["base_output_dir"] and returns
-    the stats dict.  Left out: LPIPS (no pretrained weights), and MS_SSIM with a warning when the image side is <= 160 px (the reference
-    would fail pytorch_msssim's assertion there); the rendered_after_opt panels and the turntables."""
+    the stats dict.  LPIPS (harp_amd.lpips, csrc/lpips.hip) is added when `lpips_fn` is given or configs["lpips_weights"] names its weights
+    (a combined lpips.LPIPS state-dict path, or a (torchvision alexnet, lpips v0.1 head) path pair): per frame on the same y_true / y_pred,
+    [0, 1] images without `normalize` as the reference passes them, averaged like the others and written in the reference's key order (IoU,
+    L1, LPIPS, MS_SSIM); without either the output has no LPIPS line (the weights cannot be shipped).  Left out: MS_SSIM with a warning when
+    the image side is <= 160 px (the reference would fail pytorch_msssim's assertion there); the rendered_after_opt panels and the
+    turntables."""
     import os
     import warnings
     import torch.nn.functional as F
@@ -266,7 +270,14 @@ def evaluate_sequence(configs, params, images_dataset, hand_layer, device="cuda"
     with_ms = S > ops.MS_SSIM_MIN_SIDE
     if not with_ms:
         warnings.warn(f"MS_SSIM left out of the evaluation: {S} px images (pytorch_msssim needs a side > {ops.MS_SSIM_MIN_SIDE})")
-    iou, l1, ms, vert_err = [], [], [], []
+    if lpips_fn is None and configs.get("lpips_weights"):
+        from .lpips import LPIPS
+        lw = configs["lpips_weights"]
+        lpips_fn = LPIPS(weights=tuple(lw) if isinstance(lw, (list, tuple)) else lw).to(device)
+    with_lpips = lpips_fn is not None and S >= ops.LPIPS_MIN_SIDE
+    if lpips_fn is not None and not with_lpips:
+        warnings.warn(f"LPIPS left out of the evaluation: {S} px images (AlexNet needs a side >= {ops.LPIPS_MIN_SIDE})")
+    iou, l1, ms, lp, vert_err = [], [], [], [], []
     n = len(images_dataset)
     with torch.no_grad():
         for lo in range(0, n, batch_size):
@@ -306,6 +317,8 @@ def evaluate_sequence(configs, params, images_dataset, hand_layer, device="cuda"
             else:                                     # no MS-SSIM at this size, so no metrics kernel: sil_iou / l1_diff per frame
                 iou.append(torch.stack([torch.as_tensor(sil_iou(y_sil_true[b:b + 1], y_sil_pred[b:b + 1])) for b in range(B)]).cpu())
                 l1.append((y_true - y_pred).abs().double().sum((1, 2, 3)).cpu())
+            if with_lpips:                            # :51-53 of utils/eval_util.py, per frame
+                lp.append(lpips_fn(y_true.permute(0, 3, 1, 2), y_pred.permute(0, 3, 1, 2)).reshape(B).double().cpu())
             if configs["eval_mesh"]:                 # :760-774
                 for b in range(B):
                     gt = load_gt_vert(fid[b:b + 1], configs["gt_mesh_dir"], dataset="synthetic", start_from_one=True, idx_offset=500)
@@ -318,6 +331,9 @@ def evaluate_sequence(configs, params, images_dataset, hand_layer, device="cuda"
     per_pixel = float(S * S * 3)
     stats = {"Silhouette IoU": float(np.mean([iou[c].mean().item() for c in chunks])),
              "L1": float(np.mean([l1[c].sum().item() / ((c.stop - c.start) * per_pixel) for c in chunks]))}
+    if with_lpips:
+        lp = torch.cat(lp)
+        stats["LPIPS"] = float(np.mean([lp[c].mean().item() for c in chunks]))
     if with_ms:
         ms = torch.cat(ms)
         stats["MS_SSIM"] = float(np.mean([ms[c].mean().item() for c in chunks]))
@@ -331,6 +347,13 @@ def evaluate_sequence(configs, params, images_dataset, hand_layer, device="cuda"
         for k, v in stats.items():
             f_out.write(" %s: %.5f\n" % (k, v))
     return stats
+
+
+def lpips_weights_arg(paths):
+    """--lpips-weights PATH [PATH]: one combined state dict, or the (alexnet, lpips head) pair"""
+    if len(paths) not in (1, 2):
+        raise SystemExit("--lpips-weights takes one lpips.LPIPS state dict or two paths (torchvision alexnet, lpips v0.1 alex head)")
+    return paths[0] if len(paths) == 1 else tuple(paths)
 
 
 def main(argv=None):
@@ -350,9 +373,14 @@ def main(argv=None):
     ap.add_argument("--config", required=True, help="yaml with the keys of utils/config_utils.get_config")
     ap.add_argument("--batch-size", type=int, default=18)
     ap.add_argument("--eval", action="store_true", help="after the fit, the evaluation of optimize_sequence.py:595-816 (evaluate_sequence)")
+    ap.add_argument("--lpips-weights", nargs="+", default=None, metavar="PATH",
+                    help="LPIPS in the evaluation: one lpips.LPIPS(net='alex') state dict, or torchvision's alexnet state dict and the lpips "
+                         "v0.1 alex head (configs['lpips_weights'])")
     args = ap.parse_args(argv)
     with open(args.config) as f:
         configs = get_config(write_yaml=False, **yaml.safe_load(f))
+    if args.lpips_weights:
+        configs["lpips_weights"] = lpips_weights_arg(args.lpips_weights)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     shared = os.environ.get("HARP_ALL_ON_GPU0") == "1"

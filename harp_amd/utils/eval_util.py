@@ -1,7 +1,7 @@
 """Evaluation metrics of the reference's utils/eval_util.py: silhouette IoU, masked-free L1, white-background
 fill, Procrustes alignment, MS-SSIM (harp_amd.pytorch_msssim: the HIP kernels of csrc/metrics.hip, so it needs a HIP device) and the
-ground-truth vertex loader.  LPIPS needs pretrained AlexNet + LPIPS head weights that cannot be shipped: `image_eval` reports it as None.
-IoU and L1 run on whatever device the tensors live on."""
+ground-truth vertex loader, and LPIPS (harp_amd.lpips: csrc/lpips.hip) when an `lpips_fn` is given — its pretrained AlexNet + head weights
+cannot be shipped, so without one `image_eval` reports LPIPS as None.  IoU and L1 run on whatever device the tensors live on."""
 import warnings
 
 import numpy as np
@@ -38,10 +38,22 @@ def ms_ssim_diff(ref_images, pred_images):
     return torch.mean(diff).cpu().numpy()
 
 
-def image_eval(images_for_eval, device=None):
+def lpips_diff(ref_images, pred_images, lpips_fn=None):
+    """utils/eval_util.py:51-53: the batch mean of lpips_fn(ref, pred) over (N,H,W,3) images (permuted views, read in place).  As in the
+    reference the [0, 1] images go in without `normalize`, so LPIPS reads them as if they were in [-1, 1] (kept on purpose: the numbers stay
+    comparable with the reference's eval_results.txt).  lpips_fn: a harp_amd.lpips.LPIPS(net='alex', ...) with its weights."""
+    if lpips_fn is None:
+        raise ValueError("lpips_diff needs lpips_fn = harp_amd.lpips.LPIPS(net='alex', ...) with pretrained weights (none ship here)")
+    with torch.no_grad():
+        diff = lpips_fn(ref_images.permute(0, 3, 1, 2), pred_images.permute(0, 3, 1, 2))
+    return torch.mean(diff).cpu().numpy()
+
+
+def image_eval(images_for_eval, device=None, lpips_fn=None):
     """utils/eval_util.py:10-26: dict of lists of (n,H,W[,3]) tensors -> {"Silhouette IoU", "L1", "LPIPS", "MS_SSIM"}.
     MS_SSIM is computed when the images are HIP tensors or `device` names a HIP device (they are copied there); on CPU tensors without
-    a device it is None, as is LPIPS.  Images whose smaller side is <= 160 px (pytorch_msssim asserts there) also give None, with a warning."""
+    a device it is None.  Images whose smaller side is <= 160 px (pytorch_msssim asserts there) also give None, with a warning.
+    LPIPS (lpips_diff) only with an `lpips_fn`, on `device`, the images' HIP device or else the module's; None without one."""
     ev = {k: torch.vstack(v) for k, v in images_for_eval.items()}
     stat = {"Silhouette IoU": sil_iou(ev["ref_mask"], ev["pred_mask"]),
             "L1": l1_diff(ev["ref_image"], ev["ref_mask"], ev["pred_image"], ev["pred_mask"]),
@@ -53,6 +65,9 @@ def image_eval(images_for_eval, device=None):
             warnings.warn(f"MS_SSIM left out: images of {ref.shape[1]} x {ref.shape[2]} px (pytorch_msssim needs both sides > {ops.MS_SSIM_MIN_SIDE})")
         else:
             stat["MS_SSIM"] = ms_ssim_diff(ref.to(dev, torch.float32), pred.to(dev, torch.float32))
+    if lpips_fn is not None:
+        ldev = dev if dev is not None else next(lpips_fn.parameters()).device
+        stat["LPIPS"] = lpips_diff(ref.to(ldev, torch.float32), pred.to(ldev, torch.float32), lpips_fn)
     return stat
 
 

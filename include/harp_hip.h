@@ -766,6 +766,31 @@ int harp_image_metrics(const float* ref, const float* pred, const float* ref_mas
                        long long sy, long long sx, int N, int C, int H, int W, float data_range, const float* weights, int n_levels,
                        float K1, float K2, float sigma, void* ws, float* out, hipStream_t stream);
 
+/* ---- LPIPS v0.1 / AlexNet of the post-fit evaluation (csrc/lpips.hip) ------------------------------------------------------------
+ * replaces lpips.LPIPS(net='alex') as built at utils/eval_util.py:7 and called at :51-53 (lpips_diff, per 64-frame chunk from
+ * optimize_sequence.py:737 / :795): version 0.1, lpips=True, spatial=False, eval mode; forward only, float32 (every convolution a float32
+ * fma chain on v_mfma_f32_32x32x2_f32).  Scaling layer x' = (x - shift) / scale, shift (-0.030, -0.088, -0.188), scale (0.458, 0.448,
+ * 0.450) (normalize != 0: x -> 2x - 1 first; the reference passes [0, 1] images without it); torchvision alexnet.features[0:12] with taps
+ * after the five ReLUs; per tap f / (||f||_2 over channels + 1e-10), sum_c lin_k[c] (ref - pred)^2, mean over the tap's H x W.
+ * harp_lpips_alex_pack: device float32 weights in torch's layouts — w[k] (Cout,Cin,KS,KS) = (64,3,11,11), (192,64,5,5), (384,192,3,3),
+ *   (256,384,3,3), (256,256,3,3); bias[k] (Cout); lin[k] (C_k) = the (1,C_k,1,1) head weights — into `net`, harp_lpips_alex_net_bytes()
+ *   bytes, 256-B aligned, opaque (only enqueues: the sources must stay alive until the stream reaches it).
+ * harp_lpips_alex: ref / pred (N images, 3 channels, H x W) read in place through element strides (sn, sc, sy, sx) shared by both
+ *   (the reference's (N,H,W,3) renders: (3HW, 1, 3W, 3); NCHW: (3HW, HW, W, 1)); both go through the network as one batch of 2N.
+ *   out: per image 6 floats: LPIPS, then the five taps' spatial means (relu1 .. relu5; the total is their float64 sum).
+ *   ws: harp_lpips_alex_ws_bytes(N, H, W) bytes, 256-B aligned, no initial contents.  Deterministic: no atomics, fixed reduction order;
+ *   identical ref and pred give exactly 0.  Returns HARP_ERR_ARG without launching for NULL net / images / ws / out, misaligned net or ws,
+ *   min(H, W) < 31 (the second pool's input would be smaller than its window), N outside 1..65535, or a tap map of more than 2^31 / 384
+ *   pixels (32-bit offsets inside one image).
+ * harp_lpips_alex_ws_bytes: pure host arithmetic, 0 for those sizes — with h1 = (H - 7) / 4 + 1, h2 = (h1 - 3) / 2 + 1, h3 = (h2 - 3) / 2 + 1
+ *   (w likewise, integer division), P = 2N, A(b) = b rounded up to 256 and t_k = ceil(h_k w_k / 64) (h_3 = h_4 = h_5 = h3):
+ *   A(256 P h1 w1) + A(256 P h2 w2) + A(768 P h2 w2) + A(768 P h3 w3) + A(1536 P h3 w3) + 2 A(1024 P h3 w3)  +  sum_{k=1..5} A(4 N t_k). */
+size_t harp_lpips_alex_net_bytes(void);
+int harp_lpips_alex_pack(const float* const* w, const float* const* bias, const float* const* lin, void* net, hipStream_t stream);
+size_t harp_lpips_alex_ws_bytes(int N, int H, int W);
+int harp_lpips_alex(const void* net, const float* ref, const float* pred, long long sn, long long sc, long long sy, long long sx, int N,
+                    int H, int W, int normalize, void* ws, float* out, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
