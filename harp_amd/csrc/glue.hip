@@ -172,7 +172,7 @@ int harp_light_setup_bwd(const float* centroid, const float* light_pos, const fl
 }
 
 int harp_scale(const float* x, float s, int n, float* y, hipStream_t stream) {
-  if (!x || !y) return HARP_ERR_ARG;
+  if (!x || !y || n <= 0) return HARP_ERR_ARG;
   hipLaunchKernelGGL(scale_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, x, s, n, y);
   HARP_CHECK_LAUNCH();
   return HARP_OK;

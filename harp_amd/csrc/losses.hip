@@ -677,7 +677,7 @@ int harp_adam_apply2(float* p, const float* g, float* m, float* v, size_t o0, si
 
 int harp_image_l1(const float* pred, const float* target, const float* mask, const int32_t* fid, int B, int n_per_frame, int C,
                   const float* w, float* loss, float* g_pred, hipStream_t stream) {
-  if (!pred || !target || !loss || B <= 0) return HARP_ERR_ARG;
+  if (!pred || !target || !loss || B <= 0 || n_per_frame <= 0 || C <= 0 || n_per_frame % C) return HARP_ERR_ARG;
   const float inv = 1.0f / ((float)B * (float)n_per_frame);
   const int gx = min((n_per_frame + 255) / 256, 64);
   hipLaunchKernelGGL(image_l1_kernel, dim3(gx, B), dim3(256), 0, stream, pred, target, mask, fid, n_per_frame, C, inv, w, loss, g_pred);
@@ -687,7 +687,7 @@ int harp_image_l1(const float* pred, const float* target, const float* mask, con
 
 int harp_kps_loss(const float* gt, const int32_t* fid, const float* pred, int B, int n_joints_pred, const float* w, float* loss,
                   float* g_pred, hipStream_t stream) {
-  if (!gt || !pred || !loss || n_joints_pred < 21) return HARP_ERR_ARG;
+  if (!gt || !pred || !loss || n_joints_pred < 21 || B <= 0) return HARP_ERR_ARG;
   hipLaunchKernelGGL(kps_kernel, dim3(B), dim3(64), 0, stream, gt, fid, pred, B, n_joints_pred, w, loss, g_pred);
   HARP_CHECK_LAUNCH();
   return HARP_OK;
@@ -757,7 +757,7 @@ int harp_texture_terms(const float* tex, const float* nmap, const float* mask, c
 }
 
 int harp_sum_squares(const float* x, int n, const float* w, float* loss, float* g, hipStream_t stream) {
-  if (!x || !loss) return HARP_ERR_ARG;
+  if (!x || !loss || n <= 0) return HARP_ERR_ARG;
   hipLaunchKernelGGL(sumsq_kernel, dim3(min((n + 255) / 256, 64)), dim3(256), 0, stream, x, n, w, loss, g);
   HARP_CHECK_LAUNCH();
   return HARP_OK;
@@ -772,28 +772,28 @@ int harp_mse(const float* x, const float* y, int n, float* loss, float* g_x, hip
 
 int harp_texture_smooth_reg(const float* tex, const int32_t* dist, const float* mask, int H, int W, const float* w, float* loss,
                             float* g_tex, hipStream_t stream) {
-  if (!tex || !dist || !loss) return HARP_ERR_ARG;
+  if (!tex || !dist || !loss || H <= 0 || W <= 0) return HARP_ERR_ARG;
   hipLaunchKernelGGL(tex_smooth_kernel, dim3(min((H * W + 255) / 256, 512)), dim3(256), 0, stream, tex, dist, mask, H, W, w, loss, g_tex);
   HARP_CHECK_LAUNCH();
   return HARP_OK;
 }
 
 int harp_close_to_z_reg(const float* nm, int H, int W, float scale, const float* w, float* loss, float* g_nm, hipStream_t stream) {
-  if (!nm || !loss) return HARP_ERR_ARG;
+  if (!nm || !loss || H <= 0 || W <= 0) return HARP_ERR_ARG;
   hipLaunchKernelGGL(close_to_z_kernel, dim3(H), dim3(256), 0, stream, nm, H, W, w, scale, loss, g_nm);
   HARP_CHECK_LAUNCH();
   return HARP_OK;
 }
 
 int harp_normalize3_fwd(const float* x, int n, float* y, hipStream_t stream) {
-  if (!x || !y) return HARP_ERR_ARG;
+  if (!x || !y || n <= 0) return HARP_ERR_ARG;
   hipLaunchKernelGGL(normalize3_fwd_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, x, n, y);
   HARP_CHECK_LAUNCH();
   return HARP_OK;
 }
 
 int harp_normalize3_bwd(const float* x, const float* gy, int n, float* gx, hipStream_t stream) {
-  if (!x || !gy || !gx) return HARP_ERR_ARG;
+  if (!x || !gy || !gx || n <= 0) return HARP_ERR_ARG;
   hipLaunchKernelGGL(normalize3_bwd_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, x, gy, n, gx);
   HARP_CHECK_LAUNCH();
   return HARP_OK;
@@ -801,7 +801,7 @@ int harp_normalize3_bwd(const float* x, const float* gy, int n, float* gx, hipSt
 
 int harp_adam_step(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps, int step,
                    float grad_scale, hipStream_t stream) {
-  if (!p || !g || !m || !v || step < 1) return HARP_ERR_ARG;
+  if (!p || !g || !m || !v || step < 1 || n == 0) return HARP_ERR_ARG;
   const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
   const float step_size = (float)((double)lr / bc1), inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
   const int blocks = (int)min((size_t)2048, (n + 255) / 256);

@@ -201,7 +201,7 @@ extern "C" {
 
 int harp_subdivide_fwd(const float* v0, const int32_t* edges0, int B, int V0, int E0, float scale, float* vs,
                        hipStream_t stream) {
-  if (!v0 || !edges0 || !vs) return HARP_ERR_ARG;
+  if (!v0 || !edges0 || !vs || B <= 0 || V0 <= 0 || E0 < 0) return HARP_ERR_ARG;
   hipLaunchKernelGGL(subdivide_fwd_kernel, dim3((V0 + E0 + 255) / 256, B), dim3(256), 0, stream, v0, edges0, V0, E0, scale, vs);
   HARP_CHECK_LAUNCH();
   return HARP_OK;
@@ -209,7 +209,7 @@ int harp_subdivide_fwd(const float* v0, const int32_t* edges0, int B, int V0, in
 
 int harp_subdivide_bwd(const float* g_vs, const int32_t* sub_off, const int32_t* sub_idx, int B, int V0, int V, float scale,
                        float* g_v0, hipStream_t stream) {
-  if (!g_vs || !sub_off || !sub_idx || !g_v0) return HARP_ERR_ARG;
+  if (!g_vs || !sub_off || !sub_idx || !g_v0 || B <= 0 || V0 <= 0 || V < V0) return HARP_ERR_ARG;
   hipLaunchKernelGGL(subdivide_bwd_kernel, dim3((V0 + 255) / 256, B), dim3(256), 0, stream, g_vs, sub_off, sub_idx, V0, V, scale, g_v0);
   HARP_CHECK_LAUNCH();
   return HARP_OK;
@@ -218,7 +218,7 @@ int harp_subdivide_bwd(const float* g_vs, const int32_t* sub_off, const int32_t*
 // n (B,V,3) unit normals, inv_len (B,V) saved for backward; if disp != NULL also vd = v + n*disp (disp (V,))
 int harp_vertex_normals_fwd(const float* v, const int32_t* faces, const int32_t* vf_off, const int32_t* vf_idx, int B, int V,
                             float* n, float* inv_len, const float* disp, float* vd, hipStream_t stream) {
-  if (!v || !faces || !vf_off || !vf_idx || !n || (disp && !vd)) return HARP_ERR_ARG;
+  if (!v || !faces || !vf_off || !vf_idx || !n || (disp && !vd) || B <= 0 || V <= 0) return HARP_ERR_ARG;
   hipLaunchKernelGGL(normals_fwd_kernel, dim3((V + 255) / 256, B), dim3(256), 0, stream, v, faces, vf_off, vf_idx, V, n, inv_len, disp, vd);
   HARP_CHECK_LAUNCH();
   return HARP_OK;
@@ -227,7 +227,7 @@ int harp_vertex_normals_fwd(const float* v, const int32_t* faces, const int32_t*
 // g_v (B,V,3) += d n / d v ^T g_n ; tmp: (B,V,3) scratch
 int harp_vertex_normals_bwd(const float* v, const int32_t* faces, const int32_t* vf_off, const int32_t* vf_idx, int B, int V,
                             const float* n, const float* inv_len, const float* g_n, float* tmp, float* g_v, hipStream_t stream) {
-  if (!v || !faces || !n || !inv_len || !g_n || !tmp || !g_v) return HARP_ERR_ARG;
+  if (!v || !faces || !vf_off || !vf_idx || !n || !inv_len || !g_n || !tmp || !g_v || B <= 0 || V <= 0) return HARP_ERR_ARG;
   hipLaunchKernelGGL(normals_bwd_gN_kernel, dim3((B * V + 255) / 256), dim3(256), 0, stream, n, inv_len, g_n, B * V, tmp);
   hipLaunchKernelGGL(normals_bwd_gv_kernel, dim3((V + 255) / 256, B), dim3(256), 0, stream, v, faces, vf_off, vf_idx, V, tmp, g_v);
   HARP_CHECK_LAUNCH();
@@ -236,7 +236,7 @@ int harp_vertex_normals_bwd(const float* v, const int32_t* faces, const int32_t*
 
 int harp_displace_bwd(const float* g_vd, const float* n, const float* disp, int B, int V, float* g_n, float* g_disp,
                       hipStream_t stream) {
-  if (!g_vd || !n || !disp || !g_n || !g_disp) return HARP_ERR_ARG;
+  if (!g_vd || !n || !disp || !g_n || !g_disp || B <= 0 || V <= 0) return HARP_ERR_ARG;
   hipLaunchKernelGGL(displace_bwd_kernel, dim3((V + 255) / 256), dim3(256), 0, stream, g_vd, n, disp, B, V, g_n, g_disp);
   HARP_CHECK_LAUNCH();
   return HARP_OK;
@@ -244,7 +244,7 @@ int harp_displace_bwd(const float* g_vd, const float* n, const float* disp, int 
 
 int harp_project_fwd(const float* v, const float* R, const float* T, int B, int V, float focal, float ppx, float ppy, int S,
                      float* ndc, hipStream_t stream) {
-  if (!v || !R || !T || !ndc) return HARP_ERR_ARG;
+  if (!v || !R || !T || !ndc || B <= 0 || V <= 0) return HARP_ERR_ARG;
   hipLaunchKernelGGL(project_fwd_kernel, dim3((V + 255) / 256, B), dim3(256), 0, stream, v, R, T, V, focal, ppx, ppy, 0.5f * S, ndc);
   HARP_CHECK_LAUNCH();
   return HARP_OK;
@@ -253,14 +253,14 @@ int harp_project_fwd(const float* v, const float* R, const float* T, int B, int 
 // accumulating: g_v (B,V,3), g_R (B,9) or NULL, g_T (B,3) or NULL
 int harp_project_bwd(const float* v, const float* R, const float* T, const float* g_ndc, int B, int V, float focal, int S,
                      float* g_v, float* g_R, float* g_T, hipStream_t stream) {
-  if (!v || !R || !T || !g_ndc || !g_v) return HARP_ERR_ARG;
+  if (!v || !R || !T || !g_ndc || !g_v || B <= 0 || V <= 0) return HARP_ERR_ARG;
   hipLaunchKernelGGL(project_bwd_kernel, dim3((V + 255) / 256, B), dim3(256), 0, stream, v, R, T, g_ndc, V, focal, 0.5f * S, g_v, g_R, g_T);
   HARP_CHECK_LAUNCH();
   return HARP_OK;
 }
 
 int harp_centroid(const float* v, int B, int V, float* c, hipStream_t stream) {
-  if (!v || !c) return HARP_ERR_ARG;
+  if (!v || !c || B <= 0 || V <= 0) return HARP_ERR_ARG;
   hipLaunchKernelGGL(centroid_kernel, dim3(B), dim3(256), 0, stream, v, V, c);
   HARP_CHECK_LAUNCH();
   return HARP_OK;

@@ -247,7 +247,10 @@ int harp_shade_sil_bwd(const harp_shade_args* a, float blur_radius, float sigma,
 /* ---- mesh preparation --------------------------------------------------------------------------------------------
  * replaces the PyTorch3D object churn of utils/visualize.py:prepare_mesh (:45-64): Meshes(...), SubdivideMeshes
  * (optimize_sequence.py:67-89), verts_normals_padded, displacement; and Meshes.verts_normals_packed in the shaders
- * (renderer_helper.py:495).  CSR tables come from harp_amd/topology.py. */
+ * (renderer_helper.py:495).  CSR tables come from harp_amd/topology.py.  Every call below returns HARP_ERR_ARG without launching
+ * for a NULL input or output table, B <= 0, V <= 0 or V0 <= 0 (E0 < 0, V < V0 for the subdivision).  Accumulating outputs (+=):
+ * g_v of harp_vertex_normals_bwd and harp_project_bwd, g_R / g_T of harp_project_bwd (each may be NULL), g_disp of
+ * harp_displace_bwd (summed over the batch); g_n of harp_displace_bwd is overwritten. */
 int harp_subdivide_fwd(const float* v0, const int32_t* edges0, int B, int V0, int E0, float scale, float* vs, hipStream_t stream);
 int harp_subdivide_bwd(const float* g_vs, const int32_t* sub_off, const int32_t* sub_idx, int B, int V0, int V, float scale,
                        float* g_v0, hipStream_t stream);
@@ -393,7 +396,8 @@ int harp_mesh_chain_bwd_wide(const harp_mesh_chain* a, float* part_ws, hipStream
 
 /* ---- losses, texture helpers, optimiser ---------------------------------------------------------------------------
  * Every loss call accumulates (+=) its value into `loss` and, if `w` (device pointer to the weight(s) = d total/d term)
- * and the gradient output are non-NULL, its weighted gradient (+= unless noted). */
+ * and the gradient output are non-NULL, its weighted gradient (+= unless noted).  Sizes (B, n, n_per_frame, C, H, W) <= 0 return
+ * HARP_ERR_ARG without launching, as do n == 0 for harp_adam_step and n_per_frame not a multiple of C for harp_image_l1. */
 /* torch.nn.L1Loss between pred*mask and target[fid]*mask[fid] (optimize_sequence.py:519, 543); g_pred is overwritten */
 int harp_image_l1(const float* pred, const float* target, const float* mask, const int32_t* fid, int B, int n_per_frame, int C,
                   const float* w, float* loss, float* g_pred, hipStream_t stream);
@@ -582,6 +586,7 @@ int harp_arm_back_wide_bwd(const harp_arm_front* h, const float* g_colors, float
 int harp_light_setup_fwd(const float* centroid, const float* light_pos, int B, float* light_R, float* light_T, hipStream_t stream);
 int harp_light_setup_bwd(const float* centroid, const float* light_pos, const float* g_light_R, const float* g_light_T, int B, int V,
                          float* g_light_pos, float* g_centroid, float* g_verts, hipStream_t stream);
+/* y = s * x over n floats (n <= 0: HARP_ERR_ARG, no launch) */
 int harp_scale(const float* x, float s, int n, float* y, hipStream_t stream);
 /* replaces the DataLoader's batch of frame ids (optimize_sequence.py:396-399, :446): row (counter[0] mod n_rows) of a device-resident
  * (n_rows,B) int32 schedule -> fid (B,), tfid = fid - target_offset; then counter[0] = row + 1.  Graph-replayable. */

@@ -66,3 +66,37 @@ def test_product_does_not_import_oracle():
         for f in files:
             if f.endswith(".py"):
                 assert "oracle" not in open(os.path.join(dirpath, f)).read().replace("# oracle", ""), f
+
+
+def test_building_blocks_refuse_empty_sizes_without_launch(lib):
+    """The stand-alone entry points return HARP_ERR_ARG (1) for empty sizes before any launch (include/harp_hip.h).  Only sizes 0 and -1
+    and B = 0 are used: for each of them an entry point WITHOUT the check would compute an empty grid and fail its launch (status 2 + the
+    HIP error), so no kernel can reach the fake pointers.  The cases whose grid would not be empty (centroid with V = 0, displace with
+    B = 0, close-to-z with W = 0, ...) are checked with real buffers in tests/test_gpu_building_blocks.py."""
+    f = 1 << 20                                                # a fake device pointer, never dereferenced
+    for B, V0, E0 in [(0, 4, 2), (1, 0, 0), (1, -1, 0), (1, 0, -1)]:
+        assert lib.harp_subdivide_fwd(f, f, B, V0, E0, 1.0, f, None) == 1, (B, V0, E0)
+    for B, V0 in [(0, 4), (1, 0), (1, -1)]:
+        assert lib.harp_subdivide_bwd(f, f, f, B, V0, 6, 1.0, f, None) == 1, (B, V0)
+    for B, V in [(0, 4), (1, 0), (1, -1)]:
+        assert lib.harp_vertex_normals_fwd(f, f, f, f, B, V, f, f, None, None, None) == 1, (B, V)
+        assert lib.harp_vertex_normals_fwd(f, f, f, f, B, V, f, f, f, f, None) == 1, (B, V)
+        assert lib.harp_vertex_normals_bwd(f, f, f, f, B, V, f, f, f, f, f, None) == 1, (B, V)
+        assert lib.harp_project_fwd(f, f, f, B, V, 500.0, 128.0, 128.0, 256, f, None) == 1, (B, V)
+        assert lib.harp_project_bwd(f, f, f, f, B, V, 500.0, 256, f, f, f, None) == 1, (B, V)
+    for V in (0, -1):
+        assert lib.harp_displace_bwd(f, f, f, 1, V, f, f, None) == 1, V
+    assert lib.harp_centroid(f, 0, 4, f, None) == 1
+    for n in (0, -1):
+        assert lib.harp_scale(f, 2.0, n, f, None) == 1, n
+        assert lib.harp_sum_squares(f, n, f, f, f, None) == 1, n
+        assert lib.harp_mse(f, f, n, f, f, None) == 1, n
+        assert lib.harp_normalize3_fwd(f, n, f, None) == 1, n
+        assert lib.harp_normalize3_bwd(f, f, n, f, None) == 1, n
+        assert lib.harp_image_l1(f, f, None, None, 1, n, 3, f, f, f, None) == 1, n
+    for H, W in [(0, 5), (5, 0), (-1, 5), (5, -1)]:
+        assert lib.harp_texture_smooth_reg(f, f, None, H, W, f, f, f, None) == 1, (H, W)
+    assert lib.harp_close_to_z_reg(f, 0, 5, 1.0, f, f, f, None) == 1
+    assert lib.harp_adam_step(f, f, f, f, 0, 1e-3, 0.9, 0.999, 1e-8, 1, 1.0, None) == 1
+    assert lib.harp_kps_loss(f, None, f, 0, 21, f, f, f, None) == 1
+    assert lib.harp_image_l1(f, f, None, None, 0, 12, 3, f, f, f, None) == 1
