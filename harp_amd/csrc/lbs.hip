@@ -415,7 +415,7 @@ int harp_lbs_mano_fwd(const harp_mano_model* m, const float* pose, const float* 
 // g_verts (B,778,3) is MODIFIED (tip-joint gradients are folded in). Outputs: g_pose (B,48), g_betas (B,10), g_trans (B,3).
 int harp_lbs_mano_bwd(const harp_mano_model* m, const float* pose, const float* betas, const float* trans, int B, float* ws,
                       float* g_verts, const float* g_joints, float* g_pose, float* g_betas, float* g_trans, hipStream_t stream) {
-  if (!m || !pose || !betas || !ws || !g_verts || !g_joints || !g_pose || !g_betas || !g_trans) return HARP_ERR_ARG;
+  if (!m || !pose || !betas || !ws || !g_verts || !g_joints || !g_pose || !g_betas || !g_trans || B <= 0) return HARP_ERR_ARG;
   const LbsWs w = lbs_ws(ws, B);
   hipLaunchKernelGGL(lbs_joints_bwd_kernel, dim3(B), dim3(256), 0, stream, g_joints, B, w.g_j16, g_verts, g_trans, w.g_A, B * (192 + 135),
                      g_betas, B * NB);

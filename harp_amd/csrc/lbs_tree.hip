@@ -307,7 +307,9 @@ int harp_lbs_tree_fwd(const harp_tree_model* m, const float* in_pose, const floa
 // g_verts (B,NV,3) is MODIFIED (vertex-joint gradients are folded in). Outputs: g_in_pose (B,n_pose_in,3), g_betas (B,NB), g_transl (B,3).
 int harp_lbs_tree_bwd(const harp_tree_model* m, const float* in_pose, const float* betas, const float* transl, int B, float* ws,
                       float* g_verts, const float* g_joints, float* g_in_pose, float* g_betas, float* g_transl, hipStream_t stream) {
-  if (!m || !in_pose || !betas || !ws || !g_verts || !g_joints || !g_in_pose || !g_betas || !g_transl) return HARP_ERR_ARG;
+  if (!m || !in_pose || !betas || !ws || !g_verts || !g_joints || !g_in_pose || !g_betas || !g_transl || B <= 0 ||
+      m->NJ > MAXJ || m->NB > MAXB)
+    return HARP_ERR_ARG;
   const TreeWs w = tree_ws(m, ws, B);
   // (g_pm / g_Gt were cleared by harp_lbs_tree_fwd on this workspace, and again by the last backward call that consumed them)
   const int nth = max(B * m->n_joints_out * 3, B * m->NB);

@@ -125,7 +125,8 @@ __global__ void __launch_bounds__(BS) mesh_reg_kernel(const float* __restrict__ 
     if (term == 0) {
       float a[3] = {0.f, 0.f, 0.f};
       for (int k = s; k < e; ++k) for (int c = 0; c < 3; ++c) a[c] += vb[3 * nbr_idx[k] + c];
-      const float invd = 1.0f / (float)(e - s);
+      // degree 0 (an isolated vertex): PyTorch3D's laplacian_packed sets 1/deg to 0 there, so the row is -v (1/0 gave 0 * inf = NaN)
+      const float invd = (e > s) ? 1.0f / (float)(e - s) : 0.f;
       float lv[3], n2 = 0.f;
       for (int c = 0; c < 3; ++c) { lv[c] = a[c] * invd - pu[c]; n2 += lv[c] * lv[c]; }
       const float n = sqrtf(n2);
@@ -140,7 +141,7 @@ __global__ void __launch_bounds__(BS) mesh_reg_kernel(const float* __restrict__ 
         const int s2 = nbr_off[nb], e2 = nbr_off[nb + 1];
         float a[3] = {0.f, 0.f, 0.f};
         for (int q = s2; q < e2; ++q) for (int c = 0; c < 3; ++c) a[c] += vb[3 * nbr_idx[q] + c];
-        const float invd = 1.0f / (float)(e2 - s2);
+        const float invd = (e2 > s2) ? 1.0f / (float)(e2 - s2) : 0.f;     // (same guard; nb has u as a neighbour in a symmetric table)
         float lv[3], n2 = 0.f;
         for (int c = 0; c < 3; ++c) { lv[c] = a[c] * invd - pn[c]; n2 += lv[c] * lv[c]; }
         const float n = sqrtf(n2);
@@ -696,7 +697,7 @@ int harp_kps_loss(const float* gt, const int32_t* fid, const float* pred, int B,
 static int mesh_terms_launch(const float* verts, const float* ref_verts, const int32_t* nbr_off, const int32_t* nbr_idx,
                              const int32_t* nc_pairs, const int32_t* vp_off, const int32_t* vp_idx, int B, int V, int P, int E,
                              const float* w, float* loss, float* g_verts, const KpsArgs& K, hipStream_t stream) {
-  if (!verts || !nbr_off || !nbr_idx || !nc_pairs || !vp_off || !vp_idx || !loss) return HARP_ERR_ARG;
+  if (!verts || !nbr_off || !nbr_idx || !nc_pairs || !vp_off || !vp_idx || !loss || B <= 0 || V <= 0 || P < 0 || E < 0) return HARP_ERR_ARG;
   const int nz = K.gt ? 4 : 3;
   const size_t lds = (size_t)V * 3 * sizeof(float);
   // 512 threads per workgroup: a workgroup stages the whole frame (V * 12 B) whatever its size — 7 stagings per (frame, term) instead of the

@@ -286,7 +286,9 @@ size_t harp_lbs_mano_ws_floats(int B);
 /* pose (B,48) = [root axis-angle, 45 hand pose], betas (B,10), trans (B,3) -> verts (B,778,3) mm, joints (B,21,3) mm */
 int harp_lbs_mano_fwd(const harp_mano_model* m, const float* pose, const float* betas, const float* trans, int B, float* ws,
                       float* verts, float* joints, hipStream_t stream);
-/* ws must be the workspace of the forward call; g_verts is modified in place (tip-joint gradients folded in) */
+/* ws must be the workspace of the forward call; g_verts is modified in place (tip-joint gradients folded in: g_verts[tip] +=
+ * g_joints[tip joint]); g_pose, g_betas and g_trans are overwritten.  The call may be repeated on one forward workspace (with the
+ * original g_verts each time).  B <= 0 returns HARP_ERR_ARG without launching (harp_lbs_mano_fwd likewise). */
 int harp_lbs_mano_bwd(const harp_mano_model* m, const float* pose, const float* betas, const float* trans, int B, float* ws,
                       float* g_verts, const float* g_joints, float* g_pose, float* g_betas, float* g_trans, hipStream_t stream);
 
@@ -318,7 +320,9 @@ int harp_lbs_tree_fwd(const harp_tree_model* m, const float* in_pose, const floa
 /* ws: the workspace harp_lbs_tree_fwd filled for the same inputs AND THE SAME B (the layout of ws is a function of B).  The forward call
  * clears the accumulators this call adds to, and this call leaves them cleared again: it may be repeated on one forward pass, and a
  * workspace may be reused for another batch size by running harp_lbs_tree_fwd at that size first.  Calling it on a workspace whose last
- * forward ran at another B, or that the caller filled itself, accumulates into whatever those bytes hold. */
+ * forward ran at another B, or that the caller filled itself, accumulates into whatever those bytes hold.  g_verts is modified in place
+ * (vertex-joint gradients folded in: g_verts[vertex] += g_joints[its joint]); g_in_pose (the rows pose_src names), g_betas and g_transl are overwritten.
+ * B <= 0, NJ > 64 or NB > 32 return HARP_ERR_ARG without launching (harp_lbs_tree_fwd likewise). */
 int harp_lbs_tree_bwd(const harp_tree_model* m, const float* in_pose, const float* betas, const float* transl, int B, float* ws,
                       float* g_verts, const float* g_joints, float* g_in_pose, float* g_betas, float* g_transl, hipStream_t stream);
 
@@ -405,8 +409,11 @@ int harp_image_l1(const float* pred, const float* target, const float* mask, con
 int harp_kps_loss(const float* gt, const int32_t* fid, const float* pred, int B, int n_joints_pred, const float* w, float* loss,
                   float* g_pred, hipStream_t stream);
 /* loss[0..2], w[0..2] = mesh_laplacian_smoothing, mesh_normal_consistency (optimize_sequence.py:536-537),
- * arap_loss (loss/arap.py:4-57; ref_verts (V,3), NULL skips it); nbr_*: vertex->neighbour CSR (= the edge list, E edges),
- * nc_pairs (P,4) [v0,v1,a,b] per face pair sharing edge (v0,v1), vp_*: vertex -> (pair*4+role) CSR (harp_amd/topology.py) */
+ * arap_loss (loss/arap.py:4-57; ref_verts (V,3), NULL skips it and leaves loss[2] untouched); nbr_*: vertex->neighbour CSR (= the edge
+ * list, E edges), nc_pairs (P,4) [v0,v1,a,b] per face pair sharing edge (v0,v1), vp_*: vertex -> (pair*4+role) CSR (harp_amd/topology.py).
+ * loss[0..2] and g_verts (B,V,3) accumulate; w or g_verts NULL: the losses only, g_verts untouched.  A vertex of degree 0 has the
+ * Laplacian row -v (1/deg taken as 0, as PyTorch3D's laplacian_packed does); P = 0 gives a normal-consistency loss of 0.  B <= 0,
+ * V <= 0, P < 0 or E < 0 return HARP_ERR_ARG without launching (harp_mesh_kps_terms likewise). */
 int harp_mesh_regularizers(const float* verts, const float* ref_verts, const int32_t* nbr_off, const int32_t* nbr_idx,
                            const int32_t* nc_pairs, const int32_t* vp_off, const int32_t* vp_idx, int B, int V, int P, int E,
                            const float* w, float* loss, float* g_verts, hipStream_t stream);

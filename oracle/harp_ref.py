@@ -412,11 +412,12 @@ def smplx_batch_rodrigues(rot_vecs):
     return ident + sin * K + (1 - cos) * torch.bmm(K, K)
 
 
-def smplxarm_forward(model, betas, global_orient, transl, right_hand_pose, right_wrist_pose):
+def smplxarm_forward(model, betas, global_orient, transl, right_hand_pose, right_wrist_pose, expression=None):
     """SMPLXARM.forward(..., return_type='mano_w_arm') on an ARM-SLICED model dict (the LBS of the other ~9400 body vertices is
     discarded by the reference's final slice, body_models.py:2383-2390, and the joint regressor is folded into J_template /
     J_shapedirs): v_template (Va,3), shapedirs (Va,3,20), posedirs (486, Va*3), J_template (55,3), J_shapedirs (55,3,20),
     weights (Va,55), pose_mean (165,), tip_verts (5,) arm-local ids of the right thumb..pinky tips.
+    expression (B,10): the last 10 shape coefficients (None: zeros, as SMPLXARM.forward passes).
     Returns verts (B,Va,3) mm, joints (B,22,3) mm."""
     B = betas.shape[0]
     dt = betas.dtype
@@ -425,7 +426,8 @@ def smplxarm_forward(model, betas, global_orient, transl, right_hand_pose, right
     full_pose[:, 21] = right_wrist_pose                                               # body_pose[:, 60:63], :2299-2301
     full_pose[:, 40:55] = right_hand_pose.reshape(B, 15, 3)
     full_pose = full_pose.reshape(B, 165) + model["pose_mean"][None]                  # :2315
-    shape_components = torch.cat([betas, torch.zeros(B, 10, dtype=dt)], dim=-1)       # expression defaults to zeros, :2323
+    expr = torch.zeros(B, 10, dtype=dt) if expression is None else expression
+    shape_components = torch.cat([betas, expr], dim=-1)                               # expression defaults to zeros, :2323
     v_shaped = model["v_template"][None] + torch.einsum("bl,mkl->bmk", shape_components, model["shapedirs"])
     J = model["J_template"][None] + torch.einsum("bl,jkl->bjk", shape_components, model["J_shapedirs"])
     rot_mats = smplx_batch_rodrigues(full_pose.view(-1, 3)).view(B, 55, 3, 3)

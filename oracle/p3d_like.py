@@ -312,12 +312,14 @@ def point_light_diffuse(points, normals, light_location, diffuse_color):
 
 
 def mesh_laplacian_smoothing_uniform(verts, nbr_off, nbr_idx):
-    """Appendix A.11 with a CSR neighbour table; verts (B,V,3) -> scalar."""
+    """Appendix A.11 with a CSR neighbour table; verts (B,V,3) -> scalar.  A vertex of degree 0 has 1/deg = 0 (PyTorch3D's
+    laplacian_packed: deg > 0 ? 1 / deg : 0), so its row is -v and it adds |v| / V."""
     B, V, _ = verts.shape
     deg = (nbr_off[1:] - nbr_off[:-1]).to(verts.dtype)
+    inv_deg = torch.where(deg > 0, 1.0 / deg.clamp_min(1), torch.zeros_like(deg))
     row = torch.repeat_interleave(torch.arange(V), (nbr_off[1:] - nbr_off[:-1]).long())
     acc = torch.zeros_like(verts).index_add(1, row, verts[:, nbr_idx.long()])
-    lv = acc / deg[None, :, None] - verts
+    lv = acc * inv_deg[None, :, None] - verts
     return (lv.norm(dim=-1) / V).sum() / B
 
 

@@ -100,3 +100,15 @@ def test_building_blocks_refuse_empty_sizes_without_launch(lib):
     assert lib.harp_adam_step(f, f, f, f, 0, 1e-3, 0.9, 0.999, 1e-8, 1, 1.0, None) == 1
     assert lib.harp_kps_loss(f, None, f, 0, 21, f, f, f, None) == 1
     assert lib.harp_image_l1(f, f, None, None, 0, 12, 3, f, f, f, None) == 1
+    # mesh regularisers: B = 0 (grid y), V = 0 or V = -1 (grid x = (V + 511) / 512 or (V + 255) / 256 = 0); P < 0 / E < 0 would launch
+    for B, V in [(0, 4), (1, 0), (1, -1)]:
+        assert lib.harp_mesh_regularizers(f, f, f, f, f, f, f, B, V, 2, 5, f, f, f, None) == 1, (B, V)
+        assert lib.harp_mesh_kps_terms(f, f, f, f, f, f, f, B, V, 2, 5, f, f, f, f, None, f, 21, f, f, f, None) == 1, (B, V)
+    # skinning backward calls, B = 0 only (B = -1 gives a non-empty dim3(B)); the model struct is read on the host: a real one holding
+    # fake device pointers
+    from harp_amd import _lib
+    mano = _lib.ManoModel(*([f] * len(_lib.ManoModel._fields_)))
+    assert lib.harp_lbs_mano_bwd(ctypes.byref(mano), f, f, f, 0, f, f, f, f, f, f, None) == 1
+    tree = _lib.TreeModel(NV=1026, NJ=55, NB=20, n_pose_in=17, center_joint=21, n_joints_out=22,
+                          **{n: f for n, t in _lib.TreeModel._fields_ if t is ctypes.c_void_p})
+    assert lib.harp_lbs_tree_bwd(ctypes.byref(tree), f, f, f, 0, f, f, f, f, f, f, None) == 1

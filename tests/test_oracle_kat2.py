@@ -268,6 +268,22 @@ def test_laplacian_uniform_closed_form():
     assert pairs.shape[0] == 6                                                # six interior edges, boundary edges have no pair
 
 
+def test_laplacian_isolated_vertex_adds_its_norm():
+    # PyTorch3D's laplacian_packed takes 1/deg = 0 at a vertex of degree 0: its row is -v, which adds |v| / V (and not 0 * inf = NaN)
+    faces = np.array([[0, 1, 2], [1, 0, 3]])
+    off, idx, _ = _tables(faces, 5)                                           # vertex 4 is in no face
+    assert off[5] - off[4] == 0
+    v = torch.tensor([[[0.0, 0.0, 0.0], [2.0, 0.0, 0.0], [1.0, 3.0, 0.0], [1.0, -1.0, 2.0], [3.0, -4.0, 12.0]]], dtype=F64)
+    nb = {0: [1, 2, 3], 1: [0, 2, 3], 2: [0, 1], 3: [0, 1]}
+    rest = sum((v[0, nb[i]].mean(0) - v[0, i]).norm() for i in range(4))
+    vv = v.clone().requires_grad_()
+    got = P.mesh_laplacian_smoothing_uniform(vv, off, idx)
+    assert abs(got.item() - (rest.item() + 13.0) / 5.0) < 1e-12             # |(3, -4, 12)| = 13
+    got.backward()
+    assert torch.allclose(vv.grad[0, 4], v[0, 4] / 13.0 / 5.0, rtol=0, atol=1e-15)   # d|v|/dv / V: the row's own gradient only
+    assert torch.isfinite(vv.grad).all()
+
+
 def test_normal_consistency_closed_form_and_torch111_clamp():
     faces = np.array([[0, 1, 2], [1, 0, 3]])
     _, _, pairs = _tables(faces, 4)
