@@ -278,3 +278,9 @@ SIGNATURES.update({
     "harp_lpips_alex_ws_bytes": (_sz, [_i, _i, _i]),
     "harp_lpips_alex": (_i, [_vp, _vp, _vp, _ll, _ll, _ll, _ll, _i, _i, _i, _i, _vp, _vp, _vp]),
 })
+
+# normal image and uint8 panel strips of the post-fit pass (csrc/present.hip)
+SIGNATURES.update({
+    "harp_normal_image": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _f, ctypes.POINTER(_f), _vp, _ll, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "harp_panels_u8": (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_ll), _i, _vp, _vp, _i, _i, _i, _vp, _vp]),
+})

@@ -545,3 +545,114 @@ def lpips_alex(ref, pred, net, channels_last=True, normalize=False):
                                _lib.ptr(out), _lib.stream())
     _lib.check(rc, "harp_lpips_alex")
     return out
+
+
+# ------------------------------------------------------------------------------------------------------
+# what a fit is looked at with (csrc/present.hip): the K-fragment normal image and the uint8 panel strips
+# ------------------------------------------------------------------------------------------------------
+NORMAL_IMAGE_MAX_K = 16
+
+
+def normal_image(ndc, vnormals, faces, S, K=10, nmap=None, verts_uvs=None, faces_uvs=None, sigma=1e-4, gamma=1e-4, znear=1.0, zfar=100.0,
+                 background=(1.0, 1.0, 1.0), check_uvs=True):
+    """MeshRenderer(MeshRasterizer(K, blur 0), SoftPhongNormalShader) (renderer_helper.py:83-101, 216-301) in one kernel, forward only:
+    ndc (B,V,3) from ops.project, vnormals (B,V,3), faces (F,3) int32 -> (B,S,S,4) float32 as softmax_rgb_blend returns it.  nmap: the
+    NORMALISED normal map, (Ht,Wt,3) shared by the batch or (B,Ht,Wt,3), with verts_uvs (VT,2) / faces_uvs (F,3).  K = 1..16.  No tensor
+    with a fragment dimension is allocated: output + the rasteriser workspace is all."""
+    check_forward_only(ndc, vnormals, *([nmap] if nmap is not None else []))
+    if not (ndc.is_cuda and vnormals.is_cuda and faces.is_cuda):
+        raise RuntimeError("harp_amd ops need HIP device tensors (no CPU path)")
+    B, V, _ = ndc.shape
+    if vnormals.shape != ndc.shape:
+        raise ValueError(f"vnormals {tuple(vnormals.shape)} must match ndc {tuple(ndc.shape)}")
+    if not 1 <= int(K) <= NORMAL_IMAGE_MAX_K:
+        raise ValueError(f"normal_image keeps 1 to {NORMAL_IMAGE_MAX_K} fragments per pixel, got K = {K}")
+    ndc, vnormals = _f32(ndc.detach()), _f32(vnormals.detach())
+    dev = ndc.device
+    Fn = faces.shape[0]
+    stride, Ht, Wt = 0, 0, 0
+    if nmap is not None:
+        if verts_uvs is None or faces_uvs is None:
+            raise ValueError("a normal map needs verts_uvs and faces_uvs")
+        nmap = _f32(nmap.detach())
+        if nmap.dim() == 4 and nmap.shape[0] == 1:
+            nmap = nmap[0]
+        if nmap.dim() == 4:
+            if nmap.shape[0] != B:
+                raise ValueError(f"{nmap.shape[0]} normal maps for a batch of {B}")
+            stride = nmap.shape[1] * nmap.shape[2] * 3
+        if nmap.shape[-1] != 3:
+            raise ValueError(f"normal map {tuple(nmap.shape)}: 3 channels last")
+        Ht, Wt = nmap.shape[-3], nmap.shape[-2]
+        verts_uvs = _f32(verts_uvs).reshape(-1, 2)
+        faces_uvs = faces_uvs.to(torch.int32).reshape(-1, 3).contiguous()
+        if faces_uvs.shape[0] != Fn:
+            raise ValueError(f"faces_uvs has {faces_uvs.shape[0]} rows for {Fn} faces")
+        if check_uvs:                                      # the kernel reads verts_uvs[faces_uvs] without a bounds check
+            lo, hi = int(faces_uvs.min()), int(faces_uvs.max())
+            if lo < 0 or hi >= verts_uvs.shape[0]:
+                raise ValueError(f"faces_uvs must index verts_uvs ({verts_uvs.shape[0]} rows): found indices in [{lo}, {hi}]")
+    ws = rasterize_workspace(B, Fn, int(S), dev)
+    out = torch.empty(B, S, S, 4, dtype=torch.float32, device=dev)
+    bg = (ctypes.c_float * 3)(*[float(x) for x in background])
+    with torch.cuda.device(dev):
+        rc = _lib.lib().harp_normal_image(_lib.ptr(ndc), _lib.ptr(vnormals), _lib.ptr(faces), B, V, Fn, int(S), int(K), float(sigma), float(gamma),
+                                          float(znear), float(zfar), bg, _lib.ptr(nmap), stride, Ht, Wt, _lib.ptr(verts_uvs), _lib.ptr(faces_uvs),
+                                          _lib.ptr(ws), _lib.ptr(out), _lib.stream())
+    _lib.check(rc, "harp_normal_image")
+    return out
+
+
+def panels_u8(images, mask_true=None, mask_pred=None, channels_last=True):
+    """The uint8 strip of optimize_sequence.py:744-755 on the device: `images` = up to three float32 HIP images (N,H,W,C >= 3) (or
+    (N,C,H,W) with channels_last=False), read in place through their strides, each a panel uint8(trunc(clip(x, 0, 1) * 255)) of its first
+    three channels; with both masks (N,H,W[,1]) one more panel (uint8(trunc(m_true * 225)), 0, uint8(trunc(m_pred * 225))).  Returns
+    (N, H, P * W, 3) uint8 on the device — bit for bit what numpy gives.  One image and no masks: the clip * 255 -> uint8 of a render."""
+    if torch.is_tensor(images):
+        images = [images]
+    images = list(images)
+    if len(images) > 3:
+        raise ValueError(f"at most three colour panels, got {len(images)}")
+    if (mask_true is None) != (mask_pred is None):
+        raise ValueError("pass both masks or neither")
+    if not images and mask_true is None:
+        raise ValueError("no panel to write")
+    first = images[0] if images else mask_true
+    if not first.is_cuda:
+        raise RuntimeError("harp_amd ops need HIP device tensors (no CPU path)")
+    dev = first.device
+    shape = None
+    ptrs, strides = [], []
+    for im in images:
+        if not im.is_cuda:
+            raise RuntimeError("harp_amd ops need HIP device tensors (no CPU path)")
+        if im.dtype != torch.float32 or im.dim() != 4:
+            raise TypeError(f"panels_u8 takes 4-D float32 images, got {im.dtype} {tuple(im.shape)}")
+        im = im.detach()
+        if min(im.stride()) < 0:
+            im = im.contiguous()
+        N, H, W, C = im.shape if channels_last else (im.shape[0], im.shape[2], im.shape[3], im.shape[1])
+        if C < 3:
+            raise ValueError(f"a colour panel needs 3 channels, got {C}")
+        if shape is not None and shape != (N, H, W):
+            raise ValueError(f"panels of different sizes: {shape} and {(N, H, W)}")
+        shape = (N, H, W)
+        s = im.stride()
+        strides += [s[0], s[1], s[2], s[3]] if channels_last else [s[0], s[2], s[3], s[1]]
+        ptrs.append(im)
+    masks = (None, None)
+    if mask_true is not None:
+        n = mask_true.shape[0]
+        masks = tuple(m.detach().reshape(n, m.shape[1], m.shape[2]).to(device=dev, dtype=torch.float32).contiguous() for m in (mask_true, mask_pred))
+        if shape is not None and tuple(masks[0].shape) != shape or masks[0].shape != masks[1].shape:
+            raise ValueError(f"masks {tuple(masks[0].shape)} / {tuple(masks[1].shape)} do not match the images {shape}")
+        shape = tuple(masks[0].shape)
+    N, H, W = shape
+    P = len(ptrs) + (masks[0] is not None)
+    out = torch.empty(N, H, P * W, 3, dtype=torch.uint8, device=dev)
+    pa = (ctypes.c_void_p * max(1, len(ptrs)))(*[t.data_ptr() for t in ptrs])
+    sa = (ctypes.c_longlong * max(1, len(strides)))(*strides)
+    with torch.cuda.device(dev):
+        rc = _lib.lib().harp_panels_u8(pa, sa, len(ptrs), _lib.ptr(masks[0]), _lib.ptr(masks[1]), N, H, W, _lib.ptr(out), _lib.stream())
+    _lib.check(rc, "harp_panels_u8")
+    return out

@@ -87,9 +87,9 @@ def stage_flags(epoch_id, training_stage):
 def optimize_hand_sequence(configs, input_params, images_dataset, val_params, val_images_dataset, hand_layer,
                            VERTS_UVS=None, FACES_UVS=None, VERTS_COLOR=None, device="cuda", uv_mask=None, batch_size=18, log_fn=None,
                            seed=0, vgg=None, rank=None, world_size=None, shards=None, plateau_patience=40, plateau_threshold=1e-4, device_schedule=True,
-                           evaluate=False):
+                           evaluate=False, panels=False, turntable=False):
     """Fit the sequence (optimize_sequence.py:313-596).  Returns the parameter dict in the reference's checkpoint layout; evaluate=True
-    then runs the post-fit evaluation `evaluate_sequence` (:595-816) on rank 0 (off by default).
+    then runs the post-fit evaluation `evaluate_sequence` (:595-816) on rank 0 (off by default), with its panels / turntable switches.
     `images_dataset[i]` -> (fid, y_true (S,S,3), y_sil (S,S,1), y_sil_eroded (S,S,1)) like utils/data_util.ImagesDataset.
 
     Data-parallel (the reference is single-device): launched under `torch.distributed.run` (or with rank / world_size given)
@@ -219,14 +219,15 @@ def optimize_hand_sequence(configs, input_params, images_dataset, val_params, va
             torch.cuda.synchronize(eng.dev)
             comm.destroy()                                           # drops the step graphs that captured it
     if evaluate and rank == 0:
-        evaluate_sequence(configs, params, images_dataset, hand_layer, device=device, uv_mask=uv_mask)
+        evaluate_sequence(configs, params, images_dataset, hand_layer, device=device, uv_mask=uv_mask, panels=panels, turntable=turntable)
     return params
 
 
 EVAL_CHUNK = 64                  # optimize_sequence.py:716: image_eval runs on every 64 frames; the final stats are means of the chunk means
 
 
-def evaluate_sequence(configs, params, images_dataset, hand_layer, device="cuda", batch_size=32, uv_mask=None, lpips_fn=None):
+def evaluate_sequence(configs, params, images_dataset, hand_layer, device="cuda", batch_size=32, uv_mask=None, lpips_fn=None, panels=False,
+                      turntable=False, panel_hook=None):
     """The post-fit evaluation of optimize_sequence.py:595-816: re-render every dataset item in order with the fitted `params` through the
     reference-API mirror (silhouette: get_renderers(silh_sigma=1e-7, silh_faces_per_pixel=50)[1]; image: render_image_with_RT through
     get_shadow_renderers with self_shadow, else render_image with the phong renderer), `batch_size` frames per render call; per-frame
@@ -238,8 +239,12 @@ def evaluate_sequence(configs, params, images_dataset, hand_layer, device="cuda"
     (a combined lpips.LPIPS state-dict path, or a (torchvision alexnet, lpips v0.1 head) path pair): per frame on the same y_true / y_pred,
     [0, 1] images without `normalize` as the reference passes them, averaged like the others and written in the reference's key order (IoU,
     L1, LPIPS, MS_SSIM); without either the output has no LPIPS line (the weights cannot be shipped).  Left out: MS_SSIM with a warning when
-    the image side is <= 160 px (the reference would fail pytorch_msssim's assertion there); the rendered_after_opt panels and the
-    turntables."""
+    the image side is <= 160 px (the reference would fail pytorch_msssim's assertion there).
+    What the reference writes for the eye is off by default and leaves metrics and files as they are when off.  panels=True: per batch one
+    more prepare_mesh(vis_normal=True) + normal render (:710-714), one ops.panels_u8 and one `true | pred | normal | overlay` JPEG per frame,
+    rendered_after_opt[_test]/<fid %04d>.jpg (:742-757); panel_hook(fid, strip), if given, sees every (S, 4S, 3) uint8 strip before it is
+    encoded.  turntable=True: for the dataset item whose fid is 0 (:716-727) render_360 with the phong and the normal renderer,
+    concat_image_in_dir into render_360_combine and render_360_light, each with its out.gif."""
     import os
     import warnings
     import torch.nn.functional as F
@@ -248,7 +253,8 @@ def evaluate_sequence(configs, params, images_dataset, hand_layer, device="cuda"
     from .renderer import renderer_helper
     from .structures import Meshes
     from .utils.eval_util import align_w_scale, load_gt_vert, sil_iou
-    from .utils.visualize import prepare_materials, prepare_mesh, render_image, render_image_with_RT
+    from .utils.visualize import (concat_image_in_dir, prepare_materials, prepare_mesh, render_360, render_360_light, render_image,
+                                  render_image_with_RT)
     S, focal = int(configs["img_size"]), configs["focal_length"]
     base = configs["base_output_dir"]
     test_name = "_test" if configs["known_appearance"] else ""
@@ -278,6 +284,9 @@ def evaluate_sequence(configs, params, images_dataset, hand_layer, device="cuda"
     if lpips_fn is not None and not with_lpips:
         warnings.warn(f"LPIPS left out of the evaluation: {S} px images (AlexNet needs a side >= {ops.LPIPS_MIN_SIDE})")
     iou, l1, ms, lp, vert_err = [], [], [], [], []
+    panel_dir = os.path.join(base, "rendered_after_opt" + test_name)
+    if panels:
+        os.makedirs(panel_dir, exist_ok=True)                      # :660
     n = len(images_dataset)
     with torch.no_grad():
         for lo in range(0, n, batch_size):
@@ -291,7 +300,7 @@ def evaluate_sequence(configs, params, images_dataset, hand_layer, device="cuda"
                 light_positions = P["light_positions"][0].repeat(B, 1)
             else:
                 light_positions = P["light_positions"][fd]
-            phong_renderer, silhouette_renderer, _ = renderer_helper.get_renderers(
+            phong_renderer, silhouette_renderer, normal_renderer = renderer_helper.get_renderers(
                 image_size=S, light_posi=light_positions, silh_sigma=1e-7, silh_gamma=1e-1, silh_faces_per_pixel=50, device=device)
             _, hand_verts, faces, textures = prepare_mesh(P, fid, hand_layer, False, sub, False, configs, device=device, use_arm=use_arm)
             materials_properties = prepare_materials(P, B, device=device)
@@ -309,6 +318,27 @@ def evaluate_sequence(configs, params, images_dataset, hand_layer, device="cuda"
                 y_pred = render_image(meshes, cam, B, phong_renderer, S, focal, silhouette=False, materials_properties=materials_properties,
                                       device=device)
             y_pred = y_pred.float()
+            if panels:                                # :710-714, :742-757
+                _, verts_n, faces_n, textures_n = prepare_mesh(P, fid, hand_layer, False, sub, False, configs, device=device, vis_normal=True,
+                                                               use_arm=use_arm)
+                y_pred_normal = render_image(Meshes(verts_n, faces_n, textures_n), cam, B, normal_renderer, S, focal, silhouette=False,
+                                             materials_properties=materials_properties, device=device)
+                strips = ops.panels_u8([y_true, y_pred, y_pred_normal], y_sil_true, y_sil_pred).cpu().numpy()
+                for b in range(B):
+                    if panel_hook is not None:
+                        panel_hook(int(fid[b]), strips[b])
+                    Image.fromarray(strips[b]).save(os.path.join(panel_dir, "%04d.jpg" % int(fid[b])))
+            if turntable and bool((fid == 0).any()):   # :716-727: one frame turned through 360 degrees and lit from 40 positions
+                i0 = int((fid == 0).nonzero()[0])
+                f0 = fid[i0:i0 + 1]
+                phong0, _, normal0 = renderer_helper.get_renderers(image_size=S, light_posi=light_positions[i0:i0 + 1], silh_sigma=1e-7,
+                                                                   silh_gamma=1e-1, silh_faces_per_pixel=50, device=device)
+                kw360 = dict(configs=configs, use_arm=use_arm, verts_textures=False, mesh_subdivider=sub, global_pose=False, save_img_dir=base,
+                             device=device)
+                render_360(P, f0, phong0, S, focal, hand_layer, **kw360)
+                render_360(P, f0, normal0, S, focal, hand_layer, render_normal=True, **kw360)
+                concat_image_in_dir(os.path.join(base, "render_360"), os.path.join(base, "render_360_normal"), os.path.join(base, "render_360_combine"))
+                render_360_light(P, f0, hand_verts[i0:i0 + 1], faces, textures, S, focal, save_img_dir=base, device=device)
             if with_ms:
                 m = ops.image_metrics(y_true, y_pred, y_sil_true, y_sil_pred)
                 iou.append(m["iou"].cpu())
@@ -373,6 +403,8 @@ def main(argv=None):
     ap.add_argument("--config", required=True, help="yaml with the keys of utils/config_utils.get_config")
     ap.add_argument("--batch-size", type=int, default=18)
     ap.add_argument("--eval", action="store_true", help="after the fit, the evaluation of optimize_sequence.py:595-816 (evaluate_sequence)")
+    ap.add_argument("--panels", action="store_true", help="with --eval: one true | pred | normal | overlay JPEG per frame under rendered_after_opt/")
+    ap.add_argument("--turntable", action="store_true", help="with --eval: render_360/, render_360_normal/, render_360_combine/ and render_360_light/ of frame 0")
     ap.add_argument("--lpips-weights", nargs="+", default=None, metavar="PATH",
                     help="LPIPS in the evaluation: one lpips.LPIPS(net='alex') state dict, or torchvision's alexnet state dict and the lpips "
                          "v0.1 alex head (configs['lpips_weights'])")
@@ -399,7 +431,8 @@ def main(argv=None):
         configs["metro_output_dir"], configs["image_dir"], train_list=configs["train_list"], val_list=configs["val_list"],
         average_cam_sequence=configs["average_cam_sequence"], use_smooth_seq=configs["use_smooth_seq"], model_type=configs["model_type"])
     params = optimize_hand_sequence(configs, mano_params, images_dataset, val_mano_params, val_images_dataset, hand_layer, VERTS_UVS, FACES_UVS,
-                                    VERTS_COLOR, device=device, batch_size=args.batch_size, evaluate=args.eval)
+                                    VERTS_COLOR, device=device, batch_size=args.batch_size, evaluate=args.eval, panels=args.panels,
+                                    turntable=args.turntable)
     if world > 1:
         tdist.barrier()
         tdist.destroy_process_group()

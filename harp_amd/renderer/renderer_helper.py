@@ -199,22 +199,49 @@ def apply_normal_map(pixel_normals, nm):
 class NormalRenderer:
     """MeshRenderer(MeshRasterizer(K=10, blur 0), SoftPhongNormalShader) (renderer_helper.py:82-101, 192-258): the interpolated vertex
     normals (through the normal map when the materials carry one), y / z flipped, mapped to [0,1], softmax-blended over the K=10
-    fragments.  Visualisation only in the reference (`vis_normal`), hence plain torch ops over the fragment-level rasteriser."""
+    fragments.  Visualisation only in the reference (`vis_normal`).  Without an autograd graph to build it is one ops.project + one
+    ops.normal_image (csrc/present.hip: no fragment tensor exists); with one (the vertices or the map require grad while grad mode is on),
+    or for K > 16, the differentiable torch ops over the fragment-level rasteriser."""
 
     def __init__(self, image_size, faces_per_pixel=10):
         self.rasterizer = MeshRasterizer(image_size, 0.0, faces_per_pixel)
 
     def __call__(self, mesh, materials=None, **kw):
+        use_map = materials is not None and getattr(materials, "use_normal_map", False)
+        K = self.rasterizer.faces_per_pixel
+        needs_graph = torch.is_grad_enabled() and (mesh.verts_padded().requires_grad or
+                                                   (use_map and materials.normal_maps.maps_padded().requires_grad))
+        if not needs_graph and K <= ops.NORMAL_IMAGE_MAX_K:
+            return self._fused(mesh, materials if use_map else None, **kw)
         fr = self.rasterizer(mesh, **kw)
         B = len(mesh)
         faces = mesh.topo.faces.long()
         vn = mesh.verts_normals_padded()
         fn = vn[:, faces].reshape(B * faces.shape[0], 3, 3)
         pix_n = interpolate_face_attributes(fr.pix_to_face, fr.bary_coords, fn)
-        if materials is not None and getattr(materials, "use_normal_map", False):                  # renderer_helper.py:226-232 (`vis_normal`)
+        if use_map:                                                                                # renderer_helper.py:226-232 (`vis_normal`)
             pix_n = apply_normal_map(pix_n, sample_textures_uv(materials.normal_maps, fr, faces.shape[0]))
         pix_n = pix_n * torch.tensor([1.0, -1.0, -1.0], device=pix_n.device)                    # renderer_helper.py:211-212
         return softmax_rgb_blend((pix_n + 1.0) / 2.0, fr)                                          # :213, :255-257
+
+    def _fused(self, mesh, materials, principal_point=None, focal_length=None, T=None, R=None, image_size=None, **kw):
+        S = _size(image_size) if image_size is not None else self.rasterizer.image_size
+        dev = mesh.device
+        pp = _pp(principal_point) if principal_point is not None else (S / 2.0, S / 2.0)
+        with torch.no_grad():
+            ndc = ops.project(mesh.verts_padded(), R.to(dev), T.to(dev), _scalar(focal_length), S, pp)
+            vn = mesh.verts_normals_padded()
+            nmap = vuv = fuv = None
+            if materials is not None:
+                tex = materials.normal_maps
+                nmap = tex.maps_padded()
+                if nmap.shape[0] > 1 and nmap.stride(0) == 0:                                      # an expanded shared map: read it once
+                    nmap = nmap[0]
+                topo = mesh.topo
+                topo.set_uvs(tex.verts_uvs, tex.faces_uvs)                                         # (checks the index range once per table)
+                vuv, fuv = topo.verts_uvs, topo.faces_uvs
+            return ops.normal_image(ndc, vn, mesh.topo.faces, S, self.rasterizer.faces_per_pixel, nmap=nmap, verts_uvs=vuv, faces_uvs=fuv,
+                                    check_uvs=False)
 
 
 def get_renderers(image_size, light_posi=((1.0, 1.0, -5.0),), silh_sigma=1e-7, silh_gamma=1e-1, silh_faces_per_pixel=50, device="cuda"):

@@ -1,5 +1,13 @@
-"""Mirror of the scene-assembly half of utils/visualize.py (prepare_mesh :16-88, prepare_materials :91-108, render_image
-:258-285, render_image_with_RT :288-319).  The turntable / gif helpers are offline visualisation (out of scope)."""
+"""Mirror of utils/visualize.py: the scene assembly (prepare_mesh :16-88, prepare_materials :91-108, render_image :258-285,
+render_image_with_RT :288-319) and the playback helpers of the post-fit pass (change_pose :111-142, render_360 :145-196,
+render_360_light :199-228, concat_image_in_dir :322-345, save_gif :349-355) with the reference's signatures, directory and file names.
+A turntable is rendered as ONE batch of 72 (or 40) views and quantised on the device (ops.panels_u8); the helpers also return the uint8
+stack they wrote (the reference returns None).  `render_with_rotation` is left out: the reference marks it "Currently not used" and it
+reads an undefined `idx`."""
+import glob
+import os
+
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -114,3 +122,139 @@ def render_image_with_RT(mesh, light_t, light_r, cam_t, cam_r, batch_size, rende
                    R=light_r.to(device), cam_T=cam_t.to(device), cam_R=cam_r.to(device), materials=materials,
                    image_size=torch.Tensor([(img_size, img_size)]))
     return img[:, :, :, 3] if silhouette else img[:, :, :, 0:3]
+
+
+# the demo pose of change_pose (utils/visualize.py:117-140): 15 joints x 3 axis-angle components, index, middle, pinky, ring, thumb
+DEMO_POSE = (0.0, -0.3, 0.7, 0.0, 0.0, -0.1, 0.0, 0.0, 0.0,
+             0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0,
+             0.0, 0.0, 0.0, 0.2, 0.0, -0.6, -0.0, 0.0, 0.0,
+             0.0, -0.2, 0.8, 0.0, 0.0, 0.8, 0.0, 0.0, 0.0,
+             0.5, 0.5, 0.1, 0.6, -0.7, 1.0, 0.0, -1.0, 0.1)
+
+
+def change_pose(params, idx):
+    """utils/visualize.py:111-142: frame 0's 45 finger-pose numbers become the demo pose (`idx` is unused there too)"""
+    with torch.no_grad():
+        params["pose"][0][0:45] = torch.tensor(DEMO_POSE, dtype=params["pose"].dtype, device=params["pose"].device)
+    return params
+
+
+def _axis_rotation(axis, degrees, device):
+    """RotateAxisAngle(degrees, axis).get_matrix()[:, :3, :3] of pytorch3d (row vectors: p' = p @ M), float32"""
+    a = torch.tensor(float(degrees), dtype=torch.float32, device=device) / 180.0 * np.pi
+    c, s, one, zero = torch.cos(a), torch.sin(a), torch.ones((), device=device), torch.zeros((), device=device)
+    rows = {"X": (one, zero, zero, zero, c, -s, zero, s, c), "Y": (c, zero, s, zero, one, zero, -s, zero, c),
+            "Z": (c, -s, zero, s, c, zero, zero, zero, one)}[axis]
+    return torch.stack(rows).reshape(3, 3).t()
+
+
+def turntable_vertices(hand_verts):
+    """The 36 + 36 vertex sets of render_360 (:164-194) for the first mesh of `hand_verts` (B,V,3) -> (72,V,3): 10 degrees about Y applied
+    cumulatively to the already rotated vertices in float32, about the centroid of the UNROTATED mesh, then 10 degrees about X continuing
+    from where the Y sweep ended."""
+    v = hand_verts[0:1].detach().float()
+    center = v.mean(dim=1, keepdim=True)
+    out = []
+    for axis in ("Y", "X"):
+        M = _axis_rotation(axis, 10, v.device)
+        for _ in range(36):
+            v = torch.matmul(v - center, M) + center
+            out.append(v[0])
+    return torch.stack(out)
+
+
+def _write_frames(u8, out_dir, names):
+    from PIL import Image
+    frames = u8.cpu().numpy()
+    for img, name in zip(frames, names):
+        Image.fromarray(img).save(os.path.join(out_dir, name))
+    return frames
+
+
+def _first_light(renderer, n):
+    """the turntable renders n views of ONE frame: a renderer built for a batch keeps its first frame's light"""
+    lp = torch.as_tensor(getattr(renderer, "light_posi", ((0.0, 0.0, 0.0),)), dtype=torch.float32).reshape(-1, 3)
+    if lp.shape[0] in (1, n) or not hasattr(renderer, "light_posi"):
+        return renderer
+    import copy
+    r = copy.copy(renderer)
+    r.light_posi = lp[0:1]
+    return r
+
+
+def render_360(params, fid, renderer, img_size, focal_length, mano_layer, configs, render_normal=False, verts_textures=True,
+               mesh_subdivider=None, global_pose=False, global_betas=True, device="cuda", save_img_dir=None, use_arm=False):
+    """utils/visualize.py:145-196: frame fid[0] turned about its centroid, 36 views about Y (`%04d.jpg`) then 36 about X (`h_%04d.jpg`)
+    plus out.gif, under save_img_dir/render_360 (render_360_normal with render_normal).  All 72 views go through `renderer` as one batch.
+    Returns the (72,S,S,3) uint8 stack that was written."""
+    fid = torch.as_tensor(fid).long().reshape(-1)
+    out_dir = os.path.join(save_img_dir, "render_360_normal" if render_normal else "render_360")
+    os.makedirs(out_dir, exist_ok=True)
+    with torch.no_grad():
+        _, hand_verts, faces, textures = prepare_mesh(params, fid[0:1], mano_layer, verts_textures, mesh_subdivider, global_pose, configs=configs,
+                                                      device=device, use_arm=use_arm)
+        materials_properties = prepare_materials(params, 1, device=device)
+        verts = turntable_vertices(hand_verts)
+        n = verts.shape[0]
+        cam = params["cam"][fid[0:1].to(params["cam"].device)].to(device).expand(n, -1)
+        img = render_image(Meshes(verts, faces, textures), cam, n, _first_light(renderer, n), img_size, focal_length, device=device,
+                           materials_properties=materials_properties)
+        u8 = ops.panels_u8(img)
+    frames = _write_frames(u8, out_dir, ["%04d.jpg" % i for i in range(36)] + ["h_%04d.jpg" % i for i in range(36)])
+    save_gif(out_dir, os.path.join(out_dir, "out.gif"))
+    return frames
+
+
+def light_sweep_positions(num=40, start=-5.0, end=5.0):
+    """the light positions (1, 1, z_k), z_k = start + (end - start) / num * k, of render_360_light (:208-214)"""
+    return torch.tensor([(1.0, 1.0, start + (end - start) / num * k) for k in range(num)], dtype=torch.float32)
+
+
+def render_360_light(params, fid, hand_verts, faces, textures, img_size, focal_length, save_img_dir=None, device="cuda"):
+    """utils/visualize.py:199-228: 40 phong renders (no shadow pass, no normal map, as in the reference) of the first mesh with the light
+    swept from z = -5 towards +5, `%04d.jpg` + out.gif under save_img_dir/render_360_light, rendered as one batch.  Returns the
+    (40,S,S,3) uint8 stack that was written."""
+    from ..renderer import renderer_helper
+    fid = torch.as_tensor(fid).long().reshape(-1)
+    out_dir = os.path.join(save_img_dir, "render_360_light")
+    os.makedirs(out_dir, exist_ok=True)
+    lights = light_sweep_positions()
+    n = lights.shape[0]
+    with torch.no_grad():
+        cam = params["cam"][fid[0:1].to(params["cam"].device)].to(device).expand(n, -1)
+        phong_renderer, _, _ = renderer_helper.get_renderers(image_size=img_size, light_posi=lights, silh_sigma=1e-7, silh_gamma=1e-1,
+                                                             silh_faces_per_pixel=50, device=device)
+        topo = getattr(faces, "_harp_topo", None)
+        mesh = Meshes(hand_verts[0:1].detach().float().expand(n, -1, -1).contiguous(), faces, textures, topo)
+        u8 = ops.panels_u8(render_image(mesh, cam, n, phong_renderer, img_size, focal_length, device=device))
+    frames = _write_frames(u8, out_dir, ["%04d.jpg" % i for i in range(n)])
+    save_gif(out_dir, os.path.join(out_dir, "out.gif"))
+    return frames
+
+
+def _images_in(d):
+    return sorted(os.path.join(d, f) for f in os.listdir(d) if f.endswith(".png") or f.endswith(".jpg"))
+
+
+def concat_image_in_dir(dir1, dir2, out_dir):
+    """utils/visualize.py:322-345: the sorted .png / .jpg files of two directories side by side, pair by pair (the longer directory's
+    surplus is ignored), as `%04d.jpg` + out.gif under out_dir.  Returns the list of uint8 strips."""
+    from PIL import Image
+    os.makedirs(out_dir, exist_ok=True)
+    strips = []
+    for idx, (f1, f2) in enumerate(zip(_images_in(dir1), _images_in(dir2))):
+        strip = np.concatenate([np.asarray(Image.open(f1).convert("RGB")), np.asarray(Image.open(f2).convert("RGB"))], axis=1).astype(np.uint8)
+        Image.fromarray(strip).save(os.path.join(out_dir, "%04d.jpg" % idx))
+        strips.append(strip)
+    save_gif(out_dir, os.path.join(out_dir, "out.gif"))
+    return strips
+
+
+def save_gif(in_dir, outname):
+    """utils/visualize.py:349-355 (imageio.mimsave(duration=0.1)) with PIL: the sorted *.jpg of in_dir, 100 ms per frame"""
+    from PIL import Image
+    frames = [Image.open(f).convert("RGB") for f in sorted(glob.glob(os.path.join(in_dir, "*.jpg")))]
+    if not frames:
+        raise ValueError(f"no *.jpg under {in_dir}")
+    frames[0].save(outname, save_all=True, append_images=frames[1:], duration=100, loop=0)
+    return len(frames)

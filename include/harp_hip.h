@@ -803,6 +803,38 @@ size_t harp_lpips_alex_ws_bytes(int N, int H, int W);
 int harp_lpips_alex(const void* net, const float* ref, const float* pred, long long sn, long long sc, long long sy, long long sx, int N,
                     int H, int W, int normalize, void* ws, float* out, hipStream_t stream);
 
+/* ---- what a fit is looked at with: normal image and uint8 panel strips (csrc/present.hip) -------------------------------------------
+ * harp_normal_image replaces MeshRenderer(MeshRasterizer(faces_per_pixel = K, blur_radius = 0), SoftPhongNormalShader) as built at
+ * renderer/renderer_helper.py:83-101 and run at :216-301 (called from optimize_sequence.py:710-714 for every frame and from
+ * utils/visualize.py:172, 188 for the normal turntable), forward only, in one pass: no (B,S,S,K) fragment buffer is read or written.
+ *   ndc (B,V,3) camera-view (x_ndc, y_ndc, z_view) as harp_project_fwd writes them; vnormals (B,V,3); faces (F,3);
+ *   ws: harp_rasterize_ws_bytes(B, F, S) bytes, no initial contents (the face set-up of harp_rasterize_fragments_fwd runs first).
+ *   Per pixel: the candidates of harp_rasterize_fragments_fwd with blur_radius = 0 (pixel centre inside the face, pz >= 0), the K
+ *   nearest by pz kept, ties keep the lower face index; per kept fragment the interpolated vertex normal (perspective-correct
+ *   barycentrics, not clipped, not normalised) — with nmap: the bilinear sample (align_corners = True, border padding, v flipped) of the
+ *   NORMALISED map at the interpolated uv through PBRMaterials.apply_normal_map (pbr_materials.py:58-124: n' = normalize(-u m.x - v m.y
+ *   + n m.z)) — then (x, -y, -z), (. + 1) / 2, and pytorch3d's softmax_rgb_blend(sigma, gamma, znear, zfar, background).
+ *   nmap: NULL or (Ht,Wt,3) float32 maps, frame b reading nmap + b * nmap_frame_stride (elements; 0: one shared map), which then needs
+ *   verts_uvs (VT,2) and faces_uvs (F,3) (indices are NOT bounds-checked).  background: 3 HOST floats.
+ *   out (B,S,S,4) float32: blended rgb, alpha = 1 - prod(1 - prob).  A pixel without a fragment is exactly (background, 0).
+ *   Deterministic: no atomics.  Returns HARP_ERR_ARG without launching for NULL ndc / vnormals / faces / background / ws / out,
+ *   B outside 1..65535, V, F, S <= 0, K outside 1..16, sigma or gamma <= 0, zfar <= znear, a map without uvs or with Ht, Wt <= 0.
+ * harp_panels_u8 replaces the host statement of optimize_sequence.py:744-755 (clip, * 255, concatenate, astype(uint8)) and the
+ * clip * 255 -> uint8 of every turntable frame (utils/visualize.py:174-175, 190-191, 222-223): out (N, H, P * W, 3) uint8 with
+ * P = n_images + (masks ? 1 : 0) panels side by side.
+ *   images: n_images (0..3) HOST pointers to device float32 images, read in place; strides: 4 HOST element strides per image
+ *   (image, row, column, channel): an (N,H,W,3) render is (3HW, 3W, 3, 1), the rgb of an (N,H,W,4) normal image (4HW, 4W, 4, 1), NCHW
+ *   (3HW, W, 1, HW).  Colour panels: uint8(trunc(clip(x, 0, 1) * 255)), the product in float32 as numpy forms it.
+ *   mask_true / mask_pred: both or neither, (N,H,W) contiguous float32; they give the last panel (uint8(trunc(m_true * 225)), 0,
+ *   uint8(trunc(m_pred * 225))), the product in float64 as numpy forms it (225 is the reference's factor), saturating outside [0, 255].
+ *   Returns HARP_ERR_ARG without launching for NULL out, n_images outside 0..3, a NULL image / strides, a negative stride, one mask without
+ *   the other, no panel at all, N, H, W <= 0. */
+int harp_normal_image(const float* ndc, const float* vnormals, const int32_t* faces, int B, int V, int F, int S, int K, float sigma, float gamma,
+                      float znear, float zfar, const float* background, const float* nmap, long long nmap_frame_stride, int Ht, int Wt,
+                      const float* verts_uvs, const int32_t* faces_uvs, void* ws, float* out, hipStream_t stream);
+int harp_panels_u8(const float* const* images, const long long* strides, int n_images, const float* mask_true, const float* mask_pred, int N,
+                   int H, int W, unsigned char* out, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
