@@ -135,7 +135,7 @@ extern "C" {
 int harp_frame_setup_fwd(const harp_frame_tables* t, const int32_t* fid, int B, int S, float focal, int self_shadow, float* pose48,
                          float* betas, float* trans_b, float* cam_R, float* cam_T, float* light_pos, float* colors,
                          hipStream_t stream) {
-  if (!t || !fid || !pose48 || !betas || !trans_b || !cam_R || !cam_T || !light_pos || !colors) return HARP_ERR_ARG;
+  if (!t || !fid || !pose48 || !betas || !trans_b || !cam_R || !cam_T || !light_pos || !colors || B <= 0) return HARP_ERR_ARG;
   hipLaunchKernelGGL(frame_setup_fwd_kernel, dim3((B + 63) / 64), dim3(64), 0, stream, *t, fid, B, S, focal, self_shadow, pose48, betas,
                      trans_b, cam_R, cam_T, light_pos, colors);
   HARP_CHECK_LAUNCH();
@@ -145,7 +145,7 @@ int harp_frame_setup_fwd(const harp_frame_tables* t, const int32_t* fid, int B, 
 int harp_frame_setup_bwd(const harp_frame_tables* t, const int32_t* fid, int B, int S, float focal, int self_shadow,
                          const float* g_pose48, const float* g_betas, const float* g_trans_b, const float* g_cam_T,
                          const float* g_light_pos, const float* g_colors, hipStream_t stream) {
-  if (!t || !fid) return HARP_ERR_ARG;
+  if (!t || !fid || B <= 0) return HARP_ERR_ARG;
   hipLaunchKernelGGL(frame_setup_bwd_kernel, dim3(B), dim3(64), 0, stream, *t, fid, B, S, focal, self_shadow, g_pose48,
                      g_betas, g_trans_b, g_cam_T, g_light_pos, g_colors);
   HARP_CHECK_LAUNCH();
@@ -153,7 +153,7 @@ int harp_frame_setup_bwd(const harp_frame_tables* t, const int32_t* fid, int B, 
 }
 
 int harp_light_setup_fwd(const float* centroid, const float* light_pos, int B, float* light_R, float* light_T, hipStream_t stream) {
-  if (!centroid || !light_pos || !light_R || !light_T) return HARP_ERR_ARG;
+  if (!centroid || !light_pos || !light_R || !light_T || B <= 0) return HARP_ERR_ARG;
   hipLaunchKernelGGL(light_setup_kernel<false>, dim3((B + 63) / 64), dim3(64), 0, stream, centroid, light_pos, B, light_R, light_T,
                      nullptr, nullptr, nullptr, nullptr);
   HARP_CHECK_LAUNCH();
@@ -163,7 +163,7 @@ int harp_light_setup_fwd(const float* centroid, const float* light_pos, int B, f
 // g_light_pos (B,3) (+=); g_centroid (B,3) overwritten; then g_verts (B,V,3) (+=) g_centroid / V if g_verts != NULL
 int harp_light_setup_bwd(const float* centroid, const float* light_pos, const float* g_light_R, const float* g_light_T, int B, int V,
                          float* g_light_pos, float* g_centroid, float* g_verts, hipStream_t stream) {
-  if (!centroid || !light_pos || !g_light_R || !g_light_T || !g_light_pos || !g_centroid) return HARP_ERR_ARG;
+  if (!centroid || !light_pos || !g_light_R || !g_light_T || !g_light_pos || !g_centroid || B <= 0) return HARP_ERR_ARG;
   hipLaunchKernelGGL(light_setup_kernel<true>, dim3((B + 63) / 64), dim3(64), 0, stream, centroid, light_pos, B, nullptr, nullptr,
                      g_light_R, g_light_T, g_light_pos, g_centroid);
   if (g_verts) hipLaunchKernelGGL(centroid_bwd_kernel, dim3((V + 255) / 256, B), dim3(256), 0, stream, g_centroid, V, g_verts);

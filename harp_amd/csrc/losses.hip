@@ -538,16 +538,23 @@ __global__ void adam_tick_kernel(harp_adam_hyper* hs, int count) {
     h->inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
   }
 }
+// One element of the device-hyper-parameter Adam step, shared by harp_adam_apply and both paths of harp_adam_apply2.  Contraction is
+// switched off so that the three loops round alike whatever the compiler would fuse in each of them: harp_adam_apply2 is "two
+// harp_adam_apply calls in one launch", bit for bit (tests/test_gpu_frame_glue.py; its four-wide path used to fuse the parameter update).
+__device__ __forceinline__ void adam_dev_elem(float& p, float g, float& m, float& v, float step_size, float beta1, float beta2, float eps,
+                                              float isb, float gs) {
+#pragma clang fp contract(off)
+  const float gi = g * gs;
+  const float mi = m + (gi - m) * (1.0f - beta1);
+  const float vi = v * beta2 + (1.0f - beta2) * gi * gi;
+  m = mi; v = vi;
+  p = p - step_size * (mi / (sqrtf(vi) * isb + eps));
+}
 __global__ void adam_dev_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                                 size_t n, const harp_adam_hyper* __restrict__ h) {
   const float step_size = h->step_size, beta1 = h->beta1, beta2 = h->beta2, eps = h->eps, isb = h->inv_sqrt_bc2, gs = h->grad_scale;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-    const float gi = g[i] * gs;
-    const float mi = m[i] + (gi - m[i]) * (1.0f - beta1);
-    const float vi = v[i] * beta2 + (1.0f - beta2) * gi * gi;
-    m[i] = mi; v[i] = vi;
-    p[i] -= step_size * (mi / (sqrtf(vi) * isb + eps));
-  }
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x)
+    adam_dev_elem(p[i], g[i], m[i], v[i], step_size, beta1, beta2, eps, isb, gs);
 }
 
 // The head of a step's second stream in ONE launch (it was a fill, adam_tick, draw_offsets and bump_counter: four launches of ~5 us each in
@@ -597,14 +604,10 @@ __global__ void adam_dev2_kernel(float* __restrict__ p, const float* __restrict_
       const float beta1 = h->beta1, beta2 = h->beta2, gs = h->grad_scale, ss = h->step_size, isb = h->inv_sqrt_bc2, eps = h->eps;
       const float4 G = *reinterpret_cast<const float4*>(g + i);
       float4 M = *reinterpret_cast<float4*>(m + i), Vv = *reinterpret_cast<float4*>(v + i), P = *reinterpret_cast<float4*>(p + i);
-      const float gq[4] = {G.x * gs, G.y * gs, G.z * gs, G.w * gs};
+      const float gq[4] = {G.x, G.y, G.z, G.w};
       float mq[4] = {M.x, M.y, M.z, M.w}, vq[4] = {Vv.x, Vv.y, Vv.z, Vv.w}, pq[4] = {P.x, P.y, P.z, P.w};
 #pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        mq[c] = mq[c] + (gq[c] - mq[c]) * (1.0f - beta1);
-        vq[c] = vq[c] * beta2 + (1.0f - beta2) * gq[c] * gq[c];
-        pq[c] -= ss * (mq[c] / (sqrtf(vq[c]) * isb + eps));
-      }
+      for (int c = 0; c < 4; ++c) adam_dev_elem(pq[c], gq[c], mq[c], vq[c], ss, beta1, beta2, eps, isb, gs);
       *reinterpret_cast<float4*>(m + i) = make_float4(mq[0], mq[1], mq[2], mq[3]);
       *reinterpret_cast<float4*>(v + i) = make_float4(vq[0], vq[1], vq[2], vq[3]);
       *reinterpret_cast<float4*>(p + i) = make_float4(pq[0], pq[1], pq[2], pq[3]);
@@ -615,12 +618,7 @@ __global__ void adam_dev2_kernel(float* __restrict__ p, const float* __restrict_
     const bool first = k < n0;
     const harp_adam_hyper* h = hs + (first ? 0 : 1);
     const size_t i = first ? o0 + k : o1 + (k - n0);
-    const float beta1 = h->beta1, beta2 = h->beta2;
-    const float gi = g[i] * h->grad_scale;
-    const float mi = m[i] + (gi - m[i]) * (1.0f - beta1);
-    const float vi = v[i] * beta2 + (1.0f - beta2) * gi * gi;
-    m[i] = mi; v[i] = vi;
-    p[i] -= h->step_size * (mi / (sqrtf(vi) * h->inv_sqrt_bc2 + h->eps));
+    adam_dev_elem(p[i], g[i], m[i], v[i], h->step_size, h->beta1, h->beta2, h->eps, h->inv_sqrt_bc2, h->grad_scale);
   }
 }
 

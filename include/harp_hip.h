@@ -333,7 +333,9 @@ int harp_lbs_tree_bwd(const harp_tree_model* m, const float* in_pose, const floa
  * MeshRasterizer.transform of both views do between the hand layer and the rasterisers — and one launch for their autograd.
  * Same arithmetic as harp_subdivide_* / harp_vertex_normals_* / harp_displace_bwd / harp_centroid / harp_light_setup_* /
  * harp_project_*; exists because every kernel node of a captured step costs ~4.5 us of dispatch latency.  V0 + E0 <=
- * harp_mesh_chain_max_vertices().  All pointers device memory; "(+=)" outputs accumulate. */
+ * harp_mesh_chain_max_vertices(), NJ * 3 <= 1024.  PRECONDITION: every vertex of the (subdivided) mesh lies in at least one face
+ * (vf_off[i + 1] > vf_off[i] for all i): the kernels pre-fetch vf_tri[vf_off[i] + min(q, n - 1)], which for a vertex in no face
+ * reads one entry before its range.  All pointers device memory; "(+=)" outputs accumulate. */
 typedef struct harp_mesh_chain {
   const int32_t* edges0;    /* (E0,2) base-mesh edges (midpoint i = V0 + i) */
   const int32_t* vf_off;    /* (V+1) vertex -> incident (face, corner) CSR offsets */
@@ -477,7 +479,8 @@ int harp_step_prologue(float* zero, size_t n_zero, harp_adam_hyper* hyper_dev, i
  * replaces the row gathers params[k][fid] of utils/visualize.py:26-27,38-39 / optimize_sequence.py:464, the camera
  * convention of utils/visualize.py:268-271, optimize_sequence.py:453-456 (shared light), :478-480 + renderer_helper.py:
  * 435-441 (ambient ratio -> light colours) and process_info_for_shadow (renderer_helper.py:454-468).
- * The tables are the reference's parameter dict (optimize_sequence.py:181-250) laid out in one flat fp32 arena. */
+ * The tables are the reference's parameter dict (optimize_sequence.py:181-250) laid out in one flat fp32 arena.
+ * B <= 0 returns HARP_ERR_ARG without launching (harp_frame_setup_fwd / _bwd, harp_light_setup_fwd / _bwd), as the sizes of the loss calls. */
 typedef struct harp_frame_tables {
   const float *pose, *rot, *trans, *cam;   /* (T,45) (T,3) (T,3) (T,3) */
   const float *shape;                      /* (10,) */

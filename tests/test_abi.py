@@ -112,3 +112,12 @@ def test_building_blocks_refuse_empty_sizes_without_launch(lib):
     tree = _lib.TreeModel(NV=1026, NJ=55, NB=20, n_pose_in=17, center_joint=21, n_joints_out=22,
                           **{n: f for n, t in _lib.TreeModel._fields_ if t is ctypes.c_void_p})
     assert lib.harp_lbs_tree_bwd(ctypes.byref(tree), f, f, f, 0, f, f, f, f, f, f, None) == 1
+    # per-frame glue: B <= 0 is refused on the host.  As above only the sizes whose launch would be empty WITHOUT the check are tried with
+    # fake pointers: B = 0 and B = -1 for the 64-lane grids, B = 0 for harp_frame_setup_bwd, whose grid is dim3(B) (its B = -1 is refused
+    # with real buffers in tests/test_gpu_frame_glue.py)
+    tables = _lib.FrameTables(n_betas_out=10, **{n: f for n, t in _lib.FrameTables._fields_ if t is ctypes.c_void_p})
+    for B in (0, -1):
+        assert lib.harp_frame_setup_fwd(ctypes.byref(tables), f, B, 64, 500.0, 1, f, f, f, f, f, f, f, None) == 1, B
+        assert lib.harp_light_setup_fwd(f, f, B, f, f, None) == 1, B
+        assert lib.harp_light_setup_bwd(f, f, f, f, B, 4, f, f, None, None) == 1, B
+    assert lib.harp_frame_setup_bwd(ctypes.byref(tables), f, 0, 64, 500.0, 1, f, f, f, f, f, f, None) == 1

@@ -627,7 +627,7 @@ def test_adam_step_against_torch_adam_float64():
     values the kernel receives (lr, betas and eps rounded to float32), on grad * grad_scale.  harp_adam_tick + harp_adam_apply derive the
     same bias corrections (host double pow vs the device's: the float32 results agree exactly, checked every step) but do NOT give the same
     bits: the compiler contracts the two kernels' identical source differently (adam_kernel fuses grad * grad_scale into the exp_avg
-    lerp, fma(g, gs, -m); adam_dev_kernel fuses (1 - beta2) gi * gi into the exp_avg_sq update), so both are held to the float64 bounds."""
+    lerp, fma(g, gs, -m); adam_dev_kernel is compiled without contraction, to round like harp_adam_apply2), so both are held to the float64 bounds."""
     L, p, st, ck = _L()
     n, steps = 1100003, 10
     lr, b1, b2, eps, gs = _f32(1e-2), _f32(0.9), _f32(0.999), _f32(1e-8), _f32(0.37)
