@@ -284,3 +284,9 @@ SIGNATURES.update({
     "harp_normal_image": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _f, ctypes.POINTER(_f), _vp, _ll, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "harp_panels_u8": (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_ll), _i, _vp, _vp, _i, _i, _i, _vp, _vp]),
 })
+
+# Taubin smoothing of the exported meshes (csrc/smooth.hip)
+SIGNATURES.update({
+    "harp_taubin_ws_bytes": (_sz, [_i, _i]),
+    "harp_taubin_smooth": (_i, [_vp, _vp, _vp, _i, _i, _f, _f, _i, _i, _vp, _vp, _vp]),
+})

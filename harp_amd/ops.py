@@ -656,3 +656,50 @@ def panels_u8(images, mask_true=None, mask_pred=None, channels_last=True):
         rc = _lib.lib().harp_panels_u8(pa, sa, len(ptrs), _lib.ptr(masks[0]), _lib.ptr(masks[1]), N, H, W, _lib.ptr(out), _lib.stream())
     _lib.check(rc, "harp_panels_u8")
     return out
+
+
+# ------------------------------------------------------------------------------------------------------
+# export of the fitted avatar (csrc/smooth.hip): Taubin smoothing of the meshes that save_obj writes
+# ------------------------------------------------------------------------------------------------------
+TAUBIN_LDS_MAX_V = 4096                                  # vertices one workgroup keeps resident in LDS (mode 1)
+
+
+def taubin_smooth(verts, topo, lambd=0.53, mu=-0.53, num_iter=10, mode=0):
+    """The passes of pytorch3d.ops.taubin_smoothing (optimize_sequence.py:780) on plain tensors, forward only: verts (B,V,3) or (V,3)
+    float32 HIP tensor (any strides), topo = anything with the vertex -> neighbour CSR `nbr_off` (V+1) / `nbr_idx` int32 on the same device
+    (a DeviceTopology) -> a new tensor of the same shape.  mode 0 picks the kernel, 1 = LDS-resident (V <= TAUBIN_LDS_MAX_V), 2 = one
+    launch per pass through a workspace.  A vertex without neighbours keeps its position (PyTorch3D: NaN)."""
+    if torch.is_grad_enabled() and verts.requires_grad:
+        raise NotImplementedError("taubin_smooth is forward-only (the reference calls it under torch.no_grad()): detach the vertices")
+    if not verts.is_cuda:
+        raise RuntimeError("harp_amd ops need HIP device tensors (no CPU path)")
+    if verts.dim() not in (2, 3) or verts.shape[-1] != 3:
+        raise ValueError(f"taubin_smooth takes (B,V,3) or (V,3) vertices, got {tuple(verts.shape)}")
+    v = _f32(verts.detach())
+    v3 = v.reshape(-1, v.shape[-2], 3)
+    B, V = v3.shape[0], v3.shape[1]
+    if topo.nbr_off.numel() != V + 1:
+        raise ValueError(f"the neighbour table is for {topo.nbr_off.numel() - 1} vertices, the mesh has {V}")
+    if int(num_iter) < 0 or int(mode) not in (0, 1, 2):
+        raise ValueError(f"num_iter >= 0 and mode in (0, 1, 2), got {num_iter}, {mode}")
+    if int(mode) == 1 and V > TAUBIN_LDS_MAX_V:
+        raise ValueError(f"mode 1 keeps at most {TAUBIN_LDS_MAX_V} vertices in LDS, the mesh has {V}")
+    out = torch.empty_like(v3)
+    if B == 0 or V == 0:
+        return out.reshape(v.shape)
+    L = _lib.lib()
+    ws = None
+    if int(num_iter) > 0 and (int(mode) == 2 or V > TAUBIN_LDS_MAX_V):
+        ws = torch.empty(L.harp_taubin_ws_bytes(B, V), dtype=torch.uint8, device=v.device)
+    with torch.cuda.device(v.device):
+        rc = L.harp_taubin_smooth(_lib.ptr(v3), _lib.ptr(topo.nbr_off), _lib.ptr(topo.nbr_idx), B, V, float(lambd), float(mu), int(num_iter),
+                                  int(mode), _lib.ptr(out), _lib.ptr(ws), _lib.stream())
+    _lib.check(rc, "harp_taubin_smooth")
+    return out.reshape(v.shape)
+
+
+def taubin_smoothing(meshes, lambd=0.53, mu=-0.53, num_iter=10):
+    """pytorch3d.ops.taubin_smoothing(meshes, lambd, mu, num_iter) as optimize_sequence.py:780 calls it: a new harp_amd.structures.Meshes
+    with smoothed vertices and the same faces, textures and topology."""
+    from .structures import Meshes
+    return Meshes(taubin_smooth(meshes.verts_padded(), meshes.topo, lambd, mu, num_iter), meshes.faces_padded(), meshes.textures, meshes.topo)

@@ -87,9 +87,10 @@ def stage_flags(epoch_id, training_stage):
 def optimize_hand_sequence(configs, input_params, images_dataset, val_params, val_images_dataset, hand_layer,
                            VERTS_UVS=None, FACES_UVS=None, VERTS_COLOR=None, device="cuda", uv_mask=None, batch_size=18, log_fn=None,
                            seed=0, vgg=None, rank=None, world_size=None, shards=None, plateau_patience=40, plateau_threshold=1e-4, device_schedule=True,
-                           evaluate=False, panels=False, turntable=False):
+                           evaluate=False, panels=False, turntable=False, export_mesh=False):
     """Fit the sequence (optimize_sequence.py:313-596).  Returns the parameter dict in the reference's checkpoint layout; evaluate=True
-    then runs the post-fit evaluation `evaluate_sequence` (:595-816) on rank 0 (off by default), with its panels / turntable switches.
+    then runs the post-fit evaluation `evaluate_sequence` (:595-816) on rank 0 (off by default), with its panels / turntable / export_mesh
+    switches.
     `images_dataset[i]` -> (fid, y_true (S,S,3), y_sil (S,S,1), y_sil_eroded (S,S,1)) like utils/data_util.ImagesDataset.
 
     Data-parallel (the reference is single-device): launched under `torch.distributed.run` (or with rank / world_size given)
@@ -219,7 +220,8 @@ def optimize_hand_sequence(configs, input_params, images_dataset, val_params, va
             torch.cuda.synchronize(eng.dev)
             comm.destroy()                                           # drops the step graphs that captured it
     if evaluate and rank == 0:
-        evaluate_sequence(configs, params, images_dataset, hand_layer, device=device, uv_mask=uv_mask, panels=panels, turntable=turntable)
+        evaluate_sequence(configs, params, images_dataset, hand_layer, device=device, uv_mask=uv_mask, panels=panels, turntable=turntable,
+                          export_mesh=export_mesh)
     return params
 
 
@@ -227,7 +229,7 @@ EVAL_CHUNK = 64                  # optimize_sequence.py:716: image_eval runs on 
 
 
 def evaluate_sequence(configs, params, images_dataset, hand_layer, device="cuda", batch_size=32, uv_mask=None, lpips_fn=None, panels=False,
-                      turntable=False, panel_hook=None):
+                      turntable=False, panel_hook=None, export_mesh=False):
     """The post-fit evaluation of optimize_sequence.py:595-816: re-render every dataset item in order with the fitted `params` through the
     reference-API mirror (silhouette: get_renderers(silh_sigma=1e-7, silh_faces_per_pixel=50)[1]; image: render_image_with_RT through
     get_shadow_renderers with self_shadow, else render_image with the phong renderer), `batch_size` frames per render call; per-frame
@@ -244,12 +246,16 @@ def evaluate_sequence(configs, params, images_dataset, hand_layer, device="cuda"
     more prepare_mesh(vis_normal=True) + normal render (:710-714), one ops.panels_u8 and one `true | pred | normal | overlay` JPEG per frame,
     rendered_after_opt[_test]/<fid %04d>.jpg (:742-757); panel_hook(fid, strip), if given, sees every (S, 4S, 3) uint8 strip before it is
     encoded.  turntable=True: for the dataset item whose fid is 0 (:716-727) render_360 with the phong and the normal renderer,
-    concat_image_in_dir into render_360_combine and render_360_light, each with its out.gif."""
+    concat_image_in_dir into render_360_combine and render_360_light, each with its out.gif.  export_mesh=True (the reference's constant
+    EXPORT_MESH, :776-791): per batch one ops.taubin_smoothing(meshes) (csrc/smooth.hip) and one device -> host copy, then per frame
+    mesh/<fid %04d>.obj, .mtl and .png through harp_amd.io.save_obj with the reference's arguments — smoothed vertices, the faces of the
+    unsmoothed mesh, the textures' verts_uvs / faces_uvs and maps_padded()[0].clamp(0, 1), whose PNG is encoded once (the texture is shared)."""
     import os
     import warnings
     import torch.nn.functional as F
     from PIL import Image
     from . import ops
+    from .io import encode_png, save_obj
     from .renderer import renderer_helper
     from .structures import Meshes
     from .utils.eval_util import align_w_scale, load_gt_vert, sil_iou
@@ -287,6 +293,9 @@ def evaluate_sequence(configs, params, images_dataset, hand_layer, device="cuda"
     panel_dir = os.path.join(base, "rendered_after_opt" + test_name)
     if panels:
         os.makedirs(panel_dir, exist_ok=True)                      # :660
+    mesh_dir, png = os.path.join(base, "mesh"), None
+    if export_mesh:
+        os.makedirs(mesh_dir, exist_ok=True)                       # :783
     n = len(images_dataset)
     with torch.no_grad():
         for lo in range(0, n, batch_size):
@@ -355,6 +364,16 @@ def evaluate_sequence(configs, params, images_dataset, hand_layer, device="cuda"
                     pred = hand_verts[b, hand_layer.right_mano_idx] if use_arm else hand_verts[b, :778]
                     err = gt - align_w_scale(gt, pred.detach().cpu().numpy())
                     vert_err.append(float(np.linalg.norm(err, axis=1).mean()) * 1000.0)
+            if export_mesh:                           # :776-791
+                smoothed = ops.taubin_smoothing(meshes).verts_padded().cpu()
+                faces_cpu = meshes.faces_padded()[0].cpu()
+                verts_uvs = meshes.textures.verts_uvs_padded()[0].detach().cpu()
+                faces_uvs = meshes.textures.faces_uvs_padded()[0].detach().cpu()
+                if png is None:                       # prepare_mesh repeats ONE texture over every frame of every batch: encoded once
+                    png = encode_png(meshes.textures.maps_padded()[0].detach().cpu().clamp(0, 1))
+                for b in range(B):
+                    save_obj(os.path.join(mesh_dir, "%04d.obj" % int(fid[b])), verts=smoothed[b], faces=faces_cpu, verts_uvs=verts_uvs,
+                             faces_uvs=faces_uvs, texture_png=png)
     # ---- the reference's averaging: image_eval per 64-frame chunk (:713-731), then np.mean over the chunks (:733-738)
     iou, l1 = torch.cat(iou).double(), torch.cat(l1)
     chunks = [slice(c, min(n, c + EVAL_CHUNK)) for c in range(0, n, EVAL_CHUNK)]
@@ -405,6 +424,7 @@ def main(argv=None):
     ap.add_argument("--eval", action="store_true", help="after the fit, the evaluation of optimize_sequence.py:595-816 (evaluate_sequence)")
     ap.add_argument("--panels", action="store_true", help="with --eval: one true | pred | normal | overlay JPEG per frame under rendered_after_opt/")
     ap.add_argument("--turntable", action="store_true", help="with --eval: render_360/, render_360_normal/, render_360_combine/ and render_360_light/ of frame 0")
+    ap.add_argument("--export-mesh", action="store_true", help="with --eval: the Taubin-smoothed textured mesh of every frame as mesh/<fid>.obj, .mtl, .png")
     ap.add_argument("--lpips-weights", nargs="+", default=None, metavar="PATH",
                     help="LPIPS in the evaluation: one lpips.LPIPS(net='alex') state dict, or torchvision's alexnet state dict and the lpips "
                          "v0.1 alex head (configs['lpips_weights'])")
@@ -432,7 +452,7 @@ def main(argv=None):
         average_cam_sequence=configs["average_cam_sequence"], use_smooth_seq=configs["use_smooth_seq"], model_type=configs["model_type"])
     params = optimize_hand_sequence(configs, mano_params, images_dataset, val_mano_params, val_images_dataset, hand_layer, VERTS_UVS, FACES_UVS,
                                     VERTS_COLOR, device=device, batch_size=args.batch_size, evaluate=args.eval, panels=args.panels,
-                                    turntable=args.turntable)
+                                    turntable=args.turntable, export_mesh=args.export_mesh)
     if world > 1:
         tdist.barrier()
         tdist.destroy_process_group()

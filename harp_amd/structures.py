@@ -14,6 +14,16 @@ class TexturesUV:
     def maps_padded(self):
         return self.maps
 
+    def verts_uvs_padded(self):
+        """(N,VT,2): the table as given, with a leading mesh dimension (optimize_sequence.py:788 reads [0])"""
+        t = torch.as_tensor(self.verts_uvs)
+        return t if t.dim() == 3 else t[None]
+
+    def faces_uvs_padded(self):
+        """(N,F,3), see verts_uvs_padded (optimize_sequence.py:789)"""
+        t = torch.as_tensor(self.faces_uvs)
+        return t if t.dim() == 3 else t[None]
+
 
 class Meshes:
     """verts (B,V,3) float32 HIP tensor; faces (B,F,3) or (F,3) carrying a `_harp_topo` attribute (set by

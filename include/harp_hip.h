@@ -838,6 +838,26 @@ int harp_normal_image(const float* ndc, const float* vnormals, const int32_t* fa
 int harp_panels_u8(const float* const* images, const long long* strides, int n_images, const float* mask_true, const float* mask_pred, int N,
                    int H, int W, unsigned char* out, hipStream_t stream);
 
+/* ---- export of the fitted avatar: Taubin smoothing (csrc/smooth.hip) ----------------------------------------------------------------
+ * optimize_sequence.py:780  pytorch3d.ops.taubin_smoothing(meshes, lambd=0.53, mu=-0.53, num_iter=10), forward only (the reference calls
+ * it under no_grad).  PyTorch3D is not installed where this was written: the semantics are its v0.6.2 taubin_smoothing / norm_laplacian
+ * AS RECALLED, restated here in full.  verts / out (B,V,3) float32; nbr_off (V+1) / nbr_idx the vertex -> neighbour CSR of
+ * harp_amd/topology.py, shared by all frames (indices are NOT bounds-checked).  Per frame, num_iter times: one pass with factor lambd, then
+ * one with factor mu.  A pass with factor f moves every vertex from the PREVIOUS pass's positions (Jacobi), weights recomputed per pass:
+ *   w_ij = 1 / (|v_i - v_j| + 1e-12) for j in nbr(i),   v_i' = (1 - f) v_i + f (sum_j w_ij v_j) / (sum_j w_ij)
+ * (evaluated as v_i + f sum_j w_ij (v_j - v_i) / sum_j w_ij).  Deviation: a vertex without neighbours keeps its position (PyTorch3D
+ * yields 0/0 = NaN there).  num_iter = 0 copies verts to out bit for bit.  out may alias verts.  Stream-ordered and capturable: no
+ * allocation, no synchronisation.  Deterministic: no atomics.
+ * mode 1: one workgroup per frame, the positions resident in LDS for all 2 * num_iter passes; V <= 4096 (64 KiB), otherwise HARP_ERR_ARG;
+ *   ws is not used.  mode 2: one launch per pass, ping-pong through ws = harp_taubin_ws_bytes(B, V) bytes (256-B aligned, no initial
+ *   contents); any V.  mode 0: mode 1 where V fits, else mode 2.
+ * Returns HARP_ERR_ARG without launching for NULL verts / nbr_off / nbr_idx / out, B <= 0, V <= 0, num_iter < 0, mode outside 0..2, and a
+ * NULL ws where mode 2 runs with num_iter > 0.
+ * harp_taubin_ws_bytes: pure host arithmetic, 2 * (12 B V rounded up to 256); 0 for B <= 0 or V <= 0. */
+size_t harp_taubin_ws_bytes(int B, int V);
+int harp_taubin_smooth(const float* verts, const int32_t* nbr_off, const int32_t* nbr_idx, int B, int V, float lambd, float mu, int num_iter,
+                       int mode, float* out, void* ws, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
