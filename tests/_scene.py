@@ -318,3 +318,29 @@ def assert_blocks(eng, g, ref, tag=""):
     bad = {k: (e, block_bound(k)) for k, e in errs.items() if e > block_bound(k)}
     assert not bad, (tag, bad, errs)
     return errs
+
+
+# The switch combinations of tests/test_gpu_parity.py::test_schedule_switches_give_the_default_schedules_result; tests/_trace.py pins the
+# enqueue sequence of the same list.
+SCHEDULE_SWITCHES = [dict(graph_order=False), dict(mesh_third=True), dict(mesh_third=True, fold_step=False), dict(mesh_third=True, graph_order=False), dict(camera_first=False), dict(overlap=False),
+                     dict(graph_order=False, mesh_third=False), dict(mesh_third=False, camera_first=False),
+                     dict(graph_order=False, mesh_third=False, camera_first=False), dict(early_terms=False),
+                     dict(mesh_terms_first=False, mesh_third=False), dict(tail_side=True), dict(consume_gzl=False), dict(keep_depth=False),
+                     dict(fold_step=False), dict(fused_terms=False), dict(fold_step=False, fused_terms=False),
+                     dict(fold_step=False, mesh_third=False), dict(fused_terms=False, consume_gzl=False), dict(zl_tile_flags=True),
+                     dict(fused_terms=False, zl_tile_flags=True),
+                     # round 5: four-workgroups-per-frame forms, paired rasteriser set-up, late terms (harp_amd/engine.py)
+                     dict(front_auto=False), dict(front_auto=False, wide_front=True), dict(wide_back=False), dict(front_auto=False, wide_front=True, wide_back=False), dict(front_auto=False, hybrid_front=True),
+                     dict(paired_setup=True), dict(paired_setup=True, front_auto=False, wide_front=True), dict(paired_setup=True, overlap=False),
+                     dict(late_texture_terms=True), dict(late_texture_terms=True, mesh_terms_first=False), dict(sil_late=True), dict(mesh_terms_late=True),
+                     dict(mesh_terms_late=True, graph_order=False), dict(mesh_terms_late=True, sil_late=True),
+                     dict(paired_setup=True, keep_depth=False),
+                     # round 6: texel gradients as records + harp_texel_reduce on a branch of its own (default) vs the in-kernel table form
+                     dict(texel_records=False), dict(texel_records=False, tail_side=True), dict(texel_records=False, fused_terms=False), dict(tail_side=True, fused_terms=False),
+                     # ... and the silhouette backward inside the camera-view raster launch (harp_rasterize_l1_fwd_bwd) vs the stand-alone launch beside the shader backward (default)
+                     dict(fused_sil_bwd=True), dict(fused_sil_bwd=True, texel_records=False), dict(fused_sil_bwd=True, graph_order=False), dict(fused_sil_bwd=True, overlap=False),
+                     dict(fused_sil_bwd=True, fold_step=False), dict(fused_sil_bwd=True, mesh_third=True),
+                     dict(split_adam=False), dict(split_adam=False, texel_records=False),
+                     # the shader backward's vertex gradients as one interleaved buffer unpacked by riders of the depth backward (default) vs three arrays
+                     dict(vert9=False), dict(vert9=False, texel_records=False), dict(vert9=True, texel_records=False), dict(vert9=True, consume_gzl=False),
+                     dict(vert9=True, texel_records=False, fused_terms=False), dict(vert9=True, zl_tile_flags=True), dict(vert9=True, fused_bwd=True)]

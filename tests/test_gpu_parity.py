@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests._scene import block_bound, block_errors, check_removed, make_scene, mask_scene_targets, oracle_params, rel, scene_f64
+from tests._scene import SCHEDULE_SWITCHES, block_bound, block_errors, check_removed, make_scene, mask_scene_targets, oracle_params, rel, scene_f64
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
@@ -1238,28 +1238,7 @@ def test_light_camera_incl_look_at_replacement_branch():
             assert err < (2e-4 if b == 0 else 1e-3), (b, name, err, got.cpu(), ref)
 
 
-@pytest.mark.parametrize("switches", [dict(graph_order=False), dict(mesh_third=True), dict(mesh_third=True, fold_step=False), dict(mesh_third=True, graph_order=False), dict(camera_first=False), dict(overlap=False),
-                                      dict(graph_order=False, mesh_third=False), dict(mesh_third=False, camera_first=False),
-                                      dict(graph_order=False, mesh_third=False, camera_first=False), dict(early_terms=False),
-                                      dict(mesh_terms_first=False, mesh_third=False), dict(tail_side=True), dict(consume_gzl=False), dict(keep_depth=False),
-                                      dict(fold_step=False), dict(fused_terms=False), dict(fold_step=False, fused_terms=False),
-                                      dict(fold_step=False, mesh_third=False), dict(fused_terms=False, consume_gzl=False), dict(zl_tile_flags=True),
-                                      dict(fused_terms=False, zl_tile_flags=True),
-                                      # round 5: four-workgroups-per-frame forms, paired rasteriser set-up, late terms (harp_amd/engine.py)
-                                      dict(front_auto=False), dict(front_auto=False, wide_front=True), dict(wide_back=False), dict(front_auto=False, wide_front=True, wide_back=False), dict(front_auto=False, hybrid_front=True),
-                                      dict(paired_setup=True), dict(paired_setup=True, front_auto=False, wide_front=True), dict(paired_setup=True, overlap=False),
-                                      dict(late_texture_terms=True), dict(late_texture_terms=True, mesh_terms_first=False), dict(sil_late=True), dict(mesh_terms_late=True),
-                                      dict(mesh_terms_late=True, graph_order=False), dict(mesh_terms_late=True, sil_late=True),
-                                      dict(paired_setup=True, keep_depth=False),
-                                      # round 6: texel gradients as records + harp_texel_reduce on a branch of its own (default) vs the in-kernel table form
-                                      dict(texel_records=False), dict(texel_records=False, tail_side=True), dict(texel_records=False, fused_terms=False), dict(tail_side=True, fused_terms=False),
-                                      # ... and the silhouette backward inside the camera-view raster launch (harp_rasterize_l1_fwd_bwd) vs the stand-alone launch beside the shader backward (default)
-                                      dict(fused_sil_bwd=True), dict(fused_sil_bwd=True, texel_records=False), dict(fused_sil_bwd=True, graph_order=False), dict(fused_sil_bwd=True, overlap=False),
-                                      dict(fused_sil_bwd=True, fold_step=False), dict(fused_sil_bwd=True, mesh_third=True),
-                                      dict(split_adam=False), dict(split_adam=False, texel_records=False),
-                                      # the shader backward's vertex gradients as one interleaved buffer unpacked by riders of the depth backward (default) vs three arrays
-                                      dict(vert9=False), dict(vert9=False, texel_records=False), dict(vert9=True, texel_records=False), dict(vert9=True, consume_gzl=False),
-                                      dict(vert9=True, texel_records=False, fused_terms=False), dict(vert9=True, zl_tile_flags=True), dict(vert9=True, fused_bwd=True)])
+@pytest.mark.parametrize("switches", SCHEDULE_SWITCHES)
 def test_schedule_switches_give_the_default_schedules_result(switches):
     """The stream / capture-order switches of FitEngine (graph_order, mesh_third, camera_first, overlap, early_terms, mesh_terms_first,
     tail_side) only move launches between streams: losses and the whole gradient arena of every non-default combination must equal the

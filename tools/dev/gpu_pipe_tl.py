@@ -1,4 +1,4 @@
-"""graph replays of the bench workload with FitEngine attributes set from HARP_ENG (e.g. "pipelined=1,mesh_third=0"): for rocprofv3 timelines"""
+"""graph replays of the bench workload with FitEngine attributes set from HARP_ENG (e.g. "mesh_third=1,sil_late=0"): for rocprofv3 timelines"""
 import sys, os; sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', '..'))
 import torch, bench
 kind, img = os.environ.get("HARP_TL_KIND", "hand"), int(os.environ.get("HARP_TL_IMG", "512"))      # C5: HARP_TL_KIND=arm HARP_TL_IMG=1024
