@@ -7,6 +7,8 @@
 // [0,1] and renormalised when blur_radius > 0; a face is a candidate if the pixel centre is inside its blur-dilated bbox and either
 // inside the face or closer than sqrt(blur_radius) to an edge; pz = sum bary_i z_i >= 0; the K nearest by pz are kept in ascending
 // order, ties keep the lower face index; empty slots hold -1 in every output.
+#include <cfloat>
+
 #include "shade_common.h"
 
 int harp_detail_raster_setup(const float* ndc, const int32_t* faces, int B, int V, int F, int S, float r, void* ws, hipStream_t stream);
@@ -174,7 +176,9 @@ extern "C" {
 
 int harp_rasterize_fragments_fwd(const float* ndc, const int32_t* faces, int B, int V, int F, int S, float blur_radius, int K, void* ws,
                                  int32_t* pix_to_face, float* zbuf, float* bary, float* dists, hipStream_t stream) {
-  if (!ndc || !faces || !ws || !pix_to_face || !zbuf || !bary || !dists || B <= 0 || F <= 0 || S <= 0 || K < 1 || K > kMaxK || blur_radius < 0.f)
+  // !(x >= 0 && x <= FLT_MAX) also refuses a NaN blur radius, which `x < 0` lets through
+  if (!ndc || !faces || !ws || !pix_to_face || !zbuf || !bary || !dists || B <= 0 || V <= 0 || F <= 0 || S <= 0 || K < 1 || K > kMaxK ||
+      !(blur_radius >= 0.f && blur_radius <= FLT_MAX))
     return HARP_ERR_ARG;
   const int rc = harp_detail_raster_setup(ndc, faces, B, V, F, S, sqrtf(blur_radius), ws, stream);
   if (rc != HARP_OK) return rc;
@@ -189,7 +193,8 @@ int harp_rasterize_fragments_bwd(const float* ndc, const int32_t* faces, const i
                                  const float* g_bary, const float* g_dists, int B, int V, int F, int S, float blur_radius, int K,
                                  float* g_ndc, hipStream_t stream) {
   (void)F;
-  if (!ndc || !faces || !pix_to_face || !g_ndc || B <= 0 || S <= 0 || K < 1 || K > kMaxK) return HARP_ERR_ARG;
+  if (!ndc || !faces || !pix_to_face || !g_ndc || B <= 0 || V <= 0 || S <= 0 || K < 1 || K > kMaxK || !(blur_radius >= 0.f && blur_radius <= FLT_MAX))
+    return HARP_ERR_ARG;
   const size_t total = (size_t)B * S * S * K;
   hipLaunchKernelGGL(fragments_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, ndc, faces, pix_to_face, g_zbuf, g_bary,
                      g_dists, B, V, S, blur_radius, K, g_ndc);

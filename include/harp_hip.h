@@ -116,7 +116,9 @@ int harp_depth_bwd_tiles(const int32_t* face_id, const void* ws, const int32_t* 
  * For callers that keep PyTorch3D-style shader classes.  K = faces_per_pixel is a CAP (1 <= K <= 64): the K nearest candidates are
  * kept in ascending depth, ties keep the lower face index.  Outputs (B,S,S,K): pix_to_face int32 frame-local (-1 = empty slot; the
  * PyTorch3D "packed" index is b*F + f), zbuf, bary (B,S,S,K,3), dists (signed squared NDC distance to the nearest edge); empty slots
- * hold -1 everywhere.  ws: harp_rasterize_ws_bytes(B,F,S).  Backward: any of g_zbuf / g_bary / g_dists may be NULL; g_ndc (+=). */
+ * hold -1 everywhere.  ws: harp_rasterize_ws_bytes(B,F,S).  Backward: any of g_zbuf / g_bary / g_dists may be NULL; g_ndc (+=); an
+ * empty slot (pix_to_face < 0) contributes nothing, whatever its cotangents hold.  Both return HARP_ERR_ARG without a launch for a
+ * NULL required pointer, B / V / S (forward: F) < 1, K outside 1..64, and a blur_radius that is negative, NaN or infinite. */
 int harp_rasterize_fragments_fwd(const float* ndc, const int32_t* faces, int B, int V, int F, int S, float blur_radius, int K, void* ws,
                                  int32_t* pix_to_face, float* zbuf, float* bary, float* dists, hipStream_t stream);
 int harp_rasterize_fragments_bwd(const float* ndc, const int32_t* faces, const int32_t* pix_to_face, const float* g_zbuf,
