@@ -14,10 +14,11 @@
 //           tree_gA_mfma, tree_gpm_mfma   UNCHANGED: the two reductions over the vertices stay on the matrix cores
 //           arm_chain_bwd_kernel          kinematic chain + Rodrigues backward, adding rot / wrist_pose / pose / shape to their rows
 // 32 -> 23 kernel nodes per step.  Same arithmetic as the stand-alone kernels (lbs_tree.hip, chain.hip, glue.hip), which stay as the
-// C-ABI building blocks and serve the API path.
+// C-ABI building blocks and serve the API path.  Schedule row, row gathers, clear of the mesh gradients, table scatter and step epilogue are
+// frame_body.h (shared with hand_front.hip / hand_back.hip), the joint chain and its backward lbs_tree_body.h, the mesh chain chain_body.h.
 //   reference: hand_models_harp/body_models.py:2163-2390 (SMPLXARM.forward), utils/visualize.py:16-88 (prepare_mesh),
 //   renderer_helper.py:454-468, the row gathers params[...][fid] (utils/visualize.py:26-27, 37-40) and their autograd.
-#include "chain_body.h"
+#include "frame_body.h"
 #include "lbs_tree_body.h"
 
 int harp_detail_tree_blend(const harp_tree_model& m, float* ws, const float* betas, int B, hipStream_t stream);
@@ -37,48 +38,11 @@ __global__ void __launch_bounds__(kFrontThreads) arm_front_kernel(const harp_arm
   __shared__ float s_pose[64], s_beta[MAXB];
   const harp_mesh_chain& A = H.chain;
   const harp_tree_model& M = H.tree;
-  const harp_frame_tables& T = H.tables;
   const int b = blockIdx.x, tid = threadIdx.x, B = A.B;
-  // ---- optional step prologue (harp_step_frame): this workgroup's frame from the device schedule
-  int f;
-  if (H.step.schedule) {
-    const int row = (int)((unsigned)H.step.sched_row[0] % (unsigned)H.step.n_rows);     // bumped by arm_back_kernel, a later launch
-    f = H.step.schedule[(size_t)row * B + b];
-    if (tid == 0) {
-      const_cast<int32_t*>(H.fid)[b] = f;
-      if (H.step.tfid_out) H.step.tfid_out[b] = H.step.tschedule ? H.step.tschedule[(size_t)row * B + b] : f - H.step.target_offset;
-    }
-  } else {
-    f = H.fid[b];
-  }
-  // ---- frame set-up (glue.hip: frame_setup_fwd_kernel, arm rows [rot(3), wrist_pose(3), pose(45)], betas padded with zeros)
-  const int ps = M.n_pose_in * 3, nbo = M.NB;
-  if (tid < ps) {
-    const float p = (tid < 3) ? T.rot[f * 3 + tid] : (tid < 6) ? T.wrist_pose[f * 3 + tid - 3] : T.pose[f * 45 + tid - 6];
-    s_pose[tid] = p; H.pose_in[b * ps + tid] = p;
-  } else if (tid >= 64 && tid < 64 + nbo) {
-    const int k = tid - 64;
-    const float v = (k < 10) ? T.shape[k] : 0.f;
-    s_beta[k] = v; H.betas[b * nbo + k] = v;
-  } else if (tid >= 128 && tid < 131) {
-    const int k = tid - 128;
-    H.trans_b[b * 3 + k] = T.trans[f * 3 + k];
-    const int lf = T.share_light ? 0 : f;
-    H.light_pos[b * 3 + k] = T.light_positions[lf * 3 + k];
-  } else if (tid == 192) {
-    const float c0 = T.cam[f * 3], c1 = T.cam[f * 3 + 1], c2 = T.cam[f * 3 + 2];
-    const float ct[3] = {-c1, -c2, 2.0f * A.focal / ((float)A.S * c0 + 1e-9f)};
-    const float R[9] = {-1.f, 0.f, 0.f, 0.f, -1.f, 0.f, 0.f, 0.f, 1.f};
-    for (int k = 0; k < 9; ++k) H.cam_R[b * 9 + k] = R[k];
-    for (int k = 0; k < 3; ++k) H.cam_T[b * 3 + k] = ct[k];
-  } else if (tid == 193 && b == 0) {
-    if (H.self_shadow) {
-      const float amb = 1.0f / (1.0f + expf(-T.amb_ratio[0]));            // nn.Sigmoid()(params['amb_ratio'])
-      for (int c = 0; c < 3; ++c) { H.colors[c] = amb; H.colors[3 + c] = 1.0f - amb; H.colors[6 + c] = 0.f; }
-    } else {
-      for (int c = 0; c < 3; ++c) { H.colors[c] = 0.5f; H.colors[3 + c] = 0.4f; H.colors[6 + c] = 0.1f; }   // renderer_helper.py:70-73
-    }
-  }
+  // ---- optional step prologue (harp_step_frame): this workgroup's frame from the device schedule; then the frame set-up (frame_body.h),
+  //      arm rows [rot(3), wrist_pose(3), pose(45)], betas padded with zeros
+  const int f = fb::step_frame_of(H.step, H.fid, b, B, tid == 0);
+  fb::frame_rows<true, 193>(H, H.pose_in, M.n_pose_in * 3, M.NB, f, b, tid, true, s_pose, s_beta, nullptr, nullptr, nullptr);
   __syncthreads();
   joints_body<kFrontThreads>(M, s_pose, s_beta, b, tree_ws(&M, H.lbs_ws, B), S);
 }
@@ -111,11 +75,7 @@ __global__ void __launch_bounds__(kChainThreads) arm_mid_kernel(const harp_arm_f
   const int V = A.V0 + A.E0, NJ = M.NJ, NV = M.NV;
   const TreeWs W = tree_ws(&M, H.lbs_ws, B);
   float* s_p = s_dyn;
-  if (H.step.clear_mesh_grads) {               // the two gradient segments the key-point / mesh terms accumulate into (they start after this kernel)
-    float* gv = const_cast<float*>(A.g_vd) + (size_t)b * V * 3;
-    for (int i = tid; i < V * 3; i += kChainThreads) gv[i] = 0.f;
-    if (tid < A.NJ * 3) const_cast<float*>(A.g_joints_m)[(size_t)b * A.NJ * 3 + tid] = 0.f;
-  }
+  if (H.step.clear_mesh_grads) fb::clear_mesh_grads(A, b, 0, 1, tid, kChainThreads);      // (the terms that accumulate into them start after this kernel)
   for (int i = tid; i < NJ * 12; i += kChainThreads) s_A[i] = W.A[(size_t)b * NJ * 12 + i];
   if (tid >= 960 && tid < 963) {
     const int c = tid - 960;
@@ -206,52 +166,10 @@ __global__ void __launch_bounds__(kChainThreads) arm_back_kernel(const harp_arm_
     __syncthreads();
     if (tid < NJ * 3) W.g_Gt[(size_t)b * NJ * 3 + tid] = s_gGt[tid];
   }
-  // ---- scatter what is final by now into the gradient rows of the parameter tables (frame_setup_bwd_kernel's trans / cam / light part);
-  //      duplicates of a frame in one batch are legal and the shared light is summed over the frames -> atomics
-  const int f = H.fid[b];
-  if (tid < 3) {
-    const int k = tid;
-    if (T.g_trans && !lean) atomicAdd(T.g_trans + f * 3 + k, s_tot[k]);
-    if (T.g_cam && !lean) {
-      if (k == 0) {
-        const float c0 = T.cam[f * 3];
-        const float den = (float)A.S * c0 + 1e-9f;
-        atomicAdd(T.g_cam + f * 3, A.g_cam_T[b * 3 + 2] * (-2.0f * A.focal * (float)A.S / (den * den)));
-      } else {
-        atomicAdd(T.g_cam + f * 3 + k, -A.g_cam_T[b * 3 + (k - 1)]);
-      }
-    }
-    if (g_colors && A.g_light_pos && T.g_light_positions) {
-      const int lf = T.share_light ? 0 : f;
-      atomicAdd(T.g_light_positions + lf * 3 + k, A.g_light_pos[b * 3 + k]);
-    }
-  } else if (tid == 64 && b == 0 && H.self_shadow && g_colors && T.g_amb_ratio) {
-    const float amb = 1.0f / (1.0f + expf(-T.amb_ratio[0]));
-    const float g_amb = (g_colors[0] + g_colors[1] + g_colors[2]) - (g_colors[3] + g_colors[4] + g_colors[5]);
-    atomicAdd(T.g_amb_ratio, g_amb * amb * (1.0f - amb));
-  }
-  // ---- optional step epilogue (harp_step_frame): every kernel that reads the schedule row, adds to the loss vector or reads the draw
-  //      counter is an EARLIER launch of the step (stream order / joins), so one workgroup can turn the three over for the next step
-  if (b == 0) {
-    const harp_step_frame& E = H.step;
-    if ((tid >> 6) == 2) {                          // wave 2 (lanes 128 .. 191), whole: the wave sum below needs every lane
-      const int k = tid - 128;
-      const bool on = E.loss && k < E.n_loss;       // n_loss <= 64 (checked by the launcher)
-      const float v = on ? E.loss[k] : 0.f;
-      if (on) {
-        if (E.loss_out) E.loss_out[k] = v;
-        E.loss[k] = 0.f;
-      }
-      if (E.loss_w && E.loss_total) {
-        const float tot = wave_sum_u(on ? E.loss_w[k] * v : 0.f);
-        if (k == 0) E.loss_total[0] += tot;
-      }
-    } else if (tid == 192 && E.schedule) {
-      E.sched_row[0] = (int)((unsigned)E.sched_row[0] % (unsigned)E.n_rows) + 1;
-    } else if (tid == 193 && E.draw_counter) {
-      E.draw_counter[0] += 1;
-    }
-  }
+  // ---- scatter what is final by now into the gradient rows of the parameter tables, then the optional step epilogue (frame_body.h)
+  if (tid < 3) fb::tables_scatter(T, A, H.fid[b], b, tid, s_tot[tid], !lean, !lean, g_colors != nullptr);
+  else if (tid == 64 && b == 0) fb::amb_scatter(T, H.self_shadow, g_colors);
+  if (b == 0) fb::step_epilogue<2>(H.step, tid);
 }
 
 // ---- wide forms (csrc/chain_wide.hip): skinning / skinning backward on kChainParts workgroups per frame (a contiguous quarter of the NV
@@ -360,49 +278,10 @@ __global__ void __launch_bounds__(kArmWide) arm_back_wide_kernel(const harp_arm_
   float* gGt = W.g_Gt + (size_t)b * NJ * 3;
   if (lead && tid < NJ * 3 && s_gGt[tid] != 0.f) atomicAdd(gGt + tid, s_gGt[tid]);
   if (tid >= 64 && tid < 67 && M.center_joint >= 0) atomicAdd(gGt + M.center_joint * 3 + tid - 64, -s_tot[tid - 64]);
-  // ---- scatter into the gradient rows of the parameter tables (frame_setup_bwd_kernel's trans / cam / light part)
-  const int f = H.fid[b];
-  if (tid < 3) {
-    const int k = tid;
-    if (T.g_trans) atomicAdd(T.g_trans + f * 3 + k, s_tot[k]);
-    if (T.g_cam && lead) {
-      if (k == 0) {
-        const float c0 = T.cam[f * 3];
-        const float den = (float)A.S * c0 + 1e-9f;
-        atomicAdd(T.g_cam + f * 3, A.g_cam_T[b * 3 + 2] * (-2.0f * A.focal * (float)A.S / (den * den)));
-      } else {
-        atomicAdd(T.g_cam + f * 3 + k, -A.g_cam_T[b * 3 + (k - 1)]);
-      }
-    }
-    if (lead && g_colors && A.g_light_pos && T.g_light_positions) {
-      const int lf = T.share_light ? 0 : f;
-      atomicAdd(T.g_light_positions + lf * 3 + k, A.g_light_pos[b * 3 + k]);
-    }
-  } else if (tid == 128 && lead && b == 0 && H.self_shadow && g_colors && T.g_amb_ratio) {
-    const float amb = 1.0f / (1.0f + expf(-T.amb_ratio[0]));
-    const float g_amb = (g_colors[0] + g_colors[1] + g_colors[2]) - (g_colors[3] + g_colors[4] + g_colors[5]);
-    atomicAdd(T.g_amb_ratio, g_amb * amb * (1.0f - amb));
-  }
-  if (b == 0 && lead) {                             // step epilogue (harp_step_frame), as in arm_back_kernel
-    const harp_step_frame& E = H.step;
-    if ((tid >> 6) == 3) {                          // wave 3 (lanes 192 .. 255), whole: the wave sum below needs every lane
-      const int k = tid - 192;
-      const bool on = E.loss && k < E.n_loss;
-      const float vv = on ? E.loss[k] : 0.f;
-      if (on) {
-        if (E.loss_out) E.loss_out[k] = vv;
-        E.loss[k] = 0.f;
-      }
-      if (E.loss_w && E.loss_total) {
-        const float tot = wave_sum_u(on ? E.loss_w[k] * vv : 0.f);
-        if (k == 0) E.loss_total[0] += tot;
-      }
-    } else if (tid == 256 && E.schedule) {
-      E.sched_row[0] = (int)((unsigned)E.sched_row[0] % (unsigned)E.n_rows) + 1;
-    } else if (tid == 257 && E.draw_counter) {
-      E.draw_counter[0] += 1;
-    }
-  }
+  // ---- scatter into the gradient rows of the parameter tables (every part its share of the translation sum), step epilogue
+  if (tid < 3) fb::tables_scatter(T, A, H.fid[b], b, tid, s_tot[tid], true, lead, lead && g_colors);
+  else if (tid == 128 && lead && b == 0) fb::amb_scatter(T, H.self_shadow, g_colors);
+  if (b == 0 && lead) fb::step_epilogue<3>(H.step, tid);
 }
 
 // one wave per frame: chain + Rodrigues backward, adding rot / wrist_pose / pose / shape straight to their rows (lbs_tree_body.h)
@@ -422,8 +301,7 @@ bool arm_ok(const harp_arm_front* h) {
          a.V0 + a.E0 <= harp_mesh_chain_max_vertices() && a.NJ * 3 <= kFrontThreads && m.NJ > 0 && m.NJ <= MAXJ && m.NB >= 10 && m.NB <= MAXB &&
          m.n_pose_in == 17 && m.v_template && m.shapedirs_T && m.posedirs_T && m.posedirs && m.J_template && m.J_dirs && m.weights &&
          m.pose_mean && m.parents && m.pose_src && m.joint_src && h->weights_T && h->fid && h->pose_in && h->betas && h->trans_b && h->cam_R &&
-         h->cam_T && h->light_pos && h->colors && h->lbs_ws && h->tables.wrist_pose && h->tables.n_betas_out == m.NB &&
-         !(h->step.schedule && (!h->step.sched_row || h->step.n_rows <= 0));
+         h->cam_T && h->light_pos && h->colors && h->lbs_ws && h->tables.wrist_pose && h->tables.n_betas_out == m.NB;
 }
 
 }  // namespace
@@ -433,9 +311,7 @@ extern "C" {
 int harp_arm_front_fwd(const harp_arm_front* h, hipStream_t stream) {
   if (!arm_ok(h)) return HARP_ERR_ARG;
   const harp_mesh_chain& a = h->chain;
-  if (!a.verts_mm || !a.joints_mm || !a.joints_m || !a.vs || !a.n1 || !a.il1 || !a.vd || !a.n2 || !a.il2 || !a.ndc_c ||
-      (a.shadow && (!a.centroid || !a.light_R || !a.light_T || !a.ndc_l)) || (h->step.clear_mesh_grads && (!a.g_vd || !a.g_joints_m)))
-    return HARP_ERR_ARG;
+  if (!fb::chain_fwd_ok(a) || !fb::step_ok(h->step, a, false)) return HARP_ERR_ARG;
   hipLaunchKernelGGL(arm_front_kernel, dim3(a.B), dim3(kFrontThreads), 0, stream, *h);
   const int rc = harp_detail_tree_blend(h->tree, h->lbs_ws, h->betas, a.B, stream);
   if (rc != HARP_OK) return rc;
@@ -448,12 +324,7 @@ int harp_arm_front_fwd(const harp_arm_front* h, hipStream_t stream) {
 int harp_arm_back_bwd(const harp_arm_front* h, const float* g_colors, float* g_pose_scratch, float* g_betas_scratch, hipStream_t stream) {
   if (!arm_ok(h) || !g_pose_scratch || !g_betas_scratch) return HARP_ERR_ARG;
   const harp_mesh_chain* a = &h->chain;
-  if (!a->sub_off || !a->sub_idx || !a->vd || !a->vs || !a->n1 || !a->il1 || !a->cam_R || !a->cam_T || !a->g_vd || !a->g_ndc_c ||
-      !a->g_joints_m || !a->g_joints_mm || !a->g_v0 || !a->g_cam_T || !a->g_disp || (a->has_normal_grad && (!a->n2 || !a->il2 || !a->g_n2)) ||
-      (a->shadow && (!a->light_pos || !a->centroid || !a->light_R || !a->light_T || !a->g_ndc_l || !a->g_light_R || !a->g_light_T ||
-                     !a->g_light_pos)))
-    return HARP_ERR_ARG;
-  if (h->step.loss && (h->step.n_loss < 0 || h->step.n_loss > 64)) return HARP_ERR_ARG;
+  if (!fb::chain_bwd_ok(*a) || !fb::step_ok(h->step, *a, true)) return HARP_ERR_ARG;
   const size_t lds = (size_t)(a->V0 + a->E0) * 9 * sizeof(float);
   // dynamic LDS above 64 KB has to be requested (147 KB on the arm mesh); per-device attribute, set on every call
   if (hipFuncSetAttribute((const void*)arm_back_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return HARP_ERR_ARG;
@@ -479,9 +350,8 @@ static bool arm_wide_ok(const harp_arm_front* h) {
 int harp_arm_front_wide_fwd(const harp_arm_front* h, float* part_ws, hipStream_t stream) {
   if (!arm_ok(h) || !part_ws || !arm_wide_ok(h) || (h->chain.V0 + h->chain.E0) * 12 > 64 * 1024) return HARP_ERR_ARG;
   const harp_mesh_chain& a = h->chain;
-  if (!a.verts_mm || !a.joints_mm || !a.joints_m || !a.vs || !a.n1 || !a.il1 || !a.vd || !a.n2 || !a.il2 || !a.ndc_c || !a.cam_R || !a.cam_T ||
-      (a.shadow && (!a.centroid || !a.light_R || !a.light_T || !a.ndc_l || !a.light_pos)) || (h->step.clear_mesh_grads && (!a.g_vd || !a.g_joints_m)))
-    return HARP_ERR_ARG;
+  // (the wide chain reads the camera and the light position from the chain struct's rows, not from LDS)
+  if (!fb::chain_fwd_ok(a) || !a.cam_R || !a.cam_T || (a.shadow && !a.light_pos) || !fb::step_ok(h->step, a, false)) return HARP_ERR_ARG;
   hipLaunchKernelGGL(arm_front_kernel, dim3(a.B), dim3(kFrontThreads), 0, stream, *h);
   const int rc = harp_detail_tree_blend(h->tree, h->lbs_ws, h->betas, a.B, stream);
   if (rc != HARP_OK) return rc;
@@ -496,12 +366,7 @@ int harp_arm_back_wide_bwd(const harp_arm_front* h, const float* g_colors, float
   if (h->chain.light_only) return harp_arm_back_bwd(h, g_colors, g_pose_scratch, g_betas_scratch, stream);
   if (!arm_ok(h) || !g_pose_scratch || !g_betas_scratch || !arm_wide_ok(h) || (h->chain.V0 + h->chain.E0) * 24 > 160 * 1024 - 256) return HARP_ERR_ARG;
   const harp_mesh_chain* a = &h->chain;
-  if (!a->sub_off || !a->sub_idx || !a->vd || !a->vs || !a->n1 || !a->il1 || !a->cam_R || !a->cam_T || !a->g_vd || !a->g_ndc_c ||
-      !a->g_joints_m || !a->g_joints_mm || !a->g_v0 || !a->g_cam_T || !a->g_disp || (a->has_normal_grad && (!a->n2 || !a->il2 || !a->g_n2)) ||
-      (a->shadow && (!a->light_pos || !a->centroid || !a->light_R || !a->light_T || !a->g_ndc_l || !a->g_light_R || !a->g_light_T ||
-                     !a->g_light_pos)))
-    return HARP_ERR_ARG;
-  if (h->step.loss && (h->step.n_loss < 0 || h->step.n_loss > 64)) return HARP_ERR_ARG;
+  if (!fb::chain_bwd_ok(*a) || !fb::step_ok(h->step, *a, true)) return HARP_ERR_ARG;
   const float* G = nullptr;
   int rc = harp_detail_chain_wide_bwd(*a, part_ws, &G, stream);
   if (rc != HARP_OK) return rc;

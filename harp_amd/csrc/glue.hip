@@ -4,7 +4,8 @@
 // renderer_helper.py:435-441) and the light camera of process_info_for_shadow (renderer_helper.py:454-468, with
 // PyTorch3D look_at_rotation) — as one forward and one backward kernel each, one lane per frame.  The backward scatters
 // straight into the flat gradient arena of the parameter tables (dense-Adam semantics: untouched rows keep zero grad).
-#include "chain_body.h"      // V3 helpers + the light camera (process_info_for_shadow / look_at_rotation), shared with the fused chain
+#include "frame_body.h"      // the camera / colour / schedule arithmetic shared with the fused front and back kernels; chain_body.h: V3 helpers +
+                             // the light camera (process_info_for_shadow / look_at_rotation), shared with the fused chain
 
 namespace {
 
@@ -15,14 +16,7 @@ __global__ void frame_setup_fwd_kernel(const harp_frame_tables t, const int32_t*
                                        float* __restrict__ trans_b, float* __restrict__ cam_R, float* __restrict__ cam_T,
                                        float* __restrict__ light_pos, float* __restrict__ colors) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b == 0) {
-    if (self_shadow) {
-      const float amb = 1.0f / (1.0f + expf(-t.amb_ratio[0]));            // nn.Sigmoid()(params['amb_ratio'])
-      for (int c = 0; c < 3; ++c) { colors[c] = amb; colors[3 + c] = 1.0f - amb; colors[6 + c] = 0.f; }
-    } else {
-      for (int c = 0; c < 3; ++c) { colors[c] = 0.5f; colors[3 + c] = 0.4f; colors[6 + c] = 0.1f; }   // renderer_helper.py:70-73
-    }
-  }
+  if (b == 0) fb::light_colors(self_shadow, t.amb_ratio, colors);
   if (b >= B) return;
   const int f = fid[b];
   const int ps = t.wrist_pose ? 51 : 48, ho = t.wrist_pose ? 6 : 3, nbo = t.n_betas_out > 0 ? t.n_betas_out : 10;
@@ -31,10 +25,7 @@ __global__ void frame_setup_fwd_kernel(const harp_frame_tables t, const int32_t*
   for (int k = 0; k < 45; ++k) pose48[b * ps + ho + k] = t.pose[f * 45 + k];
   for (int k = 0; k < nbo; ++k) betas[b * nbo + k] = (k < 10) ? t.shape[k] : 0.f;
   for (int k = 0; k < 3; ++k) trans_b[b * 3 + k] = t.trans[f * 3 + k];
-  const float c0 = t.cam[f * 3], c1 = t.cam[f * 3 + 1], c2 = t.cam[f * 3 + 2];
-  cam_T[b * 3] = -c1; cam_T[b * 3 + 1] = -c2; cam_T[b * 3 + 2] = 2.0f * focal / ((float)S * c0 + 1e-9f);
-  const float R[9] = {-1.f, 0.f, 0.f, 0.f, -1.f, 0.f, 0.f, 0.f, 1.f};
-  for (int k = 0; k < 9; ++k) cam_R[b * 9 + k] = R[k];
+  fb::cam_from_row(t.cam + f * 3, focal, S, cam_R + b * 9, cam_T + b * 3);
   const int lf = t.share_light ? 0 : f;
   for (int k = 0; k < 3; ++k) light_pos[b * 3 + k] = t.light_positions[lf * 3 + k];
 }
@@ -46,11 +37,7 @@ __global__ void frame_setup_bwd_kernel(const harp_frame_tables t, const int32_t*
   // one wave per frame, one lane per element: the ~70 scatter atomics of a frame are issued at once (one lane per frame walked
   // them one after the other: 22 us of pure latency)
   const int b = blockIdx.x, k = threadIdx.x;
-  if (b == 0 && k == 0 && self_shadow && g_colors && t.g_amb_ratio) {
-    const float amb = 1.0f / (1.0f + expf(-t.amb_ratio[0]));
-    const float g_amb = (g_colors[0] + g_colors[1] + g_colors[2]) - (g_colors[3] + g_colors[4] + g_colors[5]);
-    atomicAdd(t.g_amb_ratio, g_amb * amb * (1.0f - amb));
-  }
+  if (b == 0 && k == 0) fb::amb_scatter(t, self_shadow, g_colors);
   if (b >= B) return;
   const int f = fid[b];
   // duplicates of a frame inside one batch are legal -> atomics
@@ -63,15 +50,7 @@ __global__ void frame_setup_bwd_kernel(const harp_frame_tables t, const int32_t*
   }
   if (g_betas && t.g_shape && k < 10) atomicAdd(t.g_shape + k, g_betas[b * nbo + k]);
   if (g_trans_b && t.g_trans && k < 3) atomicAdd(t.g_trans + f * 3 + k, g_trans_b[b * 3 + k]);
-  if (g_cam_T && t.g_cam && k < 3) {
-    if (k == 0) {
-      const float c0 = t.cam[f * 3];
-      const float den = (float)S * c0 + 1e-9f;
-      atomicAdd(t.g_cam + f * 3, g_cam_T[b * 3 + 2] * (-2.0f * focal * (float)S / (den * den)));
-    } else {
-      atomicAdd(t.g_cam + f * 3 + k, -g_cam_T[b * 3 + (k - 1)]);
-    }
-  }
+  if (g_cam_T && t.g_cam && k < 3) atomicAdd(t.g_cam + f * 3 + k, fb::cam_row_bwd(t.cam + f * 3, focal, S, g_cam_T + b * 3, k));
   if (g_light_pos && t.g_light_positions && k < 3) {
     const int lf = t.share_light ? 0 : f;
     atomicAdd(t.g_light_positions + lf * 3 + k, g_light_pos[b * 3 + k]);
@@ -122,7 +101,7 @@ __global__ void schedule_next_kernel(const int32_t* __restrict__ sched, const in
   for (int i = threadIdx.x; i < B; i += blockDim.x) {
     const int f = sched[(size_t)row * B + i];
     fid[i] = f;
-    tfid[i] = tsched ? tsched[(size_t)row * B + i] : f - target_offset;
+    tfid[i] = fb::step_tfid(tsched, (size_t)row * B + i, f, target_offset);
   }
   __syncthreads();
   if (threadIdx.x == 0) counter[0] = row + 1;

@@ -7,11 +7,14 @@
 // end of mesh_chain_fwd, 67 us of kernel time + 38 us of node-to-node gaps), every one of them one workgroup per frame or less.  A
 // frame's data fits one CU, so the stages are separated by workgroup barriers instead of graph edges: 27 us (tools/dev/
 // gpu_front_stages.py).  Same arithmetic as the stand-alone kernels, which stay as the C-ABI building blocks (and serve the SMPL-X arm
-// path, whose skinning is shared across frames on MFMA: lbs_tree.hip).  The rasteriser set-up was tried in here as well and taken
+// path, whose skinning is shared across frames on MFMA: lbs_tree.hip).  The schedule row, the row gathers and the clear of the mesh
+// gradients are frame_body.h (shared with glue.hip and arm_front.hip), the mesh chain is chain_body.h.  The joint stage and the per-vertex
+// blend / skinning are typed out in both kernels below: as shared device functions the compiler contracted their multiply-adds differently
+// (results 1 ulp off the stand-alone kernels' history), so they stay as they are.  The rasteriser set-up was tried in here as well and taken
 // out again: face records + binning of 6152 faces x 2 views are throughput work, and on ONE CU per frame they cost 130 us.
 //   reference: utils/visualize.py:16-88 (prepare_mesh), manopth/manolayer.py:108-296, renderer_helper.py:454-468,
 //   MeshRasterizer.transform for both views (renderer_helper.py:344, 353).
-#include "chain_body.h"
+#include "frame_body.h"
 #include "lbs_body.h"
 
 namespace {
@@ -25,9 +28,7 @@ __global__ void __launch_bounds__(kChainThreads) hand_front_kernel(const harp_ha
   __shared__ float sR[NJ][9], sJ[NJ][3], sG[NJ][12], s_j16[NJ][3], s_tip[5][3];
   const harp_mesh_chain& A = H.chain;
   const harp_mano_model& M = H.mano;
-  const harp_frame_tables& T = H.tables;
   const int b = blockIdx.x, tid = threadIdx.x, B = A.B;
-  const int V = A.V0 + A.E0;
   float* s_p = s_dyn;
   // ---- L2 warm-up: the blend-shape rows (1.35 MB) were evicted from this XCD's L2 by the rest of the previous step, and one CU
   //      pulling them from HBM / MALL with ~45 loads per wave in flight is latency-bound (stage stamps in a replayed step: 23 us for
@@ -48,51 +49,10 @@ __global__ void __launch_bounds__(kChainThreads) hand_front_kernel(const harp_ha
   // ---- optional step prologue (harp_step_frame): this workgroup's frame from the device schedule — what schedule_next_kernel did as a
   //      launch of its own in front of this one (6 us + a node gap on the critical path) —, and the clear of the frame's slice of the two
   //      gradient segments the key-point / mesh terms accumulate into (they start after this kernel)
-  int f;
-  if (H.step.schedule) {
-    const int row = (int)((unsigned)H.step.sched_row[0] % (unsigned)H.step.n_rows);     // bumped by hand_back_kernel, a later launch
-    f = H.step.schedule[(size_t)row * B + b];
-    if (tid == 0) {
-      const_cast<int32_t*>(H.fid)[b] = f;
-      if (H.step.tfid_out) H.step.tfid_out[b] = H.step.tschedule ? H.step.tschedule[(size_t)row * B + b] : f - H.step.target_offset;
-    }
-  } else {
-    f = H.fid[b];
-  }
-  if (H.step.clear_mesh_grads) {
-    float* gv = const_cast<float*>(A.g_vd) + (size_t)b * V * 3;          // (inputs of the backward launch of the same struct)
-    for (int i = tid; i < V * 3; i += kChainThreads) gv[i] = 0.f;
-    if (tid < A.NJ * 3) const_cast<float*>(A.g_joints_m)[(size_t)b * A.NJ * 3 + tid] = 0.f;
-  }
-  // ---- frame set-up (glue.hip: frame_setup_fwd_kernel)
-  if (tid < 48) {
-    const float p = (tid < 3) ? T.rot[f * 3 + tid] : T.pose[f * 45 + tid - 3];
-    s_pose[tid] = p; H.pose48[b * 48 + tid] = p;
-  } else if (tid >= 64 && tid < 64 + NB) {
-    const int k = tid - 64;
-    const float v = T.shape[k];
-    s_beta[k] = v; H.betas[b * NB + k] = v;
-  } else if (tid >= 128 && tid < 131) {
-    const int k = tid - 128;
-    const float v = T.trans[f * 3 + k];
-    s_tr[k] = v; H.trans_b[b * 3 + k] = v;
-    const int lf = T.share_light ? 0 : f;
-    const float lp = T.light_positions[lf * 3 + k];
-    s_lpos[k] = lp; H.light_pos[b * 3 + k] = lp;
-  } else if (tid == 192) {
-    const float c0 = T.cam[f * 3], c1 = T.cam[f * 3 + 1], c2 = T.cam[f * 3 + 2];
-    const float ct[3] = {-c1, -c2, 2.0f * A.focal / ((float)A.S * c0 + 1e-9f)};
-    const float R[9] = {-1.f, 0.f, 0.f, 0.f, -1.f, 0.f, 0.f, 0.f, 1.f};
-    for (int k = 0; k < 9; ++k) { s_cam[k] = R[k]; H.cam_R[b * 9 + k] = R[k]; }
-    for (int k = 0; k < 3; ++k) { s_cam[9 + k] = ct[k]; H.cam_T[b * 3 + k] = ct[k]; }
-  } else if (tid == 256 && b == 0) {
-    if (H.self_shadow) {
-      const float amb = 1.0f / (1.0f + expf(-T.amb_ratio[0]));            // nn.Sigmoid()(params['amb_ratio'])
-      for (int c = 0; c < 3; ++c) { H.colors[c] = amb; H.colors[3 + c] = 1.0f - amb; H.colors[6 + c] = 0.f; }
-    } else {
-      for (int c = 0; c < 3; ++c) { H.colors[c] = 0.5f; H.colors[3 + c] = 0.4f; H.colors[6 + c] = 0.1f; }   // renderer_helper.py:70-73
-    }
-  }
+  const int f = fb::step_frame_of(H.step, H.fid, b, B, tid == 0);
+  if (H.step.clear_mesh_grads) fb::clear_mesh_grads(A, b, 0, 1, tid, kChainThreads);
+  // ---- frame set-up (frame_body.h, the arithmetic of glue.hip: frame_setup_fwd_kernel)
+  fb::frame_rows<false, 256>(H, H.pose48, 48, NB, f, b, tid, true, s_pose, s_beta, s_tr, s_cam, s_lpos);
   __syncthreads();
   // ---- hand layer, joints (lbs.hip: lbs_joints_kernel); workspace rows are kept for the backward pass
   const LbsWs Wl = lbs_ws(H.lbs_ws, B);
@@ -169,7 +129,7 @@ __global__ void __launch_bounds__(kChainThreads) hand_front_kernel(const harp_ha
       const float c = s_pm[k];
       q0 += r[0] * c; q1 += r[1] * c; q2 += r[2] * c;
     }
-    float* vpo = w_vposed + ((size_t)b * NV + v) * 3;
+    float* vpo = Wl.vposed + ((size_t)b * NV + v) * 3;
     vpo[0] = q0; vpo[1] = q1; vpo[2] = q2;
     float Tm[12];
 #pragma unroll
@@ -210,7 +170,6 @@ __global__ void __launch_bounds__(kWideThreads) hand_front_wide_kernel(const har
   __shared__ float sR[NJ][9], sJ[NJ][3], sG[NJ][12], s_j16[NJ][3];
   const harp_mesh_chain& A = H.chain;
   const harp_mano_model& M = H.mano;
-  const harp_frame_tables& T = H.tables;
   const int b = blockIdx.x / cb::kChainParts, part = blockIdx.x % cb::kChainParts, tid = threadIdx.x, B = A.B;
   const bool lead = part == 0;
   constexpr int kPer = (NV + cb::kChainParts - 1) / cb::kChainParts;
@@ -230,50 +189,9 @@ __global__ void __launch_bounds__(kWideThreads) hand_front_wide_kernel(const har
 #pragma unroll
     for (int q = 0; q < kEach; ++q) warm += t[q];
   }
-  int f;
-  if (H.step.schedule) {
-    const int row = (int)((unsigned)H.step.sched_row[0] % (unsigned)H.step.n_rows);     // bumped by hand_back_kernel, a later launch
-    f = H.step.schedule[(size_t)row * B + b];
-    if (tid == 0 && lead) {
-      const_cast<int32_t*>(H.fid)[b] = f;
-      if (H.step.tfid_out) H.step.tfid_out[b] = H.step.tschedule ? H.step.tschedule[(size_t)row * B + b] : f - H.step.target_offset;
-    }
-  } else {
-    f = H.fid[b];
-  }
-  // ---- frame set-up (glue.hip: frame_setup_fwd_kernel)
-  if (tid < 48) {
-    const float p = (tid < 3) ? T.rot[f * 3 + tid] : T.pose[f * 45 + tid - 3];
-    s_pose[tid] = p;
-    if (lead) H.pose48[b * 48 + tid] = p;
-  } else if (tid >= 64 && tid < 64 + NB) {
-    const int k = tid - 64;
-    const float v = T.shape[k];
-    s_beta[k] = v;
-    if (lead) H.betas[b * NB + k] = v;
-  } else if (tid >= 128 && tid < 131) {
-    const int k = tid - 128;
-    const float v = T.trans[f * 3 + k];
-    s_tr[k] = v;
-    if (lead) {
-      H.trans_b[b * 3 + k] = v;
-      const int lf = T.share_light ? 0 : f;
-      H.light_pos[b * 3 + k] = T.light_positions[lf * 3 + k];
-    }
-  } else if (tid == 192 && lead) {
-    const float c0 = T.cam[f * 3], c1 = T.cam[f * 3 + 1], c2 = T.cam[f * 3 + 2];
-    const float ct[3] = {-c1, -c2, 2.0f * A.focal / ((float)A.S * c0 + 1e-9f)};
-    const float R[9] = {-1.f, 0.f, 0.f, 0.f, -1.f, 0.f, 0.f, 0.f, 1.f};
-    for (int k = 0; k < 9; ++k) H.cam_R[b * 9 + k] = R[k];
-    for (int k = 0; k < 3; ++k) H.cam_T[b * 3 + k] = ct[k];
-  } else if (tid == 193 && lead && b == 0) {
-    if (H.self_shadow) {
-      const float amb = 1.0f / (1.0f + expf(-T.amb_ratio[0]));            // nn.Sigmoid()(params['amb_ratio'])
-      for (int c = 0; c < 3; ++c) { H.colors[c] = amb; H.colors[3 + c] = 1.0f - amb; H.colors[6 + c] = 0.f; }
-    } else {
-      for (int c = 0; c < 3; ++c) { H.colors[c] = 0.5f; H.colors[3 + c] = 0.4f; H.colors[6 + c] = 0.1f; }   // renderer_helper.py:70-73
-    }
-  }
+  const int f = fb::step_frame_of(H.step, H.fid, b, B, tid == 0 && lead);
+  // ---- frame set-up (frame_body.h); the rows are written by part 0
+  fb::frame_rows<false, 193>(H, H.pose48, 48, NB, f, b, tid, lead, s_pose, s_beta, s_tr, nullptr, nullptr);
   __syncthreads();
   // ---- hand layer, joints (lbs.hip: lbs_joints_kernel); workspace rows are kept for the backward pass (written by part 0)
   const LbsWs Wl = lbs_ws(H.lbs_ws, B);
@@ -330,12 +248,8 @@ __global__ void __launch_bounds__(kWideThreads) hand_front_wide_kernel(const har
   }
   __syncthreads();
   if (warm == 1.2345e-30f) H.colors[9] = warm;      // keeps the warm-up loads alive (never true)
-  if (clear_here && H.step.clear_mesh_grads) {       // (hybrid front: the one-workgroup chain that follows does not clear)
-    const int V = A.V0 + A.E0, per = (V * 3 + cb::kChainParts - 1) / cb::kChainParts;
-    float* gv = const_cast<float*>(A.g_vd) + (size_t)b * V * 3;
-    for (int k = part * per + tid; k < min((part + 1) * per, V * 3); k += kWideThreads) gv[k] = 0.f;
-    if (lead && tid < A.NJ * 3) const_cast<float*>(A.g_joints_m)[(size_t)b * A.NJ * 3 + tid] = 0.f;
-  }
+  // (hybrid front: the one-workgroup chain that follows does not clear)
+  if (clear_here && H.step.clear_mesh_grads) fb::clear_mesh_grads(A, b, part, cb::kChainParts, tid, kWideThreads);
   // ---- blend shapes + skinning (lbs.hip: lbs_skin_kernel), one lane per vertex of this part's quarter
   const int v = part * kPer + tid;
   if (tid < kPer && v < NV) {
@@ -389,17 +303,9 @@ int harp_detail_chain_wide_tail(const harp_mesh_chain& a, int clear_grads, float
 extern "C" {
 
 int harp_hand_front_fwd(const harp_hand_front* h, hipStream_t stream) {
-  if (!h) return HARP_ERR_ARG;
+  if (!hand_ok(h) || !hand_rows_ok(h)) return HARP_ERR_ARG;
   const harp_mesh_chain& a = h->chain;
-  if (!a.edges0 || !a.vf_off || !a.vf_tri || !a.disp || a.B <= 0 || a.V0 != NV || a.E0 < 0 || a.NJ != 21 ||
-      a.V0 + a.E0 > harp_mesh_chain_max_vertices() || !a.verts_mm || !a.joints_mm || !a.joints_m || !a.vs || !a.n1 || !a.il1 || !a.vd ||
-      !a.n2 || !a.il2 || !a.ndc_c || (a.shadow && (!a.centroid || !a.light_R || !a.light_T || !a.ndc_l)))
-    return HARP_ERR_ARG;
-  if (!h->fid || !h->pose48 || !h->betas || !h->trans_b || !h->cam_R || !h->cam_T || !h->light_pos || !h->colors || !h->lbs_ws ||
-      h->tables.wrist_pose)
-    return HARP_ERR_ARG;
-  if ((h->step.schedule && (!h->step.sched_row || h->step.n_rows <= 0)) || (h->step.clear_mesh_grads && (!a.g_vd || !a.g_joints_m)))
-    return HARP_ERR_ARG;
+  if (!fb::chain_fwd_ok(a) || a.V0 + a.E0 > harp_mesh_chain_max_vertices() || !fb::step_ok(h->step, a, false)) return HARP_ERR_ARG;
   // The kernel needs V*12 B (<= 48 KB) of dynamic LDS and asks for (almost) the whole CU's 160 KB: a workgroup of it is a frame's latency
   // chain, and while it runs the parameter-only regularisers start on the second stream — a kernel of 1 500 small workgroups with a few
   // bytes of LDS each, which can then not land on this CU and take issue slots / L1 from the chain (-3 us / step, same-box A/B x3;
@@ -415,17 +321,10 @@ int harp_hand_front_fwd(const harp_hand_front* h, hipStream_t stream) {
 // The same front on kChainParts workgroups per frame: hand layer (hand_front_wide_kernel) + the wide mesh chain (chain_wide.hip), three
 // launches.  part_ws: harp_mesh_chain_wide_ws_floats(B) floats.
 int harp_hand_front_wide_fwd(const harp_hand_front* h, float* part_ws, hipStream_t stream) {
-  if (!h || !part_ws) return HARP_ERR_ARG;
+  if (!hand_ok(h) || !hand_rows_ok(h) || !part_ws) return HARP_ERR_ARG;
   const harp_mesh_chain& a = h->chain;
-  if (!a.edges0 || !a.vf_off || !a.vf_tri || !a.disp || a.B <= 0 || a.V0 != NV || a.E0 < 0 || a.NJ != 21 ||
-      (a.V0 + a.E0 + cb::kChainParts - 1) / cb::kChainParts > kChainThreads || (a.V0 + a.E0) * 12 > 64 * 1024 || !a.verts_mm || !a.joints_mm ||
-      !a.joints_m || !a.vs || !a.n1 || !a.il1 || !a.vd || !a.n2 || !a.il2 || !a.ndc_c ||
-      (a.shadow && (!a.centroid || !a.light_R || !a.light_T || !a.ndc_l)))
-    return HARP_ERR_ARG;
-  if (!h->fid || !h->pose48 || !h->betas || !h->trans_b || !h->cam_R || !h->cam_T || !h->light_pos || !h->colors || !h->lbs_ws ||
-      h->tables.wrist_pose)
-    return HARP_ERR_ARG;
-  if ((h->step.schedule && (!h->step.sched_row || h->step.n_rows <= 0)) || (h->step.clear_mesh_grads && (!a.g_vd || !a.g_joints_m)))
+  if (!fb::chain_fwd_ok(a) || (a.V0 + a.E0 + cb::kChainParts - 1) / cb::kChainParts > kChainThreads || (a.V0 + a.E0) * 12 > 64 * 1024 ||
+      !fb::step_ok(h->step, a, false))
     return HARP_ERR_ARG;
   hipLaunchKernelGGL(hand_front_wide_kernel, dim3(a.B * cb::kChainParts), dim3(kWideThreads), 0, stream, *h, 0);
   HARP_CHECK_LAUNCH();
@@ -435,12 +334,10 @@ int harp_hand_front_wide_fwd(const harp_hand_front* h, float* part_ws, hipStream
 // Hybrid: the hand layer on four workgroups per frame (above), then the mesh chain as ONE workgroup per frame (harp_mesh_chain_fwd): two
 // launches.  Same outputs.
 int harp_hand_front_hybrid_fwd(const harp_hand_front* h, hipStream_t stream) {
-  if (!h) return HARP_ERR_ARG;
+  if (!hand_ok(h) || !hand_rows_ok(h)) return HARP_ERR_ARG;
   const harp_mesh_chain& a = h->chain;
-  if (a.B <= 0 || a.V0 != NV || a.E0 < 0 || a.NJ != 21 || !a.verts_mm || !a.joints_mm || !h->fid || !h->pose48 || !h->betas || !h->trans_b ||
-      !h->cam_R || !h->cam_T || !h->light_pos || !h->colors || !h->lbs_ws || h->tables.wrist_pose ||
-      (h->step.schedule && (!h->step.sched_row || h->step.n_rows <= 0)) || (h->step.clear_mesh_grads && (!a.g_vd || !a.g_joints_m)))
-    return HARP_ERR_ARG;
+  // (the mesh inputs, the chain's outputs and the size limit are checked by harp_mesh_chain_fwd below)
+  if (!a.verts_mm || !a.joints_mm || !fb::step_ok(h->step, a, false)) return HARP_ERR_ARG;
   hipLaunchKernelGGL(hand_front_wide_kernel, dim3(a.B * cb::kChainParts), dim3(kWideThreads), 0, stream, *h, 1);
   HARP_CHECK_LAUNCH();
   return harp_mesh_chain_fwd(&a, stream);

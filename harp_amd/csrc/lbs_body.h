@@ -1,8 +1,10 @@
 // MANO hand-layer arithmetic shared by the stand-alone LBS kernels (lbs.hip) and the fused per-frame front / back kernels
-// (hand_front.hip): Rodrigues via quaternion forward / backward (rodrigues_layer.py:43-54, :15-40), the kinematic parents
-// (manolayer.py:209-239), the finger-tip vertices and the joint re-ordering (:270, :279).
+// (hand_front.hip, hand_back.hip): Rodrigues via quaternion forward / backward (rodrigues_layer.py:43-54, :15-40), the kinematic parents
+// (manolayer.py:209-239), the finger-tip vertices and the joint re-ordering (:270, :279), the workspace layout, the joint-gradient split and
+// the per-vertex skinning backward of the two fused back kernels (autograd of manolayer.py:108-296).
 #pragma once
 #include "harp_common.h"
+#include "harp_hip.h"
 
 namespace lb {
 
@@ -70,5 +72,64 @@ __host__ __device__ inline LbsWs lbs_ws(float* ws, int B) {
   return w;
 }
 
+// ---- per-vertex skinning backward of the fused back kernels (hand_back.hip), one lane per vertex v
+// the 16 skinning weights of a vertex
+__device__ __forceinline__ void skin_weights(const harp_mano_model& M, int v, float4 w4s[4]) {
+  const float4* wr = (const float4*)(M.weights + (size_t)v * NJ);
+#pragma unroll
+  for (int j4 = 0; j4 < 4; ++j4) w4s[j4] = wr[j4];
+}
+
+// T = sum_j w_j A_j (row-major 3 x 4)
+__device__ __forceinline__ void skin_T(const float4 w4s[4], const float* s_A, float Tm[12]) {
+#pragma unroll
+  for (int k = 0; k < 12; ++k) Tm[k] = 0.f;
+#pragma unroll
+  for (int j4 = 0; j4 < NJ / 4; ++j4) {
+    const float4 w4 = w4s[j4];
+    const float wj[4] = {w4.x, w4.y, w4.z, w4.w};
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+#pragma unroll
+      for (int k = 0; k < 12; ++k) Tm[k] += wj[u] * s_A[(j4 * 4 + u) * 12 + k];
+  }
+}
+
+// backward of out = (T [q; 1] + trans) * 1000 for g = dL/d out * 1000: g_vp = T^T g, M = [g (x) q | g]
+__device__ __forceinline__ void skin_bwd_vertex(const float Tm[12], const float g[3], const float q[3], float* gvp, float* mo) {
+#pragma unroll
+  for (int c = 0; c < 3; ++c) gvp[c] = Tm[c] * g[0] + Tm[4 + c] * g[1] + Tm[8 + c] * g[2];
+#pragma unroll
+  for (int r = 0; r < 3; ++r) {
+    mo[r * 4] = g[r] * q[0]; mo[r * 4 + 1] = g[r] * q[1]; mo[r * 4 + 2] = g[r] * q[2]; mo[r * 4 + 3] = g[r];
+  }
+}
+
+// ---- joint gradients, lane t < 63 of frame b: chain joints -> g_j16 [metres] (LDS; the workspace row where `lead`), finger tips -> s_gtip
+//      for the lanes of their vertices (tip_grad)
+__device__ __forceinline__ void joints_grad_split(const float* g_joints_m, const LbsWs& W, int b, int t, bool lead, float (*s_gj16)[3],
+                                                  float (*s_gtip)[3]) {
+  const int k = t / 3, c = t % 3, src = c_reorder[k];
+  const float gj = g_joints_m[(size_t)b * 63 + t] * 1e-3f;            // (= g_joints_mm)
+  if (src < NJ) { s_gj16[src][c] = gj * 1000.0f; if (lead) W.g_j16[((size_t)b * NJ + src) * 3 + c] = gj * 1000.0f; }
+  else s_gtip[src - NJ][c] = gj;
+}
+// g (dL/d vertex v, per millimetre) += its finger-tip joint's gradient, then per metre
+__device__ __forceinline__ void tip_grad(int v, const float (*s_gtip)[3], float g[3]) {
+#pragma unroll
+  for (int k = 0; k < 5; ++k)
+    if (v == c_tips[k]) { g[0] += s_gtip[k][0]; g[1] += s_gtip[k][1]; g[2] += s_gtip[k][2]; }
+#pragma unroll
+  for (int c = 0; c < 3; ++c) g[c] *= 1000.0f;
+}
+
+// ---- host side: what all five fused MANO entry points require of the struct, and the gathered rows of the three fronts
+inline bool hand_ok(const harp_hand_front* h) {
+  return h && h->chain.B > 0 && h->chain.V0 == NV && h->chain.E0 >= 0 && h->chain.NJ == 21 && h->fid && h->pose48 && h->lbs_ws &&
+         !h->tables.wrist_pose;
+}
+inline bool hand_rows_ok(const harp_hand_front* h) {
+  return h->betas && h->trans_b && h->cam_R && h->cam_T && h->light_pos && h->colors;
+}
 
 }  // namespace lb

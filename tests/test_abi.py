@@ -121,3 +121,115 @@ def test_building_blocks_refuse_empty_sizes_without_launch(lib):
         assert lib.harp_light_setup_fwd(f, f, B, f, f, None) == 1, B
         assert lib.harp_light_setup_bwd(f, f, f, f, B, 4, f, f, None, None) == 1, B
     assert lib.harp_frame_setup_bwd(ctypes.byref(tables), f, 0, 64, 500.0, 1, f, f, f, f, f, f, None) == 1
+
+
+_F = 1 << 20                                                   # a fake device pointer, never dereferenced
+
+
+def _ptr_fields(cls):
+    return [n for n, t in cls._fields_ if t is ctypes.c_void_p]
+
+
+def _full_chain(V0, E0, NJ):
+    from harp_amd import _lib
+    return _lib.MeshChain(B=3, V0=V0, E0=E0, NJ=NJ, S=128, focal=500.0, shadow=1, has_normal_grad=1, light_only=0,
+                          **{n: _F for n in _ptr_fields(_lib.MeshChain)})
+
+
+def _full_step():
+    from harp_amd import _lib
+    return _lib.StepFrame(n_rows=4, target_offset=0, clear_mesh_grads=1, n_loss=8, **{n: _F for n in _ptr_fields(_lib.StepFrame)})
+
+
+def _full_hand():
+    from harp_amd import _lib
+    tables = _lib.FrameTables(n_betas_out=10, **{n: _F for n in _ptr_fields(_lib.FrameTables) if "wrist" not in n})
+    return _lib.HandFront(chain=_full_chain(778, 2328, 21), mano=_lib.ManoModel(*([_F] * len(_lib.ManoModel._fields_))), tables=tables,
+                          self_shadow=1, step=_full_step(), **{n: _F for n in _ptr_fields(_lib.HandFront)})
+
+
+def _full_arm():
+    from harp_amd import _lib
+    tables = _lib.FrameTables(n_betas_out=20, **{n: _F for n in _ptr_fields(_lib.FrameTables)})
+    tree = _lib.TreeModel(NV=1026, NJ=55, NB=20, n_pose_in=17, center_joint=21, n_joints_out=22, **{n: _F for n in _ptr_fields(_lib.TreeModel)})
+    return _lib.ArmFront(chain=_full_chain(1026, 3000, 22), tree=tree, tables=tables, self_shadow=1, step=_full_step(),
+                         **{n: _F for n in _ptr_fields(_lib.ArmFront)})
+
+
+def _mutated(make, path, value):
+    h = make()
+    obj, names = h, path.split(".")
+    for n in names[:-1]:
+        obj = getattr(obj, n)
+    setattr(obj, names[-1], value)
+    return h
+
+
+_CHAIN_IN = ["chain.edges0", "chain.vf_off", "chain.vf_tri", "chain.disp"]
+_CHAIN_FWD = ["chain." + n for n in ("verts_mm", "joints_mm", "joints_m", "vs", "n1", "il1", "vd", "n2", "il2", "ndc_c")]
+_CHAIN_FWD_SHADOW = ["chain." + n for n in ("centroid", "light_R", "light_T", "ndc_l")]
+_CHAIN_BWD = ["chain." + n for n in ("sub_off", "sub_idx", "vd", "vs", "n1", "il1", "cam_R", "cam_T", "g_vd", "g_ndc_c", "g_joints_m", "g_joints_mm",
+                                     "g_v0", "g_cam_T", "g_disp", "n2", "il2", "g_n2",                      # (has_normal_grad is set)
+                                     "light_pos", "centroid", "light_R", "light_T", "g_ndc_l", "g_light_R", "g_light_T", "g_light_pos")]
+_HAND_ROWS = ["fid", "pose48", "betas", "trans_b", "cam_R", "cam_T", "light_pos", "colors", "lbs_ws"]
+_ARM_OK = (_CHAIN_IN + ["tree." + n for n in ("v_template", "shapedirs_T", "posedirs_T", "posedirs", "J_template", "J_dirs", "weights", "pose_mean",
+                                               "parents", "pose_src", "joint_src")] +
+           ["weights_T", "fid", "pose_in", "betas", "trans_b", "cam_R", "cam_T", "light_pos", "colors", "lbs_ws", "tables.wrist_pose"])
+_CLEAR = ["chain.g_vd", "chain.g_joints_m"]                    # (step.clear_mesh_grads is set)
+_ARM_SIZES = [("tree.NJ", 0), ("tree.NJ", 65), ("tree.NB", 9), ("tree.NB", 33), ("tree.n_pose_in", 16), ("tables.n_betas_out", 10)]
+
+# entry point -> (struct, number of trailing scratch pointers, required pointers, further (path, value) mutations)
+_FUSED = {
+    "harp_hand_front_fwd": (_full_hand, 0, _CHAIN_IN + _CHAIN_FWD + _CHAIN_FWD_SHADOW + _HAND_ROWS + _CLEAR, [("chain.E0", 4097 - 778)]),
+    "harp_hand_front_wide_fwd": (_full_hand, 1, _CHAIN_IN + _CHAIN_FWD + _CHAIN_FWD_SHADOW + _HAND_ROWS + _CLEAR, [("chain.E0", 4097 - 778)]),
+    # the hybrid front leaves the mesh inputs, the chain outputs and the size limit to harp_mesh_chain_fwd, its second launch
+    "harp_hand_front_hybrid_fwd": (_full_hand, 0, ["chain.verts_mm", "chain.joints_mm"] + _HAND_ROWS + _CLEAR, []),
+    "harp_hand_back_bwd": (_full_hand, 2, _CHAIN_IN + _CHAIN_BWD + ["fid", "pose48", "lbs_ws"], [("chain.E0", 4097 - 778), ("step.n_loss", 65)]),
+    "harp_hand_back_wide_bwd": (_full_hand, 3, _CHAIN_IN[1:] + _CHAIN_BWD + ["fid", "pose48", "lbs_ws"],
+                                [("chain.E0", 4097 - 778), ("step.n_loss", 65)]),
+    "harp_arm_front_fwd": (_full_arm, 0, _ARM_OK + _CHAIN_FWD + _CHAIN_FWD_SHADOW + _CLEAR, [("chain.E0", 4097 - 1026)] + _ARM_SIZES),
+    "harp_arm_front_wide_fwd": (_full_arm, 1, _ARM_OK + _CHAIN_FWD + _CHAIN_FWD_SHADOW + _CLEAR + ["chain.cam_R", "chain.cam_T", "chain.light_pos"],
+                                [("chain.E0", 4097 - 1026)] + _ARM_SIZES),
+    "harp_arm_back_bwd": (_full_arm, 3, _ARM_OK + _CHAIN_BWD, [("chain.E0", 4097 - 1026), ("step.n_loss", 65)] + _ARM_SIZES),
+    "harp_arm_back_wide_bwd": (_full_arm, 4, _ARM_OK + _CHAIN_BWD, [("chain.E0", 4097 - 1026), ("step.n_loss", 65)] + _ARM_SIZES),
+}
+
+
+@pytest.mark.skipif(torch.cuda.is_available(), reason="fake pointers: an entry point that lost a check would launch on them")
+def test_fused_entry_points_refuse_bad_arguments(lib):
+    """The nine fused front / back entry points return HARP_ERR_ARG (1) for every single broken argument: a fully populated struct of fake
+    pointers with legal sizes, then ONE mutation per case — B = 0, V0 != NV, a wrong NJ, V0 + E0 over the limit of that form, every required
+    pointer nulled on its own, wrist_pose set on the hand path / missing on the arm path, a schedule without its row counter or with
+    n_rows = 0, n_loss = 65, clear_mesh_grads without g_vd, shadow without the light rows.
+    Skipped when a GPU is visible: most of these cases have a non-empty grid, so an entry point that lost a check would launch its kernel on
+    the fake pointers; on a machine without a device such a call fails in the runtime instead (a status other than 1, so the test fails
+    without touching memory).  For the same reason the unmutated struct is checked on the front launchers only (they reach their launch:
+    status >= 2).  The back launchers return 1 for the unmutated struct as well on a CPU-only machine, from the call that raises the
+    kernel's LDS limit: for them this test proves "still rejected" and cannot prove "not rejected more"."""
+    for name, (make, n_scratch, pointers, more) in _FUSED.items():
+        fn = getattr(lib, name)
+        is_arm, is_back, is_wide = "_arm_" in name, "_back_" in name, "_wide_" in name
+        scratch = [_F] * n_scratch
+
+        def call(h, scratch=scratch):
+            return fn(ctypes.byref(h), *scratch, None)
+
+        if not is_back:
+            assert call(make()) >= 2, name                     # legal: it gets as far as the launch (no device here)
+        cases = [("chain.B", 0), ("chain.V0", 777 if not is_arm else 1025), ("chain.NJ", 20 if not is_arm else 21), ("chain.E0", -1)]
+        cases += [(p, None) for p in pointers] + more
+        cases += [("tables.wrist_pose", _F)] if not is_arm else []                       # (missing on the arm path: in `pointers`)
+        cases += [("step.sched_row", None), ("step.n_rows", 0)]
+        for path, value in cases:
+            assert call(_mutated(make, path, value)) == 1, (name, path, value)
+        if is_arm and is_wide:                                 # a quarter of the arm's vertices per 320-thread workgroup
+            h = make()
+            h.chain.V0 = h.tree.NV = 1284; h.chain.E0 = 100
+            assert call(h) == 1, (name, "NV over 4 x 320")
+        # the scratch pointers of the call itself; a null struct
+        for k in range(n_scratch):
+            if is_back and k == 0:
+                continue                                       # g_colors may be NULL (no appearance gradient)
+            args = list(scratch); args[k] = None
+            assert fn(ctypes.byref(make()), *args, None) == 1, (name, "scratch", k)
+        assert fn(None, *scratch, None) == 1, name
