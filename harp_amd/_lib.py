@@ -285,6 +285,9 @@ SIGNATURES.update({
     "harp_panels_u8": (_i, [ctypes.POINTER(_vp), ctypes.POINTER(_ll), _i, _vp, _vp, _i, _i, _i, _vp, _vp]),
 })
 
+# uint8 contact sheets of the in-fit monitor (csrc/sheet.hip)
+SIGNATURES["harp_sheet_u8"] = (_i, [_i, _vp, ctypes.POINTER(_ll), _vp, ctypes.POINTER(_ll), _vp, ctypes.POINTER(_ll), _i, _i, _i, _i, _i, _i, _vp, _vp])
+
 # Taubin smoothing of the exported meshes (csrc/smooth.hip)
 SIGNATURES.update({
     "harp_taubin_ws_bytes": (_sz, [_i, _i]),

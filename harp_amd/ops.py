@@ -658,6 +658,69 @@ def panels_u8(images, mask_true=None, mask_pred=None, channels_last=True):
     return out
 
 
+SHEET_MODES = {"image": 0, "overlay": 1, "absdiff": 2, "normal": 3}
+SHEET_MAX_D, SHEET_MAX_CELLS = 8, 64
+
+
+def sheet_u8(a, b=None, mask=None, mode="image", grid=(3, 3), d=1, channels_last=True):
+    """One uint8 contact sheet (csrc/sheet.hip; show_img_pair, optimize_sequence.py:37-64) in one launch: the frames of `a` (N,H,W,C >= 3)
+    (or (N,C,H,W) with channels_last=False; (N,H,W[,1]) masks in "overlay" mode), float32 HIP tensors read in place through their
+    strides, laid out edge to edge on a grid = (rows, cols) of cells of ceil(H / d) x ceil(W / d) pixels, each output pixel the float32
+    box average of its d x d source pixels; cells past N are white.  mode "image": clip(a); "overlay": (clip(a), 0, clip(b)) with
+    a = true and b = predicted mask; "absdiff": clip(|a * mask - b * mask|); "normal": clip(normalize(a) * 0.5 + 0.5).
+    Returns (rows * ceil(H / d), cols * ceil(W / d), 3) uint8 on the device."""
+    if mode not in SHEET_MODES:
+        raise ValueError(f"mode is one of {sorted(SHEET_MODES)}, got {mode!r}")
+    m = SHEET_MODES[mode]
+    rows, cols, d = int(grid[0]), int(grid[1]), int(d)
+    if (m in (1, 2)) != (b is not None) or (m == 2) != (mask is not None):
+        raise ValueError(f"mode {mode!r} takes " + {0: "a", 1: "a and b", 2: "a, b and mask", 3: "a"}[m])
+
+    def view(t, single):
+        """tensor, (frame, row, column, channel) strides and (N,H,W) of an operand read in place"""
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise RuntimeError("harp_amd ops need HIP device tensors (no CPU path)")
+        if t.dtype != torch.float32:
+            raise TypeError(f"sheet_u8 takes float32 tensors, got {t.dtype}")
+        t = t.detach()
+        if t.dim() == 3 and single:
+            t = t.unsqueeze(-1 if channels_last else 1)
+        if t.dim() != 4:
+            raise TypeError(f"sheet_u8 takes (N,H,W,C) frames{' or (N,H,W) masks' if single else ''}, got {tuple(t.shape)}")
+        if min(t.stride()) < 0:
+            t = t.contiguous()
+        if not channels_last:
+            t = t.permute(0, 2, 3, 1)
+        if t.shape[3] < (1 if single else 3):
+            raise ValueError(f"a colour frame needs 3 channels, got {t.shape[3]}")
+        if single and t.shape[3] != 1:
+            raise ValueError(f"a mask has one channel, got {t.shape[3]}")
+        return t, list(t.stride()), tuple(t.shape[:3])
+
+    ta, sa, shape = view(a, m == 1)
+    tb = sb = tm = sm = None
+    if b is not None:
+        tb, sb, shape_b = view(b, m == 1)
+        if shape_b != shape:
+            raise ValueError(f"a {shape} and b {shape_b} differ in size")
+    if mask is not None:
+        tm, sm, shape_m = view(mask, True)
+        if shape_m != shape:
+            raise ValueError(f"a {shape} and mask {shape_m} differ in size")
+    N, H, W = shape
+    if rows < 1 or cols < 1 or rows * cols > SHEET_MAX_CELLS or not 1 <= d <= SHEET_MAX_D:
+        raise ValueError(f"grid of 1..{SHEET_MAX_CELLS} cells and d in 1..{SHEET_MAX_D}, got {rows} x {cols}, d = {d}")
+    if not 1 <= N <= rows * cols or H < 1 or W < 1:
+        raise ValueError(f"{N} frames of {H} x {W} do not fit a {rows} x {cols} sheet")
+    out = torch.empty(rows * -(-H // d), cols * -(-W // d), 3, dtype=torch.uint8, device=ta.device)
+    ll = lambda s, n: None if s is None else (ctypes.c_longlong * n)(*s[:n])
+    with torch.cuda.device(ta.device):
+        rc = _lib.lib().harp_sheet_u8(m, ta.data_ptr(), ll(sa, 4), None if tb is None else tb.data_ptr(), ll(sb, 4),
+                                      None if tm is None else tm.data_ptr(), ll(sm, 3), N, H, W, rows, cols, d, _lib.ptr(out), _lib.stream())
+    _lib.check(rc, "harp_sheet_u8")
+    return out
+
+
 # ------------------------------------------------------------------------------------------------------
 # export of the fitted avatar (csrc/smooth.hip): Taubin smoothing of the meshes that save_obj writes
 # ------------------------------------------------------------------------------------------------------

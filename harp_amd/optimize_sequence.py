@@ -5,6 +5,8 @@ get_optimizers (:253-310) and optimize_hand_sequence (:313-816, loop body :446-5
 learning rates, ReduceLROnPlateau(patience=40) on the coarse group, checkpoint format) but runs every step through the fused
 engine (harp_amd/engine.py) on HBM-resident targets.  The per-op API (`prepare_mesh`, `render_image`, losses) stays available
 for callers that drive autograd themselves (`visualize_val`-style code)."""
+import contextlib
+
 import numpy as np
 import torch
 
@@ -75,6 +77,58 @@ def get_optimizers(params, configs):
     return opt_coarse, opt_app, sched_coarse
 
 
+def show_img_pair(ypred_np, ytrue_np, step=-1, silhouette=False, save_img_dir=None, prefix="", max_side=1024, sheet_hook=None):
+    """optimize_sequence.py:37-64 as one 3 x 3 uint8 contact sheet made on the device (ops.sheet_u8; cells edge to edge, box-averaged by
+    harp_amd.monitor.box_factor): the first 9 frames of `ypred_np`, or with silhouette=True the overlay (true mask, 0, predicted mask).
+    Takes HIP tensors; numpy arrays and CPU tensors are uploaded.  Writes save_img_dir + prefix + ["sil_"] + "%04d.jpg" % step, or with
+    save_img_dir=None returns the (H,W,3) uint8 numpy sheet instead of opening a window.  sheet_hook(name, u8, sources) sees the sheet
+    and the float tensors it was made from."""
+    from . import monitor, ops
+    up = lambda x: (x if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))).detach().to(device="cuda", dtype=torch.float32)[:9]
+    ypred = up(ypred_np)
+    d = monitor.box_factor(max(ypred.shape[1:3]), max_side)
+    if silhouette:
+        ytrue = up(ytrue_np)
+        sheet, sources = ops.sheet_u8(ytrue, ypred, mode="overlay", d=d), {"y_sil_true": ytrue, "y_sil_pred": ypred}
+    else:
+        sheet, sources = ops.sheet_u8(ypred, mode="image", d=d), {"y_pred": ypred}
+    u8 = sheet.cpu().numpy()
+    name = prefix + ("sil_" if silhouette else "") + "%04d.jpg" % step
+    if sheet_hook is not None:
+        sheet_hook(name, u8, sources)
+    if save_img_dir is None:
+        return u8
+    monitor.encode_jpeg(save_img_dir + name, u8)
+
+
+def visualize_val(val_images_dataloader, epoch_id, device, params, val_params, configs, hand_layer, mesh_subdivider, opt_app=None,
+                  use_verts_textures=False, GLOBAL_POSE=False, SHARED_TEXTURE=True, sheet_hook=None):
+    """optimize_sequence.py:97-171 for callers that drive their own loop: the first batch of `val_images_dataloader` rendered under
+    torch.no_grad() with the fit's shape, pose, displacements, texture, normal map and light and the validation sequence's own cam, trans
+    and rot (harp_amd.monitor.merge_val_params; `val_params` itself is left as it is), written as val_%04d.jpg; the atlas as uv_%04d.jpg
+    and normal_%04d.jpg under configs["base_output_dir"].  In scope: UV textures, one shared texture, no global pose."""
+    import os
+    from . import monitor, ops
+    if use_verts_textures or GLOBAL_POSE or not SHARED_TEXTURE:
+        raise NotImplementedError("visualize_val: UV textures with one shared texture and per-frame poses are the path in scope (SURVEY.md §8)")
+    for (fid, y_true, y_sil_true, _) in val_images_dataloader:
+        print("epoch: %d" % epoch_id)
+        for param_group in (opt_app.param_groups if opt_app is not None else ()):
+            print("learning rate", param_group["lr"])
+        P = {k: (v.detach().to(device) if torch.is_tensor(v) else v) for k, v in params.items()}
+        with torch.no_grad():
+            r = mirror_render(configs, monitor.merge_val_params(P, val_params, device), torch.as_tensor(fid).long(), hand_layer, mesh_subdivider,
+                              device=device)
+        base = configs["base_output_dir"]
+        show_img_pair(r.y_pred, y_true, save_img_dir=base, step=epoch_id, silhouette=False, prefix="val_", sheet_hook=sheet_hook)
+        for name, key, mode in (("uv_%04d.jpg", "texture", "image"), ("normal_%04d.jpg", "normal_map", "normal")):
+            u8 = ops.sheet_u8(P[key], mode=mode, grid=(1, 1)).cpu().numpy()
+            if sheet_hook is not None:
+                sheet_hook(name % epoch_id, u8, {key: P[key]})
+            monitor.encode_jpeg(os.path.join(base, name % epoch_id), u8)
+        break
+
+
 def stage_flags(epoch_id, training_stage):
     """optimize_sequence.py:507-515 -> (COARSE_OPT, APP_OPT)"""
     if epoch_id < training_stage[0]:
@@ -87,10 +141,12 @@ def stage_flags(epoch_id, training_stage):
 def optimize_hand_sequence(configs, input_params, images_dataset, val_params, val_images_dataset, hand_layer,
                            VERTS_UVS=None, FACES_UVS=None, VERTS_COLOR=None, device="cuda", uv_mask=None, batch_size=18, log_fn=None,
                            seed=0, vgg=None, rank=None, world_size=None, shards=None, plateau_patience=40, plateau_threshold=1e-4, device_schedule=True,
-                           evaluate=False, panels=False, turntable=False, export_mesh=False):
+                           evaluate=False, panels=False, turntable=False, export_mesh=False, monitor=False):
     """Fit the sequence (optimize_sequence.py:313-596).  Returns the parameter dict in the reference's checkpoint layout; evaluate=True
     then runs the post-fit evaluation `evaluate_sequence` (:595-816) on rank 0 (off by default), with its panels / turntable / export_mesh
-    switches.
+    switches.  monitor: False (default: no new file, no new work), True, a dict of harp_amd.monitor.FitMonitor arguments or a FitMonitor —
+    rank 0 then writes the reference's progress sheets while the fit runs (:490-501 every 10 epochs from the epoch's first batch; :587-589
+    visualize_val every 20 epochs, which needs `val_params` and `val_images_dataset`) and monitor_log.jsonl, off the enqueueing thread.
     `images_dataset[i]` -> (fid, y_true (S,S,3), y_sil (S,S,1), y_sil_eroded (S,S,1)) like utils/data_util.ImagesDataset.
 
     Data-parallel (the reference is single-device): launched under `torch.distributed.run` (or with rank / world_size given)
@@ -167,7 +223,15 @@ def optimize_hand_sequence(configs, input_params, images_dataset, val_params, va
     gen = torch.Generator().manual_seed(seed)                        # the SAME stream of draws on every rank
     # (the loss weights of :411-422 are the engine's LOSS_WEIGHTS: its kernels scale the gradients with them and its step epilogue forms sum_loss)
     own = torch.arange(k) * per                                      # first local row of each of this rank's shards
+    mon = None
+    if monitor is not False and monitor is not None and rank == 0:
+        from .monitor import FitMonitor, due
+        mon = monitor if isinstance(monitor, FitMonitor) else FitMonitor(configs["base_output_dir"], **(monitor if isinstance(monitor, dict) else {}))
+    # a step may capture its graph, and no other thread may call the runtime meanwhile: the monitor's writer thread makes its calls under this lock
+    step_guard = mon.hip_lock if mon is not None else contextlib.nullcontext()
     try:
+        if mon is not None:
+            mon.begin(configs, eng, hand_layer, VERTS_UVS, FACES_UVS, val_params, val_images_dataset, seed=seed)
         def draw_epoch():
             """the next epoch's batches (DataLoader(shuffle=True) over the DATASET's items, :398) and — its full batches as ONE device schedule
             (parameter rows = the items' own fids, :446, :464; target rows = the items): every such step is a bare graph replay that fetches
@@ -184,11 +248,14 @@ def optimize_hand_sequence(configs, input_params, images_dataset, val_params, va
         eng.loss_total.zero_()            # the engine adds every step's sum_loss (:553-559) to it on the device: no per-step host arithmetic, no sync
         for epoch_id in range(configs["total_epoch"]):
             coarse, app = stage_flags(epoch_id, configs["training_stage"])
+            if mon is not None and due(epoch_id, mon.train_every):                     # :490: the forward pass of the epoch's first batch, before its step
+                mon.train_sheets(epoch_id, rt.fid[items[0]], items[0])
             for item in items:
-                if item.numel() == eng.B and device_schedule:
-                    eng.step(None, coarse, app)
-                else:
-                    eng.step(rt.fid[item], coarse, app, tfid=item)                     # the last, partial batch (:396-399): explicit rows, a graph of its own size
+                with step_guard:
+                    if item.numel() == eng.B and device_schedule:
+                        eng.step(None, coarse, app)
+                    else:
+                        eng.step(rt.fid[item], coarse, app, tfid=item)                 # the last, partial batch (:396-399): explicit rows, a graph of its own size
             nb = len(items)
             # one sync per epoch; N > 1: the mean over ranks (image terms are means over a rank's frames, regularisers are identical),
             # the same float on every rank
@@ -200,6 +267,8 @@ def optimize_hand_sequence(configs, input_params, images_dataset, val_params, va
                 items, sch = draw_epoch()
                 if sch is not None:
                     eng.set_schedule(sch[0], tschedule=sch[1])
+            # :587-589, enqueued behind this epoch's steps and in front of the sync below, which its two scalars ride on
+            validated = mon is not None and due(epoch_id, mon.val_every) and mon.validate(epoch_id)
             epoch_loss = float(total.item()) / nb
             mean_loss = float(hdist.mean_over_ranks(epoch_loss, device=eng.dev)) if world > 1 else epoch_loss
             if not np.isfinite(mean_loss):
@@ -209,6 +278,8 @@ def optimize_hand_sequence(configs, input_params, images_dataset, val_params, va
                 eng.set_lr(lr_coarse=dummy.param_groups[0]["lr"])
             if log_fn is not None:
                 log_fn(epoch_id, mean_loss, eng)
+            if mon is not None:
+                mon.log_epoch(epoch_id, mean_loss, dummy.param_groups[0]["lr"], coarse, app, validated)
             if epoch_id % 200 == 0 and epoch_id > 0 and rank == 0:
                 file_utils.save_result(export_params(eng, input_params, VERTS_UVS, FACES_UVS, uv_mask, hand_layer), configs["base_output_dir"],
                                        test=configs["known_appearance"])               # :590-591
@@ -216,13 +287,57 @@ def optimize_hand_sequence(configs, input_params, images_dataset, val_params, va
         if rank == 0:
             file_utils.save_result(params, configs["base_output_dir"], test=configs["known_appearance"])     # :595-596
     finally:
-        if comm is not None:
-            torch.cuda.synchronize(eng.dev)
-            comm.destroy()                                           # drops the step graphs that captured it
+        try:
+            if mon is not None:
+                mon.close()                                          # drains the writer thread; re-raises what it raised
+        finally:
+            if comm is not None:
+                torch.cuda.synchronize(eng.dev)
+                comm.destroy()                                       # drops the step graphs that captured it
     if evaluate and rank == 0:
         evaluate_sequence(configs, params, images_dataset, hand_layer, device=device, uv_mask=uv_mask, panels=panels, turntable=turntable,
                           export_mesh=export_mesh)
     return params
+
+
+def mirror_render(configs, P, fid, hand_layer, sub, device="cuda"):
+    """One forward pass of frames `fid` through the reference-API mirror, as the loop body (optimize_sequence.py:452-488), visualize_val
+    (:110-154) and the evaluation (:680-708) run it: get_renderers(silh_sigma=1e-7, silh_faces_per_pixel=50), prepare_mesh,
+    prepare_materials, the silhouette render, and the image through get_shadow_renderers + render_image_with_RT with self_shadow, else
+    render_image with the phong renderer.  P: the parameter dict on `device`.  Call under torch.no_grad().  Returns a namespace with
+    y_sil_pred (B,S,S), y_pred (B,S,S,3) float32 and the intermediates (hand_verts, faces, textures, meshes, cam, light_positions,
+    materials_properties, normal_renderer)."""
+    from types import SimpleNamespace
+    from .renderer import renderer_helper
+    from .structures import Meshes
+    from .utils.visualize import prepare_materials, prepare_mesh, render_image, render_image_with_RT
+    S, focal = int(configs["img_size"]), configs["focal_length"]
+    use_arm = bool(configs["use_arm"])
+    B = fid.shape[0]
+    fd = fid.to(device)
+    if configs["share_light_position"]:
+        light_positions = P["light_positions"][0].repeat(B, 1)
+    else:
+        light_positions = P["light_positions"][fd]
+    phong_renderer, silhouette_renderer, normal_renderer = renderer_helper.get_renderers(
+        image_size=S, light_posi=light_positions, silh_sigma=1e-7, silh_gamma=1e-1, silh_faces_per_pixel=50, device=device)
+    _, hand_verts, faces, textures = prepare_mesh(P, fid, hand_layer, False, sub, False, configs, device=device, use_arm=use_arm)
+    materials_properties = prepare_materials(P, B, device=device)
+    meshes = Meshes(hand_verts, faces, textures)
+    cam = P["cam"][fd]
+    y_sil_pred = render_image(meshes, cam, B, silhouette_renderer, S, focal, silhouette=True, device=device)
+    if configs["self_shadow"]:
+        light_R, light_T, cam_R, cam_T = renderer_helper.process_info_for_shadow(cam, light_positions, hand_verts.mean(1), image_size=S,
+                                                                                 focal_length=focal, device=device)
+        shadow_renderer = renderer_helper.get_shadow_renderers(image_size=S, light_posi=light_positions, silh_sigma=1e-7, silh_gamma=1e-1,
+                                                               silh_faces_per_pixel=50, amb_ratio=torch.sigmoid(P["amb_ratio"]), device=device)
+        y_pred = render_image_with_RT(meshes, light_T, light_R, cam_T, cam_R, B, shadow_renderer, S, focal, silhouette=False,
+                                      materials_properties=materials_properties, device=device)
+    else:
+        y_pred = render_image(meshes, cam, B, phong_renderer, S, focal, silhouette=False, materials_properties=materials_properties,
+                              device=device)
+    return SimpleNamespace(y_sil_pred=y_sil_pred, y_pred=y_pred.float(), hand_verts=hand_verts, faces=faces, textures=textures, meshes=meshes,
+                           cam=cam, light_positions=light_positions, materials_properties=materials_properties, normal_renderer=normal_renderer)
 
 
 EVAL_CHUNK = 64                  # optimize_sequence.py:716: image_eval runs on every 64 frames; the final stats are means of the chunk means
@@ -259,8 +374,7 @@ def evaluate_sequence(configs, params, images_dataset, hand_layer, device="cuda"
     from .renderer import renderer_helper
     from .structures import Meshes
     from .utils.eval_util import align_w_scale, load_gt_vert, sil_iou
-    from .utils.visualize import (concat_image_in_dir, prepare_materials, prepare_mesh, render_360, render_360_light, render_image,
-                                  render_image_with_RT)
+    from .utils.visualize import concat_image_in_dir, prepare_mesh, render_360, render_360_light, render_image
     S, focal = int(configs["img_size"]), configs["focal_length"]
     base = configs["base_output_dir"]
     test_name = "_test" if configs["known_appearance"] else ""
@@ -304,29 +418,10 @@ def evaluate_sequence(configs, params, images_dataset, hand_layer, device="cuda"
             y_true = torch.stack([torch.as_tensor(it[1]) for it in items]).to(device=device, dtype=torch.float32)
             y_sil_true = torch.stack([torch.as_tensor(it[2]) for it in items]).reshape(len(items), S, S).to(device=device, dtype=torch.float32)
             B = fid.shape[0]
-            fd = fid.to(device)
-            if configs["share_light_position"]:
-                light_positions = P["light_positions"][0].repeat(B, 1)
-            else:
-                light_positions = P["light_positions"][fd]
-            phong_renderer, silhouette_renderer, normal_renderer = renderer_helper.get_renderers(
-                image_size=S, light_posi=light_positions, silh_sigma=1e-7, silh_gamma=1e-1, silh_faces_per_pixel=50, device=device)
-            _, hand_verts, faces, textures = prepare_mesh(P, fid, hand_layer, False, sub, False, configs, device=device, use_arm=use_arm)
-            materials_properties = prepare_materials(P, B, device=device)
-            meshes = Meshes(hand_verts, faces, textures)
-            cam = P["cam"][fd]
-            y_sil_pred = render_image(meshes, cam, B, silhouette_renderer, S, focal, silhouette=True, device=device)
-            if configs["self_shadow"]:
-                light_R, light_T, cam_R, cam_T = renderer_helper.process_info_for_shadow(cam, light_positions, hand_verts.mean(1), image_size=S,
-                                                                                         focal_length=focal, device=device)
-                shadow_renderer = renderer_helper.get_shadow_renderers(image_size=S, light_posi=light_positions, silh_sigma=1e-7, silh_gamma=1e-1,
-                                                                       silh_faces_per_pixel=50, amb_ratio=torch.sigmoid(P["amb_ratio"]), device=device)
-                y_pred = render_image_with_RT(meshes, light_T, light_R, cam_T, cam_R, B, shadow_renderer, S, focal, silhouette=False,
-                                              materials_properties=materials_properties, device=device)
-            else:
-                y_pred = render_image(meshes, cam, B, phong_renderer, S, focal, silhouette=False, materials_properties=materials_properties,
-                                      device=device)
-            y_pred = y_pred.float()
+            r = mirror_render(configs, P, fid, hand_layer, sub, device=device)
+            hand_verts, faces, textures, meshes, cam = r.hand_verts, r.faces, r.textures, r.meshes, r.cam
+            light_positions, materials_properties, normal_renderer = r.light_positions, r.materials_properties, r.normal_renderer
+            y_sil_pred, y_pred = r.y_sil_pred, r.y_pred
             if panels:                                # :710-714, :742-757
                 _, verts_n, faces_n, textures_n = prepare_mesh(P, fid, hand_layer, False, sub, False, configs, device=device, vis_normal=True,
                                                                use_arm=use_arm)
@@ -425,6 +520,8 @@ def main(argv=None):
     ap.add_argument("--panels", action="store_true", help="with --eval: one true | pred | normal | overlay JPEG per frame under rendered_after_opt/")
     ap.add_argument("--turntable", action="store_true", help="with --eval: render_360/, render_360_normal/, render_360_combine/ and render_360_light/ of frame 0")
     ap.add_argument("--export-mesh", action="store_true", help="with --eval: the Taubin-smoothed textured mesh of every frame as mesh/<fid>.obj, .mtl, .png")
+    ap.add_argument("--monitor", action="store_true", help="while fitting: the progress sheets of optimize_sequence.py:490-501 every 10 epochs, "
+                    "visualize_val's val_ / uv_ / normal_ sheets every 20 and monitor_log.jsonl (harp_amd.monitor.FitMonitor)")
     ap.add_argument("--lpips-weights", nargs="+", default=None, metavar="PATH",
                     help="LPIPS in the evaluation: one lpips.LPIPS(net='alex') state dict, or torchvision's alexnet state dict and the lpips "
                          "v0.1 alex head (configs['lpips_weights'])")
@@ -452,7 +549,7 @@ def main(argv=None):
         average_cam_sequence=configs["average_cam_sequence"], use_smooth_seq=configs["use_smooth_seq"], model_type=configs["model_type"])
     params = optimize_hand_sequence(configs, mano_params, images_dataset, val_mano_params, val_images_dataset, hand_layer, VERTS_UVS, FACES_UVS,
                                     VERTS_COLOR, device=device, batch_size=args.batch_size, evaluate=args.eval, panels=args.panels,
-                                    turntable=args.turntable, export_mesh=args.export_mesh)
+                                    turntable=args.turntable, export_mesh=args.export_mesh, monitor=args.monitor)
     if world > 1:
         tdist.barrier()
         tdist.destroy_process_group()

@@ -840,6 +840,28 @@ int harp_normal_image(const float* ndc, const float* vnormals, const int32_t* fa
 int harp_panels_u8(const float* const* images, const long long* strides, int n_images, const float* mask_true, const float* mask_pred, int N,
                    int H, int W, unsigned char* out, hipStream_t stream);
 
+/* ---- what a running fit is watched with: uint8 contact sheets (csrc/sheet.hip) ---------------------------------------------------------
+ * harp_sheet_u8 replaces show_img_pair (optimize_sequence.py:37-64: a 3 x 3 matplotlib figure of the first mini-batch, called at
+ * :490-501 every 10 epochs and from visualize_val at :156) and the atlas dumps of visualize_val (:160-168): ONE launch writes one
+ * finished sheet out (rows * ch, cols * cw, 3) uint8 of up to rows * cols frames, ch = ceil(H / d), cw = ceil(W / d) for the integer box
+ * factor d.  Cell k = r * cols + c shows frame k; cells k >= N are 255 in all channels (an empty axis of the reference's white figure).
+ * The cells lie edge to edge (matplotlib's margins and its resampling to a 1000-px figure are not reproduced).
+ *   a: (N,H,W[,C]) float32 frames read in place; a_strides: 4 HOST element strides (frame, row, column, channel); b / b_strides likewise;
+ *   mask (N,H,W) with 3 HOST strides (frame, row, column).  Colour p of a source pixel, every operation rounded to float32 on its own:
+ *     mode 0 IMAGE    p = clip(a[..., 0:3], 0, 1)                                       (:54, :156: imshow clips floats)
+ *     mode 1 OVERLAY  p = (clip(a), 0, clip(b)), a = true mask, b = predicted mask; single-channel, the channel strides are ignored (:48-52)
+ *     mode 2 ABSDIFF  p = clip(|a * mask - b * mask|) per channel, the two products rounded separately, no fma             (:499-501)
+ *     mode 3 NORMAL   p = clip(a / max(|a|, 1e-12) * 0.5 + 0.5)                                                             (:166-167)
+ *   clip(x) = fminf(fmaxf(x, 0), 1), so a NaN counts as 0.  Output pixel (i, j) of a cell: v = the sum of p over the source box
+ *   y in [i d, min(H, (i + 1) d)), x in [j d, min(W, (j + 1) d)), added by one lane in row-major order from 0.0f, divided (IEEE float32)
+ *   by the number of pixels summed; written as uint8(trunc(v * 255.0f)).  d = 1 is harp_panels_u8's colour convention bit for bit.
+ *   Stream-ordered and capturable: no allocation, no synchronisation.  Deterministic: no atomics.
+ *   Returns HARP_ERR_ARG without launching for mode outside 0..3, NULL a / a_strides / out, N, H, W, rows, cols <= 0, d outside 1..8,
+ *   rows * cols > 64, N > rows * cols, a negative stride, a missing operand (modes 1, 2 need b and b_strides, mode 2 needs mask and
+ *   mask_strides) and a superfluous one (b in modes 0, 3; mask outside mode 2). */
+int harp_sheet_u8(int mode, const float* a, const long long* a_strides, const float* b, const long long* b_strides, const float* mask,
+                  const long long* mask_strides, int N, int H, int W, int rows, int cols, int d, unsigned char* out, hipStream_t stream);
+
 /* ---- export of the fitted avatar: Taubin smoothing (csrc/smooth.hip) ----------------------------------------------------------------
  * optimize_sequence.py:780  pytorch3d.ops.taubin_smoothing(meshes, lambd=0.53, mu=-0.53, num_iter=10), forward only (the reference calls
  * it under no_grad).  PyTorch3D is not installed where this was written: the semantics are its v0.6.2 taubin_smoothing / norm_laplacian
