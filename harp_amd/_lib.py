@@ -293,3 +293,10 @@ SIGNATURES.update({
     "harp_taubin_ws_bytes": (_sz, [_i, _i]),
     "harp_taubin_smooth": (_i, [_vp, _vp, _vp, _i, _i, _f, _f, _i, _i, _vp, _vp, _vp]),
 })
+
+# geometric accuracy of the post-fit evaluation (csrc/pose_eval.hip)
+SIGNATURES.update({
+    "harp_procrustes_align": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "harp_pck_counts": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "harp_point_set_fscore": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+})

@@ -766,3 +766,120 @@ def taubin_smoothing(meshes, lambd=0.53, mu=-0.53, num_iter=10):
     with smoothed vertices and the same faces, textures and topology."""
     from .structures import Meshes
     return Meshes(taubin_smooth(meshes.verts_padded(), meshes.topo, lambd, mu, num_iter), meshes.faces_padded(), meshes.textures, meshes.topo)
+
+
+# ------------------------------------------------------------------------------------------------------
+# geometric accuracy of the post-fit evaluation (csrc/pose_eval.hip): Procrustes, PCK counts, F-score
+# ------------------------------------------------------------------------------------------------------
+FSCORE_MAX_THRESHOLDS = 512                              # harp_point_set_fscore keeps 16 counters per threshold in LDS
+
+
+def _pose_eval_input(name, what, *ts):
+    for t in ts:
+        if t is None:
+            continue
+        if not torch.is_tensor(t):
+            raise TypeError(f"{name} takes tensors")
+        if torch.is_grad_enabled() and t.requires_grad:
+            raise NotImplementedError(f"{name} is forward-only ({what}): detach the inputs or evaluate under torch.no_grad()")
+        if not t.is_cuda:
+            raise RuntimeError("harp_amd ops need HIP device tensors (no CPU path)")
+        if t.device != ts[0].device:
+            raise ValueError(f"{name}: the tensors live on different devices")
+
+
+def procrustes_align(gt, pred, valid=None, pred_idx=None, return_trafo=False):
+    """align_w_scale (utils/eval_util.py:212-235) for N frames in one launch, forward only, float64 inside (include/harp_hip.h).
+
+    gt (N,K,3) or (K,3), pred (N,Kp,3) or (Kp,3) HIP tensors; pred_idx: K indices into the Kp points (the gather without a copy), else
+    Kp = K; valid (N,K) or (K,), non-zero = the point is used.  Returns (aligned, err, n_valid): float32 (N,K,3) and (N,K), NaN at points
+    not used and in frames with fewer than 3 used points, and int32 (N,) — without the leading axis for (K,3) inputs.  With return_trafo a
+    fourth tensor: (N,14) float64 = R row-major, s, s1, t1 - t2 (the reference's tuple).  No determinant correction: a mirrored
+    prediction is aligned by a reflection, as scipy's orthogonal_procrustes does."""
+    _pose_eval_input("procrustes_align", "no gradient through the alignment", gt, pred, valid, pred_idx)
+    if gt.dim() not in (2, 3) or gt.shape[-1] != 3 or pred.dim() != gt.dim() or pred.shape[-1] != 3:
+        raise ValueError(f"procrustes_align takes (N,K,3) or (K,3) point sets, got {tuple(gt.shape)} and {tuple(pred.shape)}")
+    single = gt.dim() == 2
+    g = _f32(gt.detach()).reshape(-1, gt.shape[-2], 3)
+    p = _f32(pred.detach()).reshape(-1, pred.shape[-2], 3)
+    N, K, Kp = g.shape[0], g.shape[1], p.shape[1]
+    if p.shape[0] != N:
+        raise ValueError(f"{N} frames of ground truth, {p.shape[0]} of prediction")
+    if pred_idx is not None:
+        pred_idx = pred_idx.detach().to(torch.int32).contiguous().reshape(-1)
+        if pred_idx.numel() != K:
+            raise ValueError(f"pred_idx holds {pred_idx.numel()} indices, the ground truth {K} points")
+    elif Kp != K:
+        raise ValueError(f"{K} points of ground truth, {Kp} of prediction and no pred_idx")
+    if valid is not None:
+        valid = valid.detach().to(torch.float32).contiguous()
+        if valid.numel() != N * K:
+            raise ValueError(f"valid has {valid.numel()} entries for {N} x {K} points")
+    if N == 0 or K == 0 or Kp == 0:
+        raise ValueError("procrustes_align needs at least one frame and one point")
+    dev = g.device
+    aligned = torch.empty(N, K, 3, dtype=torch.float32, device=dev)
+    err = torch.empty(N, K, dtype=torch.float32, device=dev)
+    n_valid = torch.empty(N, dtype=torch.int32, device=dev)
+    trafo = torch.empty(N, 14, dtype=torch.float64, device=dev) if return_trafo else None
+    with torch.cuda.device(dev):
+        rc = _lib.lib().harp_procrustes_align(_lib.ptr(g), _lib.ptr(p), _lib.ptr(pred_idx), _lib.ptr(valid), N, K, Kp, _lib.ptr(aligned),
+                                              _lib.ptr(err), _lib.ptr(trafo), _lib.ptr(n_valid), _lib.stream())
+    _lib.check(rc, "harp_procrustes_align")
+    out = (aligned[0], err[0], n_valid[0]) if single else (aligned, err, n_valid)
+    return out + ((trafo[0] if single else trafo),) if return_trafo else out
+
+
+def pck_counts(err, valid, thresholds):
+    """The counting of EvalUtil.get_measures (utils/eval_util.py:103-163) per keypoint: err (N,K) float32 HIP tensor, valid (N,K) or None
+    (non-zero = visible), thresholds (n_thr,).  A measurement is seen when it is visible and not NaN.  Returns (counts (K,n_thr) int32 =
+    seen n with err <= threshold in float32, n_vis (K,) int32, err_sum (K,) float64)."""
+    _pose_eval_input("pck_counts", "counts have no gradient", err, valid, thresholds)
+    if err.dim() != 2:
+        raise ValueError(f"pck_counts takes (N,K) errors, got {tuple(err.shape)}")
+    e = _f32(err.detach())
+    N, K = e.shape
+    thr = thresholds.detach().to(torch.float32).contiguous().reshape(-1)
+    if valid is not None:
+        valid = valid.detach().to(torch.float32).contiguous()
+        if valid.numel() != N * K:
+            raise ValueError(f"valid has {valid.numel()} entries for {N} x {K} errors")
+    if N == 0 or K == 0 or thr.numel() < 1:
+        raise ValueError("pck_counts needs at least one frame, one keypoint and one threshold")
+    dev = e.device
+    counts = torch.empty(K, thr.numel(), dtype=torch.int32, device=dev)
+    n_vis = torch.empty(K, dtype=torch.int32, device=dev)
+    err_sum = torch.empty(K, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        rc = _lib.lib().harp_pck_counts(_lib.ptr(e), _lib.ptr(valid), _lib.ptr(thr), N, K, thr.numel(), _lib.ptr(counts), _lib.ptr(n_vis),
+                                        _lib.ptr(err_sum), _lib.stream())
+    _lib.check(rc, "harp_pck_counts")
+    return counts, n_vis, err_sum
+
+
+def point_set_fscore(gt, pred, thresholds):
+    """Precision, recall and F between two point sets per frame (the mesh measure of the FreiHAND benchmark; include/harp_hip.h): gt
+    (N,Kg,3) or (Kg,3), pred (N,Kp,3) or (Kp,3) float32 HIP tensors, thresholds (n_thr,) distances in the points' unit.  All pairs in
+    float64; a point counts when its nearest neighbour in the other set is strictly nearer than the threshold.  Returns (out (N,n_thr,3) =
+    precision, recall, F; nn_gt (N,Kg), nn_pred (N,Kp) nearest distances) — without the leading axis for 2-D inputs."""
+    _pose_eval_input("point_set_fscore", "counts have no gradient", gt, pred, thresholds)
+    if gt.dim() not in (2, 3) or gt.shape[-1] != 3 or pred.dim() != gt.dim() or pred.shape[-1] != 3:
+        raise ValueError(f"point_set_fscore takes (N,K,3) or (K,3) point sets, got {tuple(gt.shape)} and {tuple(pred.shape)}")
+    single = gt.dim() == 2
+    g = _f32(gt.detach()).reshape(-1, gt.shape[-2], 3)
+    p = _f32(pred.detach()).reshape(-1, pred.shape[-2], 3)
+    N, Kg, Kp = g.shape[0], g.shape[1], p.shape[1]
+    thr = thresholds.detach().to(torch.float32).contiguous().reshape(-1)
+    if p.shape[0] != N:
+        raise ValueError(f"{N} frames of ground truth, {p.shape[0]} of prediction")
+    if N == 0 or Kg == 0 or Kp == 0 or not 1 <= thr.numel() <= FSCORE_MAX_THRESHOLDS:
+        raise ValueError(f"point_set_fscore needs at least one frame, one point per set and 1 to {FSCORE_MAX_THRESHOLDS} thresholds")
+    dev = g.device
+    out = torch.empty(N, thr.numel(), 3, dtype=torch.float32, device=dev)
+    nn_gt = torch.empty(N, Kg, dtype=torch.float32, device=dev)
+    nn_pred = torch.empty(N, Kp, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        rc = _lib.lib().harp_point_set_fscore(_lib.ptr(g), _lib.ptr(p), _lib.ptr(thr), N, Kg, Kp, thr.numel(), _lib.ptr(out), _lib.ptr(nn_gt),
+                                              _lib.ptr(nn_pred), _lib.stream())
+    _lib.check(rc, "harp_point_set_fscore")
+    return (out[0], nn_gt[0], nn_pred[0]) if single else (out, nn_gt, nn_pred)

@@ -305,7 +305,7 @@ def mirror_render(configs, P, fid, hand_layer, sub, device="cuda"):
     (:110-154) and the evaluation (:680-708) run it: get_renderers(silh_sigma=1e-7, silh_faces_per_pixel=50), prepare_mesh,
     prepare_materials, the silhouette render, and the image through get_shadow_renderers + render_image_with_RT with self_shadow, else
     render_image with the phong renderer.  P: the parameter dict on `device`.  Call under torch.no_grad().  Returns a namespace with
-    y_sil_pred (B,S,S), y_pred (B,S,S,3) float32 and the intermediates (hand_verts, faces, textures, meshes, cam, light_positions,
+    y_sil_pred (B,S,S), y_pred (B,S,S,3) float32 and the intermediates (hand_verts, hand_joints (m), faces, textures, meshes, cam, light_positions,
     materials_properties, normal_renderer)."""
     from types import SimpleNamespace
     from .renderer import renderer_helper
@@ -321,7 +321,7 @@ def mirror_render(configs, P, fid, hand_layer, sub, device="cuda"):
         light_positions = P["light_positions"][fd]
     phong_renderer, silhouette_renderer, normal_renderer = renderer_helper.get_renderers(
         image_size=S, light_posi=light_positions, silh_sigma=1e-7, silh_gamma=1e-1, silh_faces_per_pixel=50, device=device)
-    _, hand_verts, faces, textures = prepare_mesh(P, fid, hand_layer, False, sub, False, configs, device=device, use_arm=use_arm)
+    hand_joints, hand_verts, faces, textures = prepare_mesh(P, fid, hand_layer, False, sub, False, configs, device=device, use_arm=use_arm)
     materials_properties = prepare_materials(P, B, device=device)
     meshes = Meshes(hand_verts, faces, textures)
     cam = P["cam"][fd]
@@ -336,7 +336,7 @@ def mirror_render(configs, P, fid, hand_layer, sub, device="cuda"):
     else:
         y_pred = render_image(meshes, cam, B, phong_renderer, S, focal, silhouette=False, materials_properties=materials_properties,
                               device=device)
-    return SimpleNamespace(y_sil_pred=y_sil_pred, y_pred=y_pred.float(), hand_verts=hand_verts, faces=faces, textures=textures, meshes=meshes,
+    return SimpleNamespace(y_sil_pred=y_sil_pred, y_pred=y_pred.float(), hand_verts=hand_verts, hand_joints=hand_joints, faces=faces, textures=textures, meshes=meshes,
                            cam=cam, light_positions=light_positions, materials_properties=materials_properties, normal_renderer=normal_renderer)
 
 
@@ -344,7 +344,7 @@ EVAL_CHUNK = 64                  # optimize_sequence.py:716: image_eval runs on 
 
 
 def evaluate_sequence(configs, params, images_dataset, hand_layer, device="cuda", batch_size=32, uv_mask=None, lpips_fn=None, panels=False,
-                      turntable=False, panel_hook=None, export_mesh=False):
+                      turntable=False, panel_hook=None, export_mesh=False, pose_eval=None):
     """The post-fit evaluation of optimize_sequence.py:595-816: re-render every dataset item in order with the fitted `params` through the
     reference-API mirror (silhouette: get_renderers(silh_sigma=1e-7, silh_faces_per_pixel=50)[1]; image: render_image_with_RT through
     get_shadow_renderers with self_shadow, else render_image with the phong renderer), `batch_size` frames per render call; per-frame
@@ -364,7 +364,15 @@ def evaluate_sequence(configs, params, images_dataset, hand_layer, device="cuda"
     concat_image_in_dir into render_360_combine and render_360_light, each with its out.gif.  export_mesh=True (the reference's constant
     EXPORT_MESH, :776-791): per batch one ops.taubin_smoothing(meshes) (csrc/smooth.hip) and one device -> host copy, then per frame
     mesh/<fid %04d>.obj, .mtl and .png through harp_amd.io.save_obj with the reference's arguments — smoothed vertices, the faces of the
-    unsmoothed mesh, the textures' verts_uvs / faces_uvs and maps_padded()[0].clamp(0, 1), whose PNG is encoded once (the texture is shared)."""
+    unsmoothed mesh, the textures' verts_uvs / faces_uvs and maps_padded()[0].clamp(0, 1), whose PNG is encoded once (the texture is shared).
+    pose_eval (or configs["pose_eval"]): None, the path of an .npz or a dict with any of gt_joints (T,21,3) mm, gt_joint_valid (T,21) and
+    gt_verts (T,778,3) m, rows indexed by fid.  Given, the geometric accuracy runs on the device (csrc/pose_eval.hip), per batch one
+    ops.procrustes_align of the first 21 joints (mm, both sets root-aligned, only the valid joints), one of the vertices (gathered by
+    right_mano_idx on the arm, else the first 778; with configs["eval_mesh"] and no gt_verts they still come from load_gt_vert) and one
+    ops.point_set_fscore of the aligned vertices; after the lines above, whichever the ground truth allows of `Procrustes-aligned joint
+    error (mm)`, `Joint AUC 0-50 mm` (100 thresholds), `Procrustes-aligned vertex error (mm)`, `Vertex AUC 0-50 mm`, `F@5mm`, `F@15mm`,
+    and eval_joint_mm[_test].txt / eval_vert_mm[_test].txt with the per-frame means.  Frames with fewer than 3 valid joints are left out
+    of the joint lines.  With None everything is as before: the per-frame host loop of :760-774 included."""
     import os
     import warnings
     import torch.nn.functional as F
@@ -373,7 +381,7 @@ def evaluate_sequence(configs, params, images_dataset, hand_layer, device="cuda"
     from .io import encode_png, save_obj
     from .renderer import renderer_helper
     from .structures import Meshes
-    from .utils.eval_util import align_w_scale, load_gt_vert, sil_iou
+    from .utils.eval_util import EvalUtil, align_w_scale, load_gt_vert, sil_iou
     from .utils.visualize import concat_image_in_dir, prepare_mesh, render_360, render_360_light, render_image
     S, focal = int(configs["img_size"]), configs["focal_length"]
     base = configs["base_output_dir"]
@@ -404,6 +412,18 @@ def evaluate_sequence(configs, params, images_dataset, hand_layer, device="cuda"
     if lpips_fn is not None and not with_lpips:
         warnings.warn(f"LPIPS left out of the evaluation: {S} px images (AlexNet needs a side >= {ops.LPIPS_MIN_SIDE})")
     iou, l1, ms, lp, vert_err = [], [], [], [], []
+    pe = pose_eval if pose_eval is not None else configs.get("pose_eval")
+    if isinstance(pe, (str, os.PathLike)):
+        with np.load(pe) as z:
+            pe = {k: z[k] for k in z.files}
+    if pe is not None:
+        pe = {k: torch.as_tensor(np.asarray(v)) for k, v in pe.items() if k in ("gt_joints", "gt_joint_valid", "gt_verts")}
+        with_joints = "gt_joints" in pe
+        with_verts = "gt_verts" in pe or bool(configs["eval_mesh"])
+        joint_err, f_scores = [], []
+        joint_pck, vert_pck = EvalUtil(21), EvalUtil(778)
+        vert_idx = (torch.as_tensor(np.asarray(hand_layer.right_mano_idx)) if use_arm else torch.arange(778)).to(device=device, dtype=torch.int32)
+        f_thr = torch.tensor([0.005, 0.015], dtype=torch.float32, device=device)        # metres
     panel_dir = os.path.join(base, "rendered_after_opt" + test_name)
     if panels:
         os.makedirs(panel_dir, exist_ok=True)                      # :660
@@ -453,7 +473,28 @@ def evaluate_sequence(configs, params, images_dataset, hand_layer, device="cuda"
                 l1.append((y_true - y_pred).abs().double().sum((1, 2, 3)).cpu())
             if with_lpips:                            # :51-53 of utils/eval_util.py, per frame
                 lp.append(lpips_fn(y_true.permute(0, 3, 1, 2), y_pred.permute(0, 3, 1, 2)).reshape(B).double().cpu())
-            if configs["eval_mesh"]:                 # :760-774
+            if pe is not None:                        # the device path of :760-774 and of utils/eval_util.py:166-209
+                if with_joints:
+                    gt_j = pe["gt_joints"][fid].to(device=device, dtype=torch.float32)
+                    gt_j = gt_j - gt_j[:, :1]
+                    pred_j = r.hand_joints[:, :21].float() * 1000.0
+                    pred_j = pred_j - pred_j[:, :1]
+                    vis = (pe["gt_joint_valid"][fid] == 1).to(device) if "gt_joint_valid" in pe else torch.ones(B, 21, dtype=torch.bool, device=device)
+                    al_j, err_j, nv = ops.procrustes_align(gt_j, pred_j, valid=vis.float())
+                    ok = nv >= 3
+                    joint_err.append((torch.nan_to_num(err_j.double()).sum(1) / nv.clamp(min=1))[ok].cpu())
+                    joint_pck.feed_batch(gt_j, vis & ok[:, None], al_j)
+                if with_verts:
+                    if "gt_verts" in pe:
+                        gt_v = pe["gt_verts"][fid].to(device=device, dtype=torch.float32)
+                    else:
+                        gt_v = torch.as_tensor(np.stack([load_gt_vert(fid[b:b + 1], configs["gt_mesh_dir"], dataset="synthetic", start_from_one=True,
+                                                                      idx_offset=500) for b in range(B)]), dtype=torch.float32).to(device)
+                    al_v, err_v, _ = ops.procrustes_align(gt_v, hand_verts, pred_idx=vert_idx)
+                    vert_err.extend((err_v.double().mean(1) * 1000.0).cpu().tolist())
+                    vert_pck.feed_batch(gt_v * 1000.0, torch.ones(B, 778, device=device), al_v * 1000.0)
+                    f_scores.append(ops.point_set_fscore(gt_v, al_v, f_thr)[0][:, :, 2].double().cpu())
+            elif configs["eval_mesh"]:               # :760-774
                 for b in range(B):
                     gt = load_gt_vert(fid[b:b + 1], configs["gt_mesh_dir"], dataset="synthetic", start_from_one=True, idx_offset=500)
                     pred = hand_verts[b, hand_layer.right_mano_idx] if use_arm else hand_verts[b, :778]
@@ -481,9 +522,19 @@ def evaluate_sequence(configs, params, images_dataset, hand_layer, device="cuda"
     if with_ms:
         ms = torch.cat(ms)
         stats["MS_SSIM"] = float(np.mean([ms[c].mean().item() for c in chunks]))
+    if pe is not None and with_joints:
+        joint_err = torch.cat(joint_err).tolist()
+        if joint_err:
+            stats["Procrustes-aligned joint error (mm)"] = float(np.mean(joint_err))
+            stats["Joint AUC 0-50 mm"] = float(joint_pck.get_measures(0.0, 50.0, 100)[2])
+            np.savetxt(os.path.join(base, "eval_joint_mm" + test_name + ".txt"), joint_err)
     if vert_err:
         stats["Procrustes-aligned vertex error (mm)"] = float(np.mean(vert_err))
         np.savetxt(os.path.join(base, "eval_vert_mm" + test_name + ".txt"), vert_err)
+        if pe is not None:
+            f = torch.cat(f_scores).mean(0)
+            stats["Vertex AUC 0-50 mm"] = float(vert_pck.get_measures(0.0, 50.0, 100)[2])
+            stats["F@5mm"], stats["F@15mm"] = float(f[0]), float(f[1])
     print("  -- Evaluation --")
     for k, v in stats.items():
         print(" %s: %.5f" % (k, v))
@@ -522,6 +573,9 @@ def main(argv=None):
     ap.add_argument("--export-mesh", action="store_true", help="with --eval: the Taubin-smoothed textured mesh of every frame as mesh/<fid>.obj, .mtl, .png")
     ap.add_argument("--monitor", action="store_true", help="while fitting: the progress sheets of optimize_sequence.py:490-501 every 10 epochs, "
                     "visualize_val's val_ / uv_ / normal_ sheets every 20 and monitor_log.jsonl (harp_amd.monitor.FitMonitor)")
+    ap.add_argument("--pose-eval", default=None, metavar="PATH",
+                    help="with --eval: an .npz with any of gt_joints (T,21,3) mm, gt_joint_valid (T,21), gt_verts (T,778,3) m; adds the "
+                         "Procrustes-aligned joint / vertex errors, their AUC and the F-scores (configs['pose_eval'])")
     ap.add_argument("--lpips-weights", nargs="+", default=None, metavar="PATH",
                     help="LPIPS in the evaluation: one lpips.LPIPS(net='alex') state dict, or torchvision's alexnet state dict and the lpips "
                          "v0.1 alex head (configs['lpips_weights'])")
@@ -530,6 +584,8 @@ def main(argv=None):
         configs = get_config(write_yaml=False, **yaml.safe_load(f))
     if args.lpips_weights:
         configs["lpips_weights"] = lpips_weights_arg(args.lpips_weights)
+    if args.pose_eval:
+        configs["pose_eval"] = args.pose_eval
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     shared = os.environ.get("HARP_ALL_ON_GPU0") == "1"

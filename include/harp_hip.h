@@ -882,6 +882,46 @@ size_t harp_taubin_ws_bytes(int B, int V);
 int harp_taubin_smooth(const float* verts, const int32_t* nbr_off, const int32_t* nbr_idx, int B, int V, float lambd, float mu, int num_iter,
                        int mode, float* out, void* ws, hipStream_t stream);
 
+/* ---- geometric accuracy of the post-fit evaluation: Procrustes, PCK counts, point-set F-score (csrc/pose_eval.hip) --------------------
+ * All three only enqueue on `stream`: no allocation, no workspace, no synchronisation, capturable.  Forward only, float64 inside, no float
+ * atomics and a fixed order in every sum, so a repeated call gives the same bits.
+ *
+ * harp_procrustes_align replaces align_w_scale (utils/eval_util.py:212-235, with scipy.linalg.orthogonal_procrustes inside) as called
+ * once per frame from optimize_sequence.py:760-774 and utils/eval_util.py:199, for N frames in one launch (one workgroup per frame).
+ *   gt (N,K,3), pred (N,Kp,3) float32; pred_idx NULL (then Kp must equal K, points in order) or K int32 indices into the Kp points (the
+ *   gather `pred[:, right_mano_idx]` without a copy; an index outside [0, Kp) is never read: that point counts as invalid);
+ *   valid NULL or (N,K) float32, non-zero = the point is used.  Per frame over its used points, in float64:
+ *     t1, t2 = means;  a = gt - t1, b = pred - t2;  s1 = |a|_F + 1e-8, s2 = |b|_F + 1e-8;  M = (a / s1)^T (b / s2) = U W V^T;
+ *     R = U V^T (NO determinant correction: a mirrored prediction is aligned by a reflection, as scipy does), s = sum W;
+ *     aligned = ((b / s2) R^T) s s1 + t1.
+ *   The SVD is a one-sided Jacobi iteration; a vanishing singular value (three points, coplanar sets) gets its left vector completed
+ *   so that U stays orthogonal (its sign does not reach `aligned`: b has no component along it).
+ *   aligned NULL or (N,K,3) float32; err (N,K) float32 = |gt - aligned| from the float64 values, rounded once; both NaN at points not
+ *   used.  trafo NULL or (N,14) float64: R row-major, s, s1, t1 - t2 (the tuple of return_trafo=True).  n_valid (N) int32.
+ *   A frame with fewer than 3 used points has NaN aligned / err / trafo and its true count (the "invalid ground truth" of :204-207).
+ *   Returns HARP_ERR_ARG without launching for NULL gt / pred / err / n_valid, N, K, Kp <= 0, or Kp != K without pred_idx.
+ *
+ * harp_pck_counts replaces the counting of EvalUtil._get_pck / _get_epe / get_measures (utils/eval_util.py:103-163): one workgroup per
+ * keypoint.  err (N,K) float32, valid NULL or (N,K) float32 (non-zero = visible), thresholds (n_thr) float32 ON THE DEVICE.  A
+ * measurement is seen when it is visible and not NaN.  counts (K,n_thr) int32 = seen n with err[n][k] <= thresholds[j] (the float32
+ * comparison), n_vis (K) int32 = seen n, err_sum (K) float64 = their sum.
+ *   Returns HARP_ERR_ARG without launching for NULL err / thresholds / counts / n_vis / err_sum, N, K <= 0 or n_thr < 1.
+ *
+ * harp_point_set_fscore: precision / recall / F between two point sets per frame (the mesh measure of the FreiHAND benchmark, whose
+ * helpers the reference ships in utils/fh_utils.py; it complements the vertex error of optimize_sequence.py:760-774).  gt (N,Kg,3),
+ * pred (N,Kp,3), thresholds (n_thr) float32 on the device.  In float64: d2(p, q) = sum (double(p) - double(q))^2, nn_gt[n][i] = min over
+ * the pred points, nn_pred[n][j] = min over the gt points; per threshold t: precision = share of gt points with nn_gt < double(t)^2,
+ * recall = share of pred points with nn_pred < double(t)^2 (strict), F = 2 p r / (p + r), 0 when p + r = 0.
+ *   out (N,n_thr,3) float32 (precision, recall, F); nn_gt NULL or (N,Kg), nn_pred NULL or (N,Kp) float32 = the square roots.
+ *   All pairs, one workgroup per frame, the other set tiled through LDS.
+ *   Returns HARP_ERR_ARG without launching for NULL gt / pred / thresholds / out, N, Kg, Kp <= 0, n_thr outside 1..512. */
+int harp_procrustes_align(const float* gt, const float* pred, const int32_t* pred_idx, const float* valid, int N, int K, int Kp,
+                          float* aligned, float* err, double* trafo, int32_t* n_valid, hipStream_t stream);
+int harp_pck_counts(const float* err, const float* valid, const float* thresholds, int N, int K, int n_thr, int32_t* counts, int32_t* n_vis,
+                    double* err_sum, hipStream_t stream);
+int harp_point_set_fscore(const float* gt, const float* pred, const float* thresholds, int N, int Kg, int Kp, int n_thr, float* out,
+                          float* nn_gt, float* nn_pred, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
