@@ -300,3 +300,6 @@ SIGNATURES.update({
     "harp_pck_counts": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "harp_point_set_fscore": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
 })
+
+# decoded uint8 frames -> the resident float32 targets (csrc/ingest.hip)
+SIGNATURES["harp_targets_from_u8"] = (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp])

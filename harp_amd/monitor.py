@@ -192,7 +192,7 @@ class FitMonitor:
         self.submit(self.prefix + name, sheet, sources, marks)
 
     # ---- the fit's side ---------------------------------------------------------------------------------------------------------
-    def begin(self, configs, eng, hand_layer, verts_uvs, faces_uvs, val_params=None, val_images_dataset=None, seed=0):
+    def begin(self, configs, eng, hand_layer, verts_uvs, faces_uvs, val_params=None, val_images_dataset=None, seed=0, device_ingest=False):
         """bind to a fit: the engine's parameter views and resident targets; up to 9 validation items drawn ONCE from a generator of
         their own (seed + 1: the training shuffle's generator is not consumed) and kept resident"""
         from .optimize_sequence import get_mesh_subdivider
@@ -210,7 +210,7 @@ class FitMonitor:
         if val_params is not None and val_images_dataset is not None and len(val_images_dataset) > 0:
             g = torch.Generator().manual_seed(seed + 1)
             idx = torch.randperm(len(val_images_dataset), generator=g)[:SHEET_GRID[0] * SHEET_GRID[1]].tolist()
-            rt = ResidentTargets(val_images_dataset, frames=idx, device=self.dev)
+            rt = ResidentTargets(val_images_dataset, frames=idx, device=self.dev, ingest="device" if device_ingest else "host")
             T, Tv = eng.params["pose"].shape[0], min(torch.as_tensor(val_params[k]).shape[0] for k in ("cam", "trans", "rot"))
             if int(rt.fid.min()) < 0 or int(rt.fid.max()) >= min(T, Tv):
                 raise ValueError(f"validation frame ids span [{int(rt.fid.min())}, {int(rt.fid.max())}] but the fit's pose table holds {T} frames "

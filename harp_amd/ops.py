@@ -721,6 +721,49 @@ def sheet_u8(a, b=None, mask=None, mode="image", grid=(3, 3), d=1, channels_last
     return out
 
 
+INGEST_MAX_D = 8
+
+
+def targets_from_u8(rgb, mask, d=1, eroded=True, out=None):
+    """The three resident targets of a fit from decoded uint8 frames (csrc/ingest.hip; everything behind the image decoder in
+    utils/data_util.py:11-51) in one launch, forward only: rgb (N,H0,W0,3) and mask (N,H0,W0) uint8 HIP tensors ->
+    (y_true (N,H,W,3), y_sil (N,H,W), y_sil_col (N,H,W)) float32 with H = ceil(H0 / d), W = ceil(W0 / d) — `img[::d, ::d] / 255` and, for
+    y_sil_col, the mask eroded twice with a 3 x 3 square (out-of-image neighbours ignored), bit for bit what ImagesDataset yields.
+    eroded=False skips the erosion and returns None in its place.  out = (y_true, y_sil, y_sil_col): contiguous float32 tensors of those
+    shapes to write into, e.g. slices [n0 : n0 + N] of larger buffers (out[2] is neither read nor written with eroded=False)."""
+    for name, t in (("rgb", rgb), ("mask", mask)):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise RuntimeError("harp_amd ops need HIP device tensors (no CPU path)")
+        if t.dtype != torch.uint8:
+            raise TypeError(f"targets_from_u8 takes uint8 tensors, got {name} {t.dtype}")
+    if rgb.dim() != 4 or rgb.shape[3] != 3:
+        raise TypeError(f"targets_from_u8 takes (N,H0,W0,3) frames, got {tuple(rgb.shape)}")
+    N, H0, W0 = rgb.shape[:3]
+    if tuple(mask.shape) != (N, H0, W0) or mask.device != rgb.device:
+        raise ValueError(f"rgb {tuple(rgb.shape)} on {rgb.device} and mask {tuple(mask.shape)} on {mask.device} do not match")
+    d = int(d)
+    if not 1 <= d <= INGEST_MAX_D or N < 1 or H0 < 1 or W0 < 1:
+        raise ValueError(f"at least one frame of at least one pixel and d in 1..{INGEST_MAX_D}, got {tuple(rgb.shape)}, d = {d}")
+    H, W = -(-H0 // d), -(-W0 // d)
+    shapes = ((N, H, W, 3), (N, H, W), (N, H, W))
+    if out is None:
+        out = tuple(torch.empty(s, dtype=torch.float32, device=rgb.device) if (k < 2 or eroded) else None for k, s in enumerate(shapes))
+    else:
+        out = tuple(out)
+        if len(out) != 3:
+            raise ValueError("out = (y_true, y_sil, y_sil_col)")
+        for k, (t, s) in enumerate(zip(out, shapes)):
+            if k == 2 and not eroded:
+                continue
+            if not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != s or t.device != rgb.device or not t.is_contiguous():
+                raise ValueError(f"out[{k}] must be a contiguous float32 tensor {s} on {rgb.device}")
+    with torch.cuda.device(rgb.device):
+        rc = _lib.lib().harp_targets_from_u8(_lib.ptr(rgb), _lib.ptr(mask), N, H0, W0, d, _lib.ptr(out[0]), _lib.ptr(out[1]),
+                                             _lib.ptr(out[2]) if eroded else None, _lib.stream())
+    _lib.check(rc, "harp_targets_from_u8")
+    return out[0], out[1], (out[2] if eroded else None)
+
+
 # ------------------------------------------------------------------------------------------------------
 # export of the fitted avatar (csrc/smooth.hip): Taubin smoothing of the meshes that save_obj writes
 # ------------------------------------------------------------------------------------------------------

@@ -141,13 +141,16 @@ def stage_flags(epoch_id, training_stage):
 def optimize_hand_sequence(configs, input_params, images_dataset, val_params, val_images_dataset, hand_layer,
                            VERTS_UVS=None, FACES_UVS=None, VERTS_COLOR=None, device="cuda", uv_mask=None, batch_size=18, log_fn=None,
                            seed=0, vgg=None, rank=None, world_size=None, shards=None, plateau_patience=40, plateau_threshold=1e-4, device_schedule=True,
-                           evaluate=False, panels=False, turntable=False, export_mesh=False, monitor=False):
+                           evaluate=False, panels=False, turntable=False, export_mesh=False, monitor=False, device_ingest=False):
     """Fit the sequence (optimize_sequence.py:313-596).  Returns the parameter dict in the reference's checkpoint layout; evaluate=True
     then runs the post-fit evaluation `evaluate_sequence` (:595-816) on rank 0 (off by default), with its panels / turntable / export_mesh
     switches.  monitor: False (default: no new file, no new work), True, a dict of harp_amd.monitor.FitMonitor arguments or a FitMonitor —
     rank 0 then writes the reference's progress sheets while the fit runs (:490-501 every 10 epochs from the epoch's first batch; :587-589
     visualize_val every 20 epochs, which needs `val_params` and `val_images_dataset`) and monitor_log.jsonl, off the enqueueing thread.
     `images_dataset[i]` -> (fid, y_true (S,S,3), y_sil (S,S,1), y_sil_eroded (S,S,1)) like utils/data_util.ImagesDataset.
+    device_ingest=True: the targets (the monitor's validation frames and the evaluation's included) come from the files of the dataset's
+    image_paths / mask_paths through a thread pool of decoders and csrc/ingest.hip (ResidentTargets(ingest="device")) — the same bits,
+    `images_dataset[i]` is never called; a dataset without paths raises ValueError.
 
     Data-parallel (the reference is single-device): launched under `torch.distributed.run` (or with rank / world_size given)
     every rank calls this function with the SAME arguments.  The dataset's items are cut into `shards` (default: world) contiguous
@@ -181,7 +184,10 @@ def optimize_hand_sequence(configs, input_params, images_dataset, val_params, va
                     torch.as_tensor(uv_mask).float(), input_params, S, configs["focal_length"], b * k, device=device,
                     self_shadow=configs["self_shadow"], share_light_position=configs["share_light_position"], seed=seed,
                     use_arm=use_arm, opt_arm_pose=bool(configs.get("opt_arm_pose", False)), rank=rank, world_size=world)
-    rt = ResidentTargets(images_dataset, frames=range(lo, lo + k * per))         # decoded once, resident in HBM (utils/data_util.py)
+    if device_ingest:                                                            # decoded once on a thread pool, converted and eroded on the device
+        rt = ResidentTargets(images_dataset, frames=range(lo, lo + k * per), device=eng.dev, ingest="device")
+    else:
+        rt = ResidentTargets(images_dataset, frames=range(lo, lo + k * per))     # decoded once, resident in HBM (utils/data_util.py)
     if int(rt.fid.min()) < 0 or int(rt.fid.max()) >= T:
         raise ValueError(f"dataset frame ids span [{int(rt.fid.min())}, {int(rt.fid.max())}] but the parameter tables hold {T} frames")
     eng.set_targets(*rt.tensors())
@@ -231,7 +237,7 @@ def optimize_hand_sequence(configs, input_params, images_dataset, val_params, va
     step_guard = mon.hip_lock if mon is not None else contextlib.nullcontext()
     try:
         if mon is not None:
-            mon.begin(configs, eng, hand_layer, VERTS_UVS, FACES_UVS, val_params, val_images_dataset, seed=seed)
+            mon.begin(configs, eng, hand_layer, VERTS_UVS, FACES_UVS, val_params, val_images_dataset, seed=seed, device_ingest=device_ingest)
         def draw_epoch():
             """the next epoch's batches (DataLoader(shuffle=True) over the DATASET's items, :398) and — its full batches as ONE device schedule
             (parameter rows = the items' own fids, :446, :464; target rows = the items): every such step is a bare graph replay that fetches
@@ -296,7 +302,7 @@ def optimize_hand_sequence(configs, input_params, images_dataset, val_params, va
                 comm.destroy()                                       # drops the step graphs that captured it
     if evaluate and rank == 0:
         evaluate_sequence(configs, params, images_dataset, hand_layer, device=device, uv_mask=uv_mask, panels=panels, turntable=turntable,
-                          export_mesh=export_mesh)
+                          export_mesh=export_mesh, device_ingest=device_ingest)
     return params
 
 
@@ -344,7 +350,7 @@ EVAL_CHUNK = 64                  # optimize_sequence.py:716: image_eval runs on 
 
 
 def evaluate_sequence(configs, params, images_dataset, hand_layer, device="cuda", batch_size=32, uv_mask=None, lpips_fn=None, panels=False,
-                      turntable=False, panel_hook=None, export_mesh=False, pose_eval=None):
+                      turntable=False, panel_hook=None, export_mesh=False, pose_eval=None, device_ingest=False):
     """The post-fit evaluation of optimize_sequence.py:595-816: re-render every dataset item in order with the fitted `params` through the
     reference-API mirror (silhouette: get_renderers(silh_sigma=1e-7, silh_faces_per_pixel=50)[1]; image: render_image_with_RT through
     get_shadow_renderers with self_shadow, else render_image with the phong renderer), `batch_size` frames per render call; per-frame
@@ -372,7 +378,9 @@ def evaluate_sequence(configs, params, images_dataset, hand_layer, device="cuda"
     ops.point_set_fscore of the aligned vertices; after the lines above, whichever the ground truth allows of `Procrustes-aligned joint
     error (mm)`, `Joint AUC 0-50 mm` (100 thresholds), `Procrustes-aligned vertex error (mm)`, `Vertex AUC 0-50 mm`, `F@5mm`, `F@15mm`,
     and eval_joint_mm[_test].txt / eval_vert_mm[_test].txt with the per-frame means.  Frames with fewer than 3 valid joints are left out
-    of the joint lines.  With None everything is as before: the per-frame host loop of :760-774 included."""
+    of the joint lines.  With None everything is as before: the per-frame host loop of :760-774 included.
+    device_ingest=True: per batch the ground truth comes from utils.data_util.decode_u8 and ops.targets_from_u8(eroded=False) instead of
+    `images_dataset[i]` — the same bits, each file decoded once and no erosion computed; needs a dataset with paths (ValueError otherwise)."""
     import os
     import warnings
     import torch.nn.functional as F
@@ -381,6 +389,7 @@ def evaluate_sequence(configs, params, images_dataset, hand_layer, device="cuda"
     from .io import encode_png, save_obj
     from .renderer import renderer_helper
     from .structures import Meshes
+    from .utils.data_util import _ingest_paths, decode_u8
     from .utils.eval_util import EvalUtil, align_w_scale, load_gt_vert, sil_iou
     from .utils.visualize import concat_image_in_dir, prepare_mesh, render_360, render_360_light, render_image
     S, focal = int(configs["img_size"]), configs["focal_length"]
@@ -431,12 +440,19 @@ def evaluate_sequence(configs, params, images_dataset, hand_layer, device="cuda"
     if export_mesh:
         os.makedirs(mesh_dir, exist_ok=True)                       # :783
     n = len(images_dataset)
+    if device_ingest:
+        ingest_d = _ingest_paths(images_dataset)[2]                # ValueError for a dataset without paths, before anything is rendered
     with torch.no_grad():
         for lo in range(0, n, batch_size):
-            items = [images_dataset[i] for i in range(lo, min(n, lo + batch_size))]
-            fid = torch.as_tensor([int(it[0]) for it in items], dtype=torch.long)
-            y_true = torch.stack([torch.as_tensor(it[1]) for it in items]).to(device=device, dtype=torch.float32)
-            y_sil_true = torch.stack([torch.as_tensor(it[2]) for it in items]).reshape(len(items), S, S).to(device=device, dtype=torch.float32)
+            if device_ingest:
+                fid = torch.arange(lo, min(n, lo + batch_size), dtype=torch.long)       # ImagesDataset: the item's index is its fid
+                rgb_u8, mask_u8 = (torch.from_numpy(a).to(device) for a in decode_u8(images_dataset, fid.tolist()))
+                y_true, y_sil_true, _ = ops.targets_from_u8(rgb_u8, mask_u8, d=ingest_d, eroded=False)
+            else:
+                items = [images_dataset[i] for i in range(lo, min(n, lo + batch_size))]
+                fid = torch.as_tensor([int(it[0]) for it in items], dtype=torch.long)
+                y_true = torch.stack([torch.as_tensor(it[1]) for it in items]).to(device=device, dtype=torch.float32)
+                y_sil_true = torch.stack([torch.as_tensor(it[2]) for it in items]).reshape(len(items), S, S).to(device=device, dtype=torch.float32)
             B = fid.shape[0]
             r = mirror_render(configs, P, fid, hand_layer, sub, device=device)
             hand_verts, faces, textures, meshes, cam = r.hand_verts, r.faces, r.textures, r.meshes, r.cam
@@ -573,6 +589,9 @@ def main(argv=None):
     ap.add_argument("--export-mesh", action="store_true", help="with --eval: the Taubin-smoothed textured mesh of every frame as mesh/<fid>.obj, .mtl, .png")
     ap.add_argument("--monitor", action="store_true", help="while fitting: the progress sheets of optimize_sequence.py:490-501 every 10 epochs, "
                     "visualize_val's val_ / uv_ / normal_ sheets every 20 and monitor_log.jsonl (harp_amd.monitor.FitMonitor)")
+    ap.add_argument("--device-ingest", action="store_true",
+                    help="decode the frames once on a thread pool and convert / erode them on the device (csrc/ingest.hip): the same "
+                         "targets, for the fit, the monitor's validation frames and --eval")
     ap.add_argument("--pose-eval", default=None, metavar="PATH",
                     help="with --eval: an .npz with any of gt_joints (T,21,3) mm, gt_joint_valid (T,21), gt_verts (T,778,3) m; adds the "
                          "Procrustes-aligned joint / vertex errors, their AUC and the F-scores (configs['pose_eval'])")
@@ -605,7 +624,8 @@ def main(argv=None):
         average_cam_sequence=configs["average_cam_sequence"], use_smooth_seq=configs["use_smooth_seq"], model_type=configs["model_type"])
     params = optimize_hand_sequence(configs, mano_params, images_dataset, val_mano_params, val_images_dataset, hand_layer, VERTS_UVS, FACES_UVS,
                                     VERTS_COLOR, device=device, batch_size=args.batch_size, evaluate=args.eval, panels=args.panels,
-                                    turntable=args.turntable, export_mesh=args.export_mesh, monitor=args.monitor)
+                                    turntable=args.turntable, export_mesh=args.export_mesh, monitor=args.monitor,
+                                    device_ingest=args.device_ingest)
     if world > 1:
         tdist.barrier()
         tdist.destroy_process_group()

@@ -11,9 +11,12 @@ Same names, arguments and return values as the reference (`load_img`, `ImagesDat
 `load_multiple_sequences`, `load_sample_sequence`).  Differences: no cv2 (absent here) — the 3x3 erosion x2 of the mask
 (utils/data_util.py:17-20) is a numpy minimum filter with cv2.erode's default border rule (neighbours outside the image are ignored);
 and `ResidentTargets`, which decodes a dataset once into the three tensors `FitEngine.set_targets` keeps in HBM (the reference
-re-decodes every frame every epoch in 20 DataLoader workers, optimize_sequence.py:399, 446-450).
+re-decodes every frame every epoch in 20 DataLoader workers, optimize_sequence.py:399, 446-450).  `ResidentTargets(ingest="device")`
+moves everything behind the image decoder to the device (`decode_u8` on a thread pool, csrc/ingest.hip): same bits, opt-in.
 """
 import os
+import time
+from concurrent.futures import ThreadPoolExecutor
 import pickle
 
 import numpy as np
@@ -174,13 +177,98 @@ def load_sample_sequence(metro_output_dir, image_dir, max_size=0, val=False, val
             combine_dict_to_batch(valid[2]), ImagesDataset(valid[0], valid[1], downsample_factor=1))
 
 
+def default_workers():
+    """decoder threads: the CPUs this process may run on (not the machine's), at most 16"""
+    return max(1, min(16, len(os.sched_getaffinity(0))))
+
+
+def _ingest_paths(dataset):
+    """(image_paths, mask_paths, downsample_factor) of a dataset that decode_u8 can read, ValueError for anything else"""
+    try:
+        ips, mps, d = dataset.image_paths, dataset.mask_paths, int(dataset.downsample_factor)
+    except (AttributeError, TypeError, ValueError):
+        raise ValueError(f"device ingest decodes the files itself: it needs a dataset with image_paths, mask_paths and downsample_factor "
+                         f"(an ImagesDataset), got {type(dataset).__name__}") from None
+    if len(ips) != len(mps):
+        raise ValueError(f"{len(ips)} image paths but {len(mps)} mask paths")
+    return ips, mps, d
+
+
+def _frame_size(path):
+    with Image.open(path) as im:                                # reads the header only
+        return im.size[1], im.size[0]
+
+
+def _decode_frame(image_path, mask_path, rgb_out, mask_out):
+    with Image.open(image_path) as im:
+        a = np.asarray(im.convert("RGB"))
+    if a.shape != rgb_out.shape:
+        raise ValueError(f"{image_path} is {a.shape[0]} x {a.shape[1]}, the other frames are {rgb_out.shape[0]} x {rgb_out.shape[1]}")
+    with Image.open(mask_path) as im:
+        m = np.asarray(im.convert("L"))
+    if m.shape != a.shape[:2]:
+        raise ValueError(f"{mask_path} is {m.shape[0]} x {m.shape[1]}, its image {image_path} is {a.shape[0]} x {a.shape[1]}")
+    rgb_out[...] = a
+    mask_out[...] = m
+
+
+def decode_u8(dataset, indices, workers=None, out=None, pool=None):
+    """Items `indices` of a dataset with `image_paths`, `mask_paths` and `downsample_factor` (an ImagesDataset) as they come out of the
+    decoder: (rgb (n,H0,W0,3), mask (n,H0,W0)) uint8 numpy arrays in index order, at full size (the subsampling belongs to
+    ops.targets_from_u8).  Every file is decoded ONCE — Image.open(path).convert("RGB") / .convert("L"), the decodes load_img runs — on
+    a ThreadPoolExecutor of `workers` threads (default: default_workers()) or on `pool`.  out = (rgb, mask): arrays of those shapes to fill
+    instead, e.g. views of pinned staging tensors.  Frames of unequal size, or a mask that differs in size from its image, raise ValueError
+    naming the file; once one frame has failed no further decode is started."""
+    ips, mps, _ = _ingest_paths(dataset)
+    idx = [int(i) for i in indices]
+    if not idx:
+        raise ValueError("decode_u8: no frame asked for")
+    if out is None:
+        H0, W0 = _frame_size(ips[idx[0]])
+        out = (np.empty((len(idx), H0, W0, 3), dtype=np.uint8), np.empty((len(idx), H0, W0), dtype=np.uint8))
+    rgb, mask = out
+    if (rgb.dtype != np.uint8 or mask.dtype != np.uint8 or rgb.ndim != 4 or rgb.shape[0] != len(idx) or rgb.shape[3] != 3
+            or mask.shape != rgb.shape[:3]):
+        raise ValueError(f"out must be uint8 arrays ({len(idx)},H0,W0,3) and ({len(idx)},H0,W0), got {rgb.shape} {rgb.dtype}, {mask.shape} {mask.dtype}")
+    own = pool is None
+    if own:
+        pool = ThreadPoolExecutor(default_workers() if workers is None else max(1, int(workers)))
+    try:
+        futures = [pool.submit(_decode_frame, ips[i], mps[i], rgb[k], mask[k]) for k, i in enumerate(idx)]
+        try:
+            for f in futures:
+                f.result()
+        except BaseException:
+            for f in futures:
+                f.cancel()
+            raise
+    finally:
+        if own:
+            pool.shutdown(wait=True, cancel_futures=True)
+    return rgb, mask
+
+
 class ResidentTargets:
     """Decode an `ImagesDataset` ONCE into the tensors the fitting engine keeps resident in HBM:
     y_true (T,S,S,3), y_sil (T,S,S), y_sil_col (T,S,S) — `FitEngine.set_targets(*ResidentTargets(ds, frames).tensors())`.
-    `frames` selects / orders the items (e.g. one rank's shard, harp_amd.dist.shard_frames)."""
+    `frames` selects / orders the items (e.g. one rank's shard, harp_amd.dist.shard_frames).
+    ingest="host" (default): `dataset[i]` per frame on this thread, stacked on the host, then moved to `device`.
+    ingest="device" (needs a HIP `device` and a dataset with image_paths / mask_paths / downsample_factor): the same bits without the
+    host's float arithmetic — the three tensors are allocated once on the device and the frames walk through in chunks of `chunk`:
+    decode_u8 on `workers` threads into one of TWO pinned uint8 staging buffers, an asynchronous copy to a device uint8 buffer, one
+    ops.targets_from_u8 into the chunk's slices.  An event per staging buffer is waited for before the buffer is decoded into again, so
+    the decode of chunk k + 1 overlaps the upload and the kernel of chunk k; the host holds two chunks of 4 bytes per pixel instead
+    of every frame at 20.  eroded=False (device ingest only) leaves y_sil_col = None."""
 
-    def __init__(self, dataset, frames=None, device="cpu", pin=False):
+    def __init__(self, dataset, frames=None, device="cpu", pin=False, ingest="host", workers=None, chunk=32, eroded=True):
         idx = range(len(dataset)) if frames is None else list(frames)
+        if ingest == "device":
+            self._ingest_device(dataset, [int(i) for i in idx], device, workers, chunk, eroded)
+            return
+        if ingest != "host":
+            raise ValueError(f'ingest is "host" or "device", got {ingest!r}')
+        if not eroded:
+            raise ValueError('eroded=False belongs to ingest="device" (the host path decodes what the dataset yields)')
         items = [dataset[i] for i in idx]
         self.fid = torch.tensor([int(it[0]) for it in items], dtype=torch.int32)
         self.y_true = torch.stack([torch.as_tensor(it[1], dtype=torch.float32) for it in items])
@@ -191,6 +279,60 @@ class ResidentTargets:
             self.y_true, self.y_sil, self.y_sil_col = (t.pin_memory() for t in (self.y_true, self.y_sil, self.y_sil_col))
         if str(device) != "cpu":
             self.y_true, self.y_sil, self.y_sil_col = (t.to(device, non_blocking=pin) for t in (self.y_true, self.y_sil, self.y_sil_col))
+
+    def _ingest_device(self, dataset, idx, device, workers, chunk, eroded):
+        from .. import ops
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise ValueError(f'ingest="device" needs a HIP device, got {device!r}')
+        ips, _, d = _ingest_paths(dataset)
+        n = len(idx)
+        if n == 0:
+            raise ValueError("no frame to ingest")
+        chunk = max(1, min(int(chunk), n))
+        H0, W0 = _frame_size(ips[idx[0]])
+        H, W = -(-H0 // d), -(-W0 // d)
+        with torch.cuda.device(dev):
+            self.fid = torch.tensor(idx, dtype=torch.int32)
+            self.y_true = torch.empty((n, H, W, 3), dtype=torch.float32, device=dev)
+            self.y_sil = torch.empty((n, H, W), dtype=torch.float32, device=dev)
+            self.y_sil_col = torch.empty((n, H, W), dtype=torch.float32, device=dev) if eroded else None
+            stage = [(torch.empty((chunk, H0, W0, 3), dtype=torch.uint8, pin_memory=True),
+                      torch.empty((chunk, H0, W0), dtype=torch.uint8, pin_memory=True)) for _ in range(2)]
+            # ONE device buffer: the copy of chunk k + 1 is ordered behind the kernel of chunk k on the stream
+            dev_rgb, dev_mask = (torch.empty(t.shape, dtype=torch.uint8, device=dev) for t in stage[0])
+            free = [None, None]                                      # per staging buffer: the event behind the last copy out of it
+            self._marks, self._host = [], {"decode_s": 0.0, "wait_s": 0.0}
+            pool = ThreadPoolExecutor(default_workers() if workers is None else max(1, int(workers)))
+            try:
+                for k, lo in enumerate(range(0, n, chunk)):
+                    m, (pin_rgb, pin_mask) = min(chunk, n - lo), stage[k & 1]
+                    t0 = time.perf_counter()
+                    if free[k & 1] is not None:
+                        free[k & 1].synchronize()
+                    t1 = time.perf_counter()
+                    decode_u8(dataset, idx[lo:lo + m], out=(pin_rgb.numpy()[:m], pin_mask.numpy()[:m]), pool=pool)
+                    self._host["wait_s"] += t1 - t0
+                    self._host["decode_s"] += time.perf_counter() - t1
+                    marks = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
+                    marks[0].record()
+                    dev_rgb[:m].copy_(pin_rgb[:m], non_blocking=True)
+                    dev_mask[:m].copy_(pin_mask[:m], non_blocking=True)
+                    marks[1].record()
+                    free[k & 1] = marks[1]
+                    ops.targets_from_u8(dev_rgb[:m], dev_mask[:m], d=d, eroded=eroded,
+                                        out=(self.y_true[lo:lo + m], self.y_sil[lo:lo + m], self.y_sil_col[lo:lo + m] if eroded else None))
+                    marks[2].record()
+                    self._marks.append(marks)
+            finally:
+                pool.shutdown(wait=True, cancel_futures=True)
+            # (nothing waits for the last chunk here: the staging and device uint8 buffers go back to torch's stream-aware allocators)
+
+    def ingest_stats(self):
+        """device ingest only: host seconds spent decoding and waiting for a staging buffer, device milliseconds of every chunk's copies and
+        kernel (from the events recorded around them)"""
+        return dict(self._host, chunks=len(self._marks), copy_ms=[a.elapsed_time(b) for a, b, _ in self._marks],
+                    kernel_ms=[b.elapsed_time(c) for _, b, c in self._marks])
 
     def tensors(self):
         return self.y_true, self.y_sil, self.y_sil_col

@@ -922,6 +922,22 @@ int harp_pck_counts(const float* err, const float* valid, const float* threshold
 int harp_point_set_fscore(const float* gt, const float* pred, const float* thresholds, int N, int Kg, int Kp, int n_thr, float* out,
                           float* nn_gt, float* nn_pred, hipStream_t stream);
 
+/* ---- what a fitting job is fed with: decoded uint8 frames -> the resident float32 targets (csrc/ingest.hip) -----------------------------
+ * harp_targets_from_u8 replaces everything behind the image decoder in utils/data_util.py:11-51 (load_img called three times per frame by
+ * ImagesDataset.__getitem__: `/ 255` in float64, `[::d, ::d]`, cv2.erode(mask, ones((3,3)), iterations=2), torch.Tensor) for N frames in
+ * one launch.  rgb (N,H0,W0,3) and mask (N,H0,W0) uint8, contiguous; H = ceil(H0 / d), W = ceil(W0 / d); output pixel (y, x) reads source
+ * pixel (y d, x d), the subsampling taken BEFORE the erosion as in load_img.
+ *   y_true (N,H,W,3), y_sil (N,H,W) float32 = (float)u / 255.0f, the correctly rounded IEEE float32 division — for each of the 256 codes
+ *     the bits of float32(float64(u) / 255.0), which is what the reference's numpy division followed by torch.Tensor yields.
+ *   y_sil_col NULL (the erosion is skipped) or (N,H,W) float32 = the same conversion of the minimum of the subsampled mask over the 5 x 5
+ *     window clipped to the H x W image = two passes of the 3 x 3 erosion with out-of-image neighbours ignored (cv2's default border).
+ *   Outputs need only float alignment (a slice [n0 : n0 + N] of a larger buffer is fine); 16-byte aligned rows leave as 128-bit stores.
+ *   Stream-ordered and capturable: no allocation, no workspace, no synchronisation.  Deterministic: no atomics.
+ *   Returns HARP_ERR_ARG without launching for NULL rgb / mask / y_true / y_sil, N, H0, W0 <= 0, d outside 1..8, or more than 2^31 - 1 tiles of
+ *   16 x 64 output pixels over all frames (the grid; it also keeps every element count below 2^49). */
+int harp_targets_from_u8(const unsigned char* rgb, const unsigned char* mask, int N, int H0, int W0, int d, float* y_true, float* y_sil,
+                         float* y_sil_col, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
