@@ -303,3 +303,21 @@ SIGNATURES.update({
 
 # decoded uint8 frames -> the resident float32 targets (csrc/ingest.hip)
 SIGNATURES["harp_targets_from_u8"] = (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp])
+
+
+class BakeArgs(ctypes.Structure):
+    """mirror of `harp_bake_args` (include/harp_hip.h)"""
+    _fields_ = ([(n, _vp) for n in ("texel_idx", "texel_face", "texel_bary", "faces", "ndc", "face_id", "zbuf", "y_true", "y_mask", "rows",
+                                    "verts", "vnormals", "cam_pos", "light_pos", "colors", "sum_w", "sum_wc", "sum_wc2", "count", "best_cos")] +
+                [(n, _i) for n in ("n", "Ht", "Wt", "F", "V", "B", "S", "N")] +
+                [(n, _f) for n in ("depth_tol", "cos_min", "cos_power", "shade_floor")])
+
+
+# the frames baked into UV space (csrc/bake.hip)
+SIGNATURES.update({
+    "harp_uv_texel_map": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "harp_texture_bake_accum": (_i, [ctypes.POINTER(BakeArgs), _vp]),
+    "harp_texture_bake_finish": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "harp_texture_dilate_ws_bytes": (_sz, [_i, _i, _i]),
+    "harp_texture_dilate": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+})

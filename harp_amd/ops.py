@@ -926,3 +926,133 @@ def point_set_fscore(gt, pred, thresholds):
                                               _lib.ptr(nn_pred), _lib.stream())
     _lib.check(rc, "harp_point_set_fscore")
     return (out[0], nn_gt[0], nn_pred[0]) if single else (out, nn_gt, nn_pred)
+
+
+# ------------------------------------------------------------------------------------------------------
+# the frames baked into UV space (csrc/bake.hip): texel map, per-texel accumulation, finish, seam dilation
+# ------------------------------------------------------------------------------------------------------
+BAKE_DEFAULTS = dict(depth_tol=4e-3, cos_min=0.2, cos_power=2.0, shade_floor=0.1)      # parameters of the bake, not tolerances
+
+
+def _bake_input(name, *ts):
+    check_forward_only(*[t for t in ts if t is not None])
+    for t in ts:
+        if t is not None and not (torch.is_tensor(t) and t.is_cuda):
+            raise RuntimeError(f"{name}: harp_amd ops need HIP device tensors (no CPU path)")
+
+
+def uv_texel_map(verts_uvs, faces_uvs, Ht, Wt):
+    """The UV triangles rasterised at the texel centres of an (Ht, Wt) atlas, forward only: verts_uvs (VT,2) float32, faces_uvs (F,3)
+    int32 HIP tensors -> (texel_face (Ht,Wt) int32: the owning face, the lowest index where several contain the centre, or -1;
+    texel_bary (Ht,Wt,2) float32: b0, b1 with b2 = 1 - b0 - b1).  Texel (x, y) <-> u = x / (Wt - 1), v = 1 - y / (Ht - 1)."""
+    _bake_input("uv_texel_map", verts_uvs, faces_uvs)
+    vu = _f32(verts_uvs.detach()).reshape(-1, 2)
+    fu = faces_uvs.detach().to(torch.int32).reshape(-1, 3).contiguous()
+    Ht, Wt = int(Ht), int(Wt)
+    if vu.shape[0] < 1 or fu.shape[0] < 1 or Ht < 2 or Wt < 2:
+        raise ValueError(f"uv_texel_map needs at least one UV vertex, one face and a 2 x 2 atlas, got {tuple(vu.shape)}, {tuple(fu.shape)}, {Ht} x {Wt}")
+    face = torch.empty(Ht, Wt, dtype=torch.int32, device=vu.device)
+    bary = torch.empty(Ht, Wt, 2, dtype=torch.float32, device=vu.device)
+    with torch.cuda.device(vu.device):
+        rc = _lib.lib().harp_uv_texel_map(_lib.ptr(vu), _lib.ptr(fu), fu.shape[0], vu.shape[0], Ht, Wt, _lib.ptr(face), _lib.ptr(bary), _lib.stream())
+    _lib.check(rc, "harp_uv_texel_map")
+    return face, bary
+
+
+def bake_accumulators(Ht, Wt, device):
+    """zeroed accumulators of texture_bake_accum: dict of sum_w (Ht,Wt), sum_wc, sum_wc2 (Ht,Wt,3) float64, count (Ht,Wt) int32 and
+    best_cos (Ht,Wt) float32 (-1: never seen)"""
+    z = lambda *s, dt=torch.float64: torch.zeros(*s, dtype=dt, device=device)      # noqa: E731
+    return {"sum_w": z(Ht, Wt), "sum_wc": z(Ht, Wt, 3), "sum_wc2": z(Ht, Wt, 3), "count": z(Ht, Wt, dt=torch.int32),
+            "best_cos": torch.full((Ht, Wt), -1.0, dtype=torch.float32, device=device)}
+
+
+def texture_bake_accum(acc, texel_face, texel_bary, faces, ndc, face_id, zbuf, y_true, y_mask, rows, texel_idx=None, verts=None, vnormals=None,
+                       cam_pos=None, light_pos=None, colors=None, depth_tol=BAKE_DEFAULTS["depth_tol"], cos_min=BAKE_DEFAULTS["cos_min"],
+                       cos_power=BAKE_DEFAULTS["cos_power"], shade_floor=BAKE_DEFAULTS["shade_floor"]):
+    """Add the B frames of one call to the per-texel accumulators `acc` (bake_accumulators), in place and in frame order (include/harp_hip.h:
+    harp_texture_bake_accum).  texel_face / texel_bary from uv_texel_map; faces (F,3) int32; ndc (B,V,3) from ops.project; face_id / zbuf
+    (B,S,S) from the hard rasterize_fwd; y_true (N,S,S,3), y_mask (N,S,S) and rows (B,) int32 into them; texel_idx: int32 list of covered
+    texels (None: all).  verts / vnormals (B,V,3) and cam_pos (B,3) switch the viewing-angle test and weight on, light_pos (B,3) and
+    colors (B,9) the division by the Lambert shading.  Cutting a sequence into calls differently gives the same bits.  Returns acc."""
+    ts = (texel_face, texel_bary, faces, ndc, face_id, zbuf, y_true, y_mask, rows, texel_idx, verts, vnormals, cam_pos, light_pos, colors)
+    _bake_input("texture_bake_accum", *ts, *acc.values())
+    Ht, Wt = texel_face.shape
+    B, V, _ = ndc.shape
+    S, N = face_id.shape[-1], y_true.shape[0]
+    if tuple(face_id.shape) != (B, S, S) or tuple(zbuf.shape) != (B, S, S) or tuple(y_true.shape) != (N, S, S, 3) or y_mask.numel() != N * S * S:
+        raise ValueError(f"face_id {tuple(face_id.shape)}, zbuf {tuple(zbuf.shape)}, y_true {tuple(y_true.shape)}, y_mask {tuple(y_mask.shape)} "
+                         f"do not fit {B} frames of {S} x {S}")
+    if rows.numel() != B or tuple(texel_bary.shape) != (Ht, Wt, 2) or faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"rows {tuple(rows.shape)} for {B} frames, texel_bary {tuple(texel_bary.shape)} for a {Ht} x {Wt} atlas, faces {tuple(faces.shape)}")
+    for name, t, shape in (("verts", verts, (B, V, 3)), ("vnormals", vnormals, (B, V, 3)), ("cam_pos", cam_pos, (B, 3)),
+                           ("light_pos", light_pos, (B, 3)), ("colors", colors, (B, 9))):
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError(f"{name} {tuple(t.shape)}: expected {shape}")
+    for k, (dt, shape) in {"sum_w": (torch.float64, (Ht, Wt)), "sum_wc": (torch.float64, (Ht, Wt, 3)), "sum_wc2": (torch.float64, (Ht, Wt, 3)),
+                           "count": (torch.int32, (Ht, Wt)), "best_cos": (torch.float32, (Ht, Wt))}.items():
+        if acc[k].dtype != dt or tuple(acc[k].shape) != shape or not acc[k].is_contiguous():
+            raise ValueError(f"acc[{k!r}] must be a contiguous {dt} tensor {shape}")
+    i32 = lambda t: None if t is None else t.detach().to(torch.int32).contiguous()      # noqa: E731
+    f32 = lambda t: None if t is None else _f32(t.detach())                              # noqa: E731
+    keep = dict(texel_idx=i32(texel_idx), texel_face=i32(texel_face), texel_bary=f32(texel_bary), faces=i32(faces), ndc=f32(ndc),
+                face_id=i32(face_id), zbuf=f32(zbuf), y_true=f32(y_true), y_mask=f32(y_mask), rows=i32(rows), verts=f32(verts),
+                vnormals=f32(vnormals), cam_pos=f32(cam_pos), light_pos=f32(light_pos), colors=f32(colors))
+    a = _lib.BakeArgs()
+    for k, t in keep.items():
+        setattr(a, k, _lib.ptr(t))
+    for k, t in acc.items():
+        setattr(a, k, _lib.ptr(t))
+    a.n = keep["texel_idx"].numel() if texel_idx is not None else Ht * Wt
+    a.Ht, a.Wt, a.F, a.V, a.B, a.S, a.N = Ht, Wt, faces.shape[0], V, B, S, N
+    a.depth_tol, a.cos_min, a.cos_power, a.shade_floor = float(depth_tol), float(cos_min), float(cos_power), float(shade_floor)
+    if a.n == 0:
+        return acc
+    with torch.cuda.device(ndc.device):
+        rc = _lib.lib().harp_texture_bake_accum(ctypes.byref(a), _lib.stream())
+    _lib.check(rc, "harp_texture_bake_accum")
+    return acc
+
+
+def texture_bake_finish(acc, min_count=1):
+    """accumulators -> (mean (Ht,Wt,3) float32 = clamp(sum_wc / sum_w, 0, 1), var (Ht,Wt,3) = max(sum_wc2 / sum_w - mean^2, 0) of the
+    unclamped mean, seen (Ht,Wt) uint8 = count >= min_count and sum_w > 0); mean and var are 0 where not seen."""
+    _bake_input("texture_bake_finish", *acc.values())
+    Ht, Wt = acc["sum_w"].shape
+    dev = acc["sum_w"].device
+    mean = torch.empty(Ht, Wt, 3, dtype=torch.float32, device=dev)
+    var = torch.empty_like(mean)
+    seen = torch.empty(Ht, Wt, dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        rc = _lib.lib().harp_texture_bake_finish(_lib.ptr(acc["sum_w"]), _lib.ptr(acc["sum_wc"]), _lib.ptr(acc["sum_wc2"]), _lib.ptr(acc["count"]),
+                                                 Ht, Wt, int(min_count), _lib.ptr(mean), _lib.ptr(var), _lib.ptr(seen), _lib.stream())
+    _lib.check(rc, "harp_texture_bake_finish")
+    return mean, var, seen
+
+
+def texture_dilate(tex, valid, n_pass, allow=None, out=None):
+    """n_pass 3 x 3 Jacobi passes over tex (Ht,Wt,C <= 4) float32 and valid (Ht,Wt) (non-zero = valid): an invalid texel with a valid
+    8-neighbour becomes the float32 mean of its valid neighbours and is valid from the next pass on; allow (Ht,Wt): texels with 0 are
+    never filled and never sources.  out: None (a new tensor) or a contiguous tensor like tex, which may be tex itself.  Returns
+    (out, valid_out uint8)."""
+    _bake_input("texture_dilate", tex, valid, allow, out)
+    if tex.dim() != 3 or not 1 <= tex.shape[2] <= 4 or tex.dtype != torch.float32:
+        raise ValueError(f"texture_dilate takes a float32 (Ht,Wt,C <= 4) map, got {tex.dtype} {tuple(tex.shape)}")
+    Ht, Wt, C = tex.shape
+    if tuple(valid.shape) != (Ht, Wt) or (allow is not None and tuple(allow.shape) != (Ht, Wt)) or int(n_pass) < 0 or Ht < 1 or Wt < 1:
+        raise ValueError(f"valid / allow must be ({Ht}, {Wt}) and n_pass >= 0")
+    u8 = lambda t: None if t is None else (t != 0).to(torch.uint8).contiguous()      # noqa: E731
+    src = tex.detach() if tex.is_contiguous() else tex.detach().contiguous()
+    if out is None:
+        out = torch.empty_like(src)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (Ht, Wt, C) or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous float32 tensor ({Ht}, {Wt}, {C})")
+    v, al = u8(valid), u8(allow)
+    v_out = torch.empty(Ht, Wt, dtype=torch.uint8, device=src.device)
+    L = _lib.lib()
+    ws = torch.empty(L.harp_texture_dilate_ws_bytes(Ht, Wt, C), dtype=torch.uint8, device=src.device) if int(n_pass) > 0 else None
+    with torch.cuda.device(src.device):
+        rc = L.harp_texture_dilate(_lib.ptr(src), _lib.ptr(v), _lib.ptr(al), Ht, Wt, C, int(n_pass), _lib.ptr(out), _lib.ptr(v_out), _lib.ptr(ws),
+                                   _lib.stream())
+    _lib.check(rc, "harp_texture_dilate")
+    return out, v_out

@@ -141,7 +141,8 @@ def stage_flags(epoch_id, training_stage):
 def optimize_hand_sequence(configs, input_params, images_dataset, val_params, val_images_dataset, hand_layer,
                            VERTS_UVS=None, FACES_UVS=None, VERTS_COLOR=None, device="cuda", uv_mask=None, batch_size=18, log_fn=None,
                            seed=0, vgg=None, rank=None, world_size=None, shards=None, plateau_patience=40, plateau_threshold=1e-4, device_schedule=True,
-                           evaluate=False, panels=False, turntable=False, export_mesh=False, monitor=False, device_ingest=False):
+                           evaluate=False, panels=False, turntable=False, export_mesh=False, monitor=False, device_ingest=False, texture_init=None,
+                           coverage=False, pad_texture=0):
     """Fit the sequence (optimize_sequence.py:313-596).  Returns the parameter dict in the reference's checkpoint layout; evaluate=True
     then runs the post-fit evaluation `evaluate_sequence` (:595-816) on rank 0 (off by default), with its panels / turntable / export_mesh
     switches.  monitor: False (default: no new file, no new work), True, a dict of harp_amd.monitor.FitMonitor arguments or a FitMonitor —
@@ -151,6 +152,11 @@ def optimize_hand_sequence(configs, input_params, images_dataset, val_params, va
     device_ingest=True: the targets (the monitor's validation frames and the evaluation's included) come from the files of the dataset's
     image_paths / mask_paths through a thread pool of decoders and csrc/ingest.hip (ResidentTargets(ingest="device")) — the same bits,
     `images_dataset[i]` is never called; a dataset without paths raises ValueError.
+    texture_init (or configs["texture_init"]): None (default: nothing in this function's path changes), "bake" or a dict of
+    harp_amd.bake.bake_texture arguments — once, immediately before the first epoch whose stage has app=True, the resident frames are baked
+    into UV space under the engine's current parameters (csrc/bake.hip) and the result is copied into the texture in stream order; every
+    rank bakes its own shard and the float64 accumulators are summed over ranks before the finish, so all ranks write the same texture.
+    Refused together with known_appearance (the texture is frozen).  coverage / pad_texture: passed on to evaluate_sequence.
 
     Data-parallel (the reference is single-device): launched under `torch.distributed.run` (or with rank / world_size given)
     every rank calls this function with the SAME arguments.  The dataset's items are cut into `shards` (default: world) contiguous
@@ -165,6 +171,12 @@ def optimize_hand_sequence(configs, input_params, images_dataset, val_params, va
     from . import dist as hdist
     if configs["model_type"] != "harp":
         raise NotImplementedError("only model_type 'harp' (SURVEY.md §8: 'html' / 'nimble' are out of scope)")
+    texture_init = configs.get("texture_init") if texture_init is None else texture_init
+    if texture_init is not None:
+        if not (texture_init == "bake" or isinstance(texture_init, dict)):
+            raise ValueError(f'texture_init is None, "bake" or a dict of harp_amd.bake.bake_texture arguments, got {texture_init!r}')
+        if configs["known_appearance"]:
+            raise ValueError("texture_init with known_appearance: the texture is frozen (optimize_sequence.py:264-289), there is nothing to initialise")
     env_rank, env_world = hdist.dist_env()
     rank = env_rank if rank is None else int(rank)
     world = env_world if world_size is None else int(world_size)
@@ -252,8 +264,13 @@ def optimize_hand_sequence(configs, input_params, images_dataset, val_params, va
         if sch is not None:
             eng.set_schedule(sch[0], tschedule=sch[1])
         eng.loss_total.zero_()            # the engine adds every step's sum_loss (:553-559) to it on the device: no per-step host arithmetic, no sync
+        baked = texture_init is None
         for epoch_id in range(configs["total_epoch"]):
             coarse, app = stage_flags(epoch_id, configs["training_stage"])
+            if app and not baked:                                                      # once, in front of the first appearance epoch
+                baked = True
+                with step_guard:
+                    bake_into_engine(eng, configs, input_params, rt, hand_layer, VERTS_UVS, FACES_UVS, uv_mask, texture_init, world)
             if mon is not None and due(epoch_id, mon.train_every):                     # :490: the forward pass of the epoch's first batch, before its step
                 mon.train_sheets(epoch_id, rt.fid[items[0]], items[0])
             for item in items:
@@ -302,8 +319,32 @@ def optimize_hand_sequence(configs, input_params, images_dataset, val_params, va
                 comm.destroy()                                       # drops the step graphs that captured it
     if evaluate and rank == 0:
         evaluate_sequence(configs, params, images_dataset, hand_layer, device=device, uv_mask=uv_mask, panels=panels, turntable=turntable,
-                          export_mesh=export_mesh, device_ingest=device_ingest)
+                          export_mesh=export_mesh, device_ingest=device_ingest, coverage=coverage, pad_texture=pad_texture)
     return params
+
+
+def bake_into_engine(eng, configs, input_params, rt, hand_layer, VERTS_UVS, FACES_UVS, uv_mask, texture_init="bake", world=1):
+    """texture_init of optimize_hand_sequence: harp_amd.bake.bake_texture on the engine's current parameters and resident targets (`rt`:
+    their fids), the accumulators summed over ranks, the result copied into eng.params["texture"] on the current stream.  The engine keeps
+    one derived copy of the texture, the interleaved albedo + normal-map array `texnm` of the shaders: every appearance step repacks it from
+    the parameter before it shades (FitEngine._param_terms), and no other step reads it, so nothing is refreshed here.  The step graphs read
+    the parameter arena in place.  Returns bake_texture's dict."""
+    from types import SimpleNamespace
+    from . import bake as hbake
+    kw = dict(texture_init) if isinstance(texture_init, dict) else {}
+    fin = {k: kw.pop(k) for k in ("min_count", "fill_passes") if k in kw}
+    kw.pop("device", None)
+    for buf in (eng.m_buf, eng.v_buf):                               # Adam has not seen the texture yet: nothing to reset
+        assert not bool(eng.arena.view(buf, "texture").any()), "texture_init: the texture's Adam moments are not zero"
+    params = export_params(eng, input_params, VERTS_UVS, FACES_UVS, uv_mask, hand_layer)
+    targets = SimpleNamespace(fid=rt.fid, y_true=eng.y_true, y_sil_col=eng.y_sil_col)
+    acc, maps = hbake.bake_accumulate(configs, params, targets, hand_layer, device=eng.dev, **kw)
+    if world > 1:
+        hbake.allreduce_accumulators(acc)
+    out = hbake.bake_finish(acc, maps, params, device=eng.dev, **fin)
+    with torch.no_grad():
+        eng.params["texture"].copy_(out["texture"].reshape(eng.params["texture"].shape))
+    return out
 
 
 def mirror_render(configs, P, fid, hand_layer, sub, device="cuda"):
@@ -350,7 +391,7 @@ EVAL_CHUNK = 64                  # optimize_sequence.py:716: image_eval runs on 
 
 
 def evaluate_sequence(configs, params, images_dataset, hand_layer, device="cuda", batch_size=32, uv_mask=None, lpips_fn=None, panels=False,
-                      turntable=False, panel_hook=None, export_mesh=False, pose_eval=None, device_ingest=False):
+                      turntable=False, panel_hook=None, export_mesh=False, pose_eval=None, device_ingest=False, coverage=False, pad_texture=0):
     """The post-fit evaluation of optimize_sequence.py:595-816: re-render every dataset item in order with the fitted `params` through the
     reference-API mirror (silhouette: get_renderers(silh_sigma=1e-7, silh_faces_per_pixel=50)[1]; image: render_image_with_RT through
     get_shadow_renderers with self_shadow, else render_image with the phong renderer), `batch_size` frames per render call; per-frame
@@ -380,7 +421,13 @@ def evaluate_sequence(configs, params, images_dataset, hand_layer, device="cuda"
     and eval_joint_mm[_test].txt / eval_vert_mm[_test].txt with the per-frame means.  Frames with fewer than 3 valid joints are left out
     of the joint lines.  With None everything is as before: the per-frame host loop of :760-774 included.
     device_ingest=True: per batch the ground truth comes from utils.data_util.decode_u8 and ops.targets_from_u8(eroded=False) instead of
-    `images_dataset[i]` — the same bits, each file decoded once and no erosion computed; needs a dataset with paths (ValueError otherwise)."""
+    `images_dataset[i]` — the same bits, each file decoded once and no erosion computed; needs a dataset with paths (ValueError otherwise).
+    coverage=True: one harp_amd.bake.bake_texture pass over the dataset with the fitted parameters and delight=True (csrc/bake.hip) — writes
+    uv_out/coverage.png (8-bit, min(count, 255): in how many frames a texel was observed), uv_out/baked_texture.png (the projective albedo,
+    filled inside the charts) and uv_out/texture_std.png (the weighted standard deviation of the observed colours), and adds the line
+    ` Texel coverage: %.5f` (the share of uv_mask & covered texels seen at least once) as the last one.  pad_texture=k (export_mesh): the
+    exported PNG is dilated by k 3 x 3 passes from uv_mask > 0.5 into the rest (harp_amd.bake.pad_texture), which removes the dark band a
+    viewer's bilinear lookup pulls across the chart borders; 0 (default): today's bytes.  uv_out/texture.png stays the reference's."""
     import os
     import warnings
     import torch.nn.functional as F
@@ -522,7 +569,8 @@ def evaluate_sequence(configs, params, images_dataset, hand_layer, device="cuda"
                 verts_uvs = meshes.textures.verts_uvs_padded()[0].detach().cpu()
                 faces_uvs = meshes.textures.faces_uvs_padded()[0].detach().cpu()
                 if png is None:                       # prepare_mesh repeats ONE texture over every frame of every batch: encoded once
-                    png = encode_png(meshes.textures.maps_padded()[0].detach().cpu().clamp(0, 1))
+                    from .bake import pad_texture as pad_map
+                    png = encode_png(pad_map(meshes.textures.maps_padded()[0].detach(), uvm, pad_texture).cpu().clamp(0, 1))
                 for b in range(B):
                     save_obj(os.path.join(mesh_dir, "%04d.obj" % int(fid[b])), verts=smoothed[b], faces=faces_cpu, verts_uvs=verts_uvs,
                              faces_uvs=faces_uvs, texture_png=png)
@@ -551,6 +599,15 @@ def evaluate_sequence(configs, params, images_dataset, hand_layer, device="cuda"
             f = torch.cat(f_scores).mean(0)
             stats["Vertex AUC 0-50 mm"] = float(vert_pck.get_measures(0.0, 50.0, 100)[2])
             stats["F@5mm"], stats["F@15mm"] = float(f[0]), float(f[1])
+    if coverage:                                      # which texels did the video ever see (csrc/bake.hip)
+        from .bake import bake_texture
+        baked = bake_texture(configs, dict(P, uv_mask=torch.as_tensor(uvm)), images_dataset, hand_layer, delight=True, device=device,
+                             device_ingest=device_ingest)
+        u8 = lambda t: t.detach().float().clamp(0, 1).mul(255).to(torch.uint8).cpu().numpy()      # noqa: E731
+        Image.fromarray(baked["count"].clamp(max=255).to(torch.uint8).cpu().numpy()).save(os.path.join(uv_out_dir, "coverage.png"))
+        Image.fromarray(u8(baked["texture"][0])).save(os.path.join(uv_out_dir, "baked_texture.png"))
+        Image.fromarray(u8(baked["variance"].sqrt())).save(os.path.join(uv_out_dir, "texture_std.png"))
+        stats["Texel coverage"] = baked["coverage"]
     print("  -- Evaluation --")
     for k, v in stats.items():
         print(" %s: %.5f" % (k, v))
@@ -592,6 +649,12 @@ def main(argv=None):
     ap.add_argument("--device-ingest", action="store_true",
                     help="decode the frames once on a thread pool and convert / erode them on the device (csrc/ingest.hip): the same "
                          "targets, for the fit, the monitor's validation frames and --eval")
+    ap.add_argument("--bake-texture", action="store_true",
+                    help="before the first appearance epoch, initialise the texture by baking the frames into UV space (csrc/bake.hip; "
+                         "configs['texture_init'] = 'bake')")
+    ap.add_argument("--coverage", action="store_true", help="with --eval: uv_out/coverage.png, baked_texture.png, texture_std.png and the "
+                    "`Texel coverage` line (which texels the video ever saw)")
+    ap.add_argument("--pad-texture", type=int, default=0, metavar="K", help="with --export-mesh: dilate the exported texture K texels beyond uv_mask")
     ap.add_argument("--pose-eval", default=None, metavar="PATH",
                     help="with --eval: an .npz with any of gt_joints (T,21,3) mm, gt_joint_valid (T,21), gt_verts (T,778,3) m; adds the "
                          "Procrustes-aligned joint / vertex errors, their AUC and the F-scores (configs['pose_eval'])")
@@ -625,7 +688,8 @@ def main(argv=None):
     params = optimize_hand_sequence(configs, mano_params, images_dataset, val_mano_params, val_images_dataset, hand_layer, VERTS_UVS, FACES_UVS,
                                     VERTS_COLOR, device=device, batch_size=args.batch_size, evaluate=args.eval, panels=args.panels,
                                     turntable=args.turntable, export_mesh=args.export_mesh, monitor=args.monitor,
-                                    device_ingest=args.device_ingest)
+                                    device_ingest=args.device_ingest, texture_init="bake" if args.bake_texture else None,
+                                    coverage=args.coverage, pad_texture=args.pad_texture)
     if world > 1:
         tdist.barrier()
         tdist.destroy_process_group()

@@ -938,6 +938,90 @@ int harp_point_set_fscore(const float* gt, const float* pred, const float* thres
 int harp_targets_from_u8(const unsigned char* rgb, const unsigned char* mask, int N, int H0, int W0, int d, float* y_true, float* y_sil,
                          float* y_sil_col, hipStream_t stream);
 
+/* ---- the frames baked into UV space: texel map, per-texel accumulation, finish, seam dilation (csrc/bake.hip) ---------------------------
+ * The reference starts every texture from one flat colour (optimize_sequence.py:234), writes the fitted one multiplied by uv_mask
+ * (:627-654) and exports it as it is (:776-791, black outside the charts); it has no map from the atlas back to the frames.  These four are
+ * that map.  Forward only.  Every call only enqueues on `stream` and is capturable: no allocation, no synchronisation.  No float atomics
+ * (the texel map uses an integer atomicMin, whose result does not depend on the order) and a fixed order in every sum: a repeated call
+ * gives the same bits.  Every index read from device memory (texel list, face, vertex, target row) is range-checked before it is used;
+ * an entry that fails the check contributes nothing.
+ *
+ * harp_uv_texel_map rasterises the UV triangles at the texel centres of an (Ht, Wt) atlas.  verts_uvs (VT,2) float32, faces_uvs (F,3) int32.
+ *   Texel (x, y) <-> u = x / (Wt - 1), v = 1 - y / (Ht - 1): where the shader's bilinear lookup puts an integer sample.  In texel
+ *   coordinates (float32) with e0 = (p1 - c) x (p2 - c), e1 = (p2 - c) x (p0 - c), e2 = (p0 - c) x (p1 - c), area = (p1 - p0) x (p2 - p0),
+ *   bi = ei / area: the centre c is inside the face when all three bi >= 0.  Several faces: the LOWEST face index owns the texel.
+ *   Zero-area (and non-finite) faces own nothing; faces partly outside [0,1]^2 are clipped to the atlas.
+ *   texel_face (Ht*Wt) int32: the owning face or -1; texel_bary (Ht*Wt,2) float32: b0, b1 (b2 = 1 - b0 - b1), 0 where no face.
+ *   One wave per face over the texels of its bounding box (no texel walks all faces).
+ *   Returns HARP_ERR_ARG without launching for NULL pointers, F < 1, VT < 1, Ht < 2, Wt < 2, Ht * Wt > 2^31 - 257.
+ *
+ * harp_texture_bake_accum adds the B frames of one call to the per-texel accumulators (harp_bake_args below).  For texel t (entry of
+ *   texel_idx, or every texel when it is NULL and n = Ht * Wt) with face f = texel_face[t] >= 0, barycentrics b and the face's vertices
+ *   i = faces[f], for frame k = 0 .. B - 1 in this order, in float64:
+ *     z = sum bi z_i;  x = sum bi x_i z_i / z, y likewise (ndc (B,V,3) = (x_ndc, y_ndc, z_view) of harp_project_fwd);
+ *     fx = (1 - x) S / 2, fy = (1 - y) S / 2;  pixel (ix, iy) = floor;  continuous pixel coordinate (fx - 0.5, fy - 0.5).
+ *   The texel is OBSERVED in frame k iff rows[k] is in [0, N), z > 0, 0 <= fx, fy < S, face_id[k][iy][ix] >= 0,
+ *     z <= zbuf[k][iy][ix] (1 + depth_tol), y_mask[rows[k]][iy][ix] >= 0.5 and, with verts / vnormals / cam_pos given,
+ *     cosv = n^ . v^ >= cos_min, n^ = the interpolated vertex normal and v^ = cam_pos[k] - (interpolated position), each divided by
+ *     max(length, 1e-6).  Weight w = max(cosv, 0)^cos_power, or 1 without normals (then cosv counts as 1).
+ *   Colour: the bilinear sample of y_true[rows[k]] at the continuous pixel coordinate clamped to [0, S - 1]; with light_pos / colors given
+ *     channel c becomes (c - colors[k][6 + c]) / max(colors[k][c] + colors[k][3 + c] max(n^ . l^, 0), shade_floor), l^ towards light_pos[k]:
+ *     the inverse of the shader's `lightc * texel + specular` (shade.hip) without shadow and normal map; the specular term is the constant
+ *     of shininess 0, and 0 in the fit's shadow renderer.
+ *   sum_w += w, sum_wc[c] += w v_c, sum_wc2[c] += w v_c^2 (float64), count += 1, best_cos = max(best_cos, cosv).  The texel's one thread
+ *   reads its accumulators, adds the frames one by one and writes them back: the result is the same bits however a sequence is cut into
+ *   calls.  texel_idx must hold every texel AT MOST ONCE (the list of a `nonzero`): two entries for one texel would be two threads
+ *   reading and writing the same accumulators without atomics.  Returns HARP_ERR_ARG without launching for a NULL struct or required pointer, n, F, V, B, S, N < 1, Ht, Wt < 2, a NULL
+ *   texel_idx with n != Ht * Wt, verts / vnormals / cam_pos or light_pos / colors given in part, light without normals, depth_tol < 0,
+ *   shade_floor <= 0, cos_power < 0, cos_min < -1 (or NaN for any of the four).
+ *
+ * harp_texture_bake_finish: seen (Ht*Wt) uint8 = count >= min_count && sum_w > 0; mean (Ht*Wt,3) float32 = clamp(sum_wc / sum_w, 0, 1),
+ *   var (NULL ok) = max(sum_wc2 / sum_w - (sum_wc / sum_w)^2, 0); 0 for both where not seen.
+ *   Returns HARP_ERR_ARG without launching for NULL sums / count / mean / seen, Ht < 1, Wt < 1.
+ *
+ * harp_texture_dilate: n_pass Jacobi passes over tex (Ht,Wt,C) float32, C = 1..4, and valid (Ht,Wt) uint8.  Per pass an invalid texel with
+ *   at least one valid 8-neighbour becomes the mean of its valid neighbours — summed in float32 in row-major window order, divided once
+ *   (correctly rounded) — and is valid from the next pass on.  Valid texels never change; out-of-atlas neighbours are ignored.  allow NULL
+ *   or (Ht,Wt) uint8: texels with allow == 0 are never filled and never serve as sources.  Texels still invalid at the end keep their
+ *   input value.  One launch per pass, ping-pong through ws = harp_texture_dilate_ws_bytes(Ht, Wt, C) bytes (256-B aligned, no initial
+ *   contents), then one copy into out (and valid_out, NULL ok: the final validity).  n_pass = 0 copies bit for bit.  out may alias tex,
+ *   valid_out may alias valid.  Returns HARP_ERR_ARG without launching for NULL tex / valid / out, Ht, Wt < 1, C outside 1..4,
+ *   n_pass < 0, NULL ws with n_pass > 0.
+ * harp_texture_dilate_ws_bytes: pure host arithmetic, 2 * (4 C Ht Wt rounded up to 256) + 2 * (Ht Wt rounded up to 256); 0 for sizes the
+ *   call refuses. */
+typedef struct {
+  const int32_t* texel_idx;   /* (n) covered texels, or NULL = all Ht * Wt */
+  const int32_t* texel_face;  /* (Ht*Wt) of harp_uv_texel_map */
+  const float* texel_bary;    /* (Ht*Wt,2) */
+  const int32_t* faces;       /* (F,3) mesh faces (vertex indices into ndc / verts / vnormals) */
+  const float* ndc;           /* (B,V,3) */
+  const int32_t* face_id;     /* (B,S,S) hard camera pass */
+  const float* zbuf;          /* (B,S,S) */
+  const float* y_true;        /* (N,S,S,3) */
+  const float* y_mask;        /* (N,S,S) */
+  const int32_t* rows;        /* (B) rows of y_true / y_mask */
+  const float* verts;         /* (B,V,3) world positions, or NULL */
+  const float* vnormals;      /* (B,V,3), or NULL */
+  const float* cam_pos;       /* (B,3) world camera centres, or NULL */
+  const float* light_pos;     /* (B,3), or NULL */
+  const float* colors;        /* (B,9) ambient | diffuse | specular, or NULL */
+  double* sum_w;              /* (Ht*Wt) (+=) */
+  double* sum_wc;             /* (Ht*Wt,3) (+=) */
+  double* sum_wc2;            /* (Ht*Wt,3) (+=) */
+  int32_t* count;             /* (Ht*Wt) (+=) */
+  float* best_cos;            /* (Ht*Wt) running maximum */
+  int n, Ht, Wt, F, V, B, S, N;
+  float depth_tol, cos_min, cos_power, shade_floor;
+} harp_bake_args;
+int harp_uv_texel_map(const float* verts_uvs, const int32_t* faces_uvs, int F, int VT, int Ht, int Wt, int32_t* texel_face, float* texel_bary,
+                      hipStream_t stream);
+int harp_texture_bake_accum(const harp_bake_args* args, hipStream_t stream);
+int harp_texture_bake_finish(const double* sum_w, const double* sum_wc, const double* sum_wc2, const int32_t* count, int Ht, int Wt, int min_count,
+                             float* mean, float* var, unsigned char* seen, hipStream_t stream);
+size_t harp_texture_dilate_ws_bytes(int Ht, int Wt, int C);
+int harp_texture_dilate(const float* tex, const unsigned char* valid, const unsigned char* allow, int Ht, int Wt, int C, int n_pass, float* out,
+                        unsigned char* valid_out, void* ws, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
