@@ -6,6 +6,7 @@ The reference has no such pass: it starts from one flat colour (optimize_sequenc
 import torch
 
 from . import ops
+from .utils.visualize import _cam_RT, get_mesh_subdivider, params_on, prepare_mesh
 
 _MAP_CACHE = {}
 
@@ -57,15 +58,13 @@ def bake_accumulate(configs, params, targets, hand_layer, *, delight=True, chunk
     """The accumulation half of bake_texture: -> (accumulators of ops.bake_accumulators, (texel_face, texel_bary, texel_idx)).  Per chunk of
     `chunk` frames: prepare_mesh (the displaced, subdivided mesh as the fit sees it), ops.project, ops.vertex_normals, one hard
     ops.rasterize_fwd(want_zbuf=True), one ops.texture_bake_accum."""
-    from .optimize_sequence import get_mesh_subdivider
-    from .utils.visualize import _cam_RT, prepare_mesh
     unknown = set(kernel_params) - set(ops.BAKE_DEFAULTS)
     if unknown:
         raise TypeError(f"bake_texture: unknown kernel parameters {sorted(unknown)} (known: {sorted(ops.BAKE_DEFAULTS)})")
     dev = torch.device(device)
     S, focal, use_arm = int(configs["img_size"]), configs["focal_length"], bool(configs["use_arm"])
     rt = _resident(targets, dev, device_ingest)
-    P = {k: (v.detach().to(dev) if torch.is_tensor(v) else v) for k, v in params.items()}
+    P = params_on(params, dev)
     y_true, y_mask = rt.y_true.to(dev), rt.y_sil_col.to(dev).reshape(rt.y_true.shape[:3])
     if tuple(y_true.shape[1:]) != (S, S, 3):
         raise ValueError(f"targets {tuple(y_true.shape)} do not fit configs['img_size'] = {S}")

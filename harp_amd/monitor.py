@@ -23,6 +23,9 @@ from types import SimpleNamespace
 
 import torch
 
+from .evaluate import mirror_render
+from .utils.visualize import get_mesh_subdivider
+
 SHEET_GRID = (3, 3)                    # show_img_pair: fig.add_subplot(3, 3, ...) (:41-43)
 FIT_KEYS = ("trans", "pose", "rot", "shape", "wrist_pose", "verts_disps", "texture", "normal_map", "light_positions", "amb_ratio", "cam")
 
@@ -195,7 +198,6 @@ class FitMonitor:
     def begin(self, configs, eng, hand_layer, verts_uvs, faces_uvs, val_params=None, val_images_dataset=None, seed=0, device_ingest=False):
         """bind to a fit: the engine's parameter views and resident targets; up to 9 validation items drawn ONCE from a generator of
         their own (seed + 1: the training shuffle's generator is not consumed) and kept resident"""
-        from .optimize_sequence import get_mesh_subdivider
         from .utils.data_util import ResidentTargets
         self.cfg, self.eng, self.layer, self.dev = configs, eng, hand_layer, eng.dev
         self.d = box_factor(configs["img_size"], self.max_side, SHEET_GRID[1])
@@ -223,7 +225,6 @@ class FitMonitor:
         self._log = open(self.base + self.prefix + "monitor_log.jsonl", "w")
 
     def _render(self, P, fid):
-        from .optimize_sequence import mirror_render
         r0, r1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         with torch.no_grad():
             r0.record()

@@ -1,5 +1,6 @@
-"""Mirror of the fitting API of the reference's optimize_sequence.py: get_mesh_subdivider (:67-89), init_params (:181-250),
-get_optimizers (:253-310) and optimize_hand_sequence (:313-816, loop body :446-582).
+"""Mirror of the fitting API of the reference's optimize_sequence.py: init_params (:181-250), get_optimizers (:253-310) and
+optimize_hand_sequence (:313-816, loop body :446-582).  What looks at a fit — mirror_render and the post-fit evaluation evaluate_sequence
+(:595-816) — lives in harp_amd/evaluate.py and get_mesh_subdivider (:67-89) in utils/visualize.py; all three are re-exported here.
 
 `optimize_hand_sequence` keeps the reference's signature and schedule (stages, batch 18, shuffle, dense Adam groups and
 learning rates, ReduceLROnPlateau(patience=40) on the coarse group, checkpoint format) but runs every step through the fused
@@ -11,17 +12,11 @@ import numpy as np
 import torch
 
 from .engine import FitEngine, LOSS_NAMES
+from .evaluate import EVAL_CHUNK, evaluate_sequence, mirror_render  # noqa: F401  (re-export: the post-fit evaluation lives in evaluate.py)
 from .synth import build_topology
 from .utils import file_utils
 from .utils.data_util import ResidentTargets
-from .utils.visualize import MeshSubdivider
-
-
-def get_mesh_subdivider(hand_layer, use_arm=False, device="cuda"):
-    """optimize_sequence.py:67-89"""
-    if use_arm:
-        return MeshSubdivider(hand_layer.right_arm_faces_tensor, 1026, device)
-    return MeshSubdivider(hand_layer.th_faces, 778, device)
+from .utils.visualize import get_mesh_subdivider, params_on  # noqa: F401  (re-export: get_mesh_subdivider, :67-89)
 
 
 def load_uv_mask(configs, uv_size):
@@ -115,7 +110,7 @@ def visualize_val(val_images_dataloader, epoch_id, device, params, val_params, c
         print("epoch: %d" % epoch_id)
         for param_group in (opt_app.param_groups if opt_app is not None else ()):
             print("learning rate", param_group["lr"])
-        P = {k: (v.detach().to(device) if torch.is_tensor(v) else v) for k, v in params.items()}
+        P = params_on(params, device)
         with torch.no_grad():
             r = mirror_render(configs, monitor.merge_val_params(P, val_params, device), torch.as_tensor(fid).long(), hand_layer, mesh_subdivider,
                               device=device)
@@ -345,276 +340,6 @@ def bake_into_engine(eng, configs, input_params, rt, hand_layer, VERTS_UVS, FACE
     with torch.no_grad():
         eng.params["texture"].copy_(out["texture"].reshape(eng.params["texture"].shape))
     return out
-
-
-def mirror_render(configs, P, fid, hand_layer, sub, device="cuda"):
-    """One forward pass of frames `fid` through the reference-API mirror, as the loop body (optimize_sequence.py:452-488), visualize_val
-    (:110-154) and the evaluation (:680-708) run it: get_renderers(silh_sigma=1e-7, silh_faces_per_pixel=50), prepare_mesh,
-    prepare_materials, the silhouette render, and the image through get_shadow_renderers + render_image_with_RT with self_shadow, else
-    render_image with the phong renderer.  P: the parameter dict on `device`.  Call under torch.no_grad().  Returns a namespace with
-    y_sil_pred (B,S,S), y_pred (B,S,S,3) float32 and the intermediates (hand_verts, hand_joints (m), faces, textures, meshes, cam, light_positions,
-    materials_properties, normal_renderer)."""
-    from types import SimpleNamespace
-    from .renderer import renderer_helper
-    from .structures import Meshes
-    from .utils.visualize import prepare_materials, prepare_mesh, render_image, render_image_with_RT
-    S, focal = int(configs["img_size"]), configs["focal_length"]
-    use_arm = bool(configs["use_arm"])
-    B = fid.shape[0]
-    fd = fid.to(device)
-    if configs["share_light_position"]:
-        light_positions = P["light_positions"][0].repeat(B, 1)
-    else:
-        light_positions = P["light_positions"][fd]
-    phong_renderer, silhouette_renderer, normal_renderer = renderer_helper.get_renderers(
-        image_size=S, light_posi=light_positions, silh_sigma=1e-7, silh_gamma=1e-1, silh_faces_per_pixel=50, device=device)
-    hand_joints, hand_verts, faces, textures = prepare_mesh(P, fid, hand_layer, False, sub, False, configs, device=device, use_arm=use_arm)
-    materials_properties = prepare_materials(P, B, device=device)
-    meshes = Meshes(hand_verts, faces, textures)
-    cam = P["cam"][fd]
-    y_sil_pred = render_image(meshes, cam, B, silhouette_renderer, S, focal, silhouette=True, device=device)
-    if configs["self_shadow"]:
-        light_R, light_T, cam_R, cam_T = renderer_helper.process_info_for_shadow(cam, light_positions, hand_verts.mean(1), image_size=S,
-                                                                                 focal_length=focal, device=device)
-        shadow_renderer = renderer_helper.get_shadow_renderers(image_size=S, light_posi=light_positions, silh_sigma=1e-7, silh_gamma=1e-1,
-                                                               silh_faces_per_pixel=50, amb_ratio=torch.sigmoid(P["amb_ratio"]), device=device)
-        y_pred = render_image_with_RT(meshes, light_T, light_R, cam_T, cam_R, B, shadow_renderer, S, focal, silhouette=False,
-                                      materials_properties=materials_properties, device=device)
-    else:
-        y_pred = render_image(meshes, cam, B, phong_renderer, S, focal, silhouette=False, materials_properties=materials_properties,
-                              device=device)
-    return SimpleNamespace(y_sil_pred=y_sil_pred, y_pred=y_pred.float(), hand_verts=hand_verts, hand_joints=hand_joints, faces=faces, textures=textures, meshes=meshes,
-                           cam=cam, light_positions=light_positions, materials_properties=materials_properties, normal_renderer=normal_renderer)
-
-
-EVAL_CHUNK = 64                  # optimize_sequence.py:716: image_eval runs on every 64 frames; the final stats are means of the chunk means
-
-
-def evaluate_sequence(configs, params, images_dataset, hand_layer, device="cuda", batch_size=32, uv_mask=None, lpips_fn=None, panels=False,
-                      turntable=False, panel_hook=None, export_mesh=False, pose_eval=None, device_ingest=False, coverage=False, pad_texture=0):
-    """The post-fit evaluation of optimize_sequence.py:595-816: re-render every dataset item in order with the fitted `params` through the
-    reference-API mirror (silhouette: get_renderers(silh_sigma=1e-7, silh_faces_per_pixel=50)[1]; image: render_image_with_RT through
-    get_shadow_renderers with self_shadow, else render_image with the phong renderer), `batch_size` frames per render call; per-frame
-    Silhouette IoU, L1 and MS-SSIM from ops.image_metrics (csrc/metrics.hip); the reference's averaging — the mean over 64-frame chunks
-    (the last partial chunk included) of each chunk's mean; with configs["eval_mesh"] the Procrustes-aligned vertex error against
-    `<gt_mesh_dir>/<500 + fid + 1>_manov.xyz` (:760-774, also written to eval_vert_mm[_test].txt).  Writes eval_results[_test].txt
-    (" %s: %.5f" lines, :808-816) and uv_out/texture.png, uv_out/normal_map.png (:627-654) under configs["base_output_dir"] and returns
-    the stats dict.  LPIPS (harp_amd.lpips, csrc/lpips.hip) is added when `lpips_fn` is given or configs["lpips_weights"] names its weights
-    (a combined lpips.LPIPS state-dict path, or a (torchvision alexnet, lpips v0.1 head) path pair): per frame on the same y_true / y_pred,
-    [0, 1] images without `normalize` as the reference passes them, averaged like the others and written in the reference's key order (IoU,
-    L1, LPIPS, MS_SSIM); without either the output has no LPIPS line (the weights cannot be shipped).  Left out: MS_SSIM with a warning when
-    the image side is <= 160 px (the reference would fail pytorch_msssim's assertion there).
-    What the reference writes for the eye is off by default and leaves metrics and files as they are when off.  panels=True: per batch one
-    more prepare_mesh(vis_normal=True) + normal render (:710-714), one ops.panels_u8 and one `true | pred | normal | overlay` JPEG per frame,
-    rendered_after_opt[_test]/<fid %04d>.jpg (:742-757); panel_hook(fid, strip), if given, sees every (S, 4S, 3) uint8 strip before it is
-    encoded.  turntable=True: for the dataset item whose fid is 0 (:716-727) render_360 with the phong and the normal renderer,
-    concat_image_in_dir into render_360_combine and render_360_light, each with its out.gif.  export_mesh=True (the reference's constant
-    EXPORT_MESH, :776-791): per batch one ops.taubin_smoothing(meshes) (csrc/smooth.hip) and one device -> host copy, then per frame
-    mesh/<fid %04d>.obj, .mtl and .png through harp_amd.io.save_obj with the reference's arguments — smoothed vertices, the faces of the
-    unsmoothed mesh, the textures' verts_uvs / faces_uvs and maps_padded()[0].clamp(0, 1), whose PNG is encoded once (the texture is shared).
-    pose_eval (or configs["pose_eval"]): None, the path of an .npz or a dict with any of gt_joints (T,21,3) mm, gt_joint_valid (T,21) and
-    gt_verts (T,778,3) m, rows indexed by fid.  Given, the geometric accuracy runs on the device (csrc/pose_eval.hip), per batch one
-    ops.procrustes_align of the first 21 joints (mm, both sets root-aligned, only the valid joints), one of the vertices (gathered by
-    right_mano_idx on the arm, else the first 778; with configs["eval_mesh"] and no gt_verts they still come from load_gt_vert) and one
-    ops.point_set_fscore of the aligned vertices; after the lines above, whichever the ground truth allows of `Procrustes-aligned joint
-    error (mm)`, `Joint AUC 0-50 mm` (100 thresholds), `Procrustes-aligned vertex error (mm)`, `Vertex AUC 0-50 mm`, `F@5mm`, `F@15mm`,
-    and eval_joint_mm[_test].txt / eval_vert_mm[_test].txt with the per-frame means.  Frames with fewer than 3 valid joints are left out
-    of the joint lines.  With None everything is as before: the per-frame host loop of :760-774 included.
-    device_ingest=True: per batch the ground truth comes from utils.data_util.decode_u8 and ops.targets_from_u8(eroded=False) instead of
-    `images_dataset[i]` — the same bits, each file decoded once and no erosion computed; needs a dataset with paths (ValueError otherwise).
-    coverage=True: one harp_amd.bake.bake_texture pass over the dataset with the fitted parameters and delight=True (csrc/bake.hip) — writes
-    uv_out/coverage.png (8-bit, min(count, 255): in how many frames a texel was observed), uv_out/baked_texture.png (the projective albedo,
-    filled inside the charts) and uv_out/texture_std.png (the weighted standard deviation of the observed colours), and adds the line
-    ` Texel coverage: %.5f` (the share of uv_mask & covered texels seen at least once) as the last one.  pad_texture=k (export_mesh): the
-    exported PNG is dilated by k 3 x 3 passes from uv_mask > 0.5 into the rest (harp_amd.bake.pad_texture), which removes the dark band a
-    viewer's bilinear lookup pulls across the chart borders; 0 (default): today's bytes.  uv_out/texture.png stays the reference's."""
-    import os
-    import warnings
-    import torch.nn.functional as F
-    from PIL import Image
-    from . import ops
-    from .io import encode_png, save_obj
-    from .renderer import renderer_helper
-    from .structures import Meshes
-    from .utils.data_util import _ingest_paths, decode_u8
-    from .utils.eval_util import EvalUtil, align_w_scale, load_gt_vert, sil_iou
-    from .utils.visualize import concat_image_in_dir, prepare_mesh, render_360, render_360_light, render_image
-    S, focal = int(configs["img_size"]), configs["focal_length"]
-    base = configs["base_output_dir"]
-    test_name = "_test" if configs["known_appearance"] else ""
-    use_arm = bool(configs["use_arm"])
-    P = {k: (v.detach().to(device) if torch.is_tensor(v) else v) for k, v in params.items()}
-    # ---- texture and normal map (:627-654)
-    uv_out_dir = os.path.join(base, "uv_out")
-    os.makedirs(uv_out_dir, exist_ok=True)
-    uvm = params.get("uv_mask") if uv_mask is None else uv_mask
-    tex = P["texture"].cpu().numpy()[0]
-    uvm = np.ones(tex.shape[:2]) if uvm is None else np.asarray(torch.as_tensor(uvm).detach().cpu(), dtype=np.float64)
-    Image.fromarray(np.uint8(tex.clip(0, 1) * np.expand_dims(uvm, 2) * 255)).save(os.path.join(uv_out_dir, "texture.png"))
-    if "normal_map" in P:
-        nm = F.normalize(P["normal_map"], dim=-1).cpu().numpy()
-        nm = (nm / 2.0 + 0.5) * np.expand_dims(uvm, 2)
-        Image.fromarray(np.uint8(nm[0].clip(0, 1) * 255)).save(os.path.join(uv_out_dir, "normal_map.png"))
-    # ---- renders and per-frame metrics
-    sub = get_mesh_subdivider(hand_layer, use_arm=use_arm, device=device)
-    with_ms = S > ops.MS_SSIM_MIN_SIDE
-    if not with_ms:
-        warnings.warn(f"MS_SSIM left out of the evaluation: {S} px images (pytorch_msssim needs a side > {ops.MS_SSIM_MIN_SIDE})")
-    if lpips_fn is None and configs.get("lpips_weights"):
-        from .lpips import LPIPS
-        lw = configs["lpips_weights"]
-        lpips_fn = LPIPS(weights=tuple(lw) if isinstance(lw, (list, tuple)) else lw).to(device)
-    with_lpips = lpips_fn is not None and S >= ops.LPIPS_MIN_SIDE
-    if lpips_fn is not None and not with_lpips:
-        warnings.warn(f"LPIPS left out of the evaluation: {S} px images (AlexNet needs a side >= {ops.LPIPS_MIN_SIDE})")
-    iou, l1, ms, lp, vert_err = [], [], [], [], []
-    pe = pose_eval if pose_eval is not None else configs.get("pose_eval")
-    if isinstance(pe, (str, os.PathLike)):
-        with np.load(pe) as z:
-            pe = {k: z[k] for k in z.files}
-    if pe is not None:
-        pe = {k: torch.as_tensor(np.asarray(v)) for k, v in pe.items() if k in ("gt_joints", "gt_joint_valid", "gt_verts")}
-        with_joints = "gt_joints" in pe
-        with_verts = "gt_verts" in pe or bool(configs["eval_mesh"])
-        joint_err, f_scores = [], []
-        joint_pck, vert_pck = EvalUtil(21), EvalUtil(778)
-        vert_idx = (torch.as_tensor(np.asarray(hand_layer.right_mano_idx)) if use_arm else torch.arange(778)).to(device=device, dtype=torch.int32)
-        f_thr = torch.tensor([0.005, 0.015], dtype=torch.float32, device=device)        # metres
-    panel_dir = os.path.join(base, "rendered_after_opt" + test_name)
-    if panels:
-        os.makedirs(panel_dir, exist_ok=True)                      # :660
-    mesh_dir, png = os.path.join(base, "mesh"), None
-    if export_mesh:
-        os.makedirs(mesh_dir, exist_ok=True)                       # :783
-    n = len(images_dataset)
-    if device_ingest:
-        ingest_d = _ingest_paths(images_dataset)[2]                # ValueError for a dataset without paths, before anything is rendered
-    with torch.no_grad():
-        for lo in range(0, n, batch_size):
-            if device_ingest:
-                fid = torch.arange(lo, min(n, lo + batch_size), dtype=torch.long)       # ImagesDataset: the item's index is its fid
-                rgb_u8, mask_u8 = (torch.from_numpy(a).to(device) for a in decode_u8(images_dataset, fid.tolist()))
-                y_true, y_sil_true, _ = ops.targets_from_u8(rgb_u8, mask_u8, d=ingest_d, eroded=False)
-            else:
-                items = [images_dataset[i] for i in range(lo, min(n, lo + batch_size))]
-                fid = torch.as_tensor([int(it[0]) for it in items], dtype=torch.long)
-                y_true = torch.stack([torch.as_tensor(it[1]) for it in items]).to(device=device, dtype=torch.float32)
-                y_sil_true = torch.stack([torch.as_tensor(it[2]) for it in items]).reshape(len(items), S, S).to(device=device, dtype=torch.float32)
-            B = fid.shape[0]
-            r = mirror_render(configs, P, fid, hand_layer, sub, device=device)
-            hand_verts, faces, textures, meshes, cam = r.hand_verts, r.faces, r.textures, r.meshes, r.cam
-            light_positions, materials_properties, normal_renderer = r.light_positions, r.materials_properties, r.normal_renderer
-            y_sil_pred, y_pred = r.y_sil_pred, r.y_pred
-            if panels:                                # :710-714, :742-757
-                _, verts_n, faces_n, textures_n = prepare_mesh(P, fid, hand_layer, False, sub, False, configs, device=device, vis_normal=True,
-                                                               use_arm=use_arm)
-                y_pred_normal = render_image(Meshes(verts_n, faces_n, textures_n), cam, B, normal_renderer, S, focal, silhouette=False,
-                                             materials_properties=materials_properties, device=device)
-                strips = ops.panels_u8([y_true, y_pred, y_pred_normal], y_sil_true, y_sil_pred).cpu().numpy()
-                for b in range(B):
-                    if panel_hook is not None:
-                        panel_hook(int(fid[b]), strips[b])
-                    Image.fromarray(strips[b]).save(os.path.join(panel_dir, "%04d.jpg" % int(fid[b])))
-            if turntable and bool((fid == 0).any()):   # :716-727: one frame turned through 360 degrees and lit from 40 positions
-                i0 = int((fid == 0).nonzero()[0])
-                f0 = fid[i0:i0 + 1]
-                phong0, _, normal0 = renderer_helper.get_renderers(image_size=S, light_posi=light_positions[i0:i0 + 1], silh_sigma=1e-7,
-                                                                   silh_gamma=1e-1, silh_faces_per_pixel=50, device=device)
-                kw360 = dict(configs=configs, use_arm=use_arm, verts_textures=False, mesh_subdivider=sub, global_pose=False, save_img_dir=base,
-                             device=device)
-                render_360(P, f0, phong0, S, focal, hand_layer, **kw360)
-                render_360(P, f0, normal0, S, focal, hand_layer, render_normal=True, **kw360)
-                concat_image_in_dir(os.path.join(base, "render_360"), os.path.join(base, "render_360_normal"), os.path.join(base, "render_360_combine"))
-                render_360_light(P, f0, hand_verts[i0:i0 + 1], faces, textures, S, focal, save_img_dir=base, device=device)
-            if with_ms:
-                m = ops.image_metrics(y_true, y_pred, y_sil_true, y_sil_pred)
-                iou.append(m["iou"].cpu())
-                l1.append(m["l1_sum"].double().cpu())
-                ms.append(m["ms_ssim"].double().cpu())
-            else:                                     # no MS-SSIM at this size, so no metrics kernel: sil_iou / l1_diff per frame
-                iou.append(torch.stack([torch.as_tensor(sil_iou(y_sil_true[b:b + 1], y_sil_pred[b:b + 1])) for b in range(B)]).cpu())
-                l1.append((y_true - y_pred).abs().double().sum((1, 2, 3)).cpu())
-            if with_lpips:                            # :51-53 of utils/eval_util.py, per frame
-                lp.append(lpips_fn(y_true.permute(0, 3, 1, 2), y_pred.permute(0, 3, 1, 2)).reshape(B).double().cpu())
-            if pe is not None:                        # the device path of :760-774 and of utils/eval_util.py:166-209
-                if with_joints:
-                    gt_j = pe["gt_joints"][fid].to(device=device, dtype=torch.float32)
-                    gt_j = gt_j - gt_j[:, :1]
-                    pred_j = r.hand_joints[:, :21].float() * 1000.0
-                    pred_j = pred_j - pred_j[:, :1]
-                    vis = (pe["gt_joint_valid"][fid] == 1).to(device) if "gt_joint_valid" in pe else torch.ones(B, 21, dtype=torch.bool, device=device)
-                    al_j, err_j, nv = ops.procrustes_align(gt_j, pred_j, valid=vis.float())
-                    ok = nv >= 3
-                    joint_err.append((torch.nan_to_num(err_j.double()).sum(1) / nv.clamp(min=1))[ok].cpu())
-                    joint_pck.feed_batch(gt_j, vis & ok[:, None], al_j)
-                if with_verts:
-                    if "gt_verts" in pe:
-                        gt_v = pe["gt_verts"][fid].to(device=device, dtype=torch.float32)
-                    else:
-                        gt_v = torch.as_tensor(np.stack([load_gt_vert(fid[b:b + 1], configs["gt_mesh_dir"], dataset="synthetic", start_from_one=True,
-                                                                      idx_offset=500) for b in range(B)]), dtype=torch.float32).to(device)
-                    al_v, err_v, _ = ops.procrustes_align(gt_v, hand_verts, pred_idx=vert_idx)
-                    vert_err.extend((err_v.double().mean(1) * 1000.0).cpu().tolist())
-                    vert_pck.feed_batch(gt_v * 1000.0, torch.ones(B, 778, device=device), al_v * 1000.0)
-                    f_scores.append(ops.point_set_fscore(gt_v, al_v, f_thr)[0][:, :, 2].double().cpu())
-            elif configs["eval_mesh"]:               # :760-774
-                for b in range(B):
-                    gt = load_gt_vert(fid[b:b + 1], configs["gt_mesh_dir"], dataset="synthetic", start_from_one=True, idx_offset=500)
-                    pred = hand_verts[b, hand_layer.right_mano_idx] if use_arm else hand_verts[b, :778]
-                    err = gt - align_w_scale(gt, pred.detach().cpu().numpy())
-                    vert_err.append(float(np.linalg.norm(err, axis=1).mean()) * 1000.0)
-            if export_mesh:                           # :776-791
-                smoothed = ops.taubin_smoothing(meshes).verts_padded().cpu()
-                faces_cpu = meshes.faces_padded()[0].cpu()
-                verts_uvs = meshes.textures.verts_uvs_padded()[0].detach().cpu()
-                faces_uvs = meshes.textures.faces_uvs_padded()[0].detach().cpu()
-                if png is None:                       # prepare_mesh repeats ONE texture over every frame of every batch: encoded once
-                    from .bake import pad_texture as pad_map
-                    png = encode_png(pad_map(meshes.textures.maps_padded()[0].detach(), uvm, pad_texture).cpu().clamp(0, 1))
-                for b in range(B):
-                    save_obj(os.path.join(mesh_dir, "%04d.obj" % int(fid[b])), verts=smoothed[b], faces=faces_cpu, verts_uvs=verts_uvs,
-                             faces_uvs=faces_uvs, texture_png=png)
-    # ---- the reference's averaging: image_eval per 64-frame chunk (:713-731), then np.mean over the chunks (:733-738)
-    iou, l1 = torch.cat(iou).double(), torch.cat(l1)
-    chunks = [slice(c, min(n, c + EVAL_CHUNK)) for c in range(0, n, EVAL_CHUNK)]
-    per_pixel = float(S * S * 3)
-    stats = {"Silhouette IoU": float(np.mean([iou[c].mean().item() for c in chunks])),
-             "L1": float(np.mean([l1[c].sum().item() / ((c.stop - c.start) * per_pixel) for c in chunks]))}
-    if with_lpips:
-        lp = torch.cat(lp)
-        stats["LPIPS"] = float(np.mean([lp[c].mean().item() for c in chunks]))
-    if with_ms:
-        ms = torch.cat(ms)
-        stats["MS_SSIM"] = float(np.mean([ms[c].mean().item() for c in chunks]))
-    if pe is not None and with_joints:
-        joint_err = torch.cat(joint_err).tolist()
-        if joint_err:
-            stats["Procrustes-aligned joint error (mm)"] = float(np.mean(joint_err))
-            stats["Joint AUC 0-50 mm"] = float(joint_pck.get_measures(0.0, 50.0, 100)[2])
-            np.savetxt(os.path.join(base, "eval_joint_mm" + test_name + ".txt"), joint_err)
-    if vert_err:
-        stats["Procrustes-aligned vertex error (mm)"] = float(np.mean(vert_err))
-        np.savetxt(os.path.join(base, "eval_vert_mm" + test_name + ".txt"), vert_err)
-        if pe is not None:
-            f = torch.cat(f_scores).mean(0)
-            stats["Vertex AUC 0-50 mm"] = float(vert_pck.get_measures(0.0, 50.0, 100)[2])
-            stats["F@5mm"], stats["F@15mm"] = float(f[0]), float(f[1])
-    if coverage:                                      # which texels did the video ever see (csrc/bake.hip)
-        from .bake import bake_texture
-        baked = bake_texture(configs, dict(P, uv_mask=torch.as_tensor(uvm)), images_dataset, hand_layer, delight=True, device=device,
-                             device_ingest=device_ingest)
-        u8 = lambda t: t.detach().float().clamp(0, 1).mul(255).to(torch.uint8).cpu().numpy()      # noqa: E731
-        Image.fromarray(baked["count"].clamp(max=255).to(torch.uint8).cpu().numpy()).save(os.path.join(uv_out_dir, "coverage.png"))
-        Image.fromarray(u8(baked["texture"][0])).save(os.path.join(uv_out_dir, "baked_texture.png"))
-        Image.fromarray(u8(baked["variance"].sqrt())).save(os.path.join(uv_out_dir, "texture_std.png"))
-        stats["Texel coverage"] = baked["coverage"]
-    print("  -- Evaluation --")
-    for k, v in stats.items():
-        print(" %s: %.5f" % (k, v))
-    with open(os.path.join(base, "eval_results" + test_name + ".txt"), "w") as f_out:
-        for k, v in stats.items():
-            f_out.write(" %s: %.5f\n" % (k, v))
-    return stats
 
 
 def lpips_weights_arg(paths):

@@ -32,6 +32,18 @@ class MeshSubdivider:
         raise TypeError("call prepare_mesh(..., mesh_subdivider=this) — subdivision is fused into the mesh-prep kernels")
 
 
+def get_mesh_subdivider(hand_layer, use_arm=False, device="cuda"):
+    """optimize_sequence.py:67-89"""
+    if use_arm:
+        return MeshSubdivider(hand_layer.right_arm_faces_tensor, 1026, device)
+    return MeshSubdivider(hand_layer.th_faces, 778, device)
+
+
+def params_on(params, device):
+    """the parameter dict with every tensor detached and on `device` (the rest as it is): what prepare_mesh and the renders read under no_grad"""
+    return {k: (v.detach().to(device) if torch.is_tensor(v) else v) for k, v in params.items()}
+
+
 _RAW_TOPO = {}
 
 

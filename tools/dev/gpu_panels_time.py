@@ -31,10 +31,10 @@ def wall(f, reps=3):
 
 def main():
     from PIL import Image
-    from harp_amd.optimize_sequence import evaluate_sequence, get_mesh_subdivider
+    from harp_amd.evaluate import evaluate_sequence
     from harp_amd.renderer import renderer_helper
     from harp_amd.structures import Meshes
-    from harp_amd.utils.visualize import prepare_materials, prepare_mesh, render_image
+    from harp_amd.utils.visualize import get_mesh_subdivider, prepare_materials, prepare_mesh, render_image
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=64)
     ap.add_argument("--size", type=int, default=512)
