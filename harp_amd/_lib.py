@@ -321,3 +321,9 @@ SIGNATURES.update({
     "harp_texture_dilate_ws_bytes": (_sz, [_i, _i, _i]),
     "harp_texture_dilate": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
 })
+
+# playback of a fitted avatar (csrc/playback.hip)
+SIGNATURES.update({
+    "harp_motion_resample": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
+    "harp_resolve_u8": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _vp]),
+})

@@ -1056,3 +1056,93 @@ def texture_dilate(tex, valid, n_pass, allow=None, out=None):
                                    _lib.stream())
     _lib.check(rc, "harp_texture_dilate")
     return out, v_out
+
+
+# ------------------------------------------------------------------------------------------------------
+# playback of a fitted avatar (csrc/playback.hip): motion resampling, supersampled float render -> uint8 frames
+# ------------------------------------------------------------------------------------------------------
+RESOLVE_MAX_SS = 4
+
+
+def _playback_input(name, *ts):
+    first = None
+    for t in ts:
+        if t is None:
+            continue
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise RuntimeError("harp_amd ops need HIP device tensors (no CPU path)")
+        if first is not None and t.device != first.device:
+            raise ValueError(f"{name}: tensors on {first.device} and {t.device}")
+        first = t if first is None else first
+    check_forward_only(*[t for t in ts if t is not None and t.is_floating_point()])
+
+
+def motion_resample(keys, times, n_rot, rot_offset=None):
+    """Key-frame rows at fractional times (csrc/playback.hip: harp_motion_resample), forward only: keys (Tk, 3 n_rot + n_lin) float32 =
+    n_rot axis-angle triples then n_lin linear channels, times (Tn,) float32 in key-frame units (clamped to [0, Tk - 1]) ->
+    (Tn, 3 n_rot + n_lin).  The triples are interpolated as rotations (shortest-arc slerp) after rot_offset (3 n_rot,) — the model's pose
+    mean — has been added; a time on a key returns that row bit for bit."""
+    _playback_input("motion_resample", keys, times, rot_offset)
+    n_rot = int(n_rot)
+    if keys.dtype != torch.float32 or times.dtype != torch.float32 or (rot_offset is not None and rot_offset.dtype != torch.float32):
+        raise TypeError("motion_resample takes float32 tensors")
+    if keys.dim() != 2 or times.dim() != 1 or n_rot < 0 or keys.shape[1] < 3 * n_rot or keys.shape[1] == 0:
+        raise ValueError(f"motion_resample takes keys (Tk, 3 n_rot + n_lin) and times (Tn,), got {tuple(keys.shape)}, {tuple(times.shape)}, n_rot = {n_rot}")
+    Tk, W = keys.shape
+    Tn, n_lin = times.shape[0], W - 3 * n_rot
+    if Tk < 1 or Tn < 1:
+        raise ValueError(f"at least one key and one time, got {Tk} and {Tn}")
+    if rot_offset is not None and tuple(rot_offset.shape) != (3 * n_rot,):
+        raise ValueError(f"rot_offset must be ({3 * n_rot},), got {tuple(rot_offset.shape)}")
+    keys, times = keys.detach().contiguous(), times.detach().contiguous()
+    off = None if rot_offset is None or n_rot == 0 else rot_offset.detach().contiguous()
+    out = torch.empty(Tn, W, dtype=torch.float32, device=keys.device)
+    with torch.cuda.device(keys.device):
+        rc = _lib.lib().harp_motion_resample(_lib.ptr(keys), Tk, n_rot, n_lin, _lib.ptr(off), _lib.ptr(times), Tn, _lib.ptr(out), _lib.stream())
+    _lib.check(rc, "harp_motion_resample")
+    return out
+
+
+def resolve_u8(rgb, face_id, ss=1, background=None, bg_rows=None, bg_color=(1, 1, 1), alpha=False, out=None):
+    """A supersampled render over a background as finished 8-bit frames (csrc/playback.hip: harp_resolve_u8), forward only: rgb
+    (B, S ss, S ss, 3) float32 and face_id (B, S ss, S ss) int32 (>= 0: covered) -> (B,S,S,3) uint8, or (B,S,S,4) with alpha=True (alpha =
+    the covered share of the pixel).  background: None or (n_bg,S,S,3) uint8; bg_rows: None (n_bg must be 1 or B) or (B,) int32 rows of it,
+    a row outside [0, n_bg) taking bg_color; bg_color: three numbers in [0,1] or a (3,) float32 device tensor.  out: a contiguous uint8
+    tensor of the result's shape to write into."""
+    _playback_input("resolve_u8", rgb, face_id, background, bg_rows, bg_color if torch.is_tensor(bg_color) else None, out)
+    ss = int(ss)
+    if not 1 <= ss <= RESOLVE_MAX_SS:
+        raise ValueError(f"ss in 1..{RESOLVE_MAX_SS}, got {ss}")
+    if rgb.dtype != torch.float32 or rgb.dim() != 4 or rgb.shape[3] != 3 or rgb.shape[1] != rgb.shape[2] or rgb.shape[1] % ss or rgb.shape[0] < 1 or rgb.shape[1] < 1:
+        raise TypeError(f"resolve_u8 takes a float32 (B, S ss, S ss, 3) render, got {rgb.dtype} {tuple(rgb.shape)} with ss = {ss}")
+    B, S = rgb.shape[0], rgb.shape[1] // ss
+    if face_id.dtype != torch.int32 or tuple(face_id.shape) != tuple(rgb.shape[:3]):
+        raise TypeError(f"face_id must be int32 {tuple(rgb.shape[:3])}, got {face_id.dtype} {tuple(face_id.shape)}")
+    n_bg = 0
+    if background is not None:
+        if background.dtype != torch.uint8 or background.dim() != 4 or tuple(background.shape[1:]) != (S, S, 3) or background.shape[0] < 1:
+            raise TypeError(f"background must be uint8 (n_bg, {S}, {S}, 3), got {background.dtype} {tuple(background.shape)}")
+        n_bg = background.shape[0]
+        if bg_rows is None and n_bg not in (1, B):
+            raise ValueError(f"{n_bg} backgrounds for {B} frames: pass bg_rows")
+        background = background.contiguous()
+    if bg_rows is not None:
+        if bg_rows.dtype != torch.int32 or tuple(bg_rows.shape) != (B,):
+            raise TypeError(f"bg_rows must be int32 ({B},), got {bg_rows.dtype} {tuple(bg_rows.shape)}")
+        bg_rows = bg_rows.contiguous()
+    if torch.is_tensor(bg_color):
+        if bg_color.dtype != torch.float32 or tuple(bg_color.shape) != (3,):
+            raise TypeError(f"bg_color must be three numbers or a float32 (3,) tensor, got {bg_color.dtype} {tuple(bg_color.shape)}")
+        color = bg_color.detach().contiguous()
+    else:
+        color = torch.tensor([float(c) for c in bg_color], dtype=torch.float32).reshape(3).to(rgb.device)
+    C = 4 if alpha else 3
+    if out is None:
+        out = torch.empty(B, S, S, C, dtype=torch.uint8, device=rgb.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (B, S, S, C) or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous uint8 tensor {(B, S, S, C)}")
+    with torch.cuda.device(rgb.device):
+        rc = _lib.lib().harp_resolve_u8(_lib.ptr(rgb.detach().contiguous()), _lib.ptr(face_id.contiguous()), B, S, ss, _lib.ptr(background), n_bg,
+                                        _lib.ptr(bg_rows), _lib.ptr(color), C, _lib.ptr(out), _lib.stream())
+    _lib.check(rc, "harp_resolve_u8")
+    return out

@@ -1,0 +1,450 @@
+"""Playback of a fitted avatar: drive it with a motion it was not fitted on, at an output frame rate of the caller's choice, and composite
+it over a video or a plain background as finished 8-bit frames.  Stands in for the reference's `change_pose`
+(utils/visualize.py:111-143) and the render calls of :258-320 followed by the host-side `(img * 255).astype(np.uint8)`.
+
+`Motion` holds the per-frame rows of a motion, `Motion.resample` retimes them on the device (ops.motion_resample), and `AvatarPlayer` is
+the forward-only renderer: the fit's own fused front, rasterisers and shader (csrc/hand_front.hip, arm_front.hip, raster.hip, shade.hip)
+without a backward, a gradient slab, Adam moments or targets, followed by harp_resolve_u8 — six calls of the C ABI per batch of frames, in
+order on one stream, captured into a graph.
+
+    python -m harp_amd.playback --config CFG --motion MOTION.npz --out DIR [--fps-scale X] [--ss 2] [--background DIR] [--alpha]
+"""
+import ctypes
+import os
+
+import numpy as np
+import torch
+
+from . import _lib, ops
+
+BG_WHITE = (1.0, 1.0, 1.0)                             # the reference's BlendParams background (renderer_helper.py:49)
+
+
+def _rows_f32(name, a, width, T=None):
+    t = torch.as_tensor(np.asarray(a) if not torch.is_tensor(a) else a).detach().to(torch.float32)
+    if t.dim() != 2 or t.shape[1] != width or (T is not None and t.shape[0] != T) or t.shape[0] < 1:
+        raise ValueError(f"{name} must be ({'T' if T is None else T}, {width}), got {tuple(t.shape)}")
+    return t.contiguous()
+
+
+class Motion:
+    """The per-frame rows that animate an avatar: pose (T,45) MANO finger joints (relative to the model's pose mean, as the fit stores them),
+    rot, trans, cam (T,3), and optionally wrist_pose (T,3) (the arm model's wrist) and light_positions (T,3) (a light that moves with the
+    motion; without it the player keeps the fit's light).  float32 tensors, on any device."""
+
+    FIELDS = ("pose", "rot", "trans", "cam", "wrist_pose", "light_positions")
+
+    def __init__(self, pose, rot, trans, cam, wrist_pose=None, light_positions=None):
+        self.pose = _rows_f32("pose", pose, 45)
+        T = self.pose.shape[0]
+        self.rot, self.trans, self.cam = _rows_f32("rot", rot, 3, T), _rows_f32("trans", trans, 3, T), _rows_f32("cam", cam, 3, T)
+        self.wrist_pose = None if wrist_pose is None else _rows_f32("wrist_pose", wrist_pose, 3, T)
+        self.light_positions = None if light_positions is None else _rows_f32("light_positions", light_positions, 3, T)
+
+    def __len__(self):
+        return self.pose.shape[0]
+
+    @classmethod
+    def from_params(cls, params, rows=None, per_frame_light=False):
+        """The fit's own frames (all of them, or `rows` of its tables, in that order): the replay case.  The motion carries no light
+        unless per_frame_light=True: a fit with share_light_position (the default) reads and updates row 0 of its light table only, the
+        other rows keep their initial value, and the player then uses that row 0 for every frame as the fit did.  Pass
+        per_frame_light=True for a fit with share_light_position=False: its rows are the frames' lights."""
+        idx = None if rows is None else torch.as_tensor(rows).long().reshape(-1)
+        take = lambda k: None if params.get(k) is None else (params[k].detach() if idx is None else params[k].detach()[idx.to(params[k].device)]).clone()
+        return cls(take("pose"), take("rot"), take("trans"), take("cam"), take("wrist_pose"), take("light_positions") if per_frame_light else None)
+
+    def save(self, path):
+        np.savez(path, **{k: getattr(self, k).cpu().numpy() for k in self.FIELDS if getattr(self, k) is not None})
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path) as z:
+            return cls(**{k: z[k] for k in cls.FIELDS if k in z.files})
+
+    def resample(self, times, hand_layer, device="cuda"):
+        """The motion at `times` (n,) in units of its own frames, e.g. np.linspace(0, T - 1, n) to retime it to n frames: rotations along
+        the shortest arc with the model's pose mean as the offset, trans / cam / light linearly (ops.motion_resample); a time on a frame
+        returns that frame bit for bit."""
+        dev = torch.device(device)
+        rots = [self.rot] + ([self.wrist_pose] if self.wrist_pose is not None else []) + [self.pose]
+        lins = [self.trans, self.cam] + ([self.light_positions] if self.light_positions is not None else [])
+        keys = torch.cat([t.to(dev) for t in rots + lins], 1).contiguous()
+        n_rot = 16 + (self.wrist_pose is not None)
+        off = torch.as_tensor(pose_mean_rows(hand_layer, self.wrist_pose is not None), dtype=torch.float32).to(dev)
+        t = torch.as_tensor(np.asarray(times, dtype=np.float32)).reshape(-1).to(dev)
+        out = ops.motion_resample(keys, t, n_rot, off)
+        c = iter(out.split([3] + ([3] if self.wrist_pose is not None else []) + [45, 3, 3] + ([3] if self.light_positions is not None else []), 1))
+        rot = next(c)
+        wrist = next(c) if self.wrist_pose is not None else None
+        pose, trans, cam = next(c), next(c), next(c)
+        light = next(c) if self.light_positions is not None else None
+        return Motion(pose, rot, trans, cam, wrist, light)
+
+
+def pose_mean_rows(hand_layer, with_wrist):
+    """what the model adds to the stored rows [rot | (wrist_pose) | pose] before it turns them into rotations: zeros and MANO's hands_mean
+    (csrc/lbs.hip:35), or for the SMPL-X arm the slices of its pose mean for joints 0, 21 and 40..54 (hand_models_harp/body_models.py)"""
+    m = hand_layer._model_np
+    if "pose_mean" in m:
+        pm = np.asarray(m["pose_mean"], np.float32).reshape(-1)
+        parts = [pm[0:3]] + ([pm[63:66]] if with_wrist else []) + [pm[120:165]]
+    else:
+        parts = [np.zeros(3, np.float32)] + ([np.zeros(3, np.float32)] if with_wrist else []) + [np.asarray(m["hands_mean"], np.float32).reshape(45)]
+    return np.concatenate(parts)
+
+
+def _ck(rc, what):
+    if rc != 0:
+        raise RuntimeError(f"{what} failed with status {rc}")
+
+
+class AvatarPlayer:
+    """Forward-only renderer of a fitted avatar.  configs: the fit's (img_size, focal_length, use_arm, self_shadow,
+    share_light_position); params: its parameter dict (verts_disps, shape, texture, normal_map, amb_ratio, light_positions, verts_uvs,
+    faces_uvs are read once, here); ss: supersampling factor 1..4 — the avatar is rasterised and shaded at img_size * ss with the focal
+    length scaled alike and box-filtered down by the resolve.  Every device buffer is allocated here (or when a longer motion or a longer
+    `rows` is first seen); a call only enqueues."""
+
+    def __init__(self, configs, params, hand_layer, batch_size=32, ss=1, use_graph=True, device="cuda"):
+        from .synth import build_topology
+        self.dev = torch.device(device)
+        self.S, self.ss, self.B = int(configs["img_size"]), int(ss), int(batch_size)
+        if not 1 <= self.ss <= ops.RESOLVE_MAX_SS or self.B < 1 or self.S < 1:
+            raise ValueError(f"ss in 1..{ops.RESOLVE_MAX_SS}, batch_size >= 1 and img_size >= 1, got {ss}, {batch_size}, {configs['img_size']}")
+        self.Sh, self.focal_h = self.S * self.ss, float(configs["focal_length"]) * self.ss      # what is rasterised and shaded
+        self.use_arm, self.self_shadow = bool(configs["use_arm"]), bool(configs["self_shadow"])
+        self.share_light = bool(configs["share_light_position"])
+        self.use_graph = bool(use_graph)
+        faces0 = np.asarray((hand_layer.right_arm_faces_tensor if self.use_arm else hand_layer.th_faces).detach().cpu())
+        self.topo = ops.DeviceTopology(build_topology(faces0, 1026 if self.use_arm else 778), params["verts_uvs"], params["faces_uvs"], self.dev)
+        if self.topo.V > _lib.lib().harp_mesh_chain_max_vertices():
+            raise ValueError(f"the fused front takes meshes of at most {_lib.lib().harp_mesh_chain_max_vertices()} vertices, got {self.topo.V}")
+        if self.use_arm:
+            from .hand_models_harp.body_models import TreeDeviceModel
+            self.dm = TreeDeviceModel(hand_layer._model_np, self.dev)
+            self.n_joints, self.pose_stride, self.n_betas = 22, 51, self.dm.NB
+            self._weights_T = self.dm.weights.t().contiguous()
+        else:
+            from .manopth.manolayer import ManoDeviceModel
+            self.dm = ManoDeviceModel(hand_layer._model_np, self.dev)
+            self.n_joints, self.pose_stride, self.n_betas = 21, 48, 10
+        own = lambda k, shape: params[k].detach().to(device=self.dev, dtype=torch.float32).reshape(shape).clone().contiguous()
+        tex = params["texture"]
+        self.Ht, self.Wt = int(tex.shape[-3]), int(tex.shape[-2])
+        self.fit = dict(verts_disps=own("verts_disps", (self.topo.V, 1)), shape=own("shape", (10,)), texture=own("texture", (self.Ht, self.Wt, 3)),
+                        normal_map=own("normal_map", (self.Ht, self.Wt, 3)), amb_ratio=own("amb_ratio", (1,)),
+                        light_positions=own("light_positions", (-1, 3)))
+        self._alloc_scratch()
+        with torch.cuda.device(self.dev):
+            _ck(_lib.lib().harp_normalize3_pack(_lib.ptr(self.fit["texture"]), _lib.ptr(self.fit["normal_map"]), self.Ht * self.Wt,
+                                                _lib.ptr(self.nmap_n), _lib.ptr(self.texnm), _lib.stream()), "normalize3_pack")
+        self.T = self._cap = self._n_cap = 0
+        self.tab = self.tables = self.bg_buf = None
+        self._graphs = {}
+        self.bg_color = BG_WHITE
+
+    @property
+    def bg_color(self):
+        """the constant background colour, three numbers in [0,1] (white); kept on the device, written when it is set"""
+        return self._bg_color
+
+    @bg_color.setter
+    def bg_color(self, rgb):
+        self._bg_color = tuple(float(c) for c in rgb)
+        if len(self._bg_color) != 3:
+            raise ValueError("bg_color is three numbers")
+        self.bg_color_dev.copy_(torch.tensor(self._bg_color, dtype=torch.float32))
+
+    def _alloc_scratch(self):
+        """per-batch buffers for B frames at S * ss: what FitEngine keeps for a step's forward half, nothing of its backward"""
+        dev, V, Sh, B, tp = self.dev, self.topo.V, self.Sh, self.B, self.topo
+        f = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+        L = _lib.lib()
+        s = {}
+        s["pose48"], s["betas"], s["trans_b"] = f(B, self.pose_stride), f(B, self.n_betas), f(B, 3)
+        s["cam_R"], s["cam_T"], s["light_pos"], s["colors"] = f(B, 9), f(B, 3), f(B, 3), f(9)
+        s["lbs_ws"] = f(L.harp_lbs_tree_ws_floats(ctypes.byref(self.dm.struct), B) if self.use_arm else L.harp_lbs_mano_ws_floats(B))
+        s["verts_mm"], s["joints_mm"], s["joints_m"] = f(B, tp.V0, 3), f(B, self.n_joints, 3), f(B, self.n_joints, 3)
+        s["vs"], s["n1"], s["il1"], s["vd"], s["n2"], s["il2"] = f(B, V, 3), f(B, V, 3), f(B, V), f(B, V, 3), f(B, V, 3), f(B, V)
+        s["ndc_c"], s["ndc_l"], s["centroid"], s["light_R"], s["light_T"] = f(B, V, 3), f(B, V, 3), f(B, 3), f(B, 9), f(B, 3)
+        s["ws_c"] = ops.rasterize_workspace(B, tp.F, Sh, dev)
+        s["face_c"] = torch.empty(B, Sh, Sh, dtype=torch.int32, device=dev)
+        s["rgb"] = f(B, Sh, Sh, 3)
+        if self.self_shadow:
+            s["ws_l"] = ops.rasterize_workspace(B, tp.F, Sh, dev)
+            s["face_l"] = torch.empty(B, Sh, Sh, dtype=torch.int32, device=dev)
+            s["zl"] = f(B, Sh, Sh)
+            s["zl_state"] = torch.zeros(B * ((Sh + 63) // 64) ** 2, dtype=torch.int32, device=dev)      # harp_rasterize_fwd_keep's, zero before its first call
+        self.s = s
+        self.nmap_n = f(self.Ht, self.Wt, 3)
+        self.texnm = f(self.Ht, self.Wt, 8)
+        self.bg_color_dev = f(3)
+
+    # ---- the motion's tables --------------------------------------------------------------------------------------------------
+    def load_motion(self, motion):
+        """Copy the motion's rows into the player's tables (harp_frame_tables); they grow when the motion is longer than any before, and
+        only then are the captured graphs dropped.  The light is the motion's light_positions; without them the fit's own shared light
+        (row 0 of its table, optimize_sequence.py:453-456).  A fit with share_light_position=False has no light that applies to
+        another motion: such a motion must bring light_positions (Motion.from_params(params, per_frame_light=True) for a replay)."""
+        T = len(motion)
+        if self.use_arm and motion.wrist_pose is None:
+            raise ValueError("the arm model needs a motion with wrist_pose")
+        if motion.light_positions is None and not self.share_light:
+            raise ValueError("the fit has one light per frame (share_light_position=False): the motion must carry light_positions "
+                             "(Motion.from_params(params, per_frame_light=True) replays the fit's)")
+        if T > self._cap:
+            f = lambda w: torch.zeros(T, w, dtype=torch.float32, device=self.dev)
+            self.tab = dict(pose=f(45), rot=f(3), trans=f(3), cam=f(3), light_positions=f(3), wrist_pose=f(3))
+            t = _lib.FrameTables()                       # (every g_* pointer stays NULL)
+            for k in ("pose", "rot", "trans", "cam", "light_positions"):
+                setattr(t, k, _lib.ptr(self.tab[k]))
+            t.shape, t.amb_ratio = _lib.ptr(self.fit["shape"]), _lib.ptr(self.fit["amb_ratio"])
+            t.share_light = 0                            # the table always holds one light per row (a shared light is written to every row)
+            if self.use_arm:
+                t.wrist_pose = _lib.ptr(self.tab["wrist_pose"])
+            t.n_betas_out = self.n_betas
+            self.tables, self._cap, self._graphs = t, T, {}
+        with torch.no_grad():
+            for k in ("pose", "rot", "trans", "cam") + (("wrist_pose",) if self.use_arm else ()):
+                self.tab[k][:T].copy_(getattr(motion, k).to(self.dev))
+            light = motion.light_positions.to(self.dev) if motion.light_positions is not None else self.fit["light_positions"][0:1].expand(T, 3)
+            self.tab["light_positions"][:T].copy_(light)
+        self.T = T
+
+    # ---- structs over the player's buffers (FitEngine._chain_struct / _frame_struct / _shade_struct without a gradient pointer) -----
+    def _front_struct(self, fid):
+        s, p, tp, arm = self.s, _lib.ptr, self.topo, self.use_arm
+        h = _lib.ArmFront() if arm else _lib.HandFront()
+        c = _lib.MeshChain()                             # (every g_* pointer stays NULL)
+        for k, t in (("edges0", tp.edges0), ("vf_off", tp.vf_off), ("vf_tri", tp.vf_tri), ("sub_off", tp.sub_off), ("sub_idx", tp.sub_idx),
+                     ("disp", self.fit["verts_disps"])):
+            setattr(c, k, p(t))
+        for k in ("verts_mm", "joints_mm", "cam_R", "cam_T", "light_pos", "joints_m", "vs", "n1", "il1", "vd", "n2", "il2", "ndc_c", "centroid",
+                  "light_R", "light_T", "ndc_l"):
+            setattr(c, k, p(s[k]))
+        c.B, c.V0, c.E0, c.NJ, c.S = self.B, tp.V0, tp.E0, self.n_joints, self.Sh
+        c.focal, c.shadow, c.has_normal_grad, c.light_only = self.focal_h, int(self.self_shadow), 0, 0
+        h.chain, h.tables = c, self.tables
+        setattr(h, "tree" if arm else "mano", self.dm.struct)
+        for k, t in (("fid", fid), ("pose_in" if arm else "pose48", s["pose48"]), ("betas", s["betas"]), ("trans_b", s["trans_b"]),
+                     ("cam_R", s["cam_R"]), ("cam_T", s["cam_T"]), ("light_pos", s["light_pos"]), ("colors", s["colors"]), ("lbs_ws", s["lbs_ws"])):
+            setattr(h, k, p(t))
+        if arm:
+            h.weights_T = p(self._weights_T)
+        h.self_shadow = int(self.self_shadow)
+        return h
+
+    def _shade_struct(self):
+        s, sh = self.s, self.self_shadow
+        a = ops._shade_args(s["face_c"], s["ws_c"], self.topo, s["vd"], s["n2"], self.fit["texture"], self.nmap_n, s["light_pos"], s["colors"],
+                            s["zl"] if sh else None, s["light_R"] if sh else None, s["light_T"] if sh else None, self.Sh, self.focal_h,
+                            (self.Sh / 2.0, self.Sh / 2.0), BG_WHITE)
+        a.rgb, a.texnm = _lib.ptr(s["rgb"]), _lib.ptr(self.texnm)
+        return a
+
+    def _batch(self, fid, bg, n_bg, bg_rows, out, channels):
+        """the launches of one batch of B frames, in order on the current stream"""
+        L, s, p, tp, st = _lib.lib(), self.s, _lib.ptr, self.topo, _lib.stream()
+        B, V, F, Sh = self.B, tp.V, tp.F, self.Sh
+        h = self._front_struct(fid)
+        _ck((L.harp_arm_front_fwd if self.use_arm else L.harp_hand_front_fwd)(ctypes.byref(h), st), "front_fwd")
+        if self.self_shadow:
+            _ck(L.harp_raster_setup_pair(p(s["ndc_c"]), 0.0, p(s["ws_c"]), p(s["ndc_l"]), 0.0, p(s["ws_l"]), p(tp.faces), B, V, F, Sh, st),
+                "raster_setup_pair")
+            _ck(L.harp_rasterize_fwd(p(s["ndc_c"]), p(tp.faces), B, V, F, Sh, 4, 0.0, 1.0, p(s["ws_c"]), p(s["face_c"]), None, None, st), "raster_cam")
+            _ck(L.harp_rasterize_fwd_keep(p(s["ndc_l"]), p(tp.faces), B, V, F, Sh, 4, p(s["ws_l"]), p(s["face_l"]), p(s["zl"]), p(s["zl_state"]), st),
+                "raster_light")
+        else:                                            # one view: the rasteriser's own set-up
+            _ck(L.harp_rasterize_fwd(p(s["ndc_c"]), p(tp.faces), B, V, F, Sh, 0, 0.0, 1.0, p(s["ws_c"]), p(s["face_c"]), None, None, st), "raster_cam")
+        _ck(L.harp_shade_fwd(ctypes.byref(self._shade_struct()), st), "shade_fwd")
+        _ck(L.harp_resolve_u8(p(s["rgb"]), p(s["face_c"]), B, self.S, self.ss, bg, n_bg, bg_rows, p(self.bg_color_dev), channels, out, st), "resolve_u8")
+
+    def _grow(self, n_pad, with_bg):
+        if n_pad > self._n_cap:
+            # per rendered frame: its row of the motion | its row of the player's copy of the backgrounds (-1: the constant colour) | the row of
+            # the caller's background tensor that is copied there; staged in pinned memory and uploaded in one copy per call
+            self.idx_dev = torch.zeros(3, n_pad, dtype=torch.int32, device=self.dev)
+            self.idx_pin = torch.zeros(3, n_pad, dtype=torch.int32).pin_memory()
+            self.idx_done = None
+            self.out = torch.empty(n_pad * self.S * self.S * 4, dtype=torch.uint8, device=self.dev)
+            self.bg_buf = None
+            self._n_cap, self._graphs = n_pad, {}
+        if with_bg and self.bg_buf is None:              # (no graph reads it yet)
+            self.bg_buf = torch.empty(self._n_cap, self.S, self.S, 3, dtype=torch.uint8, device=self.dev)
+
+    def _enqueue(self, n_pad, with_bg, channels):
+        per = self.S * self.S * channels
+        for lo in range(0, n_pad, self.B):
+            self._batch(self.idx_dev[0, lo:lo + self.B], self.bg_buf.data_ptr() if with_bg else None, self._n_cap if with_bg else 0,
+                        self.idx_dev[1, lo:lo + self.B].data_ptr() if with_bg else None, self.out[lo * per:].data_ptr(), channels)
+
+    @torch.no_grad()
+    def render(self, rows, background=None, bg_rows=None, alpha=False):
+        """Frames `rows` of the loaded motion -> (len(rows), S, S, 3) uint8 on the device ((.., 4) with alpha=True: the covered share of the
+        pixel as alpha), a view of the player's buffer that the next call overwrites.  background: None (the constant `bg_color`, white) or
+        a (N,S,S,3) uint8 device tensor; frame i is composited over its row bg_rows[i], without bg_rows over row i (N == len(rows)) or row
+        0 (N == 1); a row outside [0, N) takes bg_color.  The rows in use are copied into a buffer of the player's in stream order, so
+        one captured graph serves every background tensor and the caller's tensor is free again once the call has returned."""
+        if self.tables is None:
+            raise RuntimeError("load_motion() first")
+        r = np.asarray(rows.cpu() if torch.is_tensor(rows) else rows, dtype=np.int64).reshape(-1)
+        n = r.shape[0]
+        if n < 1:
+            raise ValueError("no rows to render")
+        if r.min() < 0 or r.max() >= self.T:             # (on the host, before anything is enqueued: the kernels gather rows unchecked)
+            raise IndexError(f"rows span [{r.min()}, {r.max()}] but the motion holds {self.T} frames")
+        C = 4 if alpha else 3
+        br = None
+        if background is not None:
+            if (not torch.is_tensor(background) or background.dtype != torch.uint8 or background.device != self._device() or background.dim() != 4
+                    or tuple(background.shape[1:]) != (self.S, self.S, 3) or background.shape[0] < 1):
+                raise TypeError(f"background must be a uint8 (N, {self.S}, {self.S}, 3) tensor on {self.dev}")
+            n_bg = int(background.shape[0])
+            if bg_rows is None:
+                if n_bg not in (1, n):
+                    raise ValueError(f"{n_bg} backgrounds for {n} frames: pass bg_rows")
+                br = np.arange(n, dtype=np.int64) if n_bg == n else np.zeros(n, dtype=np.int64)
+            else:
+                br = np.asarray(bg_rows.cpu() if torch.is_tensor(bg_rows) else bg_rows, dtype=np.int64).reshape(-1)
+                if br.shape[0] != n:
+                    raise ValueError("bg_rows must have one entry per row")
+        elif bg_rows is not None:
+            raise ValueError("bg_rows without a background")
+        with_bg = br is not None
+        B = self.B
+        n_pad = -(-n // B) * B
+        with torch.cuda.device(self.dev):
+            self._grow(n_pad, with_bg)
+            if self.idx_done is not None:
+                self.idx_done.synchronize()              # the previous call's upload has read the staging buffer
+            stage = self.idx_pin.numpy()
+            stage[0, :n], stage[0, n:n_pad] = r, r[-1]   # a short last batch is padded with its last row
+            if with_bg:
+                inside = (br >= 0) & (br < n_bg)
+                stage[1, :n], stage[1, n:n_pad] = np.where(inside, np.arange(n), -1), (n - 1 if inside[-1] else -1)
+                stage[2, :n], stage[2, n:n_pad] = np.where(inside, br, 0), (br[-1] if inside[-1] else 0)
+            self.idx_dev.copy_(self.idx_pin, non_blocking=True)
+            self.idx_done = torch.cuda.Event()
+            self.idx_done.record()
+            if with_bg:
+                torch.index_select(background, 0, self.idx_dev[2, :n], out=self.bg_buf[:n])
+            if not self.use_graph:
+                self._enqueue(n_pad, with_bg, C)
+            else:
+                key = (n_pad, C, with_bg)
+                g = self._graphs.get(key)
+                if g is None:
+                    # warm-up (the first launches size their LDS with runtime calls that a capture does not allow), then capture; on the
+                    # current stream: the sequence allocates nothing and has no branches, and the player takes no stream from torch's pool
+                    self._enqueue(n_pad, with_bg, C)
+                    torch.cuda.synchronize()
+                    g = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(g):
+                        self._enqueue(n_pad, with_bg, C)
+                    self._graphs[key] = g
+                g.replay()
+        return self.out[:n * self.S * self.S * C].view(n, self.S, self.S, C)
+
+    def _device(self):
+        return self.dev if self.dev.index is not None else torch.device(self.dev.type, torch.cuda.current_device())
+
+    # ---- a whole motion to files ------------------------------------------------------------------------------------------------
+    def play(self, motion, out_dir, backgrounds=None, fmt="jpg", alpha=False):
+        """load_motion(motion), render it batch by batch and write out_dir/%04d.<fmt> (fmt "jpg" or "png"; alpha=True needs "png" and
+        writes RGBA).  backgrounds: None, a (N,S,S,3) uint8 tensor or a directory of images of that size (sorted by name); frame i is
+        composited over background i mod N.  The frames leave through two pinned host buffers, one per batch in flight, and are encoded on
+        a thread pool while the next batch renders.  Returns the list of paths."""
+        from concurrent.futures import ThreadPoolExecutor
+        from .utils.data_util import default_workers
+        if fmt not in ("jpg", "png") or (alpha and fmt != "png"):
+            raise ValueError(f'fmt is "jpg" or "png", and alpha=True needs "png"; got {fmt!r}, alpha={alpha}')
+        os.makedirs(out_dir, exist_ok=True)
+        self.load_motion(motion)
+        bgs = load_backgrounds(backgrounds, self.S, self.dev)
+        T, B, C = self.T, self.B, 4 if alpha else 3
+        pinned = [torch.empty(B, self.S, self.S, C, dtype=torch.uint8).pin_memory() for _ in range(2)]
+        pending = [[], []]
+        paths = [os.path.join(out_dir, "%04d.%s" % (i, fmt)) for i in range(T)]
+        with ThreadPoolExecutor(max(1, min(8, default_workers()))) as pool:
+            for k, lo in enumerate(range(0, T, B)):
+                rows = np.arange(lo, min(T, lo + B))
+                for fut in pending[k % 2]:                # the buffer's previous frames are on disk
+                    fut.result()
+                frames = self.render(rows, bgs, None if bgs is None else rows % bgs.shape[0], alpha)
+                host = pinned[k % 2][:len(rows)]
+                host.copy_(frames, non_blocking=True)
+                done = torch.cuda.Event()
+                done.record()
+                done.synchronize()
+                arr = host.numpy()
+                pending[k % 2] = [pool.submit(_encode, paths[i], arr[i - lo], fmt) for i in rows]
+            for futs in pending:
+                for fut in futs:
+                    fut.result()
+        return paths
+
+
+def _encode(path, u8, fmt):
+    if fmt == "jpg":
+        from .monitor import encode_jpeg
+        encode_jpeg(path, u8)
+    else:                                                # uint8 RGB / RGBA as it is (harp_amd.io.encode_png quantises a float texture)
+        from PIL import Image
+        Image.fromarray(u8).save(path, format="PNG")
+
+
+def load_backgrounds(backgrounds, S, device):
+    """None, a (N,S,S,3) uint8 tensor, or a directory of S x S images (sorted by name) -> None or that tensor on `device`"""
+    if backgrounds is None:
+        return None
+    if isinstance(backgrounds, (str, os.PathLike)):
+        from PIL import Image
+        names = sorted(f for f in os.listdir(backgrounds) if f.lower().endswith((".jpg", ".jpeg", ".png")))
+        if not names:
+            raise ValueError(f"no images in {backgrounds}")
+        backgrounds = torch.from_numpy(np.stack([np.asarray(Image.open(os.path.join(backgrounds, f)).convert("RGB")) for f in names]))
+    b = torch.as_tensor(backgrounds)
+    if b.dtype != torch.uint8 or b.dim() != 4 or tuple(b.shape[1:]) != (S, S, 3):
+        raise ValueError(f"backgrounds must be uint8 (N, {S}, {S}, 3), got {b.dtype} {tuple(b.shape)}")
+    return b.to(device).contiguous()
+
+
+def main(argv=None):
+    """A fit (the saved_params[_test].pkl under the config's base_output_dir, as the evaluation reads it) plus a motion file -> a directory
+    of frames."""
+    import argparse
+    import yaml
+    from .utils import file_utils, hand_model_utils
+    from .utils.config_utils import get_config
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--config", required=True, help="yaml with the keys of utils/config_utils.get_config (the fit's)")
+    ap.add_argument("--motion", required=True, help=".npz of pose (T,45), rot, trans, cam (T,3) [, wrist_pose, light_positions] (Motion.save)")
+    ap.add_argument("--out", required=True, help="directory for the frames %%04d.jpg / %%04d.png")
+    ap.add_argument("--fps-scale", type=float, default=1.0, help="output frames per motion frame (2: twice as many frames, half the speed)")
+    ap.add_argument("--ss", type=int, default=1, help="supersampling factor 1..4")
+    ap.add_argument("--background", default=None, help="directory of img_size x img_size images to composite over (cycled)")
+    ap.add_argument("--alpha", action="store_true", help="RGBA PNGs with the coverage as alpha")
+    ap.add_argument("--batch-size", type=int, default=32)
+    ap.add_argument("--device", default="cuda")
+    args = ap.parse_args(argv)
+    with open(args.config) as f:
+        configs = get_config(write_yaml=False, **yaml.safe_load(f))
+    configs["device"] = args.device
+    hand_layer, VERTS_UVS, FACES_UVS, _ = hand_model_utils.load_hand_model(configs)
+    params = file_utils.load_result(configs["base_output_dir"], device=args.device, test=bool(configs["known_appearance"]))
+    params["verts_uvs"], params["faces_uvs"] = VERTS_UVS, FACES_UVS
+    motion = Motion.load(args.motion)
+    if args.fps_scale != 1.0:
+        if args.fps_scale <= 0:
+            raise SystemExit("--fps-scale must be positive")
+        n = max(1, int(round((len(motion) - 1) * args.fps_scale)) + 1)
+        motion = motion.resample(np.linspace(0, len(motion) - 1, n), hand_layer, device=args.device)
+    player = AvatarPlayer(configs, params, hand_layer, batch_size=args.batch_size, ss=args.ss, device=args.device)
+    paths = player.play(motion, args.out, backgrounds=args.background, fmt="png" if args.alpha else "jpg", alpha=args.alpha)
+    print(f"wrote {len(paths)} frames to {args.out}")
+    return paths
+
+
+if __name__ == "__main__":
+    main()

@@ -1022,6 +1022,36 @@ size_t harp_texture_dilate_ws_bytes(int Ht, int Wt, int C);
 int harp_texture_dilate(const float* tex, const unsigned char* valid, const unsigned char* allow, int Ht, int Wt, int C, int n_pass, float* out,
                         unsigned char* valid_out, void* ws, hipStream_t stream);
 
+/* ---- playback of a fitted avatar (csrc/playback.hip; harp_amd/playback.py) ------------------------------------------------
+ * The forward-only player stands in for the way the reference animates and shows a fit: utils/visualize.py:111-143 `change_pose`
+ * (pose rows overwritten by hand, then prepare_mesh) and the render calls of :258-320 (render_image / render_image_with_RT, followed by
+ * `(img * 255).astype(np.uint8)` on the host).  It strings together harp_hand_front_fwd / harp_arm_front_fwd over a harp_frame_tables that
+ * holds the MOTION's rows, harp_raster_setup_pair, harp_rasterize_fwd, harp_rasterize_fwd_keep and harp_shade_fwd — all with NULL
+ * gradient pointers — and the two entries below.
+ *
+ * harp_motion_resample: keys (Tk, 3 n_rot + n_lin) = n_rot axis-angle triples, then n_lin linear channels (trans, cam, light) ->
+ * out (Tn, 3 n_rot + n_lin) at times (Tn,) in key-frame units.  Per row: t = fminf(fmaxf(time, 0), Tk - 1) (a NaN time is row 0),
+ * k = min((int)t, Tk - 2), f = t - k; f == 0 / f == 1 copy row k / k + 1 bit for bit (resampling at the key times is the identity; Tk == 1:
+ * every row is row 0).  Otherwise a rotation is rot_offset (3 n_rot, or NULL) + triple -> quaternion (sin(th/2)/th = 0.5 - th^2/48 below
+ * th = 1e-4), q1 negated when q0.q1 < 0 (the shortest arc ON ROTATIONS: an axis-angle of 4 rad is the rotation it is), nlerp when
+ * q0.q1 > 0.9995 and slerp otherwise, normalised, back with w >= 0 as 2 atan2(|v|, w) v / |v| (2 v when |v| < 1e-8), minus rot_offset;
+ * a linear channel is (1 - f) a + f b.  rot_offset: MANO's 15 finger joints are stored relative to hands_mean (csrc/lbs.hip:35), so the
+ * stored numbers are not the joint rotations — pass [0,0,0 | hands_mean], or the matching slice of harp_tree_model.pose_mean.
+ * Tk <= 0, Tn <= 0, n_rot < 0, n_lin < 0, n_rot + n_lin == 0 or a NULL keys / times / out: HARP_ERR_ARG before any launch. */
+int harp_motion_resample(const float* keys, int Tk, int n_rot, int n_lin, const float* rot_offset, const float* times, int Tn, float* out,
+                         hipStream_t stream);
+/* rgb (B, S ss, S ss, 3) and face_id (B, S ss, S ss) as harp_shade_fwd and the camera-view harp_rasterize_fwd leave them (a sub-pixel is
+ * covered when face_id >= 0), ss in 1..4 -> out (B,S,S,channels) uint8, channels 3 or 4.  Background of frame b: row bg_rows[b] of
+ * bg (n_bg,S,S,3) uint8; bg_rows == NULL: row b when n_bg == B, row 0 when n_bg == 1 (any other n_bg: HARP_ERR_ARG).  A row outside
+ * [0, n_bg), or bg == NULL (n_bg and bg_rows are then ignored), takes bg_color — 3 floats in [0,1] ON THE DEVICE, quantised like a
+ * pixel, (int)(255 clamp01(c) + 0.5), and from there on treated as an image's byte.
+ * Per pixel with n covered sub-pixels of ss^2: n == 0 copies the background byte; otherwise
+ * v_c = (sum over covered of clamp01(rgb_c) + (ss^2 - n) bg_c / 255) / ss^2, out_c = (int)(255 v_c + 0.5) clamped to 0..255, with
+ * clamp01(x) = fminf(fmaxf(x, 0), 1) (a NaN colour is 0).  Alpha (channels == 4) = (255 n + ss^2 / 2) / ss^2 in INTEGER arithmetic:
+ * 255 n / ss^2 sits exactly on .5 for (ss, n) = (2, 2) and (4, 8).  Argument errors return before a launch. */
+int harp_resolve_u8(const float* rgb, const int32_t* face_id, int B, int S, int ss, const unsigned char* bg, int n_bg, const int32_t* bg_rows,
+                    const float* bg_color, int channels, unsigned char* out, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
