@@ -327,3 +327,12 @@ SIGNATURES.update({
     "harp_motion_resample": (_i, [_vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp]),
     "harp_resolve_u8": (_i, [_vp, _vp, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _vp]),
 })
+
+
+class Layer(ctypes.Structure):
+    """mirror of `harp_layer` (include/harp_hip.h)"""
+    _fields_ = [("rgb", _vp), ("zbuf", _vp), ("flip_x", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+# several avatars in one frame (csrc/composite.hip)
+SIGNATURES["harp_composite_layers_u8"] = (_i, [ctypes.POINTER(Layer), _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp])

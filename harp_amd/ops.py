@@ -1146,3 +1146,80 @@ def resolve_u8(rgb, face_id, ss=1, background=None, bg_rows=None, bg_color=(1, 1
                                         _lib.ptr(bg_rows), _lib.ptr(color), C, _lib.ptr(out), _lib.stream())
     _lib.check(rc, "harp_resolve_u8")
     return out
+
+
+COMPOSITE_MAX_LAYERS = 4
+
+
+def composite_layers_u8(layers, ss=1, scene_depth=None, scene_rows=None, background=None, bg_rows=None, bg_color=(1, 1, 1), alpha=False,
+                        owner=False, out=None):
+    """Several supersampled renders with their view depth as ONE finished 8-bit frame with depth-correct occlusion (csrc/composite.hip:
+    harp_composite_layers_u8, whose contract include/harp_hip.h states), forward only.  layers: 1..4 of (rgb (B, S ss, S ss, 3) float32,
+    zbuf (B, S ss, S ss) float32 view depth with > 0 = covered, flip) — a flipped layer is read mirrored in x.  Per sub-sample the nearest
+    layer in front of scene_depth wins, ties going to the lower index.  scene_depth: None or (n_scene,S,S) float32 at output resolution
+    (a value > 0 is a measurement); scene_rows: None (n_scene must be 1 or B) or (B,) int32 rows of it, a row outside [0, n_scene) meaning
+    no scene depth.  background, bg_rows, bg_color, alpha, out: as resolve_u8.  Returns the (B,S,S,3|4) uint8 frames, or with owner=True
+    (frames, owner (B,S,S) uint8: 0 = background, 1 + the layer that won most of the pixel's sub-samples)."""
+    layers = [tuple(l) for l in layers]
+    if not 1 <= len(layers) <= COMPOSITE_MAX_LAYERS or any(len(l) != 3 for l in layers):
+        raise ValueError(f"composite_layers_u8 takes 1..{COMPOSITE_MAX_LAYERS} layers of (rgb, zbuf, flip), got {len(layers)}")
+    _playback_input("composite_layers_u8", *[t for l in layers for t in l[:2]], scene_depth, scene_rows, background, bg_rows,
+                    bg_color if torch.is_tensor(bg_color) else None, out)
+    ss = int(ss)
+    if not 1 <= ss <= RESOLVE_MAX_SS:
+        raise ValueError(f"ss in 1..{RESOLVE_MAX_SS}, got {ss}")
+    rgb = layers[0][0]
+    if rgb.dtype != torch.float32 or rgb.dim() != 4 or rgb.shape[3] != 3 or rgb.shape[1] != rgb.shape[2] or rgb.shape[1] % ss or rgb.shape[0] < 1 or rgb.shape[1] < 1:
+        raise TypeError(f"composite_layers_u8 takes float32 (B, S ss, S ss, 3) renders, got {rgb.dtype} {tuple(rgb.shape)} with ss = {ss}")
+    B, S = rgb.shape[0], rgb.shape[1] // ss
+    for i, (c, z, _) in enumerate(layers):
+        if c.dtype != torch.float32 or z.dtype != torch.float32:
+            raise TypeError(f"layer {i}: rgb and zbuf must be float32, got {c.dtype} and {z.dtype}")
+        if tuple(c.shape) != tuple(rgb.shape) or tuple(z.shape) != tuple(rgb.shape[:3]):
+            raise ValueError(f"layer {i}: rgb {tuple(c.shape)} and zbuf {tuple(z.shape)} must be {tuple(rgb.shape)} and {tuple(rgb.shape[:3])}")
+    n_scene = 0
+    if scene_depth is not None:
+        if scene_depth.dtype != torch.float32 or scene_depth.dim() != 3 or tuple(scene_depth.shape[1:]) != (S, S) or scene_depth.shape[0] < 1:
+            raise TypeError(f"scene_depth must be float32 (n_scene, {S}, {S}), got {scene_depth.dtype} {tuple(scene_depth.shape)}")
+        n_scene = scene_depth.shape[0]
+        if scene_rows is None and n_scene not in (1, B):
+            raise ValueError(f"{n_scene} scene depths for {B} frames: pass scene_rows")
+        scene_depth = scene_depth.detach().contiguous()
+    if scene_rows is not None:
+        if scene_depth is None:
+            raise ValueError("scene_rows without a scene_depth")
+        if scene_rows.dtype != torch.int32 or tuple(scene_rows.shape) != (B,):
+            raise TypeError(f"scene_rows must be int32 ({B},), got {scene_rows.dtype} {tuple(scene_rows.shape)}")
+        scene_rows = scene_rows.contiguous()
+    n_bg = 0
+    if background is not None:
+        if background.dtype != torch.uint8 or background.dim() != 4 or tuple(background.shape[1:]) != (S, S, 3) or background.shape[0] < 1:
+            raise TypeError(f"background must be uint8 (n_bg, {S}, {S}, 3), got {background.dtype} {tuple(background.shape)}")
+        n_bg = background.shape[0]
+        if bg_rows is None and n_bg not in (1, B):
+            raise ValueError(f"{n_bg} backgrounds for {B} frames: pass bg_rows")
+        background = background.contiguous()
+    if bg_rows is not None:
+        if bg_rows.dtype != torch.int32 or tuple(bg_rows.shape) != (B,):
+            raise TypeError(f"bg_rows must be int32 ({B},), got {bg_rows.dtype} {tuple(bg_rows.shape)}")
+        bg_rows = bg_rows.contiguous()
+    if torch.is_tensor(bg_color):
+        if bg_color.dtype != torch.float32 or tuple(bg_color.shape) != (3,):
+            raise TypeError(f"bg_color must be three numbers or a float32 (3,) tensor, got {bg_color.dtype} {tuple(bg_color.shape)}")
+        color = bg_color.detach().contiguous()
+    else:
+        color = torch.tensor([float(c) for c in bg_color], dtype=torch.float32).reshape(3).to(rgb.device)
+    C = 4 if alpha else 3
+    if out is None:
+        out = torch.empty(B, S, S, C, dtype=torch.uint8, device=rgb.device)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != (B, S, S, C) or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous uint8 tensor {(B, S, S, C)}")
+    own = torch.empty(B, S, S, dtype=torch.uint8, device=rgb.device) if owner else None
+    keep = [(c.detach().contiguous(), z.detach().contiguous()) for c, z, _ in layers]      # (alive until the launch is enqueued)
+    arr = (_lib.Layer * len(layers))(*[_lib.Layer(_lib.ptr(c), _lib.ptr(z), int(bool(l[2])), 0) for (c, z), l in zip(keep, layers)])
+    with torch.cuda.device(rgb.device):
+        rc = _lib.lib().harp_composite_layers_u8(arr, len(layers), B, S, ss, _lib.ptr(scene_depth), n_scene, _lib.ptr(scene_rows),
+                                                 _lib.ptr(background), n_bg, _lib.ptr(bg_rows), _lib.ptr(color), C, _lib.ptr(out), _lib.ptr(own),
+                                                 _lib.stream())
+    _lib.check(rc, "harp_composite_layers_u8")
+    return (out, own) if owner else out

@@ -7,7 +7,12 @@ the forward-only renderer: the fit's own fused front, rasterisers and shader (cs
 without a backward, a gradient slab, Adam moments or targets, followed by harp_resolve_u8 — six calls of the C ABI per batch of frames, in
 order on one stream, captured into a graph.
 
+`ScenePlayer` shows several such avatars in one frame: each player's launches up to the shader, then ONE harp_composite_layers_u8
+(csrc/composite.hip) that picks the nearest avatar per sub-sample, un-mirrors a flipped one (a left hand is a right-hand fit
+of mirrored frames) and tests against an optional scene depth.
+
     python -m harp_amd.playback --config CFG --motion MOTION.npz --out DIR [--fps-scale X] [--ss 2] [--background DIR] [--alpha]
+                                [--flip] [--also CFG:MOTION[:flip]]... [--scene-depth DIR] [--masks]
 """
 import ctypes
 import os
@@ -104,11 +109,13 @@ class AvatarPlayer:
     share_light_position); params: its parameter dict (verts_disps, shape, texture, normal_map, amb_ratio, light_positions, verts_uvs,
     faces_uvs are read once, here); ss: supersampling factor 1..4 — the avatar is rasterised and shaded at img_size * ss with the focal
     length scaled alike and box-filtered down by the resolve.  Every device buffer is allocated here (or when a longer motion or a longer
-    `rows` is first seen); a call only enqueues."""
+    `rows` is first seen); a call only enqueues.  keep_depth=True also keeps the camera view's depth map (s["z_c"], (B, S ss, S ss) view-space z,
+    -1 where empty), which a ScenePlayer needs; without it not one launch argument differs."""
 
-    def __init__(self, configs, params, hand_layer, batch_size=32, ss=1, use_graph=True, device="cuda"):
+    def __init__(self, configs, params, hand_layer, batch_size=32, ss=1, use_graph=True, device="cuda", keep_depth=False):
         from .synth import build_topology
         self.dev = torch.device(device)
+        self.keep_depth = bool(keep_depth)             # the camera view's depth s["z_c"] is kept: a ScenePlayer composites by it
         self.S, self.ss, self.B = int(configs["img_size"]), int(ss), int(batch_size)
         if not 1 <= self.ss <= ops.RESOLVE_MAX_SS or self.B < 1 or self.S < 1:
             raise ValueError(f"ss in 1..{ops.RESOLVE_MAX_SS}, batch_size >= 1 and img_size >= 1, got {ss}, {batch_size}, {configs['img_size']}")
@@ -171,6 +178,8 @@ class AvatarPlayer:
         s["ws_c"] = ops.rasterize_workspace(B, tp.F, Sh, dev)
         s["face_c"] = torch.empty(B, Sh, Sh, dtype=torch.int32, device=dev)
         s["rgb"] = f(B, Sh, Sh, 3)
+        if self.keep_depth:
+            s["z_c"] = f(B, Sh, Sh)
         if self.self_shadow:
             s["ws_l"] = ops.rasterize_workspace(B, tp.F, Sh, dev)
             s["face_l"] = torch.empty(B, Sh, Sh, dtype=torch.int32, device=dev)
@@ -243,22 +252,30 @@ class AvatarPlayer:
         a.rgb, a.texnm = _lib.ptr(s["rgb"]), _lib.ptr(self.texnm)
         return a
 
-    def _batch(self, fid, bg, n_bg, bg_rows, out, channels):
-        """the launches of one batch of B frames, in order on the current stream"""
+    def _render_batch(self, fid):
+        """front, rasterisers and shader of one batch of B frames, in order on the current stream: s["rgb"], s["face_c"] (and s["z_c"]
+        with keep_depth) at S * ss, everything in front of the resolve"""
         L, s, p, tp, st = _lib.lib(), self.s, _lib.ptr, self.topo, _lib.stream()
         B, V, F, Sh = self.B, tp.V, tp.F, self.Sh
+        z_c = p(s["z_c"]) if self.keep_depth else None
         h = self._front_struct(fid)
         _ck((L.harp_arm_front_fwd if self.use_arm else L.harp_hand_front_fwd)(ctypes.byref(h), st), "front_fwd")
         if self.self_shadow:
             _ck(L.harp_raster_setup_pair(p(s["ndc_c"]), 0.0, p(s["ws_c"]), p(s["ndc_l"]), 0.0, p(s["ws_l"]), p(tp.faces), B, V, F, Sh, st),
                 "raster_setup_pair")
-            _ck(L.harp_rasterize_fwd(p(s["ndc_c"]), p(tp.faces), B, V, F, Sh, 4, 0.0, 1.0, p(s["ws_c"]), p(s["face_c"]), None, None, st), "raster_cam")
+            _ck(L.harp_rasterize_fwd(p(s["ndc_c"]), p(tp.faces), B, V, F, Sh, 4, 0.0, 1.0, p(s["ws_c"]), p(s["face_c"]), z_c, None, st), "raster_cam")
             _ck(L.harp_rasterize_fwd_keep(p(s["ndc_l"]), p(tp.faces), B, V, F, Sh, 4, p(s["ws_l"]), p(s["face_l"]), p(s["zl"]), p(s["zl_state"]), st),
                 "raster_light")
         else:                                            # one view: the rasteriser's own set-up
-            _ck(L.harp_rasterize_fwd(p(s["ndc_c"]), p(tp.faces), B, V, F, Sh, 0, 0.0, 1.0, p(s["ws_c"]), p(s["face_c"]), None, None, st), "raster_cam")
+            _ck(L.harp_rasterize_fwd(p(s["ndc_c"]), p(tp.faces), B, V, F, Sh, 0, 0.0, 1.0, p(s["ws_c"]), p(s["face_c"]), z_c, None, st), "raster_cam")
         _ck(L.harp_shade_fwd(ctypes.byref(self._shade_struct()), st), "shade_fwd")
-        _ck(L.harp_resolve_u8(p(s["rgb"]), p(s["face_c"]), B, self.S, self.ss, bg, n_bg, bg_rows, p(self.bg_color_dev), channels, out, st), "resolve_u8")
+
+    def _batch(self, fid, bg, n_bg, bg_rows, out, channels):
+        """the launches of one batch of B frames, in order on the current stream"""
+        L, s, p = _lib.lib(), self.s, _lib.ptr
+        self._render_batch(fid)
+        _ck(L.harp_resolve_u8(p(s["rgb"]), p(s["face_c"]), self.B, self.S, self.ss, bg, n_bg, bg_rows, p(self.bg_color_dev), channels, out, _lib.stream()),
+            "resolve_u8")
 
     def _grow(self, n_pad, with_bg):
         if n_pad > self._n_cap:
@@ -384,6 +401,208 @@ class AvatarPlayer:
                     fut.result()
         return paths
 
+def _host_rows(name, rows, n=None):
+    r = np.asarray(rows.cpu() if torch.is_tensor(rows) else rows, dtype=np.int64).reshape(-1)
+    if n is not None and r.shape[0] != n:
+        raise ValueError(f"{name} must have one entry per row")
+    return r
+
+
+class ScenePlayer:
+    """Several avatars in one frame with depth-correct occlusion: 1 to 4 AvatarPlayers built with keep_depth=True on one
+    device with equal img_size, ss and batch_size — one camera: the focal length is the players' too, the translation comes from each
+    motion's cam — rendered batch by batch into their own buffers and resolved by ONE harp_composite_layers_u8 per batch: per sub-sample
+    the nearest avatar in front of an optional scene depth.  flip: one bool per player; a flipped avatar is shown mirrored in x, light
+    included — a LEFT hand is a right-hand fit of horizontally mirrored frames shown with flip.  The avatars cast no shadows on each
+    other.  The launches are captured into a graph when every player was built with use_graph=True."""
+
+    def __init__(self, players, flip=None):
+        players = list(players)
+        if not 1 <= len(players) <= ops.COMPOSITE_MAX_LAYERS:
+            raise ValueError(f"a scene holds 1..{ops.COMPOSITE_MAX_LAYERS} players, got {len(players)}")
+        p0 = players[0]
+        for p in players:
+            if not isinstance(p, AvatarPlayer) or not p.keep_depth:
+                raise ValueError("a scene takes AvatarPlayers built with keep_depth=True")
+            if (p.S, p.ss, p.B) != (p0.S, p0.ss, p0.B) or p._device() != p0._device():
+                raise ValueError(f"the players of a scene share img_size, ss, batch_size and the device: got {(p.S, p.ss, p.B, p._device())} "
+                                 f"and {(p0.S, p0.ss, p0.B, p0._device())}")
+        self.flip = [False] * len(players) if flip is None else [bool(f) for f in flip]
+        if len(self.flip) != len(players):
+            raise ValueError("flip holds one entry per player")
+        self.players, self.dev, self.S, self.ss, self.B = players, p0.dev, p0.S, p0.ss, p0.B
+        self.use_graph = all(p.use_graph for p in players)
+        self.bg_color_dev = torch.empty(3, dtype=torch.float32, device=self.dev)
+        self.bg_color = BG_WHITE
+        self.T = self._n_cap = 0
+        self.bg_buf = self.depth_buf = self.idx_done = None
+        self._graphs = {}
+
+    bg_color = AvatarPlayer.bg_color
+    _device = AvatarPlayer._device
+
+    def load_motions(self, motions):
+        """one motion per player, of equal length: scene row i is row i of every motion (AvatarPlayer.load_motion each)"""
+        motions = list(motions)
+        if len(motions) != len(self.players):
+            raise ValueError(f"{len(motions)} motions for {len(self.players)} players")
+        if len({len(m) for m in motions}) != 1:
+            raise ValueError(f"the motions of a scene have one length, got {[len(m) for m in motions]}")
+        tables = [p.tables for p in self.players]
+        for p, m in zip(self.players, motions):
+            p.load_motion(m)
+        if any(p.tables is not t for p, t in zip(self.players, tables)):      # (tables that grew: the captured pointers are gone)
+            self._graphs = {}
+        self.T = len(motions[0])
+
+    def _grow(self, n_pad, with_bg, with_depth):
+        if n_pad > self._n_cap:
+            # per rendered frame: its row of the motions | its row of the scene's copy of the backgrounds (-1: the constant colour) | the row of
+            # the caller's background tensor copied there | the same two for the scene depth (-1: no scene depth)
+            self.idx_dev = torch.zeros(5, n_pad, dtype=torch.int32, device=self.dev)
+            self.idx_pin = torch.zeros(5, n_pad, dtype=torch.int32).pin_memory()
+            self.idx_done = None
+            self.out = torch.empty(n_pad * self.S * self.S * 4, dtype=torch.uint8, device=self.dev)
+            self.owner = torch.empty(n_pad, self.S, self.S, dtype=torch.uint8, device=self.dev)
+            self.bg_buf = self.depth_buf = None
+            self._n_cap, self._graphs = n_pad, {}
+        if with_bg and self.bg_buf is None:              # (no graph reads it yet)
+            self.bg_buf = torch.empty(self._n_cap, self.S, self.S, 3, dtype=torch.uint8, device=self.dev)
+        if with_depth and self.depth_buf is None:
+            self.depth_buf = torch.empty(self._n_cap, self.S, self.S, dtype=torch.float32, device=self.dev)
+
+    def _enqueue(self, n_pad, with_bg, with_depth, channels, with_owner):
+        """per batch: every player's front / rasterisers / shader, then one composite"""
+        L, p, B = _lib.lib(), _lib.ptr, self.B
+        per = self.S * self.S
+        layers = (_lib.Layer * len(self.players))(*[_lib.Layer(p(pl.s["rgb"]), p(pl.s["z_c"]), int(f), 0) for pl, f in zip(self.players, self.flip)])
+        for lo in range(0, n_pad, B):
+            for pl in self.players:
+                pl._render_batch(self.idx_dev[0, lo:lo + B])
+            _ck(L.harp_composite_layers_u8(layers, len(self.players), B, self.S, self.ss,
+                                           self.depth_buf.data_ptr() if with_depth else None, self._n_cap if with_depth else 0,
+                                           self.idx_dev[3, lo:lo + B].data_ptr() if with_depth else None,
+                                           self.bg_buf.data_ptr() if with_bg else None, self._n_cap if with_bg else 0,
+                                           self.idx_dev[1, lo:lo + B].data_ptr() if with_bg else None, p(self.bg_color_dev), channels,
+                                           self.out[lo * per * channels:].data_ptr(), self.owner[lo:].data_ptr() if with_owner else None,
+                                           _lib.stream()), "composite_layers_u8")
+
+    def _staged(self, name, t, rows, n, shape, dtype):
+        """a (N, *shape) device tensor of the caller's and its rows -> (the rows checked, N), as AvatarPlayer.render treats backgrounds"""
+        if t is None:
+            if rows is not None:
+                raise ValueError(f"rows of a {name} without the {name}")
+            return None, 0
+        if (not torch.is_tensor(t) or t.dtype != dtype or t.device != self._device() or t.dim() != 1 + len(shape)
+                or tuple(t.shape[1:]) != shape or t.shape[0] < 1):
+            raise TypeError(f"{name} must be a {dtype} (N, {', '.join(map(str, shape))}) tensor on {self.dev}")
+        N = int(t.shape[0])
+        if rows is None:
+            if N not in (1, n):
+                raise ValueError(f"{N} rows of {name} for {n} frames: pass its rows")
+            return (np.arange(n, dtype=np.int64) if N == n else np.zeros(n, dtype=np.int64)), N
+        return _host_rows(f"the rows of {name}", rows, n), N
+
+    @torch.no_grad()
+    def render(self, rows, background=None, bg_rows=None, alpha=False, scene_depth=None, depth_rows=None, owner=False):
+        """Scene rows `rows` of the loaded motions -> (len(rows), S, S, 3|4) uint8 on the device, a view of the scene's buffer that the
+        next call overwrites; with owner=True (frames, owner (len(rows), S, S) uint8: 0 = background, 1 + the player that shows most of
+        the pixel).  background / bg_rows / alpha: as AvatarPlayer.render.  scene_depth: None or a float32 (N,S,S) device tensor at output
+        resolution in the unit of the avatars' view depth (a value > 0 is a measurement and hides what lies behind it); frame i is tested
+        against its row depth_rows[i], without depth_rows against row i (N == len(rows)) or row 0 (N == 1); a row outside [0, N) means no
+        scene depth.  Backgrounds and depths in use are copied into buffers of the scene's, so one captured graph per (padded length,
+        channels, background?, depth?, owner?) serves every tensor."""
+        if self.T < 1 or any(p.tables is None for p in self.players):
+            raise RuntimeError("load_motions() first")
+        r = _host_rows("rows", rows)
+        n = r.shape[0]
+        if n < 1:
+            raise ValueError("no rows to render")
+        if r.min() < 0 or r.max() >= self.T:             # (on the host, before anything is enqueued: the kernels gather rows unchecked)
+            raise IndexError(f"rows span [{r.min()}, {r.max()}] but the motions hold {self.T} frames")
+        C = 4 if alpha else 3
+        br, n_bg = self._staged("background", background, bg_rows, n, (self.S, self.S, 3), torch.uint8)
+        dr, n_d = self._staged("scene_depth", scene_depth, depth_rows, n, (self.S, self.S), torch.float32)
+        with_bg, with_depth, with_owner = br is not None, dr is not None, bool(owner)
+        B = self.B
+        n_pad = -(-n // B) * B
+        with torch.cuda.device(self.dev):
+            self._grow(n_pad, with_bg, with_depth)
+            if self.idx_done is not None:
+                self.idx_done.synchronize()              # the previous call's upload has read the staging buffer
+            stage = self.idx_pin.numpy()
+            stage[0, :n], stage[0, n:n_pad] = r, r[-1]   # a short last batch is padded with its last row
+            for k, rr, N in ((1, br, n_bg), (3, dr, n_d)):
+                if rr is not None:
+                    inside = (rr >= 0) & (rr < N)
+                    stage[k, :n], stage[k, n:n_pad] = np.where(inside, np.arange(n), -1), (n - 1 if inside[-1] else -1)
+                    stage[k + 1, :n], stage[k + 1, n:n_pad] = np.where(inside, rr, 0), (rr[-1] if inside[-1] else 0)
+            self.idx_dev.copy_(self.idx_pin, non_blocking=True)
+            self.idx_done = torch.cuda.Event()
+            self.idx_done.record()
+            if with_bg:
+                torch.index_select(background, 0, self.idx_dev[2, :n], out=self.bg_buf[:n])
+            if with_depth:
+                torch.index_select(scene_depth, 0, self.idx_dev[4, :n], out=self.depth_buf[:n])
+            if not self.use_graph:
+                self._enqueue(n_pad, with_bg, with_depth, C, with_owner)
+            else:
+                key = (n_pad, C, with_bg, with_depth, with_owner)
+                g = self._graphs.get(key)
+                if g is None:                            # warm-up, then capture on the current stream, as AvatarPlayer.render
+                    self._enqueue(n_pad, with_bg, with_depth, C, with_owner)
+                    torch.cuda.synchronize()
+                    g = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(g):
+                        self._enqueue(n_pad, with_bg, with_depth, C, with_owner)
+                    self._graphs[key] = g
+                g.replay()
+        frames = self.out[:n * self.S * self.S * C].view(n, self.S, self.S, C)
+        return (frames, self.owner[:n]) if with_owner else frames
+
+    def play(self, motions, out_dir, backgrounds=None, scene_depth=None, fmt="jpg", alpha=False, masks=False):
+        """load_motions(motions), render the scene batch by batch and write out_dir/%04d.<fmt> as AvatarPlayer.play does; with masks=True
+        also out_dir/mask_%04d.png, the owner map (8-bit grey: 0 background, 1 + the player).  backgrounds: as AvatarPlayer.play;
+        scene_depth: None, a float32 (N,S,S) tensor or a directory (load_scene_depth), frame i tested against depth i mod N.  Returns the
+        list of the frames' paths."""
+        from concurrent.futures import ThreadPoolExecutor
+        from .utils.data_util import default_workers
+        if fmt not in ("jpg", "png") or (alpha and fmt != "png"):
+            raise ValueError(f'fmt is "jpg" or "png", and alpha=True needs "png"; got {fmt!r}, alpha={alpha}')
+        os.makedirs(out_dir, exist_ok=True)
+        self.load_motions(motions)
+        bgs = load_backgrounds(backgrounds, self.S, self.dev)
+        depth = load_scene_depth(scene_depth, self.S, self.dev)
+        T, B, C = self.T, self.B, 4 if alpha else 3
+        pinned = [torch.empty(B, self.S, self.S, C + 1, dtype=torch.uint8).pin_memory() for _ in range(2)]      # (the last plane: the owner map)
+        pending = [[], []]
+        paths = [os.path.join(out_dir, "%04d.%s" % (i, fmt)) for i in range(T)]
+        with ThreadPoolExecutor(max(1, min(8, default_workers()))) as pool:
+            for k, lo in enumerate(range(0, T, B)):
+                rows = np.arange(lo, min(T, lo + B))
+                for fut in pending[k % 2]:                # the buffer's previous frames are on disk
+                    fut.result()
+                got = self.render(rows, bgs, None if bgs is None else rows % bgs.shape[0], alpha, depth,
+                                  None if depth is None else rows % depth.shape[0], owner=masks)
+                host = pinned[k % 2][:len(rows)]
+                if masks:
+                    host[..., :C].copy_(got[0], non_blocking=True)
+                    host[..., C].copy_(got[1], non_blocking=True)
+                else:
+                    host[..., :C].copy_(got, non_blocking=True)
+                done = torch.cuda.Event()
+                done.record()
+                done.synchronize()
+                arr = host.numpy()
+                pending[k % 2] = [pool.submit(_encode, paths[i], np.ascontiguousarray(arr[i - lo, :, :, :C]), fmt) for i in rows]
+                if masks:
+                    pending[k % 2] += [pool.submit(_encode, os.path.join(out_dir, "mask_%04d.png" % i), np.ascontiguousarray(arr[i - lo, :, :, C]), "png")
+                                       for i in rows]
+            for futs in pending:
+                for fut in futs:
+                    fut.result()
+        return paths
+
 
 def _encode(path, u8, fmt):
     if fmt == "jpg":
@@ -410,6 +629,27 @@ def load_backgrounds(backgrounds, S, device):
     return b.to(device).contiguous()
 
 
+def load_scene_depth(depth, S, device):
+    """None, a float32 (N,S,S) tensor, or a directory (sorted by name) of .npy float32 (S,S) in metres and / or 16-bit PNGs in millimetres,
+    0 = no measurement -> None or that tensor in metres on `device`"""
+    if depth is None:
+        return None
+    if isinstance(depth, (str, os.PathLike)):
+        from PIL import Image
+        names = sorted(f for f in os.listdir(depth) if f.lower().endswith((".npy", ".png")))
+        if not names:
+            raise ValueError(f"no .npy or .png depth maps in {depth}")
+        maps = []
+        for f in names:
+            path = os.path.join(depth, f)
+            maps.append(np.load(path).astype(np.float32) if f.lower().endswith(".npy") else np.asarray(Image.open(path)).astype(np.float32) * 1e-3)
+        depth = torch.from_numpy(np.stack(maps))
+    d = torch.as_tensor(depth)
+    if d.dtype != torch.float32 or d.dim() != 3 or tuple(d.shape[1:]) != (S, S):
+        raise ValueError(f"scene depth must be float32 (N, {S}, {S}), got {d.dtype} {tuple(d.shape)}")
+    return d.to(device).contiguous()
+
+
 def main(argv=None):
     """A fit (the saved_params[_test].pkl under the config's base_output_dir, as the evaluation reads it) plus a motion file -> a directory
     of frames."""
@@ -427,21 +667,50 @@ def main(argv=None):
     ap.add_argument("--alpha", action="store_true", help="RGBA PNGs with the coverage as alpha")
     ap.add_argument("--batch-size", type=int, default=32)
     ap.add_argument("--device", default="cuda")
+    ap.add_argument("--flip", action="store_true", help="show the avatar mirrored in x: a left hand is a right-hand fit of mirrored frames")
+    ap.add_argument("--also", action="append", default=[], metavar="CFG:MOTION[:flip]",
+                    help="a further avatar with its own fit and motion in the same frames, nearest surface in front (up to three times)")
+    ap.add_argument("--scene-depth", default=None, help="directory of .npy float32 (img_size, img_size) depth maps in metres or 16-bit PNGs in "
+                                                        "millimetres, 0 = no measurement (cycled): what is nearer hides the avatars")
+    ap.add_argument("--masks", action="store_true", help="also write mask_%%04d.png: 0 background, 1 + the avatar that owns the pixel")
     args = ap.parse_args(argv)
-    with open(args.config) as f:
-        configs = get_config(write_yaml=False, **yaml.safe_load(f))
-    configs["device"] = args.device
-    hand_layer, VERTS_UVS, FACES_UVS, _ = hand_model_utils.load_hand_model(configs)
-    params = file_utils.load_result(configs["base_output_dir"], device=args.device, test=bool(configs["known_appearance"]))
-    params["verts_uvs"], params["faces_uvs"] = VERTS_UVS, FACES_UVS
-    motion = Motion.load(args.motion)
-    if args.fps_scale != 1.0:
-        if args.fps_scale <= 0:
-            raise SystemExit("--fps-scale must be positive")
-        n = max(1, int(round((len(motion) - 1) * args.fps_scale)) + 1)
-        motion = motion.resample(np.linspace(0, len(motion) - 1, n), hand_layer, device=args.device)
-    player = AvatarPlayer(configs, params, hand_layer, batch_size=args.batch_size, ss=args.ss, device=args.device)
-    paths = player.play(motion, args.out, backgrounds=args.background, fmt="png" if args.alpha else "jpg", alpha=args.alpha)
+    if len(args.also) > ops.COMPOSITE_MAX_LAYERS - 1:
+        raise SystemExit(f"--also at most {ops.COMPOSITE_MAX_LAYERS - 1} times")
+    if args.fps_scale <= 0:
+        raise SystemExit("--fps-scale must be positive")
+
+    def load(cfg_path, motion_path):
+        with open(cfg_path) as f:
+            configs = get_config(write_yaml=False, **yaml.safe_load(f))
+        configs["device"] = args.device
+        hand_layer, VERTS_UVS, FACES_UVS, _ = hand_model_utils.load_hand_model(configs)
+        params = file_utils.load_result(configs["base_output_dir"], device=args.device, test=bool(configs["known_appearance"]))
+        params["verts_uvs"], params["faces_uvs"] = VERTS_UVS, FACES_UVS
+        motion = Motion.load(motion_path)
+        if args.fps_scale != 1.0:
+            n = max(1, int(round((len(motion) - 1) * args.fps_scale)) + 1)
+            motion = motion.resample(np.linspace(0, len(motion) - 1, n), hand_layer, device=args.device)
+        return configs, params, hand_layer, motion
+
+    fmt = "png" if args.alpha else "jpg"
+    if not (args.flip or args.also or args.scene_depth or args.masks):
+        configs, params, hand_layer, motion = load(args.config, args.motion)
+        player = AvatarPlayer(configs, params, hand_layer, batch_size=args.batch_size, ss=args.ss, device=args.device)
+        paths = player.play(motion, args.out, backgrounds=args.background, fmt=fmt, alpha=args.alpha)
+    else:
+        specs = [(args.config, args.motion, args.flip)]
+        for spec in args.also:
+            part = spec.split(":")
+            if len(part) not in (2, 3) or (len(part) == 3 and part[2] != "flip"):
+                raise SystemExit(f"--also takes CFG:MOTION or CFG:MOTION:flip, got {spec!r}")
+            specs.append((part[0], part[1], len(part) == 3))
+        players, motions = [], []
+        for cfg_path, motion_path, _ in specs:
+            configs, params, hand_layer, motion = load(cfg_path, motion_path)
+            players.append(AvatarPlayer(configs, params, hand_layer, batch_size=args.batch_size, ss=args.ss, device=args.device, keep_depth=True))
+            motions.append(motion)
+        scene = ScenePlayer(players, flip=[f for _, _, f in specs])
+        paths = scene.play(motions, args.out, backgrounds=args.background, scene_depth=args.scene_depth, fmt=fmt, alpha=args.alpha, masks=args.masks)
     print(f"wrote {len(paths)} frames to {args.out}")
     return paths
 

@@ -1052,6 +1052,41 @@ int harp_motion_resample(const float* keys, int Tk, int n_rot, int n_lin, const 
 int harp_resolve_u8(const float* rgb, const int32_t* face_id, int B, int S, int ss, const unsigned char* bg, int n_bg, const int32_t* bg_rows,
                     const float* bg_color, int channels, unsigned char* out, hipStream_t stream);
 
+/* ---- scene playback: several avatars in one frame with depth-correct occlusion (csrc/composite.hip; playback.py ScenePlayer) ----
+ * All players of one video share the camera (img_size, focal_length; the translation comes from cam), so the view depths that the
+ * camera-view harp_rasterize_fwd writes into zbuf are comparable sub-sample by sub-sample.  A LEFT hand is a right-hand fit of
+ * horizontally mirrored frames (the model is MANO / SMPL-X right), shown with flip_x: its layer, light included, is mirrored back. */
+typedef struct harp_layer {
+  const float* rgb;    /* (B, S ss, S ss, 3) as harp_shade_fwd leaves it */
+  const float* zbuf;   /* (B, S ss, S ss) view depth as the camera-view harp_rasterize_fwd leaves it (-1 = empty) */
+  int32_t flip_x;      /* != 0: the layer is read mirrored, sub-column S ss - 1 - X */
+  int32_t reserved;    /* 0 */
+} harp_layer;
+/* layers: a HOST array of n_layers in 1..4 entries, read during the call and passed to the kernel by value (nothing on the device points
+ * at host memory; a captured graph keeps working).  ss in 1..4 -> out (B,S,S,channels) uint8, channels 3 or 4, and, when owner != NULL,
+ * owner (B,S,S) uint8.  Output pixel (b, y, x), sub-sample (sy, sx) in [0, ss)^2, output-space sub-pixel (Y, X) = (y ss + sy, x ss + sx):
+ *   covered: layer l is read at (b, Y, X), or at (b, Y, S ss - 1 - X) when flip_x; z_l = its zbuf there; the layer is a CANDIDATE when
+ *     z_l > 0 (a NaN or -1 is not).
+ *   scene depth: scene_z (n_scene,S,S) float32 at OUTPUT resolution, in zbuf's unit; frame b uses row scene_rows[b]; scene_rows == NULL:
+ *     row b when n_scene == B, row 0 when n_scene == 1 (any other n_scene: HARP_ERR_ARG).  A row outside [0, n_scene), or scene_z ==
+ *     NULL (n_scene and scene_rows are then ignored), means no scene depth.  d = the value at (y, x) is valid when d > 0 (a NaN or 0:
+ *     no measurement, nothing in front); when d is valid a candidate needs z_l < d.
+ *   winner: the candidate with the smallest z_l, among exactly equal depths the lower layer index.  A sub-sample with a winner is
+ *     covered and contributes clamp01(rgb_winner), clamp01(x) = fminf(fmaxf(x, 0), 1) (a NaN colour is 0).
+ *   colour: as harp_resolve_u8 with n = the covered sub-samples of ss^2: n == 0 copies the background byte; otherwise
+ *     v_c = (sum + (ss^2 - n) bg_c / 255) / ss^2, out_c = (int)(255 v_c + 0.5) clamped to 0..255; the sum in float32 in row-major order
+ *     of the OUTPUT sub-samples (sy outer, sx inner; the same order for a flipped layer).  bg, n_bg, bg_rows, bg_color: harp_resolve_u8's
+ *     rules; backgrounds are never flipped.  Alpha (channels == 4) = (255 n + ss^2 / 2) / ss^2 in integers.
+ *   owner: 0 when n == 0, otherwise 1 + the index of the layer that won the most sub-samples of the pixel (a tie: the lower index) —
+ *     the per-hand segmentation of the finished frame.
+ * With one unflipped layer, no scene depth and zbuf > 0 <=> face_id >= 0 the bytes are harp_resolve_u8's; a flipped layer gives the
+ * bytes of the same call on arrays mirrored beforehand.
+ * HARP_ERR_ARG before any launch: layers, out or bg_color NULL; n_layers outside 1..4; a layer with a NULL rgb or zbuf or a non-zero
+ * reserved; B, S <= 0, ss outside 1..4, channels not 3 or 4, S ss > 46340, n_bg / n_scene as above. */
+int harp_composite_layers_u8(const harp_layer* layers, int n_layers, int B, int S, int ss, const float* scene_z, int n_scene,
+                             const int32_t* scene_rows, const unsigned char* bg, int n_bg, const int32_t* bg_rows, const float* bg_color,
+                             int channels, unsigned char* out, unsigned char* owner, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
