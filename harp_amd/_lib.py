@@ -336,3 +336,13 @@ class Layer(ctypes.Structure):
 
 # several avatars in one frame (csrc/composite.hip)
 SIGNATURES["harp_composite_layers_u8"] = (_i, [ctypes.POINTER(Layer), _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp])
+
+
+class IkOptions(ctypes.Structure):
+    """mirror of `harp_ik_options` (include/harp_hip.h)"""
+    _fields_ = [("iters", _i), ("lambda0", _f), ("prior_weight", _f), ("betas_per_frame", _i)]
+
+
+# batched MANO inverse kinematics (csrc/ik.hip)
+SIGNATURES["harp_mano_ik_frames_per_block"] = (_i, [])
+SIGNATURES["harp_mano_ik"] = (_i, [_mp, _vp, _vp, _vp, _vp, _i, ctypes.POINTER(IkOptions), _vp, _vp, _vp, _vp, _vp, _vp, _vp])

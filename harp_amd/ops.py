@@ -2,6 +2,7 @@
 
 These are the building blocks the reference-API mirror modules (renderer/, utils/, loss/, manopth/) and the
 fused engine call.  Every op takes/returns plain contiguous float32/int32 HIP tensors."""
+import collections
 import math
 
 import ctypes
@@ -1223,3 +1224,62 @@ def composite_layers_u8(layers, ss=1, scene_depth=None, scene_rows=None, backgro
                                                  _lib.stream())
     _lib.check(rc, "harp_composite_layers_u8")
     return (out, own) if owner else out
+
+
+# ---- batched MANO inverse kinematics (csrc/ik.hip) -----------------------------------------------------------------
+IkResult = collections.namedtuple("IkResult", "pose48 trans cost status joints jac")
+
+
+def mano_ik_frames_per_block():
+    """the frames one workgroup of harp_mano_ik solves"""
+    return int(_lib.lib().harp_mano_ik_frames_per_block())
+
+
+def mano_ik(dm, betas, targets, pose48, trans, weights=None, prior=None, iters=15, lambda0=1e-3, prior_weight=0.0, joints=False, jac=False,
+            out=None):
+    """3-D keypoints -> MANO pose rows: T Levenberg-Marquardt solves in one launch (csrc/ik.hip: harp_mano_ik, whose contract
+    include/harp_hip.h states), forward only.  dm: a ManoDeviceModel; betas (10,) for all frames or (T,10); targets (T,21,3) metres in the
+    order of the model's joints; pose48 (T,48) = [rot | pose] and trans (T,3): the start, left untouched; weights (T,21) or None (ones; a
+    joint with weight <= 0 or a non-finite target is unused); prior (T,45) or None (the mean pose) with prior_weight on
+    sum (pose - prior)^2.  Returns IkResult(pose48, trans, cost (T,2) = at the start and at the result, status (T,) int32 = accepted steps
+    or -1 for a frame with fewer than 3 used joints (returned as it came), joints (T,21,3) mm or None, jac (T,63,51) or None).
+    iters = 0 evaluates at the start.  out: an earlier IkResult of the same shapes whose tensors are written instead of new ones — the
+    call then allocates nothing and can be captured into a graph."""
+    _playback_input("mano_ik", betas, targets, pose48, trans, weights, prior)
+    for name, t in (("betas", betas), ("targets", targets), ("pose48", pose48), ("trans", trans), ("weights", weights), ("prior", prior)):
+        if t is not None and t.dtype != torch.float32:
+            raise TypeError(f"mano_ik takes float32 tensors, {name} is {t.dtype}")
+    if targets.dim() != 3 or tuple(targets.shape[1:]) != (21, 3) or targets.shape[0] < 1:
+        raise ValueError(f"targets must be (T, 21, 3), got {tuple(targets.shape)}")
+    T = targets.shape[0]
+    if tuple(betas.shape) not in ((10,), (T, 10)):
+        raise ValueError(f"betas must be (10,) or ({T}, 10), got {tuple(betas.shape)}")
+    for name, t, shape in (("pose48", pose48, (T, 48)), ("trans", trans, (T, 3)), ("weights", weights, (T, 21)), ("prior", prior, (T, 45))):
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError(f"{name} must be {shape}, got {tuple(t.shape)}")
+    iters, lambda0, prior_weight = int(iters), float(lambda0), float(prior_weight)
+    if iters < 0 or not (0.0 <= lambda0 < float("inf")) or not (0.0 <= prior_weight < float("inf")):
+        raise ValueError(f"iters >= 0 and finite lambda0, prior_weight >= 0, got {iters}, {lambda0}, {prior_weight}")
+    if dm.v_template.device != targets.device:
+        raise ValueError(f"the model is on {dm.v_template.device}, the targets on {targets.device}")
+    dev = targets.device
+    if out is None:
+        e = lambda shape, dt=torch.float32: torch.empty(shape, dtype=dt, device=dev)
+        out = IkResult(e((T, 48)), e((T, 3)), e((T, 2)), e((T,), torch.int32), e((T, 21, 3)) if joints else None, e((T, 63, 51)) if jac else None)
+    else:
+        want = ((T, 48), (T, 3), (T, 2), (T,), (T, 21, 3) if joints else None, (T, 63, 51) if jac else None)
+        for name, t, shape in zip(IkResult._fields, out, want):
+            if (t is None) != (shape is None) or (t is not None and (tuple(t.shape) != shape or t.device != dev or not t.is_contiguous()
+                                                                      or t.dtype != (torch.int32 if name == "status" else torch.float32))):
+                raise ValueError(f"out.{name} does not fit this call")
+    out.pose48.copy_(pose48.detach())
+    out.trans.copy_(trans.detach())
+    c = lambda t: None if t is None else t.detach().contiguous()
+    betas, targets, weights, prior = c(betas), c(targets), c(weights), c(prior)
+    opt = _lib.IkOptions(iters, lambda0, prior_weight, int(betas.dim() == 2))
+    with torch.cuda.device(dev):
+        rc = _lib.lib().harp_mano_ik(ctypes.byref(dm.struct), _lib.ptr(betas), _lib.ptr(targets), _lib.ptr(weights), _lib.ptr(prior), T,
+                                     ctypes.byref(opt), _lib.ptr(out.pose48), _lib.ptr(out.trans), _lib.ptr(out.cost), _lib.ptr(out.status),
+                                     _lib.ptr(out.joints), _lib.ptr(out.jac), _lib.stream())
+    _lib.check(rc, "harp_mano_ik")
+    return out

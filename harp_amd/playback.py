@@ -11,7 +11,7 @@ order on one stream, captured into a graph.
 (csrc/composite.hip) that picks the nearest avatar per sub-sample, un-mirrors a flipped one (a left hand is a right-hand fit
 of mirrored frames) and tests against an optional scene depth.
 
-    python -m harp_amd.playback --config CFG --motion MOTION.npz --out DIR [--fps-scale X] [--ss 2] [--background DIR] [--alpha]
+    python -m harp_amd.playback --config CFG (--motion MOTION.npz | --keypoints KP.npz) --out DIR [--fps-scale X] [--ss 2] [--background DIR] [--alpha]
                                 [--flip] [--also CFG:MOTION[:flip]]... [--scene-depth DIR] [--masks]
 """
 import ctypes
@@ -59,6 +59,66 @@ class Motion:
         take = lambda k: None if params.get(k) is None else (params[k].detach() if idx is None else params[k].detach()[idx.to(params[k].device)]).clone()
         return cls(take("pose"), take("rot"), take("trans"), take("cam"), take("wrist_pose"), take("light_positions") if per_frame_light else None)
 
+    @classmethod
+    def from_keypoints(cls, keypoints, params, hand_layer, cam=None, weights=None, match_bone_lengths=True, iters=15, prior_weight=1e-5,
+                       init=None, device=None):
+        """A motion from 3-D keypoints (a hand tracker, a mocap glove, a dataset) by batched inverse kinematics on the device
+        (ops.mano_ik, csrc/ik.hip).  keypoints (T,21,3) in metres, in the model's order — wrist, then thumb, index, middle,
+        ring and little, each from root to tip — and in the frame of the fit's `joints`; a joint with a non-finite coordinate or a weight
+        <= 0 (weights (T,21), default ones) is ignored.  params: the fit's parameter dict (its `shape` is the avatar's and is not solved;
+        row 0 of its `cam` is the default cam); cam: (3,) or (T,3).
+        The start (host, float64): pose zero, the root rotation and trans from the Kabsch fit of the model's palm joints (palm_start);
+        init= takes a Motion of equal length instead as a warm start.  match_bone_lengths scales the keypoints about their wrist so that
+        their chain bones sum to the model's (bone_length_scale): someone else's hand can drive the avatar.  prior_weight pulls the
+        finger pose to the model's mean pose, which decides what the keypoints leave open (the twist of a finger's last bone).
+        Every frame is solved on its own and nothing is smoothed over time: filter jittery keypoints BEFORE they come here.
+        The result carries no light: AvatarPlayer.load_motion then uses the fit's row 0.  device: where the solve runs (default: the
+        device of params["shape"] when that is a HIP device, else "cuda").  The SMPL-X arm needs a solver for its kinematic tree and raises
+        NotImplementedError."""
+        if "pose_mean" in hand_layer._model_np:
+            raise NotImplementedError("Motion.from_keypoints solves the MANO hand; the SMPL-X arm needs a kinematic-tree solver")
+        kp = np.asarray(keypoints.detach().cpu() if torch.is_tensor(keypoints) else keypoints)
+        if kp.ndim != 3 or kp.shape[1:] != (21, 3) or kp.shape[0] < 1:
+            raise ValueError(f"keypoints must be (T, 21, 3), got {kp.shape}")
+        if not np.issubdtype(kp.dtype, np.floating):
+            raise TypeError(f"keypoints must be floating point, got {kp.dtype}")
+        kp = kp.astype(np.float64)
+        T = kp.shape[0]
+        w = None
+        if weights is not None:
+            w = np.asarray(weights.detach().cpu() if torch.is_tensor(weights) else weights)
+            if w.shape != (T, 21):
+                raise ValueError(f"weights must be ({T}, 21), got {w.shape}")
+            if not np.issubdtype(w.dtype, np.floating):
+                raise TypeError(f"weights must be floating point, got {w.dtype}")
+            w = w.astype(np.float64)
+        if init is not None and (not isinstance(init, Motion) or len(init) != T):
+            raise ValueError(f"init must be a Motion of {T} frames")
+        cam = params["cam"][0] if cam is None else cam
+        cam = np.asarray(cam.detach().cpu() if torch.is_tensor(cam) else cam, dtype=np.float32)
+        if cam.shape not in ((3,), (T, 3)):
+            raise ValueError(f"cam must be (3,) or ({T}, 3), got {cam.shape}")
+        cam = np.broadcast_to(cam, (T, 3)).copy()
+        shape = params["shape"].detach().cpu().numpy().astype(np.float64).reshape(10)
+        used = np.isfinite(kp).all(-1) & (True if w is None else (w > 0))
+        rest = rest_chain_joints(hand_layer._model_np, shape)
+        if match_bone_lengths:
+            s = bone_length_scale(kp, used, rest)
+            wrist = kp[:, :1]
+            kp = np.where(np.isfinite(wrist).all(-1, keepdims=True), wrist + s * (kp - wrist), kp)      # (no wrist: the frame stays as it is)
+        if init is None:
+            rot, trans = palm_start(kp, used, rest)
+            pose = np.zeros((T, 45))
+        else:
+            rot, trans, pose = init.rot.cpu().numpy(), init.trans.cpu().numpy(), init.pose.cpu().numpy()
+        from .manopth.manolayer import ManoDeviceModel
+        dev = torch.device(device if device is not None else (params["shape"].device if params["shape"].is_cuda else "cuda"))
+        up = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
+        dm = ManoDeviceModel(hand_layer._model_np, dev)
+        res = ops.mano_ik(dm, up(shape), up(kp), up(np.concatenate([rot, pose], 1)), up(trans), weights=None if w is None else up(w),
+                          iters=iters, prior_weight=prior_weight)
+        return cls(res.pose48[:, 3:], res.pose48[:, :3], res.trans, cam)
+
     def save(self, path):
         np.savez(path, **{k: getattr(self, k).cpu().numpy() for k in self.FIELDS if getattr(self, k) is not None})
 
@@ -97,6 +157,88 @@ def pose_mean_rows(hand_layer, with_wrist):
     else:
         parts = [np.zeros(3, np.float32)] + ([np.zeros(3, np.float32)] if with_wrist else []) + [np.asarray(m["hands_mean"], np.float32).reshape(45)]
     return np.concatenate(parts)
+
+
+# ---- the host side of Motion.from_keypoints: T problems of six points each, numpy float64 ---------------------------------------------
+JOINT_REORDER = (0, 13, 14, 15, 16, 1, 2, 3, 17, 4, 5, 6, 18, 10, 11, 12, 19, 7, 8, 9, 20)      # output joint -> model joint / tip (manolayer.py:279)
+PALM = (0, 1, 5, 9, 13, 17)                            # output joints that only the root moves: the wrist and the five finger roots
+# the 15 chain bones in output joints: wrist -> finger root and the two bones after it; the tip bones are left out (pose correctives move the tips)
+CHAIN_BONES = tuple((0 if k == 0 else 4 * f + k, 4 * f + k + 1) for f in range(5) for k in range(3))
+
+
+def rest_chain_joints(model, shape):
+    """the model's 21 joints in output order at `shape` BEFORE any rotation, (21,3) float64; the five tips are NaN (they depend on the
+    pose).  The wrist, the finger roots relative to it, and every chain bone's length do not depend on the finger pose."""
+    f64 = lambda k: np.asarray(model[k], np.float64)
+    v = f64("v_template").reshape(778, 3) + f64("shapedirs").reshape(778, 3, 10) @ np.asarray(shape, np.float64).reshape(10)
+    j16 = f64("J_regressor").reshape(16, 778) @ v
+    out = np.full((21, 3), np.nan)
+    for k, src in enumerate(JOINT_REORDER):
+        if src < 16:
+            out[k] = j16[src]
+    return out
+
+
+def bone_length_scale(keypoints, used, rest):
+    """the factor that makes the keypoints' 15 chain bones sum to the model's: the model's sum over the median over the frames (those with
+    all 16 chain joints used) of the keypoints' sum; 1 when there is no such frame"""
+    a, b = np.array([i for i, _ in CHAIN_BONES]), np.array([j for _, j in CHAIN_BONES])
+    model_sum = np.linalg.norm(rest[b] - rest[a], axis=-1).sum()
+    ok = used[:, np.unique(np.concatenate([a, b]))].all(1)
+    if not ok.any():
+        return 1.0
+    kp = keypoints[ok]
+    return float(model_sum / np.median(np.linalg.norm(kp[:, b] - kp[:, a], axis=-1).sum(1)))
+
+
+def kabsch_rotation(P, Q):
+    """the rotation R (det +1) that minimises sum |R p_i - q_i|^2 over two CENTRED point sets (n,3); a mirrored set gets the best proper
+    rotation, not the reflection"""
+    U, _, Vt = np.linalg.svd(np.asarray(Q, np.float64).T @ np.asarray(P, np.float64))
+    d = np.sign(np.linalg.det(U @ Vt)) or 1.0
+    return U @ np.diag([1.0, 1.0, d]) @ Vt
+
+
+def axis_angle_of(R):
+    """rotation matrix -> axis-angle with an angle in [0, pi], through the quaternion with the largest component (stable near pi)"""
+    t = np.trace(R)
+    cand = np.array([1.0 + t, 1.0 + 2 * R[0, 0] - t, 1.0 + 2 * R[1, 1] - t, 1.0 + 2 * R[2, 2] - t])
+    i = int(np.argmax(cand))
+    if i == 0:
+        q = np.array([cand[0], R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    elif i == 1:
+        q = np.array([R[2, 1] - R[1, 2], cand[1], R[0, 1] + R[1, 0], R[0, 2] + R[2, 0]])
+    elif i == 2:
+        q = np.array([R[0, 2] - R[2, 0], R[0, 1] + R[1, 0], cand[2], R[1, 2] + R[2, 1]])
+    else:
+        q = np.array([R[1, 0] - R[0, 1], R[0, 2] + R[2, 0], R[1, 2] + R[2, 1], cand[3]])
+    q = q / np.linalg.norm(q)
+    if q[0] < 0:
+        q = -q
+    vn = np.linalg.norm(q[1:])
+    return np.zeros(3) if vn < 1e-15 else 2.0 * np.arctan2(vn, q[0]) * q[1:] / vn
+
+
+def palm_start(keypoints, used, rest):
+    """rot (T,3), trans (T,3) float64 that put the model's six palm joints (PALM, which only the root rotation and trans move:
+    R (J_k - J_0) + J_0 + trans) onto the keypoints' in the least-squares sense: the Kabsch rotation, then the difference of the two
+    centroids.  A frame whose six palm joints are not all used keeps the rotation of the last frame that had them (none yet: zero) and
+    takes its trans from the palm joints it has (none: that frame's trans as well)."""
+    T = keypoints.shape[0]
+    idx = np.array(PALM)
+    P0 = rest[idx] - rest[0]                            # about the wrist, where the model rotates
+    rot, trans = np.zeros((T, 3)), np.zeros((T, 3))
+    R, aa, tr = np.eye(3), np.zeros(3), np.zeros(3)
+    for t in range(T):
+        u = used[t, idx]
+        if u.all():
+            Q = keypoints[t, idx]
+            R = kabsch_rotation(P0 - P0.mean(0), Q - Q.mean(0))
+            aa = axis_angle_of(R)
+        if u.any():
+            tr = keypoints[t, idx[u]].mean(0) - (P0[u] @ R.T + rest[0]).mean(0)
+        rot[t], trans[t] = aa, tr
+    return rot, trans
 
 
 def _ck(rc, what):
@@ -659,7 +801,9 @@ def main(argv=None):
     from .utils.config_utils import get_config
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--config", required=True, help="yaml with the keys of utils/config_utils.get_config (the fit's)")
-    ap.add_argument("--motion", required=True, help=".npz of pose (T,45), rot, trans, cam (T,3) [, wrist_pose, light_positions] (Motion.save)")
+    ap.add_argument("--motion", default=None, help=".npz of pose (T,45), rot, trans, cam (T,3) [, wrist_pose, light_positions] (Motion.save)")
+    ap.add_argument("--keypoints", default=None, help=".npz of keypoints (T,21,3) in metres [, weights (T,21), cam (3,) or (T,3)] instead of --motion: "
+                                                      "the motion is solved from them (Motion.from_keypoints)")
     ap.add_argument("--out", required=True, help="directory for the frames %%04d.jpg / %%04d.png")
     ap.add_argument("--fps-scale", type=float, default=1.0, help="output frames per motion frame (2: twice as many frames, half the speed)")
     ap.add_argument("--ss", type=int, default=1, help="supersampling factor 1..4")
@@ -678,15 +822,22 @@ def main(argv=None):
         raise SystemExit(f"--also at most {ops.COMPOSITE_MAX_LAYERS - 1} times")
     if args.fps_scale <= 0:
         raise SystemExit("--fps-scale must be positive")
+    if (args.motion is None) == (args.keypoints is None):
+        raise SystemExit("exactly one of --motion and --keypoints")
 
-    def load(cfg_path, motion_path):
+    def load(cfg_path, motion_path, keypoints_path=None):
         with open(cfg_path) as f:
             configs = get_config(write_yaml=False, **yaml.safe_load(f))
         configs["device"] = args.device
         hand_layer, VERTS_UVS, FACES_UVS, _ = hand_model_utils.load_hand_model(configs)
         params = file_utils.load_result(configs["base_output_dir"], device=args.device, test=bool(configs["known_appearance"]))
         params["verts_uvs"], params["faces_uvs"] = VERTS_UVS, FACES_UVS
-        motion = Motion.load(motion_path)
+        if keypoints_path is not None:
+            with np.load(keypoints_path) as z:
+                motion = Motion.from_keypoints(z["keypoints"], params, hand_layer, cam=z["cam"] if "cam" in z.files else None,
+                                               weights=z["weights"] if "weights" in z.files else None, device=args.device)
+        else:
+            motion = Motion.load(motion_path)
         if args.fps_scale != 1.0:
             n = max(1, int(round((len(motion) - 1) * args.fps_scale)) + 1)
             motion = motion.resample(np.linspace(0, len(motion) - 1, n), hand_layer, device=args.device)
@@ -694,22 +845,22 @@ def main(argv=None):
 
     fmt = "png" if args.alpha else "jpg"
     if not (args.flip or args.also or args.scene_depth or args.masks):
-        configs, params, hand_layer, motion = load(args.config, args.motion)
+        configs, params, hand_layer, motion = load(args.config, args.motion, args.keypoints)
         player = AvatarPlayer(configs, params, hand_layer, batch_size=args.batch_size, ss=args.ss, device=args.device)
         paths = player.play(motion, args.out, backgrounds=args.background, fmt=fmt, alpha=args.alpha)
     else:
-        specs = [(args.config, args.motion, args.flip)]
+        specs = [(args.config, args.motion, args.flip, args.keypoints)]
         for spec in args.also:
             part = spec.split(":")
             if len(part) not in (2, 3) or (len(part) == 3 and part[2] != "flip"):
                 raise SystemExit(f"--also takes CFG:MOTION or CFG:MOTION:flip, got {spec!r}")
-            specs.append((part[0], part[1], len(part) == 3))
+            specs.append((part[0], part[1], len(part) == 3, None))
         players, motions = [], []
-        for cfg_path, motion_path, _ in specs:
-            configs, params, hand_layer, motion = load(cfg_path, motion_path)
+        for cfg_path, motion_path, _, keypoints_path in specs:
+            configs, params, hand_layer, motion = load(cfg_path, motion_path, keypoints_path)
             players.append(AvatarPlayer(configs, params, hand_layer, batch_size=args.batch_size, ss=args.ss, device=args.device, keep_depth=True))
             motions.append(motion)
-        scene = ScenePlayer(players, flip=[f for _, _, f in specs])
+        scene = ScenePlayer(players, flip=[f for _, _, f, _ in specs])
         paths = scene.play(motions, args.out, backgrounds=args.background, scene_depth=args.scene_depth, fmt=fmt, alpha=args.alpha, masks=args.masks)
     print(f"wrote {len(paths)} frames to {args.out}")
     return paths

@@ -1087,6 +1087,36 @@ int harp_composite_layers_u8(const harp_layer* layers, int n_layers, int B, int 
                              const int32_t* scene_rows, const unsigned char* bg, int n_bg, const int32_t* bg_rows, const float* bg_color,
                              int channels, unsigned char* out, unsigned char* owner, hipStream_t stream);
 
+/* ---- batched MANO inverse kinematics: 3-D keypoints -> pose rows (csrc/ik.hip; playback.py Motion.from_keypoints) ----
+ * Nothing in the reference does this: its change_pose takes another sequence's parameters.  The model inverted is harp_lbs_mano_fwd's.
+ * T independent Levenberg-Marquardt solves in one launch, forward only, no workspace, no allocation, no synchronisation, no atomics
+ * (capturable; a repeated call gives the same bits).  Unknowns per frame x = [rot 3 | pose 45 | trans 3] = the rows of pose48 and trans
+ * as harp_lbs_mano_fwd takes them; the shape is given: betas (10,) for all frames, or (T,10) with betas_per_frame != 0.
+ *   j(x) (21,3) metres = harp_lbs_mano_fwd's joints / 1000.
+ *   C(x) = sum_k w_k |j_k(x) - t_k|^2 + prior_weight sum_i (pose_i - prior_i)^2; targets (T,21,3) metres; weights (T,21) or NULL (ones);
+ *   prior (T,45) or NULL (zeros: the model's mean pose).  A joint is USED when w_k > 0 and its three target coordinates are finite; an
+ *   unused joint's target never enters arithmetic.
+ *   Iteration, exactly `iters` times: J = the exact 63 x 51 derivative of j at x; A = J^T W J + P, g = J^T W r + P (x - prior), P =
+ *   prior_weight on the 45 pose diagonals; (A + lambda diag A) d = -g by a Cholesky factorisation of the matrix scaled from both sides by
+ *   1 / sqrt(A_ii (1 + lambda)); x' = x + d; C(x') < C(x): accept, lambda = max(0.1 lambda, 1e-9); otherwise (a NaN included, and a
+ *   non-positive or non-finite pivot or diagonal) keep x, lambda = min(10 lambda, 1e6).  lambda starts at lambda0.
+ * In/out: pose48 (T,48), trans (T,3).  Out: cost (T,2) = C at the input and at the result; status (T) int32 = accepted steps, or -1 for a
+ * frame with fewer than 3 used joints, which is not solved (its pose48 / trans rows are not written).  Optional out (NULL allowed):
+ * joints (T,21,3) mm and jac (T,63,51) (metres per unit of x) at the final x.  iters == 0 evaluates cost, joints and jac at the input and
+ * writes neither pose48 nor trans.
+ * HARP_ERR_ARG before any launch: m, opt, betas, targets, pose48, trans, cost or status NULL; T <= 0; iters < 0; lambda0 or prior_weight
+ * negative or not finite.  harp_mano_ik_frames_per_block: the frames one workgroup solves (tests size their batches around it). */
+typedef struct harp_ik_options {
+  int iters;
+  float lambda0;       /* 1e-3 */
+  float prior_weight;
+  int betas_per_frame; /* 0: betas (10,); otherwise betas (T,10) */
+} harp_ik_options;
+int harp_mano_ik_frames_per_block(void);
+int harp_mano_ik(const harp_mano_model* m, const float* betas, const float* targets, const float* weights, const float* prior, int T,
+                 const harp_ik_options* opt, float* pose48, float* trans, float* cost, int32_t* status, float* joints, float* jac,
+                 hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
