@@ -346,3 +346,7 @@ class IkOptions(ctypes.Structure):
 # batched MANO inverse kinematics (csrc/ik.hip)
 SIGNATURES["harp_mano_ik_frames_per_block"] = (_i, [])
 SIGNATURES["harp_mano_ik"] = (_i, [_mp, _vp, _vp, _vp, _vp, _i, ctypes.POINTER(IkOptions), _vp, _vp, _vp, _vp, _vp, _vp, _vp])
+
+# motion smoothing: the confidence-weighted rotation-aware window filter (csrc/filter.hip)
+FILTER_MAX_RADIUS = 64                                     # HARP_FILTER_MAX_RADIUS
+SIGNATURES["harp_motion_filter"] = (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp])

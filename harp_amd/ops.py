@@ -1104,6 +1104,83 @@ def motion_resample(keys, times, n_rot, rot_offset=None):
     return out
 
 
+FILTER_MAX_RADIUS = _lib.FILTER_MAX_RADIUS
+FILTER_MAX_ITERS = 8
+
+
+def gaussian_taps(sigma, radius=None):
+    """The taps of a Gaussian window by distance, exp(-d^2 / (2 sigma^2)) for d = 0 .. radius, as a host list (motion_filter normalises by
+    the weights it actually uses).  radius defaults to ceil(3 sigma) and is capped at FILTER_MAX_RADIUS (64)."""
+    import math
+    sigma = float(sigma)
+    if not (sigma > 0 and math.isfinite(sigma)):
+        raise ValueError(f"sigma must be positive and finite, got {sigma}")
+    if radius is None:
+        radius = min(int(math.ceil(3.0 * sigma)), FILTER_MAX_RADIUS)
+    radius = int(radius)
+    if not 0 <= radius <= FILTER_MAX_RADIUS:
+        raise ValueError(f"radius in 0..{FILTER_MAX_RADIUS}, got {radius}")
+    return [math.exp(-0.5 * (d / sigma) ** 2) for d in range(radius + 1)]
+
+
+def _filter_taps(taps):
+    """a host sequence of R + 1 finite, non-negative taps with taps[0] > 0 -> list of floats"""
+    import math
+    if torch.is_tensor(taps) or isinstance(taps, (str, bytes)):
+        raise TypeError("motion_filter takes its taps as a host sequence of numbers (gaussian_taps), not a tensor")
+    taps = [float(v) for v in taps]
+    if not 1 <= len(taps) <= FILTER_MAX_RADIUS + 1:
+        raise ValueError(f"1..{FILTER_MAX_RADIUS + 1} taps (radius 0..{FILTER_MAX_RADIUS}), got {len(taps)}")
+    if not all(math.isfinite(v) and v >= 0 for v in taps) or not taps[0] > 0:
+        raise ValueError("taps must be finite and non-negative, and taps[0] positive")
+    return taps
+
+
+def motion_filter(rows, n_rot, n_vec, taps, weights=None, segment=None, trim=None, rot_offset=None, iters=2):
+    """A confidence-weighted, rotation-aware window filter over the rows of a motion (csrc/filter.hip: harp_motion_filter, whose contract
+    include/harp_hip.h states), forward only: rows (T, 3 n_rot + 3 n_vec + n_lin) float32 = n_rot axis-angle triples, n_vec 3-vectors, then
+    n_lin scalars -> (out of the same shape, used (T, nch) int32: the samples in each channel's final mean, -1 for antipodal rotations).
+    taps: R + 1 window taps by distance, a HOST sequence (gaussian_taps); the window shrinks symmetrically at the ends of the clip and
+    where `segment` (T,) int32 changes.  weights: None, (T,) or (T, nch) float32 confidences (<= 0 or not finite: the sample is not used).
+    trim: None or (nch,) float32, > 0 switches on the trimmed second pass of that channel (radians for a rotation).  Rotations are averaged
+    on the manifold after rot_offset (3 n_rot,) — the model's pose mean — has been added, with `iters` (0..8) geodesic-mean iterations."""
+    _playback_input("motion_filter", rows, weights, segment, trim, rot_offset)
+    n_rot, n_vec, iters = int(n_rot), int(n_vec), int(iters)
+    taps = _filter_taps(taps)
+    if rows.dtype != torch.float32 or any(t is not None and t.dtype != torch.float32 for t in (weights, trim, rot_offset)):
+        raise TypeError("motion_filter takes float32 tensors")
+    if segment is not None and segment.dtype != torch.int32:
+        raise TypeError(f"segment must be int32, got {segment.dtype}")
+    if rows.dim() != 2 or n_rot < 0 or n_vec < 0 or rows.shape[1] < 3 * (n_rot + n_vec) or rows.shape[1] == 0 or rows.shape[0] < 1:
+        raise ValueError(f"motion_filter takes rows (T, 3 n_rot + 3 n_vec + n_lin), got {tuple(rows.shape)} with n_rot = {n_rot}, n_vec = {n_vec}")
+    if not 0 <= iters <= FILTER_MAX_ITERS:
+        raise ValueError(f"iters in 0..{FILTER_MAX_ITERS}, got {iters}")
+    T, W = rows.shape
+    n_lin = W - 3 * (n_rot + n_vec)
+    nch = n_rot + n_vec + n_lin
+    if weights is not None and tuple(weights.shape) not in ((T,), (T, nch)):
+        raise ValueError(f"weights must be ({T},) or ({T}, {nch}), got {tuple(weights.shape)}")
+    if segment is not None and tuple(segment.shape) != (T,):
+        raise ValueError(f"segment must be ({T},), got {tuple(segment.shape)}")
+    if trim is not None and tuple(trim.shape) != (nch,):
+        raise ValueError(f"trim must be ({nch},), got {tuple(trim.shape)}")
+    if rot_offset is not None and tuple(rot_offset.shape) != (3 * n_rot,):
+        raise ValueError(f"rot_offset must be ({3 * n_rot},), got {tuple(rot_offset.shape)}")
+    c = lambda t: None if t is None else t.detach().contiguous()      # noqa: E731
+    rows, weights, segment, trim = c(rows), c(weights), c(segment), c(trim)
+    off = None if n_rot == 0 else c(rot_offset)
+    w_cols = 0 if weights is None else (1 if weights.dim() == 1 else nch)
+    taps_dev = torch.tensor(taps, dtype=torch.float32).to(rows.device)
+    out = torch.empty(T, W, dtype=torch.float32, device=rows.device)
+    used = torch.empty(T, nch, dtype=torch.int32, device=rows.device)
+    with torch.cuda.device(rows.device):
+        rc = _lib.lib().harp_motion_filter(_lib.ptr(rows), T, n_rot, n_vec, n_lin, _lib.ptr(off), _lib.ptr(taps_dev), len(taps) - 1,
+                                           _lib.ptr(weights), w_cols, _lib.ptr(segment), _lib.ptr(trim), iters, _lib.ptr(out), _lib.ptr(used),
+                                           _lib.stream())
+    _lib.check(rc, "harp_motion_filter")
+    return out, used
+
+
 def resolve_u8(rgb, face_id, ss=1, background=None, bg_rows=None, bg_color=(1, 1, 1), alpha=False, out=None):
     """A supersampled render over a background as finished 8-bit frames (csrc/playback.hip: harp_resolve_u8), forward only: rgb
     (B, S ss, S ss, 3) float32 and face_id (B, S ss, S ss) int32 (>= 0: covered) -> (B,S,S,3) uint8, or (B,S,S,4) with alpha=True (alpha =

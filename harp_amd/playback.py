@@ -13,6 +13,10 @@ of mirrored frames) and tests against an optional scene depth.
 
     python -m harp_amd.playback --config CFG (--motion MOTION.npz | --keypoints KP.npz) --out DIR [--fps-scale X] [--ss 2] [--background DIR] [--alpha]
                                 [--flip] [--also CFG:MOTION[:flip]]... [--scene-depth DIR] [--masks]
+                                [--smooth SIGMA [--smooth-trim RAD]] [--smooth-keypoints SIGMA]
+
+`Motion.smooth` and `smooth_keypoints` take the jitter out of a motion or of the keypoints it is solved from (ops.motion_filter,
+csrc/filter.hip): a confidence-weighted window filter that averages rotations on the manifold; `motion_jitter` measures it.
 """
 import ctypes
 import os
@@ -61,7 +65,7 @@ class Motion:
 
     @classmethod
     def from_keypoints(cls, keypoints, params, hand_layer, cam=None, weights=None, match_bone_lengths=True, iters=15, prior_weight=1e-5,
-                       init=None, device=None):
+                       init=None, device=None, smooth=None):
         """A motion from 3-D keypoints (a hand tracker, a mocap glove, a dataset) by batched inverse kinematics on the device
         (ops.mano_ik, csrc/ik.hip).  keypoints (T,21,3) in metres, in the model's order — wrist, then thumb, index, middle,
         ring and little, each from root to tip — and in the frame of the fit's `joints`; a joint with a non-finite coordinate or a weight
@@ -71,7 +75,10 @@ class Motion:
         init= takes a Motion of equal length instead as a warm start.  match_bone_lengths scales the keypoints about their wrist so that
         their chain bones sum to the model's (bone_length_scale): someone else's hand can drive the avatar.  prior_weight pulls the
         finger pose to the model's mean pose, which decides what the keypoints leave open (the twist of a finger's last bone).
-        Every frame is solved on its own and nothing is smoothed over time: filter jittery keypoints BEFORE they come here.
+        Every frame is solved on its own.  smooth: None, or the sigma in frames of a Gaussian window that the keypoints go through first
+        (smooth_keypoints, with `weights` as the confidences, before the bone-length scale): jitter is taken out and a joint that a
+        tracker dropped for a few frames is filled from its neighbours and then counts as used; Motion.smooth filters the solved rows
+        instead.  None leaves the keypoints as they came.
         The result carries no light: AvatarPlayer.load_motion then uses the fit's row 0.  device: where the solve runs (default: the
         device of params["shape"] when that is a HIP device, else "cuda").  The SMPL-X arm needs a solver for its kinematic tree and raises
         NotImplementedError."""
@@ -94,6 +101,11 @@ class Motion:
             w = w.astype(np.float64)
         if init is not None and (not isinstance(init, Motion) or len(init) != T):
             raise ValueError(f"init must be a Motion of {T} frames")
+        dev = torch.device(device if device is not None else (params["shape"].device if params["shape"].is_cuda else "cuda"))
+        if smooth is not None:
+            kp_s, filled = smooth_keypoints(kp, weights=w, sigma=smooth, device=dev)
+            kp = kp_s.cpu().numpy().astype(np.float64)                           # (a joint with nothing in its window comes back as it went in)
+            w = None if w is None else np.where((filled.cpu().numpy() > 0) & ~(w > 0), 1.0, w)      # a filled joint counts as used
         cam = params["cam"][0] if cam is None else cam
         cam = np.asarray(cam.detach().cpu() if torch.is_tensor(cam) else cam, dtype=np.float32)
         if cam.shape not in ((3,), (T, 3)):
@@ -112,7 +124,6 @@ class Motion:
         else:
             rot, trans, pose = init.rot.cpu().numpy(), init.trans.cpu().numpy(), init.pose.cpu().numpy()
         from .manopth.manolayer import ManoDeviceModel
-        dev = torch.device(device if device is not None else (params["shape"].device if params["shape"].is_cuda else "cuda"))
         up = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
         dm = ManoDeviceModel(hand_layer._model_np, dev)
         res = ops.mano_ik(dm, up(shape), up(kp), up(np.concatenate([rot, pose], 1)), up(trans), weights=None if w is None else up(w),
@@ -145,6 +156,113 @@ class Motion:
         pose, trans, cam = next(c), next(c), next(c)
         light = next(c) if self.light_positions is not None else None
         return Motion(pose, rot, trans, cam, wrist, light)
+
+    def smooth(self, hand_layer, sigma=2.0, radius=None, weights=None, segments=None, trim_rot=None, trim_vec=None, iters=2, fields=None,
+               device="cuda"):
+        """The motion with its jitter taken out by a Gaussian window of `sigma` frames (radius: ceil(3 sigma)) on the device
+        (ops.motion_filter), as a new Motion of equal length.  rot, wrist_pose and pose are filtered as ROTATIONS (the
+        weighted geodesic mean of the window, `iters` iterations) with the model's pose mean as the offset, exactly as `resample` assembles
+        them; trans and light_positions as 3-vectors; cam as three scalars — cam[0] is an inverse depth and is averaged as stored.
+        weights: None or (T,) confidences per frame (<= 0 or not finite: the frame is not used and is filled from its neighbours).
+        segments: None or (T,) integer clip ids; a window never crosses a change, and it shrinks symmetrically there and at the ends.
+        trim_rot (radians) / trim_vec (the unit of trans): a sample farther than that from the window's first estimate is left out of a
+        second one — a one-frame spike does not leak into its neighbours.  fields: the names to filter (default: all the motion has);
+        the others pass through bit for bit."""
+        names = [k for k in self.FIELDS if getattr(self, k) is not None]
+        fields = names if fields is None else list(fields)
+        if any(k not in names for k in fields):
+            raise ValueError(f"fields must be among {names}, got {fields}")
+        dev = torch.device(device)
+        T, wrist, light = len(self), self.wrist_pose is not None, self.light_positions is not None
+        rots = [self.rot] + ([self.wrist_pose] if wrist else []) + [self.pose]
+        vecs = [self.trans] + ([self.light_positions] if light else [])
+        rows = torch.cat([t.to(dev) for t in rots + vecs + [self.cam]], 1).contiguous()
+        n_rot, n_vec = 16 + wrist, 1 + light
+        off = torch.as_tensor(pose_mean_rows(hand_layer, wrist), dtype=torch.float32).to(dev)
+        trim = None
+        if trim_rot is not None or trim_vec is not None:
+            trim = torch.tensor([float(trim_rot or 0.0)] * n_rot + [float(trim_vec or 0.0)] * n_vec + [0.0] * 3, dtype=torch.float32).to(dev)
+        w = None
+        if weights is not None:
+            w = torch.as_tensor(np.asarray(weights) if not torch.is_tensor(weights) else weights).detach().to(torch.float32)
+            if tuple(w.shape) != (T,):
+                raise ValueError(f"weights must be ({T},), got {tuple(w.shape)}")
+            w = w.contiguous().to(dev)
+        seg = None if segments is None else _segment_ids(segments, T).to(dev)
+        out, _ = ops.motion_filter(rows, n_rot, n_vec, ops.gaussian_taps(sigma, radius), weights=w, segment=seg, trim=trim, rot_offset=off, iters=iters)
+        c = iter(out.split([3] + ([3] if wrist else []) + [45, 3] + ([3] if light else []) + [3], 1))
+        got = dict(rot=next(c))
+        if wrist:
+            got["wrist_pose"] = next(c)
+        got["pose"], got["trans"] = next(c), next(c)
+        if light:
+            got["light_positions"] = next(c)
+        got["cam"] = next(c)
+        pick = lambda k: None if getattr(self, k) is None else (got[k] if k in fields else getattr(self, k).clone())      # noqa: E731
+        return Motion(pick("pose"), pick("rot"), pick("trans"), pick("cam"), pick("wrist_pose"), pick("light_positions"))
+
+
+def _segment_ids(segments, T):
+    s = torch.as_tensor(np.asarray(segments.cpu() if torch.is_tensor(segments) else segments))
+    if s.dim() != 1 or s.shape[0] != T or s.is_floating_point() or s.dtype == torch.bool:
+        raise ValueError(f"segments must be ({T},) integers, got {s.dtype} {tuple(s.shape)}")
+    return s.to(torch.int32).contiguous()
+
+
+def smooth_keypoints(keypoints, weights=None, sigma=2.0, radius=None, trim=None, segments=None, device="cuda"):
+    """(T,21,3) keypoints through the window filter as 21 vector channels (ops.motion_filter) -> (keypoints (T,21,3) float32,
+    used (T,21) int32), both on `device`.  weights: None or (T,21) confidences.  A joint with a non-finite coordinate or a weight <= 0 has
+    weight 0: it does not pull on its neighbours and is FILLED from them when any lie in the window (used > 0); with none it comes back as
+    it went in (used == 0).  trim: None or a distance in the keypoints' unit for the trimmed second pass; segments: as Motion.smooth."""
+    kp = torch.as_tensor(np.asarray(keypoints) if not torch.is_tensor(keypoints) else keypoints).detach()
+    if kp.dim() != 3 or tuple(kp.shape[1:]) != (21, 3) or kp.shape[0] < 1 or not kp.is_floating_point():
+        raise ValueError(f"keypoints must be floating point (T, 21, 3), got {kp.dtype} {tuple(kp.shape)}")
+    T = kp.shape[0]
+    dev = torch.device(device)
+    kp = kp.to(torch.float32)
+    ok = torch.isfinite(kp).all(-1)
+    if weights is None:
+        w = ok.to(torch.float32)
+    else:
+        w = torch.as_tensor(np.asarray(weights) if not torch.is_tensor(weights) else weights).detach()
+        if tuple(w.shape) != (T, 21) or not w.is_floating_point():
+            raise ValueError(f"weights must be floating point ({T}, 21), got {w.dtype} {tuple(w.shape)}")
+        w = w.to(torch.float32).to(kp.device)
+        w = torch.where(ok & (w > 0) & torch.isfinite(w), w, torch.zeros_like(w))
+    tr = None if trim is None else torch.full((21,), float(trim), dtype=torch.float32).to(dev)
+    seg = None if segments is None else _segment_ids(segments, T).to(dev)
+    out, used = ops.motion_filter(kp.reshape(T, 63).contiguous().to(dev), 0, 21, ops.gaussian_taps(sigma, radius), weights=w.contiguous().to(dev),
+                                  segment=seg, trim=tr)
+    return out.reshape(T, 21, 3), used
+
+
+def motion_jitter(motion, params, hand_layer, other=None):
+    """How much a motion shakes, from the joints of the layer's forward at the avatar's shape (plain torch on the layer's output):
+    dict(accel_mean_mm, accel_max_mm) = the mean and the largest joint acceleration |j[t+1] - 2 j[t] + j[t-1]| in millimetres per frame^2
+    (0 for fewer than three frames); with `other`, a second Motion of equal length, also disp_mean_mm / disp_max_mm = the mean and the
+    largest distance between the two motions' joints."""
+    dev = params["shape"].device
+
+    def joints(m):
+        B = len(m)
+        betas = params["shape"].detach().reshape(1, -1).expand(B, -1).contiguous()
+        with torch.no_grad():
+            if "pose_mean" in hand_layer._model_np:          # the SMPL-X arm
+                if m.wrist_pose is None:
+                    raise ValueError("the arm model needs a motion with wrist_pose")
+                return hand_layer(betas=betas, global_orient=m.rot.to(dev), transl=m.trans.to(dev), right_hand_pose=m.pose.to(dev),
+                                  right_wrist_pose=m.wrist_pose.to(dev))[1]
+            return hand_layer(torch.cat([m.rot, m.pose], 1).to(dev), betas, m.trans.to(dev))[1]
+
+    j = joints(motion)
+    acc = (j[2:] - 2.0 * j[1:-1] + j[:-2]).norm(dim=-1) if len(motion) >= 3 else torch.zeros(1, device=j.device)
+    res = dict(accel_mean_mm=float(acc.mean()), accel_max_mm=float(acc.max()))
+    if other is not None:
+        if len(other) != len(motion):
+            raise ValueError(f"the two motions must have one length, got {len(motion)} and {len(other)}")
+        d = (joints(other) - j).norm(dim=-1)
+        res.update(disp_mean_mm=float(d.mean()), disp_max_mm=float(d.max()))
+    return res
 
 
 def pose_mean_rows(hand_layer, with_wrist):
@@ -817,7 +935,22 @@ def main(argv=None):
     ap.add_argument("--scene-depth", default=None, help="directory of .npy float32 (img_size, img_size) depth maps in metres or 16-bit PNGs in "
                                                         "millimetres, 0 = no measurement (cycled): what is nearer hides the avatars")
     ap.add_argument("--masks", action="store_true", help="also write mask_%%04d.png: 0 background, 1 + the avatar that owns the pixel")
+    ap.add_argument("--smooth", type=float, default=None, metavar="SIGMA",
+                    help="filter the loaded or solved motion with a Gaussian window of SIGMA frames before --fps-scale (Motion.smooth); prints the "
+                         "joint jitter before and after")
+    ap.add_argument("--smooth-trim", type=float, default=None, metavar="RAD",
+                    help="with --smooth: leave a rotation farther than RAD radians from its window's estimate out of a second estimate (spikes)")
+    ap.add_argument("--smooth-keypoints", type=float, default=None, metavar="SIGMA",
+                    help="with --keypoints: filter the keypoints with a Gaussian window of SIGMA frames before the solve, filling dropped joints")
     args = ap.parse_args(argv)
+    for name in ("smooth", "smooth_trim", "smooth_keypoints"):
+        v = getattr(args, name)
+        if v is not None and not v > 0:
+            raise SystemExit(f"--{name.replace('_', '-')} must be positive")
+    if args.smooth_trim is not None and args.smooth is None:
+        raise SystemExit("--smooth-trim needs --smooth")
+    if args.smooth_keypoints is not None and args.keypoints is None:
+        raise SystemExit("--smooth-keypoints needs --keypoints")
     if len(args.also) > ops.COMPOSITE_MAX_LAYERS - 1:
         raise SystemExit(f"--also at most {ops.COMPOSITE_MAX_LAYERS - 1} times")
     if args.fps_scale <= 0:
@@ -835,9 +968,17 @@ def main(argv=None):
         if keypoints_path is not None:
             with np.load(keypoints_path) as z:
                 motion = Motion.from_keypoints(z["keypoints"], params, hand_layer, cam=z["cam"] if "cam" in z.files else None,
-                                               weights=z["weights"] if "weights" in z.files else None, device=args.device)
+                                               weights=z["weights"] if "weights" in z.files else None, device=args.device,
+                                               smooth=args.smooth_keypoints)
         else:
             motion = Motion.load(motion_path)
+        if args.smooth is not None:
+            raw = motion
+            motion = raw.smooth(hand_layer, sigma=args.smooth, trim_rot=args.smooth_trim, device=args.device)
+            before, after = motion_jitter(raw, params, hand_layer), motion_jitter(motion, params, hand_layer, other=raw)
+            print(f"smoothed {len(motion)} frames (sigma {args.smooth:g}): joint acceleration mean {before['accel_mean_mm']:.3f} -> "
+                  f"{after['accel_mean_mm']:.3f} mm/frame^2, largest {before['accel_max_mm']:.3f} -> {after['accel_max_mm']:.3f}; joints moved "
+                  f"{after['disp_mean_mm']:.3f} mm on average, {after['disp_max_mm']:.3f} at most")
         if args.fps_scale != 1.0:
             n = max(1, int(round((len(motion) - 1) * args.fps_scale)) + 1)
             motion = motion.resample(np.linspace(0, len(motion) - 1, n), hand_layer, device=args.device)

@@ -1117,6 +1117,40 @@ int harp_mano_ik(const harp_mano_model* m, const float* betas, const float* targ
                  const harp_ik_options* opt, float* pose48, float* trans, float* cost, int32_t* status, float* joints, float* jac,
                  hipStream_t stream);
 
+/* ---- motion smoothing: a confidence-weighted, rotation-aware window filter (csrc/filter.hip; playback.py Motion.smooth, smooth_keypoints;
+ * DESIGN.md §25) ----
+ * Nothing in the reference does this on the device (its preprocessing removes one-frame jumps of `pose` on the host and otherwise runs an
+ * Adam loop over the sequence).  rows (T, W): per row n_rot axis-angle triples | n_vec 3-vectors | n_lin scalars; nch = n_rot + n_vec +
+ * n_lin channels, W = 3 (n_rot + n_vec) + n_lin columns.  Out: out (T, W) and used (T, nch) int32.  Forward only; one launch, no
+ * workspace, no allocation, no synchronisation, no atomics, no data-dependent exit: two calls give the same bits and the launch can be
+ * captured (one kernel node).  Per output row t and channel j:
+ *   window: R_t = the largest d <= R such that every row t - d' and t + d', d' <= d, lies in [0, T) and has segment == segment[t]
+ *     (segment (T) int32 or NULL: one segment).  The window shrinks on BOTH sides, so a track that is linear in time is reproduced and the
+ *     ends of a clip are not pulled along its slope.  Samples are visited in a fixed order — the centre, then d = 1 .. R_t with t - d before
+ *     t + d — and every sum below runs in that order, in float32.
+ *   sample weights: a_s = taps[|s - t|] c_s in float32, taps (R + 1) by distance; c_s = 1 when weights == NULL (w_cols 0), weights[s]
+ *     (w_cols 1) or weights[s nch + j] (w_cols nch).  A tap, a weight or their product that is negative or not finite counts as 0.  A
+ *     sample with a_s == 0 or a non-finite value in the channel's columns is UNUSED and never enters arithmetic.
+ *   copies: no used sample: the input is copied bit for bit, used = 0.  The centre the only used sample: the input is copied bit for bit,
+ *     used = 1 (R == 0 is the identity).
+ *   scalar and vector channels: m = sum a_s v_s / sum a_s.  With trim != NULL and trim[j] > 0 the samples with |v_s - m| > trim[j]
+ *     (Euclidean for a 3-vector) are left out and, when some but not all remain, m is that mean over the rest.
+ *   rotation channels: q_s = quat(triple_s + offset), offset = rot_offset[3 j ..] (rot_offset (3 n_rot) or NULL: zero — MANO's finger rows
+ *     are stored relative to hands_mean, harp_motion_resample's rot_offset), with sin(th/2)/th = 0.5 - th^2/48 below th = 1e-4.  Every q_s
+ *     whose dot with the FIRST used sample's quaternion is negative is negated.  S = sum a_s q_s; |S| < 1e-6 sum a_s (antipodal samples):
+ *     the input is copied, used = -1.  mu = S / |S|; then exactly `iters` times v = sum a_s log(mu^-1 q_s) / sum a_s, mu <- mu exp(v), with
+ *     log(q) taken with w >= 0 as 2 atan2(|v|, w) v / |v| (2 v when |v| < 1e-8) and exp = quat.  With trim[j] > 0 the samples farther than
+ *     trim[j] radians from mu (|log(mu^-1 q_s)|) are left out and, when some but not all remain, the estimate is computed again from scratch
+ *     over them (a vanishing chordal sum there copies the input with used = -1 as well).  out = log(mu) - offset.
+ *   trimming that would leave no sample leaves the first estimate; used = the number of samples in the final mean.
+ * HARP_ERR_ARG before any launch: rows, taps, out or used NULL; T <= 0; a negative n_rot, n_vec or n_lin; nch == 0; R outside
+ * 0..HARP_FILTER_MAX_RADIUS; iters outside 0..8; weights == NULL with w_cols != 0, or weights != NULL with w_cols not 1 or nch; T W beyond
+ * the range of an int.  Every gather is row t - d or t + d after 0 <= t - d and t + d < T. */
+#define HARP_FILTER_MAX_RADIUS 64
+int harp_motion_filter(const float* rows, int T, int n_rot, int n_vec, int n_lin, const float* rot_offset, const float* taps, int R,
+                       const float* weights, int w_cols, const int32_t* segment, const float* trim, int iters, float* out, int32_t* used,
+                       hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
