@@ -1,0 +1,30 @@
+"""Playback of a fitted avatar: drive it with a motion it was not fitted on, at an output frame rate of the caller's choice, and composite
+it over a video or a plain background as finished 8-bit frames.  Stands in for the reference's `change_pose`
+(utils/visualize.py:111-143) and the render calls of :258-320 followed by the host-side `(img * 255).astype(np.uint8)`.
+
+The package in four modules, each importing only those before it:
+
+  keypoints  the float64 host side of the keypoint solve: rest joints, bone-length scale, Kabsch start, `ik_inputs`; and `checked`, the
+             one coercion of a caller's tensor or array-like
+  motion     `Motion` (the per-frame rows), `RowLayout` (their one packed table), `Motion.resample` (ops.motion_resample),
+             `Motion.from_keypoints` (ops.mano_ik), `Motion.smooth` / `smooth_keypoints` (ops.motion_filter), `motion_jitter`
+  player     `AvatarPlayer`, the forward-only renderer — the fit's own fused front, rasterisers and shader without a backward, then
+             harp_resolve_u8: six calls of the C ABI per batch of frames, in order on one stream, captured into a graph — and `ScenePlayer`,
+             several such avatars in one frame through ONE harp_composite_layers_u8 per batch; both on `_Player`, which owns staging,
+             graphs and the way to disk
+  cli        `main`:
+
+    python -m harp_amd.playback --config CFG (--motion MOTION.npz | --keypoints KP.npz) --out DIR [--fps-scale X] [--ss 2] [--background DIR] [--alpha]
+                                [--flip] [--also CFG:MOTION[:flip]]... [--scene-depth DIR] [--masks]
+                                [--smooth SIGMA [--smooth-trim RAD]] [--smooth-keypoints SIGMA]
+
+Importing the package needs neither the built library nor a device.
+"""
+from .cli import main
+from .keypoints import CHAIN_BONES, JOINT_REORDER, PALM, axis_angle_of, bone_length_scale, kabsch_rotation, palm_start, rest_chain_joints
+from .motion import Motion, motion_jitter, pose_mean_rows, smooth_keypoints
+from .player import BG_WHITE, AvatarPlayer, ScenePlayer, load_backgrounds, load_scene_depth
+
+__all__ = ["Motion", "AvatarPlayer", "ScenePlayer", "smooth_keypoints", "motion_jitter", "pose_mean_rows", "rest_chain_joints",
+           "bone_length_scale", "kabsch_rotation", "axis_angle_of", "palm_start", "JOINT_REORDER", "PALM", "CHAIN_BONES", "load_backgrounds",
+           "load_scene_depth", "main", "BG_WHITE"]

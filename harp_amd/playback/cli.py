@@ -1,0 +1,104 @@
+"""The command line of the playback package: python -m harp_amd.playback (the package's docstring lists the options)."""
+import numpy as np
+
+from .. import ops
+from .motion import Motion, motion_jitter
+from .player import AvatarPlayer, ScenePlayer
+
+
+def main(argv=None):
+    """A fit (the saved_params[_test].pkl under the config's base_output_dir, as the evaluation reads it) plus a motion file -> a directory
+    of frames."""
+    import argparse
+    import yaml
+    from . import __doc__ as package_doc
+    from ..utils import file_utils, hand_model_utils
+    from ..utils.config_utils import get_config
+    ap = argparse.ArgumentParser(prog="python -m harp_amd.playback", description=package_doc.split("\n\n")[0])
+    ap.add_argument("--config", required=True, help="yaml with the keys of utils/config_utils.get_config (the fit's)")
+    ap.add_argument("--motion", default=None, help=".npz of pose (T,45), rot, trans, cam (T,3) [, wrist_pose, light_positions] (Motion.save)")
+    ap.add_argument("--keypoints", default=None, help=".npz of keypoints (T,21,3) in metres [, weights (T,21), cam (3,) or (T,3)] instead of --motion: "
+                                                      "the motion is solved from them (Motion.from_keypoints)")
+    ap.add_argument("--out", required=True, help="directory for the frames %%04d.jpg / %%04d.png")
+    ap.add_argument("--fps-scale", type=float, default=1.0, help="output frames per motion frame (2: twice as many frames, half the speed)")
+    ap.add_argument("--ss", type=int, default=1, help="supersampling factor 1..4")
+    ap.add_argument("--background", default=None, help="directory of img_size x img_size images to composite over (cycled)")
+    ap.add_argument("--alpha", action="store_true", help="RGBA PNGs with the coverage as alpha")
+    ap.add_argument("--batch-size", type=int, default=32)
+    ap.add_argument("--device", default="cuda")
+    ap.add_argument("--flip", action="store_true", help="show the avatar mirrored in x: a left hand is a right-hand fit of mirrored frames")
+    ap.add_argument("--also", action="append", default=[], metavar="CFG:MOTION[:flip]",
+                    help="a further avatar with its own fit and motion in the same frames, nearest surface in front (up to three times)")
+    ap.add_argument("--scene-depth", default=None, help="directory of .npy float32 (img_size, img_size) depth maps in metres or 16-bit PNGs in "
+                                                        "millimetres, 0 = no measurement (cycled): what is nearer hides the avatars")
+    ap.add_argument("--masks", action="store_true", help="also write mask_%%04d.png: 0 background, 1 + the avatar that owns the pixel")
+    ap.add_argument("--smooth", type=float, default=None, metavar="SIGMA",
+                    help="filter the loaded or solved motion with a Gaussian window of SIGMA frames before --fps-scale (Motion.smooth); prints the "
+                         "joint jitter before and after")
+    ap.add_argument("--smooth-trim", type=float, default=None, metavar="RAD",
+                    help="with --smooth: leave a rotation farther than RAD radians from its window's estimate out of a second estimate (spikes)")
+    ap.add_argument("--smooth-keypoints", type=float, default=None, metavar="SIGMA",
+                    help="with --keypoints: filter the keypoints with a Gaussian window of SIGMA frames before the solve, filling dropped joints")
+    args = ap.parse_args(argv)
+    for name in ("smooth", "smooth_trim", "smooth_keypoints"):
+        v = getattr(args, name)
+        if v is not None and not v > 0:
+            raise SystemExit(f"--{name.replace('_', '-')} must be positive")
+    if args.smooth_trim is not None and args.smooth is None:
+        raise SystemExit("--smooth-trim needs --smooth")
+    if args.smooth_keypoints is not None and args.keypoints is None:
+        raise SystemExit("--smooth-keypoints needs --keypoints")
+    if len(args.also) > ops.COMPOSITE_MAX_LAYERS - 1:
+        raise SystemExit(f"--also at most {ops.COMPOSITE_MAX_LAYERS - 1} times")
+    if args.fps_scale <= 0:
+        raise SystemExit("--fps-scale must be positive")
+    if (args.motion is None) == (args.keypoints is None):
+        raise SystemExit("exactly one of --motion and --keypoints")
+
+    def load(cfg_path, motion_path, keypoints_path=None):
+        with open(cfg_path) as f:
+            configs = get_config(write_yaml=False, **yaml.safe_load(f))
+        configs["device"] = args.device
+        hand_layer, VERTS_UVS, FACES_UVS, _ = hand_model_utils.load_hand_model(configs)
+        params = file_utils.load_result(configs["base_output_dir"], device=args.device, test=bool(configs["known_appearance"]))
+        params["verts_uvs"], params["faces_uvs"] = VERTS_UVS, FACES_UVS
+        if keypoints_path is not None:
+            with np.load(keypoints_path) as z:
+                motion = Motion.from_keypoints(z["keypoints"], params, hand_layer, cam=z["cam"] if "cam" in z.files else None,
+                                               weights=z["weights"] if "weights" in z.files else None, device=args.device,
+                                               smooth=args.smooth_keypoints)
+        else:
+            motion = Motion.load(motion_path)
+        if args.smooth is not None:
+            raw = motion
+            motion = raw.smooth(hand_layer, sigma=args.smooth, trim_rot=args.smooth_trim, device=args.device)
+            before, after = motion_jitter(raw, params, hand_layer), motion_jitter(motion, params, hand_layer, other=raw)
+            print(f"smoothed {len(motion)} frames (sigma {args.smooth:g}): joint acceleration mean {before['accel_mean_mm']:.3f} -> "
+                  f"{after['accel_mean_mm']:.3f} mm/frame^2, largest {before['accel_max_mm']:.3f} -> {after['accel_max_mm']:.3f}; joints moved "
+                  f"{after['disp_mean_mm']:.3f} mm on average, {after['disp_max_mm']:.3f} at most")
+        if args.fps_scale != 1.0:
+            n = max(1, int(round((len(motion) - 1) * args.fps_scale)) + 1)
+            motion = motion.resample(np.linspace(0, len(motion) - 1, n), hand_layer, device=args.device)
+        return configs, params, hand_layer, motion
+
+    fmt = "png" if args.alpha else "jpg"
+    if not (args.flip or args.also or args.scene_depth or args.masks):
+        configs, params, hand_layer, motion = load(args.config, args.motion, args.keypoints)
+        player = AvatarPlayer(configs, params, hand_layer, batch_size=args.batch_size, ss=args.ss, device=args.device)
+        paths = player.play(motion, args.out, backgrounds=args.background, fmt=fmt, alpha=args.alpha)
+    else:
+        specs = [(args.config, args.motion, args.flip, args.keypoints)]
+        for spec in args.also:
+            part = spec.split(":")
+            if len(part) not in (2, 3) or (len(part) == 3 and part[2] != "flip"):
+                raise SystemExit(f"--also takes CFG:MOTION or CFG:MOTION:flip, got {spec!r}")
+            specs.append((part[0], part[1], len(part) == 3, None))
+        players, motions = [], []
+        for cfg_path, motion_path, _, keypoints_path in specs:
+            configs, params, hand_layer, motion = load(cfg_path, motion_path, keypoints_path)
+            players.append(AvatarPlayer(configs, params, hand_layer, batch_size=args.batch_size, ss=args.ss, device=args.device, keep_depth=True))
+            motions.append(motion)
+        scene = ScenePlayer(players, flip=[f for _, _, f, _ in specs])
+        paths = scene.play(motions, args.out, backgrounds=args.background, scene_depth=args.scene_depth, fmt=fmt, alpha=args.alpha, masks=args.masks)
+    print(f"wrote {len(paths)} frames to {args.out}")
+    return paths

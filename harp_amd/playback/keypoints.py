@@ -1,0 +1,136 @@
+"""The host side of Motion.from_keypoints, numpy float64 and no device: the model's rest joints, the bone-length scale, the
+Kabsch start of the root (T problems of six points each), and `ik_inputs`, which checks what a caller passed and returns the arrays that
+ops.mano_ik is fed.  `checked` is the package's one coercion and check of a tensor or array-like that a caller passed."""
+import numpy as np
+import torch
+
+JOINT_REORDER = (0, 13, 14, 15, 16, 1, 2, 3, 17, 4, 5, 6, 18, 10, 11, 12, 19, 7, 8, 9, 20)      # output joint -> model joint / tip (manolayer.py:279)
+PALM = (0, 1, 5, 9, 13, 17)                            # output joints that only the root moves: the wrist and the five finger roots
+# the 15 chain bones in output joints: wrist -> finger root and the two bones after it; the tip bones are left out (pose correctives move the tips)
+CHAIN_BONES = tuple((0 if k == 0 else 4 * f + k, 4 * f + k + 1) for f in range(5) for k in range(3))
+
+
+def checked(name, x, *shapes, kind=None, split=False, tensor=False):
+    """A tensor or array-like -> a host array (tensor=True: a tensor instead, left on the device it is on) whose shape is one of `shapes`
+    (None: any length >= 1; no shapes: any shape) and whose dtype is of `kind` ("f": floating point, "i": integers, None: any); else a
+    ValueError that names the field.  split=True reports a dtype of the wrong kind as a TypeError of its own."""
+    if tensor:
+        a = x.detach() if torch.is_tensor(x) else torch.as_tensor(np.asarray(x))
+        kinds = {None: True, "f": a.is_floating_point(), "i": not a.is_floating_point() and a.dtype != torch.bool}
+    else:
+        a = np.asarray(x.detach().cpu() if torch.is_tensor(x) else x)
+        kinds = {None: True, "f": np.issubdtype(a.dtype, np.floating), "i": a.dtype.kind in "iu"}
+    ok_shape = not shapes or any(len(s) == len(a.shape) and all(d >= 1 if w is None else d == w for w, d in zip(s, a.shape)) for s in shapes)
+    if ok_shape and kinds[kind]:
+        return a
+    want = " or ".join(str(tuple("T" if w is None else w for w in s)).replace("'", "") for s in shapes)
+    if split and not ok_shape:
+        raise ValueError(f"{name} must be {want}, got {tuple(a.shape)}")
+    if split:
+        raise TypeError(f"{name} must be floating point, got {a.dtype}")
+    want = {None: want, "f": f"floating point {want}", "i": f"{want} integers"}[kind]
+    raise ValueError(f"{name} must be {want}, got {tuple(a.shape)}" if kind is None else f"{name} must be {want}, got {a.dtype} {tuple(a.shape)}")
+
+
+def rest_chain_joints(model, shape):
+    """the model's 21 joints in output order at `shape` BEFORE any rotation, (21,3) float64; the five tips are NaN (they depend on the
+    pose).  The wrist, the finger roots relative to it, and every chain bone's length do not depend on the finger pose."""
+    f64 = lambda k: np.asarray(model[k], np.float64)
+    v = f64("v_template").reshape(778, 3) + f64("shapedirs").reshape(778, 3, 10) @ np.asarray(shape, np.float64).reshape(10)
+    j16 = f64("J_regressor").reshape(16, 778) @ v
+    out = np.full((21, 3), np.nan)
+    for k, src in enumerate(JOINT_REORDER):
+        if src < 16:
+            out[k] = j16[src]
+    return out
+
+
+def bone_length_scale(keypoints, used, rest):
+    """the factor that makes the keypoints' 15 chain bones sum to the model's: the model's sum over the median over the frames (those with
+    all 16 chain joints used) of the keypoints' sum; 1 when there is no such frame"""
+    a, b = np.array([i for i, _ in CHAIN_BONES]), np.array([j for _, j in CHAIN_BONES])
+    model_sum = np.linalg.norm(rest[b] - rest[a], axis=-1).sum()
+    ok = used[:, np.unique(np.concatenate([a, b]))].all(1)
+    if not ok.any():
+        return 1.0
+    kp = keypoints[ok]
+    return float(model_sum / np.median(np.linalg.norm(kp[:, b] - kp[:, a], axis=-1).sum(1)))
+
+
+def kabsch_rotation(P, Q):
+    """the rotation R (det +1) that minimises sum |R p_i - q_i|^2 over two CENTRED point sets (n,3); a mirrored set gets the best proper
+    rotation, not the reflection"""
+    U, _, Vt = np.linalg.svd(np.asarray(Q, np.float64).T @ np.asarray(P, np.float64))
+    d = np.sign(np.linalg.det(U @ Vt)) or 1.0
+    return U @ np.diag([1.0, 1.0, d]) @ Vt
+
+
+def axis_angle_of(R):
+    """rotation matrix -> axis-angle with an angle in [0, pi], through the quaternion with the largest component (stable near pi)"""
+    t = np.trace(R)
+    cand = np.array([1.0 + t, 1.0 + 2 * R[0, 0] - t, 1.0 + 2 * R[1, 1] - t, 1.0 + 2 * R[2, 2] - t])
+    i = int(np.argmax(cand))
+    if i == 0:
+        q = np.array([cand[0], R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    elif i == 1:
+        q = np.array([R[2, 1] - R[1, 2], cand[1], R[0, 1] + R[1, 0], R[0, 2] + R[2, 0]])
+    elif i == 2:
+        q = np.array([R[0, 2] - R[2, 0], R[0, 1] + R[1, 0], cand[2], R[1, 2] + R[2, 1]])
+    else:
+        q = np.array([R[1, 0] - R[0, 1], R[0, 2] + R[2, 0], R[1, 2] + R[2, 1], cand[3]])
+    q = q / np.linalg.norm(q)
+    if q[0] < 0:
+        q = -q
+    vn = np.linalg.norm(q[1:])
+    return np.zeros(3) if vn < 1e-15 else 2.0 * np.arctan2(vn, q[0]) * q[1:] / vn
+
+
+def palm_start(keypoints, used, rest):
+    """rot (T,3), trans (T,3) float64 that put the model's six palm joints (PALM, which only the root rotation and trans move:
+    R (J_k - J_0) + J_0 + trans) onto the keypoints' in the least-squares sense: the Kabsch rotation, then the difference of the two
+    centroids.  A frame whose six palm joints are not all used keeps the rotation of the last frame that had them (none yet: zero) and
+    takes its trans from the palm joints it has (none: that frame's trans as well)."""
+    T = keypoints.shape[0]
+    idx = np.array(PALM)
+    P0 = rest[idx] - rest[0]                            # about the wrist, where the model rotates
+    rot, trans = np.zeros((T, 3)), np.zeros((T, 3))
+    R, aa, tr = np.eye(3), np.zeros(3), np.zeros(3)
+    for t in range(T):
+        u = used[t, idx]
+        if u.all():
+            Q = keypoints[t, idx]
+            R = kabsch_rotation(P0 - P0.mean(0), Q - Q.mean(0))
+            aa = axis_angle_of(R)
+        if u.any():
+            tr = keypoints[t, idx[u]].mean(0) - (P0[u] @ R.T + rest[0]).mean(0)
+        rot[t], trans[t] = aa, tr
+    return rot, trans
+
+
+def ik_inputs(keypoints, weights, cam, init, params, model, match_bone_lengths=True, smooth=None):
+    """What Motion.from_keypoints passes to ops.mano_ik, checked and prepared on the host: dict(shape (10,), keypoints (T,21,3), pose48
+    (T,48) = [rot | pose], trans (T,3), weights (T,21) or None, cam (T,3) float32), the others float64.  keypoints, weights, cam, init,
+    params, match_bone_lengths: as Motion.from_keypoints takes them (init: anything with a length and rot / trans / pose rows); model: the
+    hand layer's numpy model.  smooth: None or a function (keypoints, weights) -> (keypoints, used (T,21)) that filters the checked
+    keypoints before the bone-length scale; a joint it filled (used > 0) then counts as used."""
+    kp = checked("keypoints", keypoints, (None, 21, 3), kind="f", split=True).astype(np.float64)
+    T = kp.shape[0]
+    w = None if weights is None else checked("weights", weights, (T, 21), kind="f", split=True).astype(np.float64)
+    if init is not None and (not all(hasattr(init, k) for k in ("rot", "trans", "pose")) or len(init) != T):
+        raise ValueError(f"init must be a Motion of {T} frames")
+    if smooth is not None:
+        kp, filled = smooth(kp, w)                      # (a joint with nothing in its window comes back as it went in)
+        kp = np.asarray(kp, np.float64)
+        w = None if w is None else np.where((np.asarray(filled) > 0) & ~(w > 0), 1.0, w)
+    cam = np.broadcast_to(checked("cam", params["cam"][0] if cam is None else cam, (3,), (T, 3)).astype(np.float32), (T, 3)).copy()
+    shape = params["shape"].detach().cpu().numpy().astype(np.float64).reshape(10)
+    used = np.isfinite(kp).all(-1) & (True if w is None else (w > 0))
+    rest = rest_chain_joints(model, shape)
+    if match_bone_lengths:
+        wrist = kp[:, :1]                               # (no wrist: the frame stays as it is)
+        kp = np.where(np.isfinite(wrist).all(-1, keepdims=True), wrist + bone_length_scale(kp, used, rest) * (kp - wrist), kp)
+    if init is None:
+        (rot, trans), pose = palm_start(kp, used, rest), np.zeros((T, 45))
+    else:
+        rot, trans, pose = init.rot.cpu().numpy(), init.trans.cpu().numpy(), init.pose.cpu().numpy()
+    return dict(shape=shape, keypoints=kp, pose48=np.concatenate([rot, pose], 1), trans=trans, weights=w, cam=cam)

@@ -1,0 +1,217 @@
+"""The rows of a motion and what is done to them on the device: `Motion`, its retiming (ops.motion_resample), its solve
+from keypoints (ops.mano_ik, §24) and the window filter of a motion or of keypoints (ops.motion_filter, §25).  `RowLayout` is the one
+description of the packed table that the resampler and the filter read."""
+import numpy as np
+import torch
+
+from .. import ops
+from . import keypoints as K
+from .keypoints import checked
+
+
+def _rows_f32(name, a, width, T=None):
+    return checked(name, a, (T, width), tensor=True).to(torch.float32).contiguous()
+
+
+class RowLayout:
+    """A motion's rows as one table [rot | wrist_pose? | pose | trans | light_positions? | cam]: `fields` is the ordered list of (field,
+    width, kind) for the fields the motion has, kind "rot" (axis-angle triples), "vec" (a 3-vector) or "scalar"; n_rot triples come
+    first, then n_vec vectors, then cam's three scalars — what ops.motion_filter takes, and ops.motion_resample with everything behind
+    the rotations as linear channels."""
+
+    def __init__(self, motion):
+        wrist, light = motion.wrist_pose is not None, motion.light_positions is not None
+        self.motion = motion
+        self.fields = ([("rot", 3, "rot")] + [("wrist_pose", 3, "rot")] * wrist + [("pose", 45, "rot"), ("trans", 3, "vec")]
+                       + [("light_positions", 3, "vec")] * light + [("cam", 3, "scalar")])
+        self.widths = [w for _, w, _ in self.fields]
+        self.n_rot = sum(w // 3 for _, w, kind in self.fields if kind == "rot")
+        self.n_vec = sum(kind == "vec" for _, _, kind in self.fields)
+
+    def pack(self, device):
+        """the table (T, sum of the widths) float32 on `device`"""
+        return torch.cat([getattr(self.motion, k).to(device) for k, _, _ in self.fields], 1).contiguous()
+
+    def unpack(self, table):
+        """a table of this layout -> dict of every Motion field: its columns, None for a field the motion does not have"""
+        got = dict.fromkeys(Motion.FIELDS)
+        got.update(zip((k for k, _, _ in self.fields), table.split(self.widths, 1)))
+        return got
+
+    def trim(self, rot, vec):
+        """the filter's per-channel trim distances as a list: `rot` for every rotation, `vec` for every vector, 0 (off) for cam"""
+        return [float(rot or 0.0)] * self.n_rot + [float(vec or 0.0)] * self.n_vec + [0.0] * 3
+
+
+class Motion:
+    """The per-frame rows that animate an avatar: pose (T,45) MANO finger joints (relative to the model's pose mean, as the fit stores them),
+    rot, trans, cam (T,3), and optionally wrist_pose (T,3) (the arm model's wrist) and light_positions (T,3) (a light that moves with the
+    motion; without it the player keeps the fit's light).  float32 tensors, on any device."""
+
+    FIELDS = ("pose", "rot", "trans", "cam", "wrist_pose", "light_positions")
+
+    def __init__(self, pose, rot, trans, cam, wrist_pose=None, light_positions=None):
+        self.pose = _rows_f32("pose", pose, 45)
+        T = self.pose.shape[0]
+        self.rot, self.trans, self.cam = _rows_f32("rot", rot, 3, T), _rows_f32("trans", trans, 3, T), _rows_f32("cam", cam, 3, T)
+        self.wrist_pose = None if wrist_pose is None else _rows_f32("wrist_pose", wrist_pose, 3, T)
+        self.light_positions = None if light_positions is None else _rows_f32("light_positions", light_positions, 3, T)
+
+    def __len__(self):
+        return self.pose.shape[0]
+
+    @classmethod
+    def from_params(cls, params, rows=None, per_frame_light=False):
+        """The fit's own frames (all of them, or `rows` of its tables, in that order): the replay case.  The motion carries no light
+        unless per_frame_light=True: a fit with share_light_position (the default) reads and updates row 0 of its light table only, the
+        other rows keep their initial value, and the player then uses that row 0 for every frame as the fit did.  Pass
+        per_frame_light=True for a fit with share_light_position=False: its rows are the frames' lights."""
+        idx = None if rows is None else torch.as_tensor(rows).long().reshape(-1)
+        take = lambda k: None if params.get(k) is None else (params[k].detach() if idx is None else params[k].detach()[idx.to(params[k].device)]).clone()
+        return cls(take("pose"), take("rot"), take("trans"), take("cam"), take("wrist_pose"), take("light_positions") if per_frame_light else None)
+
+    @classmethod
+    def from_keypoints(cls, keypoints, params, hand_layer, cam=None, weights=None, match_bone_lengths=True, iters=15, prior_weight=1e-5,
+                       init=None, device=None, smooth=None):
+        """A motion from 3-D keypoints (a hand tracker, a mocap glove, a dataset) by batched inverse kinematics on the device
+        (ops.mano_ik, csrc/ik.hip).  keypoints (T,21,3) in metres, in the model's order — wrist, then thumb, index, middle,
+        ring and little, each from root to tip — and in the frame of the fit's `joints`; a joint with a non-finite coordinate or a weight
+        <= 0 (weights (T,21), default ones) is ignored.  params: the fit's parameter dict (its `shape` is the avatar's and is not solved;
+        row 0 of its `cam` is the default cam); cam: (3,) or (T,3).
+        The start (host, float64): pose zero, the root rotation and trans from the Kabsch fit of the model's palm joints (palm_start);
+        init= takes a Motion of equal length instead as a warm start.  match_bone_lengths scales the keypoints about their wrist so that
+        their chain bones sum to the model's (bone_length_scale): someone else's hand can drive the avatar.  prior_weight pulls the
+        finger pose to the model's mean pose, which decides what the keypoints leave open (the twist of a finger's last bone).
+        Every frame is solved on its own.  smooth: None, or the sigma in frames of a Gaussian window that the keypoints go through first
+        (smooth_keypoints, with `weights` as the confidences, before the bone-length scale): jitter is taken out and a joint that a
+        tracker dropped for a few frames is filled from its neighbours and then counts as used; Motion.smooth filters the solved rows
+        instead.  None leaves the keypoints as they came.
+        The result carries no light: AvatarPlayer.load_motion then uses the fit's row 0.  device: where the solve runs (default: the
+        device of params["shape"] when that is a HIP device, else "cuda").  The SMPL-X arm needs a solver for its kinematic tree and raises
+        NotImplementedError."""
+        if "pose_mean" in hand_layer._model_np:
+            raise NotImplementedError("Motion.from_keypoints solves the MANO hand; the SMPL-X arm needs a kinematic-tree solver")
+        dev = torch.device(device if device is not None else (params["shape"].device if params["shape"].is_cuda else "cuda"))
+        host = lambda pair: tuple(t.cpu().numpy() for t in pair)      # noqa: E731
+        a = K.ik_inputs(keypoints, weights, cam, init, params, hand_layer._model_np, match_bone_lengths,
+                        None if smooth is None else lambda kp, w: host(smooth_keypoints(kp, weights=w, sigma=smooth, device=dev)))
+        from ..manopth.manolayer import ManoDeviceModel
+        up = lambda x: None if x is None else torch.as_tensor(np.ascontiguousarray(x, dtype=np.float32)).to(dev)
+        res = ops.mano_ik(ManoDeviceModel(hand_layer._model_np, dev), up(a["shape"]), up(a["keypoints"]), up(a["pose48"]), up(a["trans"]),
+                          weights=up(a["weights"]), iters=iters, prior_weight=prior_weight)
+        return cls(res.pose48[:, 3:], res.pose48[:, :3], res.trans, a["cam"])
+
+    def save(self, path):
+        np.savez(path, **{k: getattr(self, k).cpu().numpy() for k in self.FIELDS if getattr(self, k) is not None})
+
+    @classmethod
+    def load(cls, path):
+        with np.load(path) as z:
+            return cls(**{k: z[k] for k in cls.FIELDS if k in z.files})
+
+    def _table(self, hand_layer, device):
+        """(the row layout, the packed table, the model's pose mean for its rotations), the last two on `device`"""
+        lay = RowLayout(self)
+        off = torch.as_tensor(pose_mean_rows(hand_layer, self.wrist_pose is not None), dtype=torch.float32).to(device)
+        return lay, lay.pack(device), off
+
+    def resample(self, times, hand_layer, device="cuda"):
+        """The motion at `times` (n,) in units of its own frames, e.g. np.linspace(0, T - 1, n) to retime it to n frames: rotations along
+        the shortest arc with the model's pose mean as the offset, trans / cam / light linearly (ops.motion_resample); a time on a frame
+        returns that frame bit for bit."""
+        dev = torch.device(device)
+        lay, keys, off = self._table(hand_layer, dev)
+        t = torch.as_tensor(np.asarray(times, dtype=np.float32)).reshape(-1).to(dev)
+        return Motion(**lay.unpack(ops.motion_resample(keys, t, lay.n_rot, off)))
+
+    def smooth(self, hand_layer, sigma=2.0, radius=None, weights=None, segments=None, trim_rot=None, trim_vec=None, iters=2, fields=None,
+               device="cuda"):
+        """The motion with its jitter taken out by a Gaussian window of `sigma` frames (radius: ceil(3 sigma)) on the device
+        (ops.motion_filter), as a new Motion of equal length.  rot, wrist_pose and pose are filtered as ROTATIONS (the
+        weighted geodesic mean of the window, `iters` iterations) with the model's pose mean as the offset, exactly as `resample` assembles
+        them; trans and light_positions as 3-vectors; cam as three scalars — cam[0] is an inverse depth and is averaged as stored.
+        weights: None or (T,) confidences per frame (<= 0 or not finite: the frame is not used and is filled from its neighbours).
+        segments: None or (T,) integer clip ids; a window never crosses a change, and it shrinks symmetrically there and at the ends.
+        trim_rot (radians) / trim_vec (the unit of trans): a sample farther than that from the window's first estimate is left out of a
+        second one — a one-frame spike does not leak into its neighbours.  fields: the names to filter (default: all the motion has);
+        the others pass through bit for bit."""
+        names = [k for k in self.FIELDS if getattr(self, k) is not None]
+        fields = names if fields is None else list(fields)
+        if any(k not in names for k in fields):
+            raise ValueError(f"fields must be among {names}, got {fields}")
+        dev = torch.device(device)
+        T = len(self)
+        lay, rows, off = self._table(hand_layer, dev)
+        trim = None if trim_rot is None and trim_vec is None else torch.tensor(lay.trim(trim_rot, trim_vec), dtype=torch.float32).to(dev)
+        w = None if weights is None else checked("weights", weights, (T,), tensor=True).to(torch.float32).contiguous().to(dev)
+        seg = None if segments is None else _segment_ids(segments, T).to(dev)
+        out, _ = ops.motion_filter(rows, lay.n_rot, lay.n_vec, ops.gaussian_taps(sigma, radius), weights=w, segment=seg, trim=trim, rot_offset=off,
+                                   iters=iters)
+        got = lay.unpack(out)
+        return Motion(**{k: got[k] if k in fields or got[k] is None else getattr(self, k).clone() for k in self.FIELDS})
+
+
+def _segment_ids(segments, T):
+    return checked("segments", segments, (T,), kind="i", tensor=True).to(torch.int32).contiguous()
+
+
+def smooth_keypoints(keypoints, weights=None, sigma=2.0, radius=None, trim=None, segments=None, device="cuda"):
+    """(T,21,3) keypoints through the window filter as 21 vector channels (ops.motion_filter) -> (keypoints (T,21,3) float32,
+    used (T,21) int32), both on `device`.  weights: None or (T,21) confidences.  A joint with a non-finite coordinate or a weight <= 0 has
+    weight 0: it does not pull on its neighbours and is FILLED from them when any lie in the window (used > 0); with none it comes back as
+    it went in (used == 0).  trim: None or a distance in the keypoints' unit for the trimmed second pass; segments: as Motion.smooth."""
+    kp = checked("keypoints", keypoints, (None, 21, 3), kind="f", tensor=True).to(torch.float32)
+    T = kp.shape[0]
+    dev = torch.device(device)
+    ok = torch.isfinite(kp).all(-1)
+    if weights is None:
+        w = ok.to(torch.float32)
+    else:
+        w = checked("weights", weights, (T, 21), kind="f", tensor=True).to(torch.float32).to(kp.device)
+        w = torch.where(ok & (w > 0) & torch.isfinite(w), w, torch.zeros_like(w))
+    tr = None if trim is None else torch.full((21,), float(trim), dtype=torch.float32).to(dev)
+    seg = None if segments is None else _segment_ids(segments, T).to(dev)
+    out, used = ops.motion_filter(kp.reshape(T, 63).contiguous().to(dev), 0, 21, ops.gaussian_taps(sigma, radius), weights=w.contiguous().to(dev),
+                                  segment=seg, trim=tr)
+    return out.reshape(T, 21, 3), used
+
+
+def motion_jitter(motion, params, hand_layer, other=None):
+    """How much a motion shakes, from the joints of the layer's forward at the avatar's shape (plain torch on the layer's output):
+    dict(accel_mean_mm, accel_max_mm) = the mean and the largest joint acceleration |j[t+1] - 2 j[t] + j[t-1]| in millimetres per frame^2
+    (0 for fewer than three frames); with `other`, a second Motion of equal length, also disp_mean_mm / disp_max_mm = the mean and the
+    largest distance between the two motions' joints."""
+    dev = params["shape"].device
+
+    def joints(m):
+        B = len(m)
+        betas = params["shape"].detach().reshape(1, -1).expand(B, -1).contiguous()
+        with torch.no_grad():
+            if "pose_mean" in hand_layer._model_np:          # the SMPL-X arm
+                if m.wrist_pose is None:
+                    raise ValueError("the arm model needs a motion with wrist_pose")
+                return hand_layer(betas=betas, global_orient=m.rot.to(dev), transl=m.trans.to(dev), right_hand_pose=m.pose.to(dev),
+                                  right_wrist_pose=m.wrist_pose.to(dev))[1]
+            return hand_layer(torch.cat([m.rot, m.pose], 1).to(dev), betas, m.trans.to(dev))[1]
+
+    j = joints(motion)
+    acc = (j[2:] - 2.0 * j[1:-1] + j[:-2]).norm(dim=-1) if len(motion) >= 3 else torch.zeros(1, device=j.device)
+    res = dict(accel_mean_mm=float(acc.mean()), accel_max_mm=float(acc.max()))
+    if other is not None:
+        if len(other) != len(motion):
+            raise ValueError(f"the two motions must have one length, got {len(motion)} and {len(other)}")
+        d = (joints(other) - j).norm(dim=-1)
+        res.update(disp_mean_mm=float(d.mean()), disp_max_mm=float(d.max()))
+    return res
+
+
+def pose_mean_rows(hand_layer, with_wrist):
+    """what the model adds to the stored rows [rot | (wrist_pose) | pose] before it turns them into rotations: zeros and MANO's hands_mean
+    (csrc/lbs.hip:35), or for the SMPL-X arm the slices of its pose mean for joints 0, 21 and 40..54 (hand_models_harp/body_models.py)"""
+    m = hand_layer._model_np
+    if "pose_mean" in m:
+        pm = np.asarray(m["pose_mean"], np.float32).reshape(-1)
+        parts = [pm[0:3]] + ([pm[63:66]] if with_wrist else []) + [pm[120:165]]
+    else:
+        parts = [np.zeros(3, np.float32)] + ([np.zeros(3, np.float32)] if with_wrist else []) + [np.asarray(m["hands_mean"], np.float32).reshape(45)]
+    return np.concatenate(parts)

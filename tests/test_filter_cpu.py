@@ -1,4 +1,4 @@
-"""CPU checks of the motion filter (csrc/filter.hip, harp_amd/playback.py Motion.smooth / smooth_keypoints): the float64
+"""CPU checks of the motion filter (csrc/filter.hip, harp_amd/playback/motion.py Motion.smooth / smooth_keypoints): the float64
 yardstick of tests/_filter_ref.py reaches the converged geodesic mean of rotation matrices in its two iterations; gaussian_taps, the
 argument checks of the binding and of the C entry point (no launch), the layer's table assembly and weight expansion over a stub that
 calls the yardstick; and the fixtures of tests/test_gpu_filter.py leave at most 2 % of their cases undecidable for float32."""

@@ -1,4 +1,4 @@
-"""-m gpu: playback of a fitted avatar (harp_amd/playback.py, csrc/playback.hip).  harp_motion_resample and harp_resolve_u8 against the
+"""-m gpu: playback of a fitted avatar (harp_amd/playback/, csrc/playback.hip).  harp_motion_resample and harp_resolve_u8 against the
 float64 restatements of tests/_playback_ref.py at their edges; AvatarPlayer against an expectation built independently of it — the
 reference-API mirror (`mirror_render`) at img_size * ss on a parameter dict that holds the motion's rows, resolved in float64 over a random
 background; the exact properties of the player (graph = eager, replay, a shorter motion on the same graph, rows checked on the host); and

@@ -1,4 +1,4 @@
-"""-m gpu: the motion filter (csrc/filter.hip: harp_motion_filter; harp_amd/playback.py Motion.smooth, smooth_keypoints, motion_jitter;
+"""-m gpu: the motion filter (csrc/filter.hip: harp_motion_filter; harp_amd/playback/motion.py Motion.smooth, smooth_keypoints, motion_jitter;
 DESIGN.md §25) against the float64 yardstick of tests/_filter_ref.py on the fixtures of tests/_filter_cases.py, its exact (bitwise)
 properties, its manifold properties, what trimming does to a spike, and the layer above it.  Every figure is printed before it is
 asserted; the bounds are 4 x the values measured on MI355X (profiles/filter_errors.txt), the project's convention for float32 against

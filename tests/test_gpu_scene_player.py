@@ -1,4 +1,4 @@
-"""-m gpu: several avatars in one frame (csrc/composite.hip, harp_amd/playback.py ScenePlayer).  harp_composite_layers_u8
+"""-m gpu: several avatars in one frame (csrc/composite.hip, harp_amd/playback/player.py ScenePlayer).  harp_composite_layers_u8
 against the float64 restatement of its contract (tests/_layers_ref.py) at its edges and byte for byte against harp_resolve_u8 where the
 two contracts coincide; ScenePlayer on two synthetic hands — exact at ss = 1, where a pixel is one sample: every pixel of the scene is
 the nearer avatar's, the other's mirrored, or the background's — with a scene depth between, in front of and absent; at ss = 2 against the

@@ -1,5 +1,5 @@
 """CPU checks of the keypoint-driven playback: the float64 yardstick of tests/_ik_ref.py against itself (Jacobian against
-central differences, convergence from the palm start), the host side of Motion.from_keypoints (Kabsch start, bone-length scale, argument
+central differences, convergence from the palm start), the host side of Motion.from_keypoints (harp_amd/playback/keypoints.py: Kabsch start, bone-length scale, argument
 errors) and harp_mano_ik's argument errors, which return before any launch."""
 import ctypes
 

@@ -1,4 +1,4 @@
-"""CPU checks of scene playback (csrc/composite.hip, harp_amd/playback.py ScenePlayer): the float64 yardstick tests/_layers_ref.py agrees
+"""CPU checks of scene playback (csrc/composite.hip, harp_amd/playback/player.py ScenePlayer): the float64 yardstick tests/_layers_ref.py agrees
 with the yardstick of harp_resolve_u8 where the two contracts coincide and has the properties the contract promises; the entry point
 refuses bad arguments before any launch; the ctypes mirror of harp_layer matches the C struct."""
 import ctypes

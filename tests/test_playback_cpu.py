@@ -1,4 +1,4 @@
-"""CPU checks of the playback feature (harp_amd/playback.py, csrc/playback.hip): the two entry points refuse empty sizes and NULL pointers
+"""CPU checks of the playback feature (harp_amd/playback/, csrc/playback.hip): the two entry points refuse empty sizes and NULL pointers
 before any launch, a Motion survives its .npz, the module imports without the built library, and the float64 slerp that the GPU tests
 measure against is the geodesic of rotation matrices."""
 import os
