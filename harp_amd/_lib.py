@@ -350,3 +350,13 @@ SIGNATURES["harp_mano_ik"] = (_i, [_mp, _vp, _vp, _vp, _vp, _i, ctypes.POINTER(I
 # motion smoothing: the confidence-weighted rotation-aware window filter (csrc/filter.hip)
 FILTER_MAX_RADIUS = 64                                     # HARP_FILTER_MAX_RADIUS
 SIGNATURES["harp_motion_filter"] = (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp])
+
+
+class VertexFitOptions(ctypes.Structure):
+    """mirror of `harp_vertex_fit_options` (include/harp_hip.h)"""
+    _fields_ = [("iters", _i), ("lambda0", _f), ("pose_prior_weight", _f), ("shape_prior_weight", _f), ("solve_shape", _i), ("betas_per_frame", _i)]
+
+
+# batched MANO vertex fit (csrc/vertex_fit.hip)
+SIGNATURES["harp_mano_vertex_fit_frames_per_block"] = (_i, [])
+SIGNATURES["harp_mano_vertex_fit"] = (_i, [_mp, _vp, _vp, _vp, _i, ctypes.POINTER(VertexFitOptions), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp])

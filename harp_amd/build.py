@@ -24,7 +24,10 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-mun
 _MEM_CLAUSE = ["-mllvm", "--amdgpu-sched-strategy=max-memory-clause"]
 # raster.hip: without the SLP vectoriser as well — the three tile kernels are VALU-issue-bound and register-tight (camera view 72 VGPRs with 12 B
 # of scratch): light view 58 -> 52 VGPRs, silhouette backward's scratch gone; camera group 0.164 -> 0.160 ms, light 0.086 -> 0.082, step -10 us (4 of 4)
-FILE_FLAGS = {"shade_bwd.hip": ["-fno-slp-vectorize"] + _MEM_CLAUSE, "conv.hip": _MEM_CLAUSE, "raster.hip": ["-fno-slp-vectorize"]}
+# vertex_fit.hip: without the SLP vectoriser — its one kernel sits at the 256 registers that two workgroups per CU leave a lane (81 loads in flight
+# beside 48 accumulators); the aligned pairs of v_pk_* cost it 3 spilled registers = 16 B of scratch per lane, without them none
+FILE_FLAGS = {"shade_bwd.hip": ["-fno-slp-vectorize"] + _MEM_CLAUSE, "conv.hip": _MEM_CLAUSE, "raster.hip": ["-fno-slp-vectorize"],
+              "vertex_fit.hip": ["-fno-slp-vectorize"]}
 
 
 def sources():

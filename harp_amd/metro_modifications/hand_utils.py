@@ -6,7 +6,8 @@ classes (:442-535), `optimize_smooth_seq` (:540-688) and the pickle helpers (`me
 These loops are the other consumers of the LBS kernel: 1200 Adam iterations of (hand layer, MSE to the METRO vertices, backward) per
 batch of frames.  In the reference every iteration is ~150 small torch launches; here `optimize_for_mano_param` is a native loop over
 the C ABI — `harp_lbs_mano_fwd`, `harp_mse`, `harp_lbs_mano_bwd`, `harp_adam_tick/apply` on one flat parameter arena — captured
-once per stage into a hipGraph of 7 nodes and replayed 500 + 700 times, for any number of frames at once.
+once per stage into a hipGraph of 7 nodes and replayed 500 + 700 times, for any number of frames at once.  `method="lm"` solves the same
+problem in one launch instead: a rigid start and the batched Levenberg-Marquardt vertex fit (csrc/vertex_fit.hip).
 """
 import ctypes
 import os
@@ -90,10 +91,44 @@ class ManoVertexFit:
         return self.loss[0].clone()
 
 
-def optimize_for_mano_param(pred_vertices, mano_layer, idx=0, vert_rgb=None, use_graph=True):
+def _optimize_for_mano_param_lm(pred_vertices, mano_layer, iters=10):
+    """method="lm" of optimize_for_mano_param: the rigid start (playback.vertex_start: one batched Kabsch fit of the mean-shape model on
+    the host) and ONE launch of the batched Levenberg-Marquardt vertex fit with the shape solved (ops.mano_vertex_fit, csrc/vertex_fit.hip,
+    DESIGN.md §27) instead of 8400 launches.  The two lines printed are the mean squared error in mm^2 at the rigid start and at the result."""
+    from .. import ops
+    from ..playback.keypoints import vertex_start
+    device = torch.device("cuda")
+    target_m = pred_vertices.detach().to(device).float().contiguous()
+    B = target_m.shape[0]
+    mano_layer = mano_layer.to(device)
+    fit = ManoVertexFit(mano_layer.device_model, target_m * 1000.0)
+    fit.forward()                                                                                     # all-zero rows: the model at rest
+    rot, trans = vertex_start(target_m.cpu().numpy(), np.ones((B, 778)), fit.verts[0].cpu().numpy().astype(np.float64) / 1000.0,
+                              fit.joints[0, 0].cpu().numpy().astype(np.float64) / 1000.0)
+    up = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).to(device)
+    fit.pose48[:, :3].copy_(up(rot))
+    res = ops.mano_vertex_fit(mano_layer.device_model, target_m, fit.pose48, fit.betas, up(trans), solve_shape=True, iters=iters)
+    mse = res.cost.double().mean(0) * 1e6 / 2334.0
+    print("After coarse alignment: %6f" % float(mse[0]))
+    print("After fine alignment: %6f" % float(mse[1]))
+    if float(mse[1]) > 10.0:
+        print("<<<<<<<<<<<<<<<<<<< ERROR TOO HIGH >>>>>>>>>>>>>>>>>>>>>>>")
+    fit.pose48.copy_(res.pose48); fit.betas.copy_(res.betas); fit.trans.copy_(res.trans)
+    fit.forward()
+    out = lambda t: t.detach().cpu().numpy().copy()
+    return {"joints": out(fit.joints), "verts": out(fit.verts), "rot": out(fit.pose48[:, :3]), "pose": out(fit.pose48[:, 3:]),
+            "shape": out(fit.betas), "trans": out(fit.trans)}
+
+
+def optimize_for_mano_param(pred_vertices, mano_layer, idx=0, vert_rgb=None, use_graph=True, method="adam"):
     """hand_utils.py:16-131.  pred_vertices (B,778,3) in metres -> dict of numpy arrays {joints, verts (mm), rot, pose, shape, trans}.
     The reference restarts up to four times while the final error exceeds 10.0 — from the same all-zero initialisation, i.e. every
-    restart reproduces the first run; one run is done here and the verdict is printed the same way."""
+    restart reproduces the first run; one run is done here and the verdict is printed the same way.
+    method: "adam" is the reference's two-stage fit; "lm" returns the same dict from the batched Levenberg-Marquardt vertex fit."""
+    if method not in ("adam", "lm"):
+        raise ValueError(f'method must be "adam" or "lm", got {method!r}')
+    if method == "lm":
+        return _optimize_for_mano_param_lm(pred_vertices, mano_layer)
     device = torch.device("cuda")
     target = pred_vertices.detach().to(device).float() * 1000.0
     mano_layer = mano_layer.to(device)

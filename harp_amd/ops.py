@@ -1360,3 +1360,69 @@ def mano_ik(dm, betas, targets, pose48, trans, weights=None, prior=None, iters=1
                                      _lib.ptr(out.joints), _lib.ptr(out.jac), _lib.stream())
     _lib.check(rc, "harp_mano_ik")
     return out
+
+
+# ---- batched MANO vertex fit (csrc/vertex_fit.hip) ------------------------------------------------------------------
+VertexFitResult = collections.namedtuple("VertexFitResult", "pose48 betas trans cost status verts jac A g")
+
+
+def mano_vertex_fit_frames_per_block():
+    """the frames one workgroup of harp_mano_vertex_fit solves"""
+    return int(_lib.lib().harp_mano_vertex_fit_frames_per_block())
+
+
+def mano_vertex_fit(dm, targets, pose48, betas, trans, weights=None, prior=None, solve_shape=True, iters=10, lambda0=1e-3, pose_prior_weight=0.0,
+                    shape_prior_weight=0.0, verts=False, jac=False, normal=False, out=None):
+    """Mesh vertices -> MANO rows: T Levenberg-Marquardt solves in one launch (csrc/vertex_fit.hip: harp_mano_vertex_fit, whose contract
+    include/harp_hip.h states), forward only.  dm: a ManoDeviceModel; targets (T,778,3) metres; pose48 (T,48) = [rot | pose], betas and
+    trans (T,3): the start, left untouched; betas (T,10) with solve_shape=True, (10,) for all frames or (T,10) with solve_shape=False (an
+    avatar's shape: given, not solved, returned as it came); weights (T,778) or None (ones; a vertex with weight <= 0 or a non-finite
+    target is unused); prior (T,45) or None (the mean pose) with pose_prior_weight on sum (pose - prior)^2; shape_prior_weight on
+    sum betas^2.  Returns VertexFitResult(pose48, betas, trans, cost (T,2) = at the start and at the result, status (T,) int32 = accepted
+    steps or -1 for a frame with fewer than 21 used vertices (returned as it came), verts (T,778,3) mm or None, jac (T,2334,61) or None,
+    A (T,61,61) and g (T,61) with normal=True, else None), the optional ones at the result.  iters = 0 evaluates at the start.  out: an
+    earlier VertexFitResult of the same shapes whose tensors are written instead of new ones — the call then allocates nothing and can be
+    captured into a graph."""
+    _playback_input("mano_vertex_fit", targets, pose48, betas, trans, weights, prior)
+    for name, t in (("targets", targets), ("pose48", pose48), ("betas", betas), ("trans", trans), ("weights", weights), ("prior", prior)):
+        if t is not None and t.dtype != torch.float32:
+            raise TypeError(f"mano_vertex_fit takes float32 tensors, {name} is {t.dtype}")
+    if targets.dim() != 3 or tuple(targets.shape[1:]) != (778, 3) or targets.shape[0] < 1:
+        raise ValueError(f"targets must be (T, 778, 3), got {tuple(targets.shape)}")
+    T = targets.shape[0]
+    solve_shape = bool(solve_shape)
+    if tuple(betas.shape) not in (((T, 10),) if solve_shape else ((10,), (T, 10))):
+        raise ValueError(f"betas must be ({T}, 10)" + ("" if solve_shape else " or (10,)") + f", got {tuple(betas.shape)}")
+    for name, t, shape in (("pose48", pose48, (T, 48)), ("trans", trans, (T, 3)), ("weights", weights, (T, 778)), ("prior", prior, (T, 45))):
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError(f"{name} must be {shape}, got {tuple(t.shape)}")
+    iters, lambda0, pose_prior_weight, shape_prior_weight = int(iters), float(lambda0), float(pose_prior_weight), float(shape_prior_weight)
+    if iters < 0 or any(not (0.0 <= v < float("inf")) for v in (lambda0, pose_prior_weight, shape_prior_weight)):
+        raise ValueError(f"iters >= 0 and finite lambda0, pose_prior_weight, shape_prior_weight >= 0, got {iters}, {lambda0}, "
+                         f"{pose_prior_weight}, {shape_prior_weight}")
+    if dm.v_template.device != targets.device:
+        raise ValueError(f"the model is on {dm.v_template.device}, the targets on {targets.device}")
+    dev = targets.device
+    want = ((T, 48), tuple(betas.shape), (T, 3), (T, 2), (T,), (T, 778, 3) if verts else None, (T, 2334, 61) if jac else None,
+            (T, 61, 61) if normal else None, (T, 61) if normal else None)
+    if out is None:
+        out = VertexFitResult(*[None if shape is None else torch.empty(shape, dtype=torch.int32 if name == "status" else torch.float32, device=dev)
+                                for name, shape in zip(VertexFitResult._fields, want)])
+    else:
+        for name, t, shape in zip(VertexFitResult._fields, out, want):
+            if (t is None) != (shape is None) or (t is not None and (tuple(t.shape) != shape or t.device != dev or not t.is_contiguous()
+                                                                      or t.dtype != (torch.int32 if name == "status" else torch.float32))):
+                raise ValueError(f"out.{name} does not fit this call")
+    out.pose48.copy_(pose48.detach())
+    out.betas.copy_(betas.detach())
+    out.trans.copy_(trans.detach())
+    c = lambda t: None if t is None else t.detach().contiguous()
+    targets, weights, prior = c(targets), c(weights), c(prior)
+    opt = _lib.VertexFitOptions(iters, lambda0, pose_prior_weight, shape_prior_weight, int(solve_shape), int(betas.dim() == 2))
+    with torch.cuda.device(dev):
+        rc = _lib.lib().harp_mano_vertex_fit(ctypes.byref(dm.struct), _lib.ptr(targets), _lib.ptr(weights), _lib.ptr(prior), T, ctypes.byref(opt),
+                                             _lib.ptr(out.pose48), _lib.ptr(out.betas), _lib.ptr(out.trans), _lib.ptr(out.cost),
+                                             _lib.ptr(out.status), _lib.ptr(out.verts), _lib.ptr(out.jac), _lib.ptr(out.A), _lib.ptr(out.g),
+                                             _lib.stream())
+    _lib.check(rc, "harp_mano_vertex_fit")
+    return out

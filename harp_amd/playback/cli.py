@@ -6,19 +6,17 @@ from .motion import Motion, motion_jitter
 from .player import AvatarPlayer, ScenePlayer
 
 
-def main(argv=None):
-    """A fit (the saved_params[_test].pkl under the config's base_output_dir, as the evaluation reads it) plus a motion file -> a directory
-    of frames."""
+def parse_args(argv=None):
+    """the command line's arguments, checked: what `main` runs on (SystemExit for a combination it does not take)"""
     import argparse
-    import yaml
     from . import __doc__ as package_doc
-    from ..utils import file_utils, hand_model_utils
-    from ..utils.config_utils import get_config
     ap = argparse.ArgumentParser(prog="python -m harp_amd.playback", description=package_doc.split("\n\n")[0])
     ap.add_argument("--config", required=True, help="yaml with the keys of utils/config_utils.get_config (the fit's)")
     ap.add_argument("--motion", default=None, help=".npz of pose (T,45), rot, trans, cam (T,3) [, wrist_pose, light_positions] (Motion.save)")
     ap.add_argument("--keypoints", default=None, help=".npz of keypoints (T,21,3) in metres [, weights (T,21), cam (3,) or (T,3)] instead of --motion: "
                                                       "the motion is solved from them (Motion.from_keypoints)")
+    ap.add_argument("--vertices", default=None, help=".npz of vertices (T,778,3) in metres, MANO topology [, weights (T,778), cam (3,) or (T,3)] "
+                                                     "instead of --motion: the motion is fitted to them (Motion.from_vertices)")
     ap.add_argument("--out", required=True, help="directory for the frames %%04d.jpg / %%04d.png")
     ap.add_argument("--fps-scale", type=float, default=1.0, help="output frames per motion frame (2: twice as many frames, half the speed)")
     ap.add_argument("--ss", type=int, default=1, help="supersampling factor 1..4")
@@ -52,10 +50,20 @@ def main(argv=None):
         raise SystemExit(f"--also at most {ops.COMPOSITE_MAX_LAYERS - 1} times")
     if args.fps_scale <= 0:
         raise SystemExit("--fps-scale must be positive")
-    if (args.motion is None) == (args.keypoints is None):
-        raise SystemExit("exactly one of --motion and --keypoints")
+    if sum(v is not None for v in (args.motion, args.keypoints, args.vertices)) != 1:
+        raise SystemExit("exactly one of --motion, --keypoints and --vertices")
+    return args
 
-    def load(cfg_path, motion_path, keypoints_path=None):
+
+def main(argv=None):
+    """A fit (the saved_params[_test].pkl under the config's base_output_dir, as the evaluation reads it) plus a motion file -> a directory
+    of frames."""
+    args = parse_args(argv)
+    import yaml
+    from ..utils import file_utils, hand_model_utils
+    from ..utils.config_utils import get_config
+
+    def load(cfg_path, motion_path, keypoints_path=None, vertices_path=None):
         with open(cfg_path) as f:
             configs = get_config(write_yaml=False, **yaml.safe_load(f))
         configs["device"] = args.device
@@ -67,6 +75,10 @@ def main(argv=None):
                 motion = Motion.from_keypoints(z["keypoints"], params, hand_layer, cam=z["cam"] if "cam" in z.files else None,
                                                weights=z["weights"] if "weights" in z.files else None, device=args.device,
                                                smooth=args.smooth_keypoints)
+        elif vertices_path is not None:
+            with np.load(vertices_path) as z:
+                motion = Motion.from_vertices(z["vertices"], params, hand_layer, cam=z["cam"] if "cam" in z.files else None,
+                                              weights=z["weights"] if "weights" in z.files else None, device=args.device)
         else:
             motion = Motion.load(motion_path)
         if args.smooth is not None:
@@ -83,22 +95,22 @@ def main(argv=None):
 
     fmt = "png" if args.alpha else "jpg"
     if not (args.flip or args.also or args.scene_depth or args.masks):
-        configs, params, hand_layer, motion = load(args.config, args.motion, args.keypoints)
+        configs, params, hand_layer, motion = load(args.config, args.motion, args.keypoints, args.vertices)
         player = AvatarPlayer(configs, params, hand_layer, batch_size=args.batch_size, ss=args.ss, device=args.device)
         paths = player.play(motion, args.out, backgrounds=args.background, fmt=fmt, alpha=args.alpha)
     else:
-        specs = [(args.config, args.motion, args.flip, args.keypoints)]
+        specs = [(args.config, args.motion, args.flip, args.keypoints, args.vertices)]
         for spec in args.also:
             part = spec.split(":")
             if len(part) not in (2, 3) or (len(part) == 3 and part[2] != "flip"):
                 raise SystemExit(f"--also takes CFG:MOTION or CFG:MOTION:flip, got {spec!r}")
-            specs.append((part[0], part[1], len(part) == 3, None))
+            specs.append((part[0], part[1], len(part) == 3, None, None))
         players, motions = [], []
-        for cfg_path, motion_path, _, keypoints_path in specs:
-            configs, params, hand_layer, motion = load(cfg_path, motion_path, keypoints_path)
+        for cfg_path, motion_path, _, keypoints_path, vertices_path in specs:
+            configs, params, hand_layer, motion = load(cfg_path, motion_path, keypoints_path, vertices_path)
             players.append(AvatarPlayer(configs, params, hand_layer, batch_size=args.batch_size, ss=args.ss, device=args.device, keep_depth=True))
             motions.append(motion)
-        scene = ScenePlayer(players, flip=[f for _, _, f, _ in specs])
+        scene = ScenePlayer(players, flip=[spec[2] for spec in specs])
         paths = scene.play(motions, args.out, backgrounds=args.background, scene_depth=args.scene_depth, fmt=fmt, alpha=args.alpha, masks=args.masks)
     print(f"wrote {len(paths)} frames to {args.out}")
     return paths

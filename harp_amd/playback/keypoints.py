@@ -134,3 +134,48 @@ def ik_inputs(keypoints, weights, cam, init, params, model, match_bone_lengths=T
     else:
         rot, trans, pose = init.rot.cpu().numpy(), init.trans.cpu().numpy(), init.pose.cpu().numpy()
     return dict(shape=shape, keypoints=kp, pose48=np.concatenate([rot, pose], 1), trans=trans, weights=w, cam=cam)
+
+
+def vertex_start(targets, used, rest_vertices, root_joint):
+    """The rigid start of the vertex fit (Motion.from_vertices, optimize_for_mano_param(method="lm")): rot (T,3) axis-angle and
+    trans (T,3), float64, that put the model's vertices at zero stored pose onto the targets in the weighted least-squares sense — ONE
+    batched SVD, no loop over the frames.  targets (T,778,3); used (T,778) bool or non-negative weights (a vertex with a non-finite target
+    is unused whatever it says); rest_vertices (778,3) or (T,778,3): the model's vertices at the frame's shape with zero stored pose and
+    zero trans; root_joint (3,) or (T,3): its root joint, about which the model rotates, so that trans = t - (J_0 - R J_0) for the Kabsch
+    fit x -> R x + t.  R has determinant +1 (a mirrored target gets the best proper rotation) and its logarithm is taken through the
+    quaternion's largest component, which stays finite and right at angles near pi.  A frame that cannot be aligned (fewer than three used
+    vertices) takes the start of the last frame before it that could (none yet: zeros)."""
+    tg = np.asarray(targets, np.float64)
+    T = tg.shape[0]
+    P = np.broadcast_to(np.asarray(rest_vertices, np.float64), tg.shape)
+    J0 = np.broadcast_to(np.asarray(root_joint, np.float64), (T, 3))
+    fin = np.isfinite(tg).all(-1)
+    w = np.where(fin, np.asarray(used, np.float64), 0.0)
+    w = np.where(w > 0, w, 0.0)                            # (a NaN weight is no weight)
+    ok = (w > 0).sum(1) >= 3
+    tg = np.where(fin[..., None], tg, 0.0)
+    n = np.where(ok, w.sum(1), 1.0)[:, None]
+    pc, tc = (w[..., None] * P).sum(1) / n, (w[..., None] * tg).sum(1) / n
+    H = np.einsum("tv,tvi,tvj->tij", w, tg - tc[:, None], P - pc[:, None])
+    H = np.where(ok[:, None, None], H, np.eye(3))
+    U, _, Vt = np.linalg.svd(H)
+    d = np.where(np.linalg.det(U @ Vt) < 0, -1.0, 1.0)
+    R = (U * np.stack([np.ones(T), np.ones(T), d], 1)[:, None, :]) @ Vt
+    # the logarithm: the quaternion from its largest component
+    tr = R[:, 0, 0] + R[:, 1, 1] + R[:, 2, 2]
+    cand = np.stack([1.0 + tr, 1.0 + 2 * R[:, 0, 0] - tr, 1.0 + 2 * R[:, 1, 1] - tr, 1.0 + 2 * R[:, 2, 2] - tr], 1)
+    a, b, c = R[:, 2, 1] - R[:, 1, 2], R[:, 0, 2] - R[:, 2, 0], R[:, 1, 0] - R[:, 0, 1]
+    e, f, g = R[:, 0, 1] + R[:, 1, 0], R[:, 0, 2] + R[:, 2, 0], R[:, 1, 2] + R[:, 2, 1]
+    variants = np.stack([np.stack([cand[:, 0], a, b, c], 1), np.stack([a, cand[:, 1], e, f], 1),
+                         np.stack([b, e, cand[:, 2], g], 1), np.stack([c, f, g, cand[:, 3]], 1)], 1)          # (T, 4 variants, 4)
+    q = np.take_along_axis(variants, np.argmax(cand, 1)[:, None, None], 1)[:, 0] if T else np.zeros((0, 4))
+    q = q / np.linalg.norm(q, axis=1, keepdims=True)
+    q = np.where(q[:, :1] < 0, -q, q)
+    vn = np.linalg.norm(q[:, 1:], axis=1, keepdims=True)
+    rot = np.where(vn < 1e-15, 0.0, 2.0 * np.arctan2(vn, q[:, :1]) * q[:, 1:] / np.where(vn < 1e-15, 1.0, vn))
+    trans = tc - np.einsum("tij,tj->ti", R, pc) - (J0 - np.einsum("tij,tj->ti", R, J0))
+    # a frame that cannot be aligned: the last one before it that could
+    src = np.maximum.accumulate(np.where(ok, np.arange(T), -1))
+    take = np.maximum(src, 0)
+    none = (src < 0)[:, None]
+    return np.where(none, 0.0, rot[take]), np.where(none, 0.0, trans[take])

@@ -1,5 +1,5 @@
 """The rows of a motion and what is done to them on the device: `Motion`, its retiming (ops.motion_resample), its solve
-from keypoints (ops.mano_ik, §24) and the window filter of a motion or of keypoints (ops.motion_filter, §25).  `RowLayout` is the one
+from keypoints (ops.mano_ik, §24) or from mesh vertices (ops.mano_vertex_fit, §27) and the window filter of a motion or of keypoints (ops.motion_filter, §25).  `RowLayout` is the one
 description of the packed table that the resampler and the filter read."""
 import numpy as np
 import torch
@@ -100,6 +100,45 @@ class Motion:
         res = ops.mano_ik(ManoDeviceModel(hand_layer._model_np, dev), up(a["shape"]), up(a["keypoints"]), up(a["pose48"]), up(a["trans"]),
                           weights=up(a["weights"]), iters=iters, prior_weight=prior_weight)
         return cls(res.pose48[:, 3:], res.pose48[:, :3], res.trans, a["cam"])
+
+    @classmethod
+    def from_vertices(cls, vertices, params, hand_layer, cam=None, weights=None, iters=10, pose_prior_weight=0.0, init=None, device=None):
+        """A motion from per-frame mesh vertices in MANO topology (a mesh regressor's output, a dataset) by the batched vertex fit on the
+        device (ops.mano_vertex_fit, csrc/vertex_fit.hip).  vertices (T,778,3) in metres, in the frame of the fit's
+        `verts`; a vertex with a non-finite coordinate or a weight <= 0 (weights (T,778), default ones) is ignored.  params: the fit's
+        parameter dict — its `shape` is the avatar's and is held fixed, so someone else's hand drives the avatar with the avatar's own
+        proportions; row 0 of its `cam` is the default cam; cam: (3,) or (T,3).
+        The start: pose zero, the root rotation and trans from the weighted Kabsch fit of the model's vertices at that shape
+        (vertex_start, host float64, one batched SVD); init= takes a Motion of equal length instead as a warm start.  pose_prior_weight
+        pulls the finger pose to the model's mean pose (0: the plain vertex distance).  Every frame is solved on its own; Motion.smooth
+        filters the result.  The result carries no light: AvatarPlayer.load_motion then uses the fit's row 0.  device: where the solve
+        runs (default: the device of params["shape"] when that is a HIP device, else "cuda").  The SMPL-X arm needs a fit over its
+        kinematic tree and raises NotImplementedError."""
+        if "pose_mean" in hand_layer._model_np:
+            raise NotImplementedError("Motion.from_vertices fits the MANO hand; the SMPL-X arm needs a fit over its kinematic tree")
+        dev = torch.device(device if device is not None else (params["shape"].device if params["shape"].is_cuda else "cuda"))
+        v = checked("vertices", vertices, (None, 778, 3), kind="f", split=True).astype(np.float64)
+        T = v.shape[0]
+        w = None if weights is None else checked("weights", weights, (T, 778), kind="f", split=True).astype(np.float64)
+        if init is not None and (not all(hasattr(init, k) for k in ("rot", "trans", "pose")) or len(init) != T):
+            raise ValueError(f"init must be a Motion of {T} frames")
+        cam = np.broadcast_to(checked("cam", params["cam"][0] if cam is None else cam, (3,), (T, 3)).astype(np.float32), (T, 3)).copy()
+        shape = params["shape"].detach().cpu().numpy().astype(np.float64).reshape(10)
+        from ..manopth.manolayer import ManoDeviceModel
+        dm = ManoDeviceModel(hand_layer._model_np, dev)
+        up = lambda x: None if x is None else torch.as_tensor(np.ascontiguousarray(x, dtype=np.float32)).to(dev)
+        targets, betas = up(v), up(shape)
+        if init is None:
+            # the model's vertices at this shape and zero stored pose: the solver's own forward, evaluated at the origin
+            zero = ops.mano_vertex_fit(dm, targets[:1], up(np.zeros((1, 48))), betas, up(np.zeros((1, 3))), solve_shape=False, iters=0, verts=True)
+            rot, trans = K.vertex_start(v, np.ones((T, 778)) if w is None else w, zero.verts[0].cpu().numpy().astype(np.float64) / 1000.0,
+                                        K.rest_chain_joints(hand_layer._model_np, shape)[0])
+            pose = np.zeros((T, 45))
+        else:
+            rot, trans, pose = init.rot.cpu().numpy(), init.trans.cpu().numpy(), init.pose.cpu().numpy()
+        res = ops.mano_vertex_fit(dm, targets, up(np.concatenate([rot, pose], 1)), betas, up(trans), weights=up(w), solve_shape=False, iters=iters,
+                                  pose_prior_weight=pose_prior_weight)
+        return cls(res.pose48[:, 3:], res.pose48[:, :3], res.trans, cam)
 
     def save(self, path):
         np.savez(path, **{k: getattr(self, k).cpu().numpy() for k in self.FIELDS if getattr(self, k) is not None})

@@ -1151,6 +1151,44 @@ int harp_motion_filter(const float* rows, int T, int n_rot, int n_vec, int n_lin
                        const float* weights, int w_cols, const int32_t* segment, const float* trim, int iters, float* out, int32_t* used,
                        hipStream_t stream);
 
+/* ---- batched MANO vertex fit: 778 mesh vertices -> pose, shape and trans rows (csrc/vertex_fit.hip; metro_modifications/hand_utils.py
+ * optimize_for_mano_param(method="lm"); playback Motion.from_vertices) ----
+ * The reference fits these rows with 500 + 700 Adam iterations (metro_modifications/hand_utils.py:16-131).  The model inverted is
+ * harp_lbs_mano_fwd's.  T independent Levenberg-Marquardt solves in one launch, forward only, no workspace, no allocation, no
+ * synchronisation, no atomics, fixed summation order (capturable; a repeated call gives the same bits).  Unknowns per frame
+ * x = [rot 3 | pose 45 | betas 10 | trans 3] = the rows of pose48, betas and trans as harp_lbs_mano_fwd takes them.
+ *   solve_shape == 0: betas are given and are not written: (10,) for all frames, or (T,10) with betas_per_frame != 0; their ten columns are
+ *   FROZEN.  solve_shape != 0: betas (T,10) are in/out (betas_per_frame is not read).
+ *   v(x) (778,3) metres = harp_lbs_mano_fwd's verts / 1000.
+ *   C(x) = sum_v w_v |v(x) - t_v|^2 + pose_prior_weight sum_i (pose_i - prior_i)^2 + shape_prior_weight sum_k betas_k^2; targets (T,778,3)
+ *   metres; weights (T,778) or NULL (ones); prior (T,45) or NULL (zeros: the model's mean pose).  A vertex is USED when w_v > 0 and its
+ *   three target coordinates are finite; an unused vertex's target never enters arithmetic.
+ *   Iteration, exactly `iters` times: J = the exact 2334 x 61 derivative of v at x; A = J^T W J + P, g = J^T W r + P (x - x_prior), P = the
+ *   two prior weights on the 45 pose and 10 shape diagonals (x_prior: prior for the pose, 0 for the shape); a frozen column has A_ii = 1,
+ *   zeros elsewhere in its row and column, and g_i = 0, so its step is exactly 0; (A + lambda diag A) d = -g by a Cholesky factorisation
+ *   of the matrix scaled from both sides by 1 / sqrt(A_ii (1 + lambda)); x' = x + d; C(x') < C(x): accept, lambda = max(0.1 lambda, 1e-9);
+ *   otherwise (a NaN included, and a non-positive or non-finite pivot or diagonal) keep x, lambda = min(10 lambda, 1e6).  lambda starts
+ *   at lambda0.
+ * In/out: pose48 (T,48), trans (T,3), betas when solve_shape.  Out: cost (T,2) = C at the input and at the result; status (T) int32 =
+ * accepted steps, or -1 for a frame with fewer than 21 used vertices (3 x 21 >= 61), which is not solved (its rows are not written).
+ * Optional out (NULL allowed), all at the final x: verts (T,778,3) mm; jac (T,2334,61), metres per unit of x, always all 61 columns; A
+ * (T,61,61) and g (T,61), unscaled, frozen columns as above.  iters == 0 evaluates all of them at the input and writes none of the in/out
+ * rows.
+ * HARP_ERR_ARG before any launch: m, opt, targets, pose48, betas, trans, cost or status NULL; T <= 0; iters < 0; lambda0 or a prior weight
+ * negative or not finite.  harp_mano_vertex_fit_frames_per_block: the frames one workgroup solves (tests size their batches around it). */
+typedef struct harp_vertex_fit_options {
+  int iters;
+  float lambda0;            /* 1e-3 */
+  float pose_prior_weight;  /* 0: the reference's unregularised MSE */
+  float shape_prior_weight; /* 0 */
+  int solve_shape;          /* 0: betas given and frozen; otherwise betas (T,10) in/out */
+  int betas_per_frame;      /* with solve_shape == 0: 0: betas (10,); otherwise betas (T,10) */
+} harp_vertex_fit_options;
+int harp_mano_vertex_fit_frames_per_block(void);
+int harp_mano_vertex_fit(const harp_mano_model* m, const float* targets, const float* weights, const float* prior, int T,
+                         const harp_vertex_fit_options* opt, float* pose48, float* betas, float* trans, float* cost, int32_t* status,
+                         float* verts, float* jac, float* A, float* g, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
