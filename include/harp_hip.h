@@ -655,20 +655,24 @@ typedef struct harp_conv3x3_args {
   float tap_scale;
   /* bounded mode (all NULL / 0 = every tile): image n belongs to frame row r = target_row[n]; only the 16x16 output tiles of that frame's
    * list are computed, and input pixels in cells this pass did not write are taken from in_alt (the same activation of another pass,
-   * e.g. the target frame's, rows through target_row) or read as zero */
+   * e.g. the target frame's, rows through target_row) or read as zero.  Everything outside the listed tiles is left as it was: `out`, `pooled` (a 2x2
+   * window belongs to the tile of its pixels) and g_tap; *loss receives the listed tiles' share only.  tile_list, tile_origin, in_valid, in_alt, out_valid
+   * and their origins are all indexed by the frame row r.  Origins are non-negative; list entries past tile_count[r] are not read */
   const int32_t* tile_list;   /* (T, max_tiles): ty * tile_pitch + tx in the frame's tile grid */
   const int32_t* tile_count;  /* (T) */
   int max_tiles;
   int in_valid_shift;         /* cells of in_valid are (8 << shift) input pixels square: 1 = the producer's 16x16 tiles, 0 = tiles of a 2x finer producer behind a pool */
-  const int32_t* in_valid;    /* (T, in_valid_pitch^2) 0/1 over the PRODUCER's tile grid */
+  const int32_t* in_valid;    /* (T, in_valid_pitch^2) 0/1 over the PRODUCER's tile grid; a cell at or beyond in_valid_pitch (in y or in x) counts as not written */
   const float* in_alt;        /* (T,H,W,in_channels) or NULL: zero */
   const int32_t* out_valid;   /* HARP_CONV_UNPOOL: (T, out_valid_pitch^2) 0/1 over the tile grid of `out` (twice this convolution's resolution); windows elsewhere are skipped */
   /* a frame's tile grid may be shifted so that its tiles hug the active region: tile (ty, tx) covers pixels [16 ty - oy, 16 ty - oy + 16) x
    * [16 tx - ox, ...), origin (oy, ox) EVEN (2x2 pool windows stay inside a tile), per frame, in the pixels of the grid's own resolution;
    * NULL = (0, 0).  pitch = tiles per row (and rows) of the grid's bitmap */
   const int32_t* tile_origin;       /* (T,2) of the grid tile_list indexes */
-  const int32_t* in_valid_origin;   /* (T,2) of the producer's grid */
-  const int32_t* out_valid_origin;  /* (T,2) of `out`'s grid */
+  const int32_t* in_valid_origin;   /* (T,2) of the producer's grid, in the PRODUCER's pixels: behind a pool (in_valid_shift 0) those are twice as fine as this
+                                     * convolution's input pixels and the origin is halved — input pixel (y, x) lies in cell ((y + oy / 2) / cell, (x + ox / 2) / cell) */
+  const int32_t* out_valid_origin;  /* (T,2) of `out`'s grid: the window of pooled pixel (y, x) lies in cell ((2 y + oy) / out_valid_cell, (2 x + ox) / out_valid_cell),
+                                     * which must exist — the bitmap has to cover `out` (out_valid_pitch is not checked against it) */
   int tile_pitch, in_valid_pitch, out_valid_pitch;
   /* tiles of 8x8 pixels (the coarse levels of the perceptual term, where a hand is a few tiles across): tile_side = 8 — tile_list / tile_origin /
    * tile_pitch then describe a grid of 8-pixel tiles and a workgroup computes four of them (one per wave); 0 or 16 = the 16x16 form.

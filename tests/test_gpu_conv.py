@@ -256,6 +256,54 @@ def test_bounded_term_equals_the_full_pass(precision):
     assert loss.item() == 0.0 and (g_rgb == 1.0).all()
 
 
+@pytest.mark.parametrize("precision", [0, 1, 2])
+@pytest.mark.parametrize("S", [8, 24, 72])
+def test_whole_term_at_the_small_and_off_grid_sizes(S, precision):
+    """harp_vgg16_term at sizes its contract admits (S % 8 == 0) and the other whole-term tests do not run: S = 72 (maps of 72, 36, 18 and
+    9 x 9: the image-side kernels' last tile row and column are partial, every level has a ragged tile), 24 (3 x 3 at the coarsest level) and 8
+    (1 x 1).  One mask touches the bottom-right corner, one is a few interior pixels, one frame is empty.  Precisions 0 and 1: the full pass
+    against the float64 torch module at the thresholds of test_bounded_term_equals_the_full_pass; every precision: the bounded pass has the
+    full pass's bits for every allowed mix of tile sides, with and without shifted grids."""
+    from harp_amd.model.vgg import Vgg16Features
+    from harp_amd.model.vgg_hip import Vgg16Hip, active_tiles
+    N, T = 2, 3
+    LW = [1, 1 / 16, 1 / 8, 1 / 4, 1]
+    vgg = Vgg16Features(layers_weights=LW, weights="random", seed=3)
+    g = torch.Generator().manual_seed(100 + S)
+    rgb = torch.rand(N, S, S, 3, generator=g, dtype=torch.float64).requires_grad_(True)
+    y_true = torch.rand(T, S, S, 3, generator=g, dtype=torch.float64)
+    mask = torch.zeros(T, S, S, dtype=torch.float64)
+    mask[0, S - 3:, S - 2:] = 1.0                                    # touches the bottom-right corner
+    mask[1, S // 2 - 1:S // 2 + 1, S // 3:S // 3 + 3] = 0.5          # a few interior pixels; frame 2 is empty
+    hip = Vgg16Hip(vgg, DEV, precision)
+    rgb_d, yt_d, mask_d = (t.detach().float().to(DEV).contiguous() for t in (rgb, y_true, mask))
+    cache = hip.features(yt_d, mask_d, all_slots=True)
+    vgg64 = Vgg16Features(layers_weights=LW, weights=vgg.state_dict()).double()
+    for rows in (torch.tensor([1, 0]), torch.tensor([2, 1])):
+        rows_d = rows.int().to(DEV)
+
+        def run(bd):
+            g_rgb, loss = torch.zeros(N, S, S, 3, device=DEV), torch.zeros(1, device=DEV)
+            hip.term(rgb_d, yt_d, mask_d, rows_d, cache, 1, g_rgb, loss, weight=1.0, bound=bd)
+            torch.cuda.synchronize()
+            return loss.item(), g_rgb.cpu()
+
+        full = run(None)
+        if precision < 2:
+            m = mask[rows].unsqueeze(-1)
+            want = F.l1_loss(vgg64((rgb * m).permute(0, 3, 1, 2)), vgg64((y_true[rows] * m).permute(0, 3, 1, 2)))
+            (g_want,) = torch.autograd.grad(want, rgb)
+            rel = ((full[1].double() - g_want).norm() / g_want.norm()).item()
+            print(f"[VGG term S {S} rows {rows.tolist()} precision {precision}] loss {full[0]:.7f} vs {want.item():.7f}, gradient rel-L2 {rel:.1e}")
+            assert abs(full[0] - want.item()) < 2e-5 * want.item() and rel < (2e-3, 6e-2)[precision], (full[0], want.item(), rel)
+        for sides in ((16, 16, 16, 16), (16, 16, 16, 8), (16, 16, 8, 8), (16, 8, 8, 8)):
+            for shift in (True, False):
+                got = run(active_tiles(mask_d, shift_grid=shift, tile_sides=sides))
+                assert torch.equal(got[1], full[1]), (S, rows.tolist(), sides, shift)
+                # (the loss: the same terms added into the double accumulator in another order, as in test_bounded_term_equals_the_full_pass)
+                assert abs(got[0] - full[0]) <= 1e-6 * full[0], (S, rows.tolist(), sides, shift, got[0], full[0])
+
+
 def test_filters_from_a_torchvision_state_dict_file(tmp_path):
     """`--vgg-weights <file>` / configs["vgg_weights"] end to end: a state dict in torchvision's vgg16 layout ("features.N.weight", plus
     the classifier entries the term does not use) on disk -> Vgg16Features(weights=path) -> packed for the matrix cores -> the HIP term.
