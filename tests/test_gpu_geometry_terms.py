@@ -447,6 +447,21 @@ def _skin_vertex_bound(theta_chain, R, mag_vp, depth):
     return 1000.0 * ((theta_chain * U + (3 * depth + 20) * U) * R + 48 * U * mag_vp)
 
 
+def _mano_vertex_bound(m64, hm, pose, betas, v_ref):
+    """_skin_vertex_bound of the MANO layer (B,1,1) [mm] for pose (B,48) / betas (B,10) float32 and the float64 vertices v_ref (B,778,3) mm;
+    m64: the model in float64 (shapedirs (778,3,10), posedirs (778,3,135)), hm (15,3) the float32 hands_mean.  Shared with
+    tests/test_gpu_step_front_back.py (the same layer inside the fused front)."""
+    B = pose.shape[0]
+    th = _angle(pose.view(B, 16, 3).double() + torch.cat([torch.zeros(1, 3), hm]).double())
+    chain = th[:, :1] + th[:, 1:].view(B, 5, 3).sum(-1).amax(-1, keepdim=True)       # root + the worst finger
+    # |v_t| + sum |S| |beta| + 2 sum |P| (|R - I| <= 2 per entry), the largest over the vertices
+    vp = (m64["v_template"].abs()[None] + torch.einsum("vck,bk->bvc", m64["shapedirs"].abs(), betas.double().abs())
+          + 2 * m64["posedirs"].abs().sum(-1)[None]).amax((1, 2))[:, None]
+    R = (v_ref / 1000).norm(dim=-1).amax(-1, keepdim=True) + 0.2                     # metres: |posed vertex| + the hand's extent
+    # capped at the golden tolerance (3e-3 mm): never looser than it
+    return _skin_vertex_bound(2 * chain + 4 * 24, R, vp, 4).clamp(max=3e-3)[:, :, None]
+
+
 def test_mano_lbs_against_float64_at_rotation_edges():
     from harp_amd import synth
     from harp_amd.manopth.manolayer import ManoDeviceModel
@@ -496,14 +511,7 @@ def test_mano_lbs_against_float64_at_rotation_edges():
                 want_gv[:, tips[src - 16]] += gj[:, k]
         assert torch.equal(outs[0][3], want_gv), B
         tag = f"mano B={B}"
-        th = _angle(pose.view(B, 16, 3).double() + torch.cat([torch.zeros(1, 3), hm]).double())
-        chain = th[:, :1] + th[:, 1:].view(B, 5, 3).sum(-1).amax(-1, keepdim=True)       # root + the worst finger
-        # |v_t| + sum |S| |beta| + 2 sum |P| (|R - I| <= 2 per entry), the largest over the vertices
-        vp = (m64["v_template"].abs()[None] + torch.einsum("vck,bk->bvc", m64["shapedirs"].abs(), betas.double().abs())
-              + 2 * m64["posedirs"].abs().sum(-1)[None]).amax((1, 2))[:, None]
-        R = (v_ref.detach() / 1000).norm(dim=-1).amax(-1, keepdim=True) + 0.2          # metres: |posed vertex| + the hand's extent
-        # capped at the golden tolerance (3e-3 mm): never looser than it
-        bv = _skin_vertex_bound(2 * chain + 4 * 24, R, vp, 4).clamp(max=3e-3)[:, :, None]
+        bv = _mano_vertex_bound(m64, hm, pose, betas, v_ref.detach())
         _worst(tag + " verts", (verts.cpu().double() - v_ref.detach()).abs(), bv)
         _worst(tag + " joints", (joints.cpu().double() - j_ref.detach()).abs(), bv)
         # gradients: the golden tolerance (rel-L2 1e-4) per frame and block, tighter than over the batch (a derived element bound would have

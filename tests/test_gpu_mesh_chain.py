@@ -286,20 +286,20 @@ def _project_bound(v64, R64, T64, ndc_ref):
 # ----------------------------------------------------------------------------------------------------------------------------------
 # forward
 # ----------------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("wide", [False, True], ids=["one_wg", "wide"])
-@pytest.mark.parametrize("mesh,B", CASES)
-def test_mesh_chain_forward_stage_by_stage_against_float64(mesh, B, wide):
-    cs = _case(mesh, B)
-    _assert_property(cs)
+def _check_forward_stages(tag, cs, out32, light, general_rotation=True):
+    """every forward output of a chain (out32: FWD_SHAPES -> float32 CPU tensors) against the float64 reference, stage by stage, each stage
+    from the kernel's own output of the stage before.  cs: verts_mm, joints_mm, cam_R (B,3,3), cam_T, disp (float32, what the chain read),
+    faces_np, edges0_np, vf_off_np, name, comps, vertical, B, V; light (B,3): the light positions the chain read.  Shared with
+    tests/test_gpu_step_front_back.py, whose chain runs inside the fused front behind the camera convention's fixed rotation
+    (general_rotation = False: the assertion that the last frame's rotation is a general one does not apply)."""
+    mesh, B = cs["name"], cs["B"]
     faces = torch.from_numpy(cs["faces_np"]).long()
     edges0 = torch.from_numpy(cs["edges0_np"]).long()
     deg = int(np.diff(cs["vf_off_np"]).max())
-    tag = f"chain_fwd {mesh} B={B} {'wide' if wide else 'one_wg'}"
-    d = _forward(cs, wide, shadow=1)
-    o = {k: d.t[k].cpu().double() for k in FWD_SHAPES}
+    o = {k: out32[k].double() for k in FWD_SHAPES}
     assert all(torch.isfinite(v).all() for v in o.values()), tag                  # every element of every output written (NaN pre-fill)
     # ---- metres + SubdivideMeshes: s v is one rounding, a midpoint (s a + s c) * 0.5 three, each within U of |s a| + |s c|
-    assert torch.equal(d.t["joints_m"].cpu(), cs["joints_mm"] * torch.tensor(MM, dtype=torch.float32)), tag
+    assert torch.equal(out32["joints_m"], cs["joints_mm"] * torch.tensor(MM, dtype=torch.float32)), tag
     a64 = cs["verts_mm"].double().abs()
     mag = torch.cat([MM * a64, MM * (a64[:, edges0[:, 0]] + a64[:, edges0[:, 1]])], 1)
     _worst(tag + " vs", (o["vs"] - C.subdivide(cs["verts_mm"].double(), edges0, MM)).abs(), 2 * U * mag + 1e-300)
@@ -326,9 +326,10 @@ def test_mesh_chain_forward_stage_by_stage_against_float64(mesh, B, wide):
     R64, T64 = cs["cam_R"].double(), cs["cam_T"].double()
     ndc_ref = C.project(o["vd"], R64, T64, S, FOCAL)
     assert ndc_ref[..., 2].min() > 0.3
-    if B > 1:
+    if B > 1 or not general_rotation:
         assert torch.equal(cs["cam_R"][0], torch.diag(torch.tensor([-1.0, -1.0, 1.0])))
-    assert (cs["cam_R"][-1] - cs["cam_R"][-1].T).abs().max() > 0.1                    # a general rotation: a transposed index would show
+    if general_rotation:
+        assert (cs["cam_R"][-1] - cs["cam_R"][-1].T).abs().max() > 0.1                # a general rotation: a transposed index would show
     _worst(tag + " ndc_c", (o["ndc_c"] - ndc_ref).abs(), _project_bound(o["vd"], R64, T64, ndc_ref))
     # ---- centroid from the kernel's vd.  harp_centroid's bound: (ceil(V / 256) + 10) roundings of sum |v| / V (here the tree is <= 3 adds
     # per lane, 6 wave levels, 16 wave sums or four part sums, the division: at most 26 roundings, usually far fewer non-zero terms)
@@ -337,18 +338,28 @@ def test_mesh_chain_forward_stage_by_stage_against_float64(mesh, B, wide):
     # ---- light camera from the kernel's centroid.  No building-block bound in U exists for it: 2e-6 (R) / 5e-6 (T, |pos| <= 2.4 m) are the
     # empirical constants at which the shared device function light_cam is already pinned by
     # test_gpu_parity.py::test_light_camera_incl_look_at_replacement_branch (34 U of a unit axis, 84 U of T), not derived ones
-    lR_ref, lT_ref = C.light_camera(o["centroid"], d.light.double(), S, FOCAL)
+    lR_ref, lT_ref = C.light_camera(o["centroid"], light.double(), S, FOCAL)
     lR = o["light_R"].view(B, 3, 3)
     _worst(tag + " light_R", (lR - lR_ref).abs(), torch.tensor(2e-6))
     _worst(tag + " light_T", (o["light_T"] - lT_ref).abs(), torch.tensor(5e-6))
     if cs["vertical"] is not None:
         b = cs["vertical"]
         assert (lR[b, :, 0] == 0).all() and (lR[b, :, 1] == 0).all() and (lR_ref[b, :, :2] == 0).all(), tag      # x = y = 0, like the reference
-        assert (d.light[b] - d.t["centroid"][b].cpu())[[0, 2]].abs().max() == 0
+        assert (light[b] - out32["centroid"][b])[[0, 2]].abs().max() == 0
     # ---- light view from the kernel's vd, light_R, light_T
     ndl_ref = C.project(o["vd"], lR, o["light_T"], S, FOCAL)
     assert ndl_ref[..., 2].min() > 1.0
     _worst(tag + " ndc_l", (o["ndc_l"] - ndl_ref).abs(), _project_bound(o["vd"], lR, o["light_T"], ndl_ref))
+
+
+@pytest.mark.parametrize("wide", [False, True], ids=["one_wg", "wide"])
+@pytest.mark.parametrize("mesh,B", CASES)
+def test_mesh_chain_forward_stage_by_stage_against_float64(mesh, B, wide):
+    cs = _case(mesh, B)
+    _assert_property(cs)
+    tag = f"chain_fwd {mesh} B={B} {'wide' if wide else 'one_wg'}"
+    d = _forward(cs, wide, shadow=1)
+    _check_forward_stages(tag, cs, {k: d.t[k].cpu() for k in FWD_SHAPES}, d.light)
     # ---- g_vd / g_joints_m are inputs of this call (clear_grads = 0): untouched
     for k in ("g_vd", "g_joints_m"):
         assert torch.equal(_bits(d.t[k]), _bits(d.pre[k])), (tag, k)
