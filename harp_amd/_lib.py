@@ -360,3 +360,16 @@ class VertexFitOptions(ctypes.Structure):
 # batched MANO vertex fit (csrc/vertex_fit.hip)
 SIGNATURES["harp_mano_vertex_fit_frames_per_block"] = (_i, [])
 SIGNATURES["harp_mano_vertex_fit"] = (_i, [_mp, _vp, _vp, _vp, _i, ctypes.POINTER(VertexFitOptions), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp])
+
+
+class ArmVertexFitOptions(ctypes.Structure):
+    """mirror of `harp_arm_vertex_fit_options` (include/harp_hip.h)"""
+    _fields_ = [("iters", _i), ("lambda0", _f), ("pose_prior_weight", _f), ("wrist_prior_weight", _f), ("shape_prior_weight", _f),
+                ("solve_shape", _i), ("solve_wrist", _i), ("betas_per_frame", _i)]
+
+
+# batched SMPL-X arm vertex fit (csrc/arm_vertex_fit.hip)
+ARM_VERTEX_FIT_MAX_VERTS = 1088                            # HARP_ARM_VERTEX_FIT_MAX_VERTS
+SIGNATURES["harp_arm_vertex_fit_frames_per_block"] = (_i, [])
+SIGNATURES["harp_arm_vertex_fit"] = (_i, [_trp, _vp, _i, _vp, _vp, _vp, _i, ctypes.POINTER(ArmVertexFitOptions), _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                          _vp, _vp, _vp])

@@ -7,7 +7,8 @@ These loops are the other consumers of the LBS kernel: 1200 Adam iterations of (
 batch of frames.  In the reference every iteration is ~150 small torch launches; here `optimize_for_mano_param` is a native loop over
 the C ABI — `harp_lbs_mano_fwd`, `harp_mse`, `harp_lbs_mano_bwd`, `harp_adam_tick/apply` on one flat parameter arena — captured
 once per stage into a hipGraph of 7 nodes and replayed 500 + 700 times, for any number of frames at once.  `method="lm"` solves the same
-problem in one launch instead: a rigid start and the batched Levenberg-Marquardt vertex fit (csrc/vertex_fit.hip).
+problem in one launch instead: a rigid start and the batched Levenberg-Marquardt vertex fit (csrc/vertex_fit.hip, DESIGN.md §27);
+`optimize_for_mano_arm_param(method="lm")` does the same for the SMPL-X arm layer (csrc/arm_vertex_fit.hip).
 """
 import ctypes
 import os
@@ -145,9 +146,44 @@ def optimize_for_mano_param(pred_vertices, mano_layer, idx=0, vert_rgb=None, use
             "shape": out(fit.betas), "trans": out(fit.trans)}
 
 
-def optimize_for_mano_arm_param(pred_vertices, mano_arm_layer, idx=0, vert_rgb=None):
+def _optimize_for_mano_arm_param_lm(pred_vertices, mano_arm_layer, iters=10):
+    """method="lm" of optimize_for_mano_arm_param: the rigid start (playback.vertex_start on the layer's rest vertices at right_mano_idx;
+    the model is wrist-centred, so it turns about the origin and trans is the wrist) and ONE launch of the batched Levenberg-Marquardt arm
+    vertex fit (ops.arm_vertex_fit, csrc/arm_vertex_fit.hip) on the 778 hand vertices with the shape solved and the wrist held
+    at zero — the reference's parameter set.  The two lines printed are the mean squared error in mm^2 at the rigid start and at the result."""
+    from .. import ops
+    from ..playback.keypoints import vertex_start
+    device = torch.device("cuda")
+    target_m = pred_vertices.detach().to(device).float().contiguous()
+    B, n = target_m.shape[0], target_m.shape[1]
+    dm, idx = mano_arm_layer.device_model, mano_arm_layer.right_mano_idx.to(device)
+    z = lambda *shape: torch.zeros(*shape, dtype=torch.float32, device=device)
+    rest = ops.arm_vertex_fit(dm, target_m[:1], z(1, 17, 3), z(1, 10), z(1, 3), vert_idx=idx, iters=0, verts=True).verts[0, idx]
+    rot, trans = vertex_start(target_m.cpu().numpy(), np.ones((B, n)), rest.cpu().numpy().astype(np.float64) / 1000.0, np.zeros(3))
+    up = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).to(device)
+    in_pose = z(B, 17, 3)
+    in_pose[:, 0] = up(rot)
+    res = ops.arm_vertex_fit(dm, target_m, in_pose, z(B, 10), up(trans), vert_idx=idx, solve_shape=True, solve_wrist=False, iters=iters)
+    mse = res.cost.double().mean(0) * 1e6 / (3.0 * n)
+    print("After coarse alignment: %6f" % float(mse[0]))
+    print("After fine alignment: %6f" % float(mse[1]))
+    if float(mse[1]) > 10.0:
+        print("<<<<<<<<<<<<<<<<<<< ERROR TOO HIGH >>>>>>>>>>>>>>>>>>>>>>>")
+    rot, pose = res.in_pose[:, 0].contiguous(), res.in_pose[:, 2:].reshape(B, 45).contiguous()
+    with torch.no_grad():
+        verts, joints = mano_arm_layer(betas=res.betas, global_orient=rot, transl=res.trans, right_hand_pose=pose, return_type="mano")
+    out = lambda t: t.detach().cpu().numpy().copy()
+    return {"joints": out(joints), "verts": out(verts), "rot": out(rot), "pose": out(pose), "shape": out(res.betas), "trans": out(res.trans)}
+
+
+def optimize_for_mano_arm_param(pred_vertices, mano_arm_layer, idx=0, vert_rgb=None, method="adam"):
     """hand_utils.py:134-240: the same two-stage fit through the SMPL-X arm layer's `return_type='mano'` vertices (HIP tree LBS behind
-    torch autograd + torch.optim.Adam; translation starts at zero, :173)."""
+    torch autograd + torch.optim.Adam; translation starts at zero, :173).
+    method: "adam" is the reference's two-stage fit; "lm" returns the same dict from the batched Levenberg-Marquardt arm vertex fit."""
+    if method not in ("adam", "lm"):
+        raise ValueError(f'method must be "adam" or "lm", got {method!r}')
+    if method == "lm":
+        return _optimize_for_mano_arm_param_lm(pred_vertices, mano_arm_layer)
     device = torch.device("cuda")
     target = pred_vertices.detach().to(device).float() * 1000.0
     B = target.shape[0]

@@ -1426,3 +1426,84 @@ def mano_vertex_fit(dm, targets, pose48, betas, trans, weights=None, prior=None,
                                              _lib.stream())
     _lib.check(rc, "harp_mano_vertex_fit")
     return out
+
+
+# ---- batched SMPL-X arm vertex fit (csrc/arm_vertex_fit.hip) --------------------------------------------------------
+ArmVertexFitResult = collections.namedtuple("ArmVertexFitResult", "in_pose betas trans cost status verts jac A g")
+
+
+def arm_vertex_fit_frames_per_block():
+    """the frames one workgroup of harp_arm_vertex_fit solves"""
+    return int(_lib.lib().harp_arm_vertex_fit_frames_per_block())
+
+
+def arm_vertex_fit(dm, targets, in_pose, betas, trans, vert_idx=None, weights=None, prior=None, solve_shape=True, solve_wrist=True, iters=10,
+                   lambda0=1e-3, pose_prior_weight=0.0, wrist_prior_weight=0.0, shape_prior_weight=0.0, verts=False, jac=False, normal=False,
+                   out=None):
+    """Mesh vertices -> SMPL-X arm rows: T Levenberg-Marquardt solves in one launch (csrc/arm_vertex_fit.hip: harp_arm_vertex_fit, whose
+    contract include/harp_hip.h states), forward only.  dm: a TreeDeviceModel (hand_models_harp.body_models); targets (T,n_t,3) metres, row
+    i belonging to model vertex vert_idx[i] ((n_t,) int32 or int64 on the device, every entry in [0, NV) — checked here; None: n_t = NV,
+    the identity); in_pose (T,17,3) = [rot | wrist | pose(15)], betas and trans (T,3): the start, left untouched; betas (T,10) with
+    solve_shape=True, (10,) for all frames or (T,10) with solve_shape=False (an avatar's shape: given, not solved, returned as it came);
+    solve_wrist=False holds the wrist row at what in_pose gives; weights (T,n_t) or None (ones; a target with weight <= 0 or a non-finite
+    coordinate is unused); prior (T,45) or None (the mean pose) with pose_prior_weight on sum (pose - prior)^2; wrist_prior_weight on
+    sum wrist^2; shape_prior_weight on sum betas^2.  Returns ArmVertexFitResult(in_pose, betas, trans, cost (T,2) = at the start and at the
+    result, status (T,) int32 = accepted steps or -1 for a frame with fewer than 22 used targets (returned as it came), verts (T,NV,3) mm
+    (all model vertices) or None, jac (T,3 n_t,64) or None, A (T,64,64) and g (T,64) with normal=True, else None), the optional ones at the
+    result.  iters = 0 evaluates at the start.  out: an earlier ArmVertexFitResult of the same shapes whose tensors are written instead of
+    new ones — the call then allocates nothing (pass an int32 vert_idx) and can be captured into a graph."""
+    _playback_input("arm_vertex_fit", targets, in_pose, betas, trans, weights, prior, vert_idx)
+    for name, t in (("targets", targets), ("in_pose", in_pose), ("betas", betas), ("trans", trans), ("weights", weights), ("prior", prior)):
+        if t is not None and t.dtype != torch.float32:
+            raise TypeError(f"arm_vertex_fit takes float32 tensors, {name} is {t.dtype}")
+    NV = int(dm.NV)
+    if targets.dim() != 3 or targets.shape[2] != 3 or targets.shape[0] < 1 or not 1 <= targets.shape[1] <= NV:
+        raise ValueError(f"targets must be (T, n_t <= {NV}, 3), got {tuple(targets.shape)}")
+    T, n_t = int(targets.shape[0]), int(targets.shape[1])
+    if vert_idx is None:
+        if n_t != NV:
+            raise ValueError(f"targets must be (T, {NV}, 3) without vert_idx, got {tuple(targets.shape)}")
+    else:
+        if vert_idx.dtype not in (torch.int32, torch.int64) or tuple(vert_idx.shape) != (n_t,):
+            raise ValueError(f"vert_idx must be ({n_t},) int32 or int64, got {tuple(vert_idx.shape)} {vert_idx.dtype}")
+        if not torch.cuda.is_current_stream_capturing() and (int(vert_idx.min()) < 0 or int(vert_idx.max()) >= NV):
+            raise ValueError(f"vert_idx must lie in [0, {NV})")
+        vert_idx = vert_idx.to(torch.int32).contiguous()
+    solve_shape, solve_wrist = bool(solve_shape), bool(solve_wrist)
+    if tuple(betas.shape) not in (((T, 10),) if solve_shape else ((10,), (T, 10))):
+        raise ValueError(f"betas must be ({T}, 10)" + ("" if solve_shape else " or (10,)") + f", got {tuple(betas.shape)}")
+    for name, t, shape in (("in_pose", in_pose, (T, 17, 3)), ("trans", trans, (T, 3)), ("weights", weights, (T, n_t)), ("prior", prior, (T, 45))):
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError(f"{name} must be {shape}, got {tuple(t.shape)}")
+    iters, lambda0 = int(iters), float(lambda0)
+    pose_prior_weight, wrist_prior_weight, shape_prior_weight = float(pose_prior_weight), float(wrist_prior_weight), float(shape_prior_weight)
+    if iters < 0 or any(not (0.0 <= v < float("inf")) for v in (lambda0, pose_prior_weight, wrist_prior_weight, shape_prior_weight)):
+        raise ValueError(f"iters >= 0 and finite lambda0, pose_prior_weight, wrist_prior_weight, shape_prior_weight >= 0, got {iters}, {lambda0}, "
+                         f"{pose_prior_weight}, {wrist_prior_weight}, {shape_prior_weight}")
+    if dm.v_template.device != targets.device:
+        raise ValueError(f"the model is on {dm.v_template.device}, the targets on {targets.device}")
+    dev = targets.device
+    want = ((T, 17, 3), tuple(betas.shape), (T, 3), (T, 2), (T,), (T, NV, 3) if verts else None, (T, 3 * n_t, 64) if jac else None,
+            (T, 64, 64) if normal else None, (T, 64) if normal else None)
+    if out is None:
+        out = ArmVertexFitResult(*[None if shape is None else torch.empty(shape, dtype=torch.int32 if name == "status" else torch.float32, device=dev)
+                                   for name, shape in zip(ArmVertexFitResult._fields, want)])
+    else:
+        for name, t, shape in zip(ArmVertexFitResult._fields, out, want):
+            if (t is None) != (shape is None) or (t is not None and (tuple(t.shape) != shape or t.device != dev or not t.is_contiguous()
+                                                                      or t.dtype != (torch.int32 if name == "status" else torch.float32))):
+                raise ValueError(f"out.{name} does not fit this call")
+    out.in_pose.copy_(in_pose.detach())
+    out.betas.copy_(betas.detach())
+    out.trans.copy_(trans.detach())
+    c = lambda t: None if t is None else t.detach().contiguous()
+    targets, weights, prior = c(targets), c(weights), c(prior)
+    opt = _lib.ArmVertexFitOptions(iters, lambda0, pose_prior_weight, wrist_prior_weight, shape_prior_weight, int(solve_shape), int(solve_wrist),
+                                   int(betas.dim() == 2))
+    with torch.cuda.device(dev):
+        rc = _lib.lib().harp_arm_vertex_fit(ctypes.byref(dm.struct), _lib.ptr(vert_idx), n_t, _lib.ptr(targets), _lib.ptr(weights), _lib.ptr(prior),
+                                            T, ctypes.byref(opt), _lib.ptr(out.in_pose), _lib.ptr(out.betas), _lib.ptr(out.trans),
+                                            _lib.ptr(out.cost), _lib.ptr(out.status), _lib.ptr(out.verts), _lib.ptr(out.jac), _lib.ptr(out.A),
+                                            _lib.ptr(out.g), _lib.stream())
+    _lib.check(rc, "harp_arm_vertex_fit")
+    return out

@@ -7,7 +7,7 @@ The package in four modules, each importing only those before it:
   keypoints  the float64 host side of the keypoint solve: rest joints, bone-length scale, Kabsch start, `ik_inputs`; `vertex_start`, the
              batched rigid start of the vertex fit; and `checked`, the one coercion of a caller's tensor or array-like
   motion     `Motion` (the per-frame rows), `RowLayout` (their one packed table), `Motion.resample` (ops.motion_resample),
-             `Motion.from_keypoints` (ops.mano_ik), `Motion.from_vertices` (ops.mano_vertex_fit), `Motion.smooth` / `smooth_keypoints` (ops.motion_filter), `motion_jitter`
+             `Motion.from_keypoints` (ops.mano_ik), `Motion.from_vertices` (ops.mano_vertex_fit), `Motion.from_arm_vertices` (ops.arm_vertex_fit), `Motion.smooth` / `smooth_keypoints` (ops.motion_filter), `motion_jitter`
   player     `AvatarPlayer`, the forward-only renderer — the fit's own fused front, rasterisers and shader without a backward, then
              harp_resolve_u8: six calls of the C ABI per batch of frames, in order on one stream, captured into a graph — and `ScenePlayer`,
              several such avatars in one frame through ONE harp_composite_layers_u8 per batch; both on `_Player`, which owns staging,

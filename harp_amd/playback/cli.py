@@ -16,7 +16,9 @@ def parse_args(argv=None):
     ap.add_argument("--keypoints", default=None, help=".npz of keypoints (T,21,3) in metres [, weights (T,21), cam (3,) or (T,3)] instead of --motion: "
                                                       "the motion is solved from them (Motion.from_keypoints)")
     ap.add_argument("--vertices", default=None, help=".npz of vertices (T,778,3) in metres, MANO topology [, weights (T,778), cam (3,) or (T,3)] "
-                                                     "instead of --motion: the motion is fitted to them (Motion.from_vertices)")
+                                                     "instead of --motion: the motion is fitted to them (Motion.from_vertices); with a use_arm "
+                                                     "config (T,778,3) or the arm's (T,1026,3) [, wrist_pose (3,) or (T,3) for 778] "
+                                                     "(Motion.from_arm_vertices)")
     ap.add_argument("--out", required=True, help="directory for the frames %%04d.jpg / %%04d.png")
     ap.add_argument("--fps-scale", type=float, default=1.0, help="output frames per motion frame (2: twice as many frames, half the speed)")
     ap.add_argument("--ss", type=int, default=1, help="supersampling factor 1..4")
@@ -77,8 +79,12 @@ def main(argv=None):
                                                smooth=args.smooth_keypoints)
         elif vertices_path is not None:
             with np.load(vertices_path) as z:
-                motion = Motion.from_vertices(z["vertices"], params, hand_layer, cam=z["cam"] if "cam" in z.files else None,
-                                              weights=z["weights"] if "weights" in z.files else None, device=args.device)
+                opt = lambda k: z[k] if k in z.files else None            # noqa: E731
+                if "pose_mean" in hand_layer._model_np:                     # the SMPL-X arm (use_arm)
+                    motion = Motion.from_arm_vertices(z["vertices"], params, hand_layer, cam=opt("cam"), weights=opt("weights"),
+                                                      wrist_pose=opt("wrist_pose"), device=args.device)
+                else:
+                    motion = Motion.from_vertices(z["vertices"], params, hand_layer, cam=opt("cam"), weights=opt("weights"), device=args.device)
         else:
             motion = Motion.load(motion_path)
         if args.smooth is not None:

@@ -1,6 +1,7 @@
 """The rows of a motion and what is done to them on the device: `Motion`, its retiming (ops.motion_resample), its solve
-from keypoints (ops.mano_ik, §24) or from mesh vertices (ops.mano_vertex_fit, §27) and the window filter of a motion or of keypoints (ops.motion_filter, §25).  `RowLayout` is the one
-description of the packed table that the resampler and the filter read."""
+from keypoints (ops.mano_ik, §24) or from mesh vertices (ops.mano_vertex_fit, §27; the SMPL-X arm: ops.arm_vertex_fit, §28) and the
+window filter of a motion or of keypoints (ops.motion_filter, §25).  `RowLayout` is the one description of the packed table that the
+resampler and the filter read."""
 import numpy as np
 import torch
 
@@ -115,7 +116,8 @@ class Motion:
         runs (default: the device of params["shape"] when that is a HIP device, else "cuda").  The SMPL-X arm needs a fit over its
         kinematic tree and raises NotImplementedError."""
         if "pose_mean" in hand_layer._model_np:
-            raise NotImplementedError("Motion.from_vertices fits the MANO hand; the SMPL-X arm needs a fit over its kinematic tree")
+            raise NotImplementedError("Motion.from_vertices fits the MANO hand; the SMPL-X arm needs a fit over its kinematic tree: "
+                                      "Motion.from_arm_vertices")
         dev = torch.device(device if device is not None else (params["shape"].device if params["shape"].is_cuda else "cuda"))
         v = checked("vertices", vertices, (None, 778, 3), kind="f", split=True).astype(np.float64)
         T = v.shape[0]
@@ -139,6 +141,64 @@ class Motion:
         res = ops.mano_vertex_fit(dm, targets, up(np.concatenate([rot, pose], 1)), betas, up(trans), weights=up(w), solve_shape=False, iters=iters,
                                   pose_prior_weight=pose_prior_weight)
         return cls(res.pose48[:, 3:], res.pose48[:, :3], res.trans, cam)
+
+    @classmethod
+    def from_arm_vertices(cls, vertices, params, arm_layer, cam=None, weights=None, iters=10, pose_prior_weight=0.0, wrist_prior_weight=0.0,
+                          wrist_pose=None, init=None, device=None):
+        """A motion WITH wrist_pose for an SMPL-X arm avatar from per-frame mesh vertices, by the batched arm vertex fit on the device
+        (ops.arm_vertex_fit, csrc/arm_vertex_fit.hip).  vertices in metres, in the frame of the fit's `verts`:
+        (T,NV,3) (1026) in ARM topology — the wrist is solved; or (T,778,3) in MANO topology (a mesh regressor's output), matched to the arm's
+        vertices arm_layer.right_mano_idx — the wrist is HELD at wrist_pose ((3,) or (T,3); default zeros, or init.wrist_pose): from hand
+        vertices alone the root and the wrist rotation are nearly interchangeable.  wrist_pose is not taken with arm topology.  A vertex
+        with a non-finite coordinate or a weight <= 0 (weights (T,n), default ones) is ignored.  params: the fit's parameter dict — its
+        `shape` is the avatar's and is held fixed; row 0 of its `cam` is the default cam; cam: (3,) or (T,3).
+        The start: wrist as held (or zero) and pose zero, the root rotation and trans from the weighted Kabsch fit of the model's vertices at
+        that shape and wrist (vertex_start; the model is wrist-centred: it turns about the origin and trans is the wrist); init= takes a
+        Motion of equal length with wrist_pose instead as a warm start.  pose_prior_weight pulls the finger pose to the model's mean pose,
+        wrist_prior_weight the solved wrist to zero.  Every frame is solved on its own; Motion.smooth filters the result.  The result
+        carries no light: AvatarPlayer.load_motion then uses the fit's row 0."""
+        if "pose_mean" not in arm_layer._model_np:
+            raise ValueError("Motion.from_arm_vertices fits the SMPL-X arm layer; Motion.from_vertices fits the MANO hand")
+        dev = torch.device(device if device is not None else (params["shape"].device if params["shape"].is_cuda else "cuda"))
+        dm = arm_layer.device_model if arm_layer._dev == dev else None
+        if dm is None:
+            from ..hand_models_harp.body_models import TreeDeviceModel
+            dm = TreeDeviceModel(arm_layer._model_np, dev)
+        NV = int(dm.NV)
+        n = int(np.shape(vertices)[1]) if np.ndim(vertices) == 3 else -1
+        if n not in (NV, 778):
+            raise ValueError(f"vertices must be (T, {NV}, 3) in arm topology or (T, 778, 3) in MANO topology, got {tuple(np.shape(vertices))}")
+        arm_topology = n == NV
+        v = checked("vertices", vertices, (None, n, 3), kind="f", split=True).astype(np.float64)
+        T = v.shape[0]
+        w = None if weights is None else checked("weights", weights, (T, n), kind="f", split=True).astype(np.float64)
+        if init is not None and (not all(getattr(init, k, None) is not None for k in ("rot", "trans", "pose", "wrist_pose")) or len(init) != T):
+            raise ValueError(f"init must be a Motion of {T} frames with wrist_pose")
+        if arm_topology and wrist_pose is not None:
+            raise ValueError("wrist_pose is what a fit to MANO-topology vertices holds the wrist at; arm-topology vertices solve it")
+        cam = np.broadcast_to(checked("cam", params["cam"][0] if cam is None else cam, (3,), (T, 3)).astype(np.float32), (T, 3)).copy()
+        shape = params["shape"].detach().cpu().numpy().astype(np.float64).reshape(10)
+        if init is not None and wrist_pose is None:
+            wrist = init.wrist_pose.cpu().numpy().astype(np.float64)
+        else:
+            wrist = np.broadcast_to(np.zeros(3) if wrist_pose is None else checked("wrist_pose", wrist_pose, (3,), (T, 3)).astype(np.float64), (T, 3))
+        up = lambda x: None if x is None else torch.as_tensor(np.ascontiguousarray(x, dtype=np.float32)).to(dev)
+        idx = None if arm_topology else arm_layer.right_mano_idx.to(dev)
+        targets, betas = up(v), up(shape)
+        rows = np.zeros((T, 17, 3))
+        rows[:, 1] = wrist
+        if init is None:
+            # the model's vertices at this shape and wrist with zero stored pose: the solver's own forward, evaluated at the origin
+            zero = ops.arm_vertex_fit(dm, targets, up(rows), betas, up(np.zeros((T, 3))), vert_idx=idx, solve_shape=False, iters=0, verts=True).verts
+            rest = (zero if idx is None else zero[:, idx]).cpu().numpy().astype(np.float64) / 1000.0
+            rot, trans = K.vertex_start(v, np.ones((T, n)) if w is None else w, rest, np.zeros(3))
+            rows[:, 0] = rot
+        else:
+            rows[:, 0], trans = init.rot.cpu().numpy(), init.trans.cpu().numpy()
+            rows[:, 2:] = init.pose.cpu().numpy().reshape(T, 15, 3)
+        res = ops.arm_vertex_fit(dm, targets, up(rows), betas, up(trans), vert_idx=idx, weights=up(w), solve_shape=False, solve_wrist=arm_topology,
+                                 iters=iters, pose_prior_weight=pose_prior_weight, wrist_prior_weight=wrist_prior_weight)
+        return cls(res.in_pose[:, 2:].reshape(T, 45), res.in_pose[:, 0], res.trans, cam, wrist_pose=res.in_pose[:, 1])
 
     def save(self, path):
         np.savez(path, **{k: getattr(self, k).cpu().numpy() for k in self.FIELDS if getattr(self, k) is not None})

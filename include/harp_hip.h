@@ -1193,6 +1193,59 @@ int harp_mano_vertex_fit(const harp_mano_model* m, const float* targets, const f
                          const harp_vertex_fit_options* opt, float* pose48, float* betas, float* trans, float* cost, int32_t* status,
                          float* verts, float* jac, float* A, float* g, hipStream_t stream);
 
+/* ---- batched SMPL-X arm vertex fit: arm or hand mesh vertices -> rot, wrist, pose, shape and trans rows (csrc/arm_vertex_fit.hip;
+ * metro_modifications/hand_utils.py optimize_for_mano_arm_param(method="lm"); playback Motion.from_arm_vertices) ----
+ * The reference fits these rows with 500 + 700 Adam iterations (metro_modifications/hand_utils.py:134-240).  The model inverted is
+ * harp_lbs_tree_fwd's.  T independent Levenberg-Marquardt solves in one launch, forward only, no workspace, no allocation, no
+ * synchronisation, no atomics, fixed summation order (capturable; a repeated call gives the same bits).  Unknowns per frame
+ * x = [rot 3 | wrist 3 | pose 45 | betas 10 | trans 3]: x[0..51) is the frame's row of in_pose (T,17,3) exactly as harp_lbs_tree_fwd takes
+ * it (row pose_src names: 0 = global orient, 1 = right wrist, 2..16 = right hand; stored relative to pose_mean), x[51..61) the first ten
+ * shape coefficients, x[61..64) transl.
+ *   v(x) (NV,3) metres = harp_lbs_tree_fwd's verts / 1000 for the shape [betas | NB - 10 zeros]: the subtraction of the posed
+ *   center_joint and the + transl included.
+ *   targets (T,n_t,3) metres: row i belongs to model vertex vert_idx[i] (n_t int32, any order, shared by the frames); vert_idx == NULL:
+ *   n_t == NV and the map is the identity.  An index outside [0, NV) is clamped into it: the caller checks the range (ops does).
+ *   weights (T,n_t) or NULL (ones); prior (T,45) or NULL (zeros: the model's mean pose).  A target is USED when its weight is > 0 and its
+ *   three coordinates are finite; an unused target never enters arithmetic.
+ *   C(x) = sum_i w_i |v_{vert_idx[i]}(x) - t_i|^2 + pose_prior_weight sum (pose - prior)^2 + wrist_prior_weight sum wrist^2 +
+ *   shape_prior_weight sum betas^2.
+ *   solve_shape == 0: betas are given and are not written: (10,) for all frames, or (T,10) with betas_per_frame != 0; their ten columns are
+ *   FROZEN.  solve_shape != 0: betas (T,10) are in/out (betas_per_frame is not read).  solve_wrist == 0: the wrist row of in_pose is read
+ *   and never written; its three columns are FROZEN.
+ *   Iteration, exactly `iters` times, harp_mano_vertex_fit's word for word: J = the exact 3 n_t x 64 derivative of the indexed vertices at
+ *   x; A = J^T W J + P, g = J^T W r + P (x - x_prior), P = the three prior weights on the 45 pose, 3 wrist and 10 shape diagonals (x_prior:
+ *   prior for the pose, 0 otherwise); a frozen column has A_ii = 1, zeros elsewhere in its row and column, and g_i = 0, so its step is
+ *   exactly 0; (A + lambda diag A) d = -g by a Cholesky factorisation of the matrix scaled from both sides by 1 / sqrt(A_ii (1 + lambda));
+ *   x' = x + d; C(x') < C(x): accept, lambda = max(0.1 lambda, 1e-9); otherwise (a NaN included, and a non-positive or non-finite pivot or
+ *   diagonal) keep x, lambda = min(10 lambda, 1e6).  lambda starts at lambda0.
+ * In/out: in_pose (T,17,3) (the wrist row only when solve_wrist), trans (T,3), betas when solve_shape.  Out: cost (T,2) = C at the input
+ * and at the result; status (T) int32 = accepted steps; -1 for a frame with fewer than 22 used targets (3 x 22 >= 64), which is not solved
+ * (its rows are not written); -2 (cost 0, nothing else written) when the model's tree is not one the kernel's tables hold: row 0 must
+ * drive joint 0, every other row a joint of its own below it, and the joints at or below the driven non-root joints, counted per driven
+ * joint, must number at most 48 (the arm: 16 for the wrist + 5 x 6 for the fingers).  The skin weights of a vertex must sum to one.
+ * Optional out (NULL allowed), all at the final x: verts (T,NV,3) mm, ALL model vertices; jac (T,3 n_t,64), metres per unit of x, always
+ * all 64 columns; A (T,64,64) and g (T,64), unscaled, frozen columns as above.  iters == 0 evaluates all of them at the input and writes
+ * none of the in/out rows.
+ * HARP_ERR_ARG before any launch: m, opt, targets, in_pose, betas, trans, cost or status NULL; T <= 0; iters < 0; n_t < 1 or n_t > NV;
+ * vert_idx == NULL with n_t != NV; n_pose_in != 17; NB < 10, NB > 32 or NJ > 64; NV > HARP_ARM_VERTEX_FIT_MAX_VERTS (the per-vertex tables
+ * of one frame live in LDS); center_joint outside [0, NJ); lambda0 or a prior weight negative or not finite.
+ * harp_arm_vertex_fit_frames_per_block: the frames one workgroup solves (tests size their batches around it). */
+#define HARP_ARM_VERTEX_FIT_MAX_VERTS 1088
+typedef struct harp_arm_vertex_fit_options {
+  int iters;
+  float lambda0;            /* 1e-3 */
+  float pose_prior_weight;  /* 0: the reference's unregularised MSE */
+  float wrist_prior_weight; /* 0 */
+  float shape_prior_weight; /* 0 */
+  int solve_shape;          /* 0: betas given and frozen; otherwise betas (T,10) in/out */
+  int solve_wrist;          /* 0: the wrist row of in_pose given and frozen */
+  int betas_per_frame;      /* with solve_shape == 0: 0: betas (10,); otherwise betas (T,10) */
+} harp_arm_vertex_fit_options;
+int harp_arm_vertex_fit_frames_per_block(void);
+int harp_arm_vertex_fit(const harp_tree_model* m, const int32_t* vert_idx, int n_t, const float* targets, const float* weights,
+                        const float* prior, int T, const harp_arm_vertex_fit_options* opt, float* in_pose, float* betas, float* trans,
+                        float* cost, int32_t* status, float* verts, float* jac, float* A, float* g, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
