@@ -373,3 +373,14 @@ ARM_VERTEX_FIT_MAX_VERTS = 1088                            # HARP_ARM_VERTEX_FIT
 SIGNATURES["harp_arm_vertex_fit_frames_per_block"] = (_i, [])
 SIGNATURES["harp_arm_vertex_fit"] = (_i, [_trp, _vp, _i, _vp, _vp, _vp, _i, ctypes.POINTER(ArmVertexFitOptions), _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                           _vp, _vp, _vp])
+
+
+class ArmIkOptions(ctypes.Structure):
+    """mirror of `harp_arm_ik_options` (include/harp_hip.h)"""
+    _fields_ = [("iters", _i), ("lambda0", _f), ("pose_prior_weight", _f), ("wrist_prior_weight", _f), ("solve_wrist", _i), ("betas_per_frame", _i)]
+
+
+# batched SMPL-X arm inverse kinematics (csrc/arm_ik.hip)
+ARM_IK_MAX_JOINTS = 22                                     # HARP_ARM_IK_MAX_JOINTS
+SIGNATURES["harp_arm_ik_frames_per_block"] = (_i, [])
+SIGNATURES["harp_arm_ik"] = (_i, [_trp, _vp, _vp, _vp, _vp, _vp, _i, ctypes.POINTER(ArmIkOptions), _vp, _vp, _vp, _vp, _vp, _vp, _vp])

@@ -1507,3 +1507,68 @@ def arm_vertex_fit(dm, targets, in_pose, betas, trans, vert_idx=None, weights=No
                                             _lib.ptr(out.g), _lib.stream())
     _lib.check(rc, "harp_arm_vertex_fit")
     return out
+
+
+# ---- batched SMPL-X arm inverse kinematics (csrc/arm_ik.hip) --------------------------------------------------------
+ArmIkResult = collections.namedtuple("ArmIkResult", "in_pose trans cost status joints jac")
+
+
+def arm_ik_frames_per_block():
+    """the frames one workgroup of harp_arm_ik solves"""
+    return int(_lib.lib().harp_arm_ik_frames_per_block())
+
+
+def arm_ik(dm, betas, targets, in_pose, trans, weights=None, prior=None, wrist_prior=None, solve_wrist=True, iters=15, lambda0=1e-3,
+           pose_prior_weight=0.0, wrist_prior_weight=0.0, joints=False, jac=False, out=None):
+    """3-D keypoints -> SMPL-X arm rows: T Levenberg-Marquardt solves in one launch (csrc/arm_ik.hip: harp_arm_ik, whose contract
+    include/harp_hip.h states), forward only.  dm: a TreeDeviceModel (hand_models_harp.body_models) with n = n_joints_out output joints
+    (the arm: 22 = the wrist, the five fingers root to tip, the elbow); betas (10,) for all frames or (T,10); targets (T,n,3) metres in the
+    order of the model's joints; in_pose (T,17,3) = [rot | wrist | pose(15)] and trans (T,3): the start, left untouched; solve_wrist=False
+    holds the wrist row at what in_pose gives; weights (T,n) or None (ones; a joint with weight <= 0 or a non-finite target is unused);
+    prior (T,45) or None (the mean pose) with pose_prior_weight on sum (pose - prior)^2; wrist_prior (T,3) or None (zeros) with
+    wrist_prior_weight on sum (wrist - wrist_prior)^2.  Returns ArmIkResult(in_pose, trans, cost (T,2) = at the start and at the result,
+    status (T,) int32 = accepted steps or -1 for a frame with fewer than 3 used joints (returned as it came), joints (T,n,3) mm or None,
+    jac (T,3 n,54) or None), the optional ones at the result.  iters = 0 evaluates at the start.  out: an earlier ArmIkResult of the same
+    shapes whose tensors are written instead of new ones — the call then allocates nothing and can be captured into a graph."""
+    _playback_input("arm_ik", betas, targets, in_pose, trans, weights, prior, wrist_prior)
+    for name, t in (("betas", betas), ("targets", targets), ("in_pose", in_pose), ("trans", trans), ("weights", weights), ("prior", prior),
+                    ("wrist_prior", wrist_prior)):
+        if t is not None and t.dtype != torch.float32:
+            raise TypeError(f"arm_ik takes float32 tensors, {name} is {t.dtype}")
+    n = int(dm.struct.n_joints_out)
+    if targets.dim() != 3 or tuple(targets.shape[1:]) != (n, 3) or targets.shape[0] < 1:
+        raise ValueError(f"targets must be (T, {n}, 3), got {tuple(targets.shape)}")
+    T = int(targets.shape[0])
+    if tuple(betas.shape) not in ((10,), (T, 10)):
+        raise ValueError(f"betas must be (10,) or ({T}, 10), got {tuple(betas.shape)}")
+    for name, t, shape in (("in_pose", in_pose, (T, 17, 3)), ("trans", trans, (T, 3)), ("weights", weights, (T, n)), ("prior", prior, (T, 45)),
+                           ("wrist_prior", wrist_prior, (T, 3))):
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError(f"{name} must be {shape}, got {tuple(t.shape)}")
+    iters, lambda0, pose_prior_weight, wrist_prior_weight = int(iters), float(lambda0), float(pose_prior_weight), float(wrist_prior_weight)
+    if iters < 0 or any(not (0.0 <= v < float("inf")) for v in (lambda0, pose_prior_weight, wrist_prior_weight)):
+        raise ValueError(f"iters >= 0 and finite lambda0, pose_prior_weight, wrist_prior_weight >= 0, got {iters}, {lambda0}, "
+                         f"{pose_prior_weight}, {wrist_prior_weight}")
+    if dm.v_template.device != targets.device:
+        raise ValueError(f"the model is on {dm.v_template.device}, the targets on {targets.device}")
+    dev = targets.device
+    want = ((T, 17, 3), (T, 3), (T, 2), (T,), (T, n, 3) if joints else None, (T, 3 * n, 54) if jac else None)
+    if out is None:
+        out = ArmIkResult(*[None if shape is None else torch.empty(shape, dtype=torch.int32 if name == "status" else torch.float32, device=dev)
+                            for name, shape in zip(ArmIkResult._fields, want)])
+    else:
+        for name, t, shape in zip(ArmIkResult._fields, out, want):
+            if (t is None) != (shape is None) or (t is not None and (tuple(t.shape) != shape or t.device != dev or not t.is_contiguous()
+                                                                      or t.dtype != (torch.int32 if name == "status" else torch.float32))):
+                raise ValueError(f"out.{name} does not fit this call")
+    out.in_pose.copy_(in_pose.detach())
+    out.trans.copy_(trans.detach())
+    c = lambda t: None if t is None else t.detach().contiguous()
+    betas, targets, weights, prior, wrist_prior = c(betas), c(targets), c(weights), c(prior), c(wrist_prior)
+    opt = _lib.ArmIkOptions(iters, lambda0, pose_prior_weight, wrist_prior_weight, int(bool(solve_wrist)), int(betas.dim() == 2))
+    with torch.cuda.device(dev):
+        rc = _lib.lib().harp_arm_ik(ctypes.byref(dm.struct), _lib.ptr(betas), _lib.ptr(targets), _lib.ptr(weights), _lib.ptr(prior),
+                                    _lib.ptr(wrist_prior), T, ctypes.byref(opt), _lib.ptr(out.in_pose), _lib.ptr(out.trans), _lib.ptr(out.cost),
+                                    _lib.ptr(out.status), _lib.ptr(out.joints), _lib.ptr(out.jac), _lib.stream())
+    _lib.check(rc, "harp_arm_ik")
+    return out

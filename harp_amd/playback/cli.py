@@ -14,7 +14,10 @@ def parse_args(argv=None):
     ap.add_argument("--config", required=True, help="yaml with the keys of utils/config_utils.get_config (the fit's)")
     ap.add_argument("--motion", default=None, help=".npz of pose (T,45), rot, trans, cam (T,3) [, wrist_pose, light_positions] (Motion.save)")
     ap.add_argument("--keypoints", default=None, help=".npz of keypoints (T,21,3) in metres [, weights (T,21), cam (3,) or (T,3)] instead of --motion: "
-                                                      "the motion is solved from them (Motion.from_keypoints)")
+                                                      "the motion is solved from them (Motion.from_keypoints); with a use_arm config (T,22,3) = "
+                                                      "the 21 hand keypoints plus the elbow as row 21 (the wrist is solved) or (T,21,3) (the "
+                                                      "wrist is held) [, weights (T,22) or (T,21), wrist_pose (3,) or (T,3)] "
+                                                      "(Motion.from_arm_keypoints)")
     ap.add_argument("--vertices", default=None, help=".npz of vertices (T,778,3) in metres, MANO topology [, weights (T,778), cam (3,) or (T,3)] "
                                                      "instead of --motion: the motion is fitted to them (Motion.from_vertices); with a use_arm "
                                                      "config (T,778,3) or the arm's (T,1026,3) [, wrist_pose (3,) or (T,3) for 778] "
@@ -74,9 +77,13 @@ def main(argv=None):
         params["verts_uvs"], params["faces_uvs"] = VERTS_UVS, FACES_UVS
         if keypoints_path is not None:
             with np.load(keypoints_path) as z:
-                motion = Motion.from_keypoints(z["keypoints"], params, hand_layer, cam=z["cam"] if "cam" in z.files else None,
-                                               weights=z["weights"] if "weights" in z.files else None, device=args.device,
-                                               smooth=args.smooth_keypoints)
+                opt = lambda k: z[k] if k in z.files else None            # noqa: E731
+                if "pose_mean" in hand_layer._model_np:                     # the SMPL-X arm (use_arm)
+                    motion = Motion.from_arm_keypoints(z["keypoints"], params, hand_layer, cam=opt("cam"), weights=opt("weights"),
+                                                       wrist_pose=opt("wrist_pose"), device=args.device, smooth=args.smooth_keypoints)
+                else:
+                    motion = Motion.from_keypoints(z["keypoints"], params, hand_layer, cam=opt("cam"), weights=opt("weights"),
+                                                   device=args.device, smooth=args.smooth_keypoints)
         elif vertices_path is not None:
             with np.load(vertices_path) as z:
                 opt = lambda k: z[k] if k in z.files else None            # noqa: E731

@@ -1,10 +1,13 @@
 """The host side of Motion.from_keypoints, numpy float64 and no device: the model's rest joints, the bone-length scale, the
 Kabsch start of the root (T problems of six points each), and `ik_inputs`, which checks what a caller passed and returns the arrays that
-ops.mano_ik is fed.  `checked` is the package's one coercion and check of a tensor or array-like that a caller passed."""
+ops.mano_ik is fed.  `checked` is the package's one coercion and check of a tensor or array-like that a caller passed.  The SMPL-X arm's
+counterparts (Motion.from_arm_keypoints): `rest_arm_joints`, `match_arm_lengths`, `arm_palm_start`."""
 import numpy as np
 import torch
 
 JOINT_REORDER = (0, 13, 14, 15, 16, 1, 2, 3, 17, 4, 5, 6, 18, 10, 11, 12, 19, 7, 8, 9, 20)      # output joint -> model joint / tip (manolayer.py:279)
+ARM_JOINT_IDX = (21, 52, 53, 54, 71, 40, 41, 42, 72, 43, 44, 45, 73, 49, 50, 51, 74, 46, 47, 48, 75, 19)      # the arm's output joint -> SMPL-X joint (71..75: tip vertices)
+ELBOW = 21                                             # the arm's last output row; rows 0..20 are MANO's keypoint order
 PALM = (0, 1, 5, 9, 13, 17)                            # output joints that only the root moves: the wrist and the five finger roots
 # the 15 chain bones in output joints: wrist -> finger root and the two bones after it; the tip bones are left out (pose correctives move the tips)
 CHAIN_BONES = tuple((0 if k == 0 else 4 * f + k, 4 * f + k + 1) for f in range(5) for k in range(3))
@@ -43,6 +46,42 @@ def rest_chain_joints(model, shape):
         if src < 16:
             out[k] = j16[src]
     return out
+
+
+def rest_arm_joints(model, shape):
+    """the SMPL-X arm's 22 joints in output order (the wrist, the five fingers root to tip, the elbow) at `shape` BEFORE any rotation,
+    (22,3) float64; the five tips are NaN (skinned vertices: they depend on the pose).  rest_chain_joints' counterpart for the arm model's
+    arrays (J_template (55,3), J_shapedirs (55,3,NB), the joint regressor already folded in): every chain bone's length and the forearm's,
+    |row 21 - row 0|, do not depend on the pose."""
+    f64 = lambda k: np.asarray(model[k], np.float64)
+    b = np.zeros(f64("J_shapedirs").shape[-1])
+    b[:10] = np.asarray(shape, np.float64).reshape(10)
+    j55 = f64("J_template").reshape(-1, 3) + f64("J_shapedirs") @ b
+    out = np.full((22, 3), np.nan)
+    for k, src in enumerate(ARM_JOINT_IDX):
+        if src < j55.shape[0]:
+            out[k] = j55[src]
+    return out
+
+
+def match_arm_lengths(keypoints, used, rest):
+    """(T,21|22,3) keypoints with someone else's proportions -> the avatar's: the 21 hand keypoints scaled about their wrist by
+    bone_length_scale (the chain bones then sum to the model's), and the elbow, when the keypoints have one, put on its ray from the
+    wrist at the MODEL's forearm length |rest[21] - rest[0]| — no unknown of the solve changes that length, so a forearm of another length
+    could only be absorbed by trans.  rest: rest_arm_joints.  A frame without a finite wrist stays as it is; so does an elbow that is
+    not finite or lies on the wrist.  Returns (keypoints, the hand's scale)."""
+    kp = np.array(keypoints, np.float64)
+    wrist = kp[:, :1]
+    has_wrist = np.isfinite(wrist).all(-1, keepdims=True)
+    scale = bone_length_scale(kp[:, :21], used[:, :21], rest[:21])
+    kp[:, :21] = np.where(has_wrist, wrist + scale * (kp[:, :21] - wrist), kp[:, :21])
+    if kp.shape[1] > ELBOW:
+        ray = kp[:, ELBOW] - wrist[:, 0]
+        with np.errstate(invalid="ignore"):
+            n = np.linalg.norm(ray, axis=-1, keepdims=True)
+            ok = has_wrist[:, 0] & np.isfinite(n) & (n > 0)
+            kp[:, ELBOW] = np.where(ok, wrist[:, 0] + ray / np.where(ok, n, 1.0) * np.linalg.norm(rest[ELBOW] - rest[0]), kp[:, ELBOW])
+    return kp, scale
 
 
 def bone_length_scale(keypoints, used, rest):
@@ -179,3 +218,16 @@ def vertex_start(targets, used, rest_vertices, root_joint):
     take = np.maximum(src, 0)
     none = (src < 0)[:, None]
     return np.where(none, 0.0, rot[take]), np.where(none, 0.0, trans[take])
+
+
+def arm_palm_start(keypoints, used, joints0):
+    """The rigid start of the arm's keypoint solve (Motion.from_arm_keypoints): rot (T,3) axis-angle and trans (T,3), float64,
+    one batched SVD (vertex_start), no loop over the frames.  keypoints (T,21|22,3); used (T,21|22) bool or non-negative weights; joints0
+    (22,3) or (T,22,3): the model's output joints in metres at the avatar's shape, the held (or prior) wrist, zero finger pose, zero root
+    and zero trans — the solver's own forward.  Their palm rows (PALM) and the elbow move rigidly under the root, about the origin (the
+    model is wrist-centred: trans is the wrist), so the Kabsch fit over those six points, and the elbow where the keypoints have one and
+    it is used, is the start.  A frame that cannot be aligned takes the last one that could."""
+    kp = np.asarray(keypoints, np.float64)
+    idx = np.array(PALM + ((ELBOW,) if kp.shape[1] > ELBOW else ()))
+    j0 = np.asarray(joints0, np.float64)
+    return vertex_start(kp[:, idx], np.asarray(used)[:, idx], j0[..., idx, :], np.zeros(3))

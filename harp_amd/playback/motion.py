@@ -1,5 +1,6 @@
 """The rows of a motion and what is done to them on the device: `Motion`, its retiming (ops.motion_resample), its solve
-from keypoints (ops.mano_ik, §24) or from mesh vertices (ops.mano_vertex_fit, §27; the SMPL-X arm: ops.arm_vertex_fit, §28) and the
+from keypoints (ops.mano_ik, §24; the SMPL-X arm: ops.arm_ik, §29) or from mesh vertices (ops.mano_vertex_fit, §27; the SMPL-X arm:
+ops.arm_vertex_fit, §28) and the
 window filter of a motion or of keypoints (ops.motion_filter, §25).  `RowLayout` is the one description of the packed table that the
 resampler and the filter read."""
 import numpy as np
@@ -89,9 +90,10 @@ class Motion:
         instead.  None leaves the keypoints as they came.
         The result carries no light: AvatarPlayer.load_motion then uses the fit's row 0.  device: where the solve runs (default: the
         device of params["shape"] when that is a HIP device, else "cuda").  The SMPL-X arm needs a solver for its kinematic tree and raises
-        NotImplementedError."""
+        NotImplementedError: Motion.from_arm_keypoints is that solver."""
         if "pose_mean" in hand_layer._model_np:
-            raise NotImplementedError("Motion.from_keypoints solves the MANO hand; the SMPL-X arm needs a kinematic-tree solver")
+            raise NotImplementedError("Motion.from_keypoints solves the MANO hand; the SMPL-X arm needs a kinematic-tree solver: "
+                                      "Motion.from_arm_keypoints")
         dev = torch.device(device if device is not None else (params["shape"].device if params["shape"].is_cuda else "cuda"))
         host = lambda pair: tuple(t.cpu().numpy() for t in pair)      # noqa: E731
         a = K.ik_inputs(keypoints, weights, cam, init, params, hand_layer._model_np, match_bone_lengths,
@@ -200,6 +202,78 @@ class Motion:
                                  iters=iters, pose_prior_weight=pose_prior_weight, wrist_prior_weight=wrist_prior_weight)
         return cls(res.in_pose[:, 2:].reshape(T, 45), res.in_pose[:, 0], res.trans, cam, wrist_pose=res.in_pose[:, 1])
 
+    @classmethod
+    def from_arm_keypoints(cls, keypoints, params, arm_layer, cam=None, weights=None, match_bone_lengths=True, iters=15, prior_weight=1e-5,
+                           wrist_prior_weight=1e-4, wrist_pose=None, init=None, device=None, smooth=None):
+        """A motion WITH wrist_pose for an SMPL-X arm avatar from 3-D keypoints (a hand tracker, a mocap glove, a body tracker that also
+        gives the elbow) by batched inverse kinematics over the arm's joint tree on the device (ops.arm_ik, csrc/arm_ik.hip, DESIGN.md
+        §29).  keypoints in metres, in the frame of the fit's `joints`:
+        (T,22,3) — the 21 hand keypoints in the model's order (wrist, then thumb, index, middle, ring and little, each from root to tip)
+        plus the ELBOW as row 21: the wrist is SOLVED, and wrist_pose ((3,) or (T,3); default zeros, or init.wrist_pose) is the centre
+        of its prior (wrist_prior_weight); a frame whose elbow is missing is still solved, and the prior then decides its wrist;
+        (T,21,3) — the hand only: the wrist is HELD at wrist_pose, because from hand points alone the root and the wrist rotation are
+        interchangeable (§28 found the same for 778 vertices).
+        A joint with a non-finite coordinate or a weight <= 0 (weights (T,n), default ones) is ignored.  params: the fit's parameter dict
+        (its `shape` is the avatar's and is not solved; row 0 of its `cam` is the default cam); cam: (3,) or (T,3).
+        The start: wrist as held (or the prior's centre) and pose zero, the root rotation and trans from the Kabsch fit of the model's palm
+        joints and elbow (arm_palm_start; host float64, one batched SVD) onto the keypoints', the model's joints taken from the solver's
+        own forward; init= takes a Motion of equal length with wrist_pose instead as a warm start.  match_bone_lengths scales the hand
+        keypoints about their wrist so that their chain bones sum to the model's and puts the elbow on its ray from the wrist at the
+        model's forearm length (match_arm_lengths): someone else's arm can drive the avatar.  prior_weight pulls the finger pose to the
+        model's mean pose.  smooth: None, or the sigma in frames of a Gaussian window that the keypoints go through first
+        (smooth_keypoints), as in from_keypoints.  Every frame is solved on its own; Motion.smooth filters the solved rows.
+        What keypoints cannot see: with the joints matched to a fraction of a millimetre the recovered VERTICES can still differ from the
+        true ones by centimetres — the twist of a finger's last bone and of the forearm about its own axis is not in 22 points; the
+        priors decide it.  The result carries no light: AvatarPlayer.load_motion then uses the fit's row 0.  A MANO layer raises
+        ValueError: Motion.from_keypoints solves that model."""
+        if "pose_mean" not in arm_layer._model_np:
+            raise ValueError("Motion.from_arm_keypoints solves the SMPL-X arm layer; Motion.from_keypoints solves the MANO hand")
+        n = int(np.shape(keypoints)[1]) if np.ndim(keypoints) == 3 else -1
+        if n not in (21, 22):
+            raise ValueError(f"keypoints must be (T, 22, 3) with the elbow or (T, 21, 3) without, got {tuple(np.shape(keypoints))}")
+        kp = checked("keypoints", keypoints, (None, n, 3), kind="f", split=True).astype(np.float64)
+        T = kp.shape[0]
+        w = None if weights is None else checked("weights", weights, (T, n), kind="f", split=True).astype(np.float64)
+        if init is not None and (not all(getattr(init, k, None) is not None for k in ("rot", "trans", "pose", "wrist_pose")) or len(init) != T):
+            raise ValueError(f"init must be a Motion of {T} frames with wrist_pose")
+        cam = np.broadcast_to(checked("cam", params["cam"][0] if cam is None else cam, (3,), (T, 3)).astype(np.float32), (T, 3)).copy()
+        shape = params["shape"].detach().cpu().numpy().astype(np.float64).reshape(10)
+        if init is not None and wrist_pose is None:
+            wrist = init.wrist_pose.cpu().numpy().astype(np.float64)
+        else:
+            wrist = np.broadcast_to(np.zeros(3) if wrist_pose is None else checked("wrist_pose", wrist_pose, (3,), (T, 3)).astype(np.float64), (T, 3))
+        dev = torch.device(device if device is not None else (params["shape"].device if params["shape"].is_cuda else "cuda"))
+        if smooth is not None:
+            kp_s, filled = smooth_keypoints(kp, weights=w, sigma=smooth, device=dev, joints=n)
+            kp = kp_s.cpu().numpy().astype(np.float64)              # (a joint with nothing in its window comes back as it went in)
+            w = None if w is None else np.where((filled.cpu().numpy() > 0) & ~(w > 0), 1.0, w)
+        used = np.isfinite(kp).all(-1) & (True if w is None else (w > 0))
+        if match_bone_lengths:
+            kp, _ = K.match_arm_lengths(kp, used, K.rest_arm_joints(arm_layer._model_np, shape))
+        dm = arm_layer.device_model if arm_layer._dev == dev else None
+        if dm is None:
+            from ..hand_models_harp.body_models import TreeDeviceModel
+            dm = TreeDeviceModel(arm_layer._model_np, dev)
+        up = lambda x: None if x is None else torch.as_tensor(np.ascontiguousarray(x, dtype=np.float32)).to(dev)
+        # the hand alone is the 22-wide problem with the elbow unused and the wrist held
+        tg = kp if n == 22 else np.concatenate([kp, np.full((T, 1, 3), np.nan)], 1)
+        wt = used.astype(np.float64) if w is None else np.where(used, w, 0.0)
+        wt = wt if n == 22 else np.concatenate([wt, np.zeros((T, 1))], 1)
+        targets, betas = up(tg), up(shape)
+        rows = np.zeros((T, 17, 3))
+        rows[:, 1] = wrist if init is None or n == 21 else init.wrist_pose.cpu().numpy()      # (a solved wrist starts where init has it)
+        if init is None:
+            # the model's joints at this shape and wrist with zero stored pose: the solver's own forward, evaluated at the origin
+            zero = ops.arm_ik(dm, betas, targets, up(rows), up(np.zeros((T, 3))), iters=0, joints=True).joints
+            rot, trans = K.arm_palm_start(kp, used, zero.cpu().numpy().astype(np.float64) / 1000.0)
+            rows[:, 0] = rot
+        else:
+            rows[:, 0], trans = init.rot.cpu().numpy(), init.trans.cpu().numpy()
+            rows[:, 2:] = init.pose.cpu().numpy().reshape(T, 15, 3)
+        res = ops.arm_ik(dm, betas, targets, up(rows), up(trans), weights=up(wt), wrist_prior=up(wrist), solve_wrist=n == 22, iters=iters,
+                         pose_prior_weight=prior_weight, wrist_prior_weight=wrist_prior_weight)
+        return cls(res.in_pose[:, 2:].reshape(T, 45), res.in_pose[:, 0], res.trans, cam, wrist_pose=res.in_pose[:, 1])
+
     def save(self, path):
         np.savez(path, **{k: getattr(self, k).cpu().numpy() for k in self.FIELDS if getattr(self, k) is not None})
 
@@ -254,25 +328,26 @@ def _segment_ids(segments, T):
     return checked("segments", segments, (T,), kind="i", tensor=True).to(torch.int32).contiguous()
 
 
-def smooth_keypoints(keypoints, weights=None, sigma=2.0, radius=None, trim=None, segments=None, device="cuda"):
+def smooth_keypoints(keypoints, weights=None, sigma=2.0, radius=None, trim=None, segments=None, device="cuda", joints=21):
     """(T,21,3) keypoints through the window filter as 21 vector channels (ops.motion_filter) -> (keypoints (T,21,3) float32,
-    used (T,21) int32), both on `device`.  weights: None or (T,21) confidences.  A joint with a non-finite coordinate or a weight <= 0 has
+    used (T,21) int32), both on `device`.  joints=22: the SMPL-X arm's layout, the elbow as one more point row of the same call.  weights: None or (T,21) confidences.  A joint with a non-finite coordinate or a weight <= 0 has
     weight 0: it does not pull on its neighbours and is FILLED from them when any lie in the window (used > 0); with none it comes back as
     it went in (used == 0).  trim: None or a distance in the keypoints' unit for the trimmed second pass; segments: as Motion.smooth."""
-    kp = checked("keypoints", keypoints, (None, 21, 3), kind="f", tensor=True).to(torch.float32)
+    n = int(joints)
+    kp = checked("keypoints", keypoints, (None, n, 3), kind="f", tensor=True).to(torch.float32)
     T = kp.shape[0]
     dev = torch.device(device)
     ok = torch.isfinite(kp).all(-1)
     if weights is None:
         w = ok.to(torch.float32)
     else:
-        w = checked("weights", weights, (T, 21), kind="f", tensor=True).to(torch.float32).to(kp.device)
+        w = checked("weights", weights, (T, n), kind="f", tensor=True).to(torch.float32).to(kp.device)
         w = torch.where(ok & (w > 0) & torch.isfinite(w), w, torch.zeros_like(w))
-    tr = None if trim is None else torch.full((21,), float(trim), dtype=torch.float32).to(dev)
+    tr = None if trim is None else torch.full((n,), float(trim), dtype=torch.float32).to(dev)
     seg = None if segments is None else _segment_ids(segments, T).to(dev)
-    out, used = ops.motion_filter(kp.reshape(T, 63).contiguous().to(dev), 0, 21, ops.gaussian_taps(sigma, radius), weights=w.contiguous().to(dev),
+    out, used = ops.motion_filter(kp.reshape(T, 3 * n).contiguous().to(dev), 0, n, ops.gaussian_taps(sigma, radius), weights=w.contiguous().to(dev),
                                   segment=seg, trim=tr)
-    return out.reshape(T, 21, 3), used
+    return out.reshape(T, n, 3), used
 
 
 def motion_jitter(motion, params, hand_layer, other=None):

@@ -1246,6 +1246,51 @@ int harp_arm_vertex_fit(const harp_tree_model* m, const int32_t* vert_idx, int n
                         const float* prior, int T, const harp_arm_vertex_fit_options* opt, float* in_pose, float* betas, float* trans,
                         float* cost, int32_t* status, float* verts, float* jac, float* A, float* g, hipStream_t stream);
 
+/* ---- batched SMPL-X arm inverse kinematics: 3-D keypoints -> rot, wrist, pose and trans rows (csrc/arm_ik.hip; playback
+ * Motion.from_arm_keypoints) ----
+ * Nothing in the reference does this.  The model inverted is harp_lbs_tree_fwd's.  T independent Levenberg-Marquardt solves in one launch,
+ * forward only, no workspace, no allocation, no synchronisation, no atomics, fixed summation order (capturable; a repeated call gives the
+ * same bits).  Unknowns per frame x = [rot 3 | wrist 3 | pose 45 | trans 3]: x[0..51) is the frame's row of in_pose (T,17,3) exactly as
+ * harp_lbs_tree_fwd takes it (row pose_src names: 0 = global orient, 1 = right wrist, 2..16 = right hand; stored relative to pose_mean),
+ * x[51..54) transl.  The shape is given: betas (10,) for all frames, or (T,10) with betas_per_frame != 0; the model's other NB - 10
+ * coefficients are zero.
+ *   j(x) (n_out,3) metres = harp_lbs_tree_fwd's joints / 1000, n_out = n_joints_out (the arm: 22 — the wrist, the five fingers root to tip,
+ *   the elbow): the subtraction of the posed center_joint and the + transl included.  Row k is joint_src[k]: >= 0 a joint of the tree, < 0 a
+ *   skinned vertex (shape blend, the pose correctives of all NJ - 1 joints, skinning over all NJ joints).
+ *   C(x) = sum_k w_k |j_k(x) - t_k|^2 + pose_prior_weight sum (pose - prior)^2 + wrist_prior_weight sum (wrist - wrist_prior)^2; targets
+ *   (T,n_out,3) metres; weights (T,n_out) or NULL (ones); prior (T,45) or NULL (zeros: the model's mean pose); wrist_prior (T,3) or NULL
+ *   (zeros).  A joint is USED when w_k > 0 and its three target coordinates are finite; an unused joint's target never enters arithmetic.
+ *   solve_wrist == 0: the wrist row of in_pose is read and never written; its three columns are FROZEN.
+ *   Iteration, exactly `iters` times, harp_mano_ik's and harp_arm_vertex_fit's: J = the exact 3 n_out x 54 derivative of j at x; A = J^T W J
+ *   + P, g = J^T W r + P (x - x_prior), P = the two prior weights on the 45 pose and 3 wrist diagonals; a frozen column has A_ii = 1, zeros
+ *   elsewhere in its row and column, and g_i = 0, so its step is exactly 0; (A + lambda diag A) d = -g by a Cholesky factorisation of the
+ *   matrix scaled from both sides by 1 / sqrt(A_ii (1 + lambda)); x' = x + d; C(x') < C(x): accept, lambda = max(0.1 lambda, 1e-9);
+ *   otherwise (a NaN included, and a non-positive or non-finite pivot or diagonal) keep x, lambda = min(10 lambda, 1e6).  lambda starts at
+ *   lambda0.
+ * In/out: in_pose (T,17,3) (the wrist row only when solve_wrist), trans (T,3).  Out: cost (T,2) = C at the input and at the result; status
+ * (T) int32 = accepted steps; -1 for a frame with fewer than 3 used joints, which is not solved (its rows are not written); -2 (cost 0,
+ * nothing else written) when the model's tree is not one the kernel's tables hold, by harp_arm_vertex_fit's rule: row 0 must drive joint
+ * 0, every other row a joint of its own below it, and the joints at or below the driven non-root joints, counted per driven joint, must
+ * number at most 48.  The skin weights of a vertex row must sum to one.  Optional out (NULL allowed), at the final x: joints (T,n_out,3)
+ * mm and jac (T,3 n_out,54), metres per unit of x, always all 54 columns.  iters == 0 evaluates cost, joints and jac at the input and
+ * writes neither in_pose nor trans.
+ * HARP_ERR_ARG before any launch: m, opt, betas, targets, in_pose, trans, cost or status NULL; T <= 0; iters < 0; lambda0 or a prior weight
+ * negative or not finite; n_joints_out outside 1..HARP_ARM_IK_MAX_JOINTS; center_joint outside [0, NJ); n_pose_in != 17; NB < 10, NB > 32
+ * or NJ > 64.  harp_arm_ik_frames_per_block: the frames one workgroup solves (tests size their batches around it). */
+#define HARP_ARM_IK_MAX_JOINTS 22
+typedef struct harp_arm_ik_options {
+  int iters;
+  float lambda0;            /* 1e-3 */
+  float pose_prior_weight;  /* 0 */
+  float wrist_prior_weight; /* 0 */
+  int solve_wrist;          /* 0: the wrist row of in_pose given and frozen */
+  int betas_per_frame;      /* 0: betas (10,); otherwise betas (T,10) */
+} harp_arm_ik_options;
+int harp_arm_ik_frames_per_block(void);
+int harp_arm_ik(const harp_tree_model* m, const float* betas, const float* targets, const float* weights, const float* prior,
+                const float* wrist_prior, int T, const harp_arm_ik_options* opt, float* in_pose, float* trans, float* cost, int32_t* status,
+                float* joints, float* jac, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
