@@ -384,3 +384,15 @@ class ArmIkOptions(ctypes.Structure):
 ARM_IK_MAX_JOINTS = 22                                     # HARP_ARM_IK_MAX_JOINTS
 SIGNATURES["harp_arm_ik_frames_per_block"] = (_i, [])
 SIGNATURES["harp_arm_ik"] = (_i, [_trp, _vp, _vp, _vp, _vp, _vp, _i, ctypes.POINTER(ArmIkOptions), _vp, _vp, _vp, _vp, _vp, _vp, _vp])
+
+
+class ReprojIkOptions(ctypes.Structure):
+    """mirror of `harp_reproj_ik_options` (include/harp_hip.h)"""
+    _fields_ = [("iters", _i), ("lambda0", _f), ("pose_prior_weight", _f), ("z_prior_weight", _f), ("betas_per_frame", _i), ("cam_per_frame", _i),
+                ("focal", _f), ("S", _i)]
+
+
+# batched 2.5-D reprojection inverse kinematics of the MANO hand (csrc/reproj_ik.hip)
+SIGNATURES["harp_mano_reproj_ik_frames_per_block"] = (_i, [])
+SIGNATURES["harp_mano_reproj_ik"] = (_i, [_mp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, ctypes.POINTER(ReprojIkOptions), _vp, _vp, _vp, _vp, _vp, _vp,
+                                          _vp])

@@ -1572,3 +1572,78 @@ def arm_ik(dm, betas, targets, in_pose, trans, weights=None, prior=None, wrist_p
                                     _lib.ptr(out.status), _lib.ptr(out.joints), _lib.ptr(out.jac), _lib.stream())
     _lib.check(rc, "harp_arm_ik")
     return out
+
+
+# ---- batched 2.5-D reprojection inverse kinematics of the MANO hand (csrc/reproj_ik.hip) ------------------------------
+ReprojIkResult = collections.namedtuple("ReprojIkResult", "pose48 trans cost status proj jac")
+
+
+def mano_reproj_ik_frames_per_block():
+    """the problems one workgroup of harp_mano_reproj_ik solves"""
+    return int(_lib.lib().harp_mano_reproj_ik_frames_per_block())
+
+
+def mano_reproj_ik(dm, betas, targets, pose48, trans, cam, focal, S, weights=None, depth_weights=None, prior=None, z_prior=None, iters=20,
+                   lambda0=1e-3, pose_prior_weight=0.0, z_prior_weight=0.0, proj=False, jac=False, out=None):
+    """Image keypoints -> MANO pose rows: N Levenberg-Marquardt solves in one launch (csrc/reproj_ik.hip: harp_mano_reproj_ik, whose
+    contract include/harp_hip.h states), forward only.  dm: a ManoDeviceModel; betas (10,) for all problems or (N,10); targets (N,21,3) =
+    (u, v, d): continuous pixels (the centre of column i at i + 0.5) and the depth relative to the wrist in metres, in the order of the
+    model's joints; pose48 (N,48) = [rot | pose] and trans (N,3): the start, left untouched; cam (3,) or (N,3), focal (pixels) and S (the
+    image size): the player's camera; weights (N,21) or None (ones) on the pixel rows and depth_weights (N,21) or None (no depth rows),
+    both in px^2 per squared unit of the residual — an entry with weight <= 0 or a non-finite target is unused; prior (N,45) or None (the
+    mean pose) with pose_prior_weight on sum (pose - prior)^2; z_prior (N,) with z_prior_weight on (trans_z - z_prior)^2 (None: the weight
+    must be 0).  Returns ReprojIkResult(pose48, trans, cost (N,2) = at the start and at the result, status (N,) int32 = accepted steps, -1
+    for a problem with fewer than 4 used pixel joints or -2 for one with a used joint behind the camera at the start (both returned as
+    they came), proj (N,21,3) = (u, v, d) or None, jac (N,63,51) or None).  iters = 0 evaluates at the start.  out: an earlier
+    ReprojIkResult of the same shapes whose tensors are written instead of new ones — the call then allocates nothing and can be
+    captured into a graph."""
+    _playback_input("mano_reproj_ik", betas, targets, pose48, trans, cam, weights, depth_weights, prior, z_prior)
+    named = (("betas", betas), ("targets", targets), ("pose48", pose48), ("trans", trans), ("cam", cam), ("weights", weights),
+             ("depth_weights", depth_weights), ("prior", prior), ("z_prior", z_prior))
+    for name, t in named:
+        if t is not None and t.dtype != torch.float32:
+            raise TypeError(f"mano_reproj_ik takes float32 tensors, {name} is {t.dtype}")
+    if targets.dim() != 3 or tuple(targets.shape[1:]) != (21, 3) or targets.shape[0] < 1:
+        raise ValueError(f"targets must be (N, 21, 3), got {tuple(targets.shape)}")
+    N = targets.shape[0]
+    if tuple(betas.shape) not in ((10,), (N, 10)):
+        raise ValueError(f"betas must be (10,) or ({N}, 10), got {tuple(betas.shape)}")
+    if tuple(cam.shape) not in ((3,), (N, 3)):
+        raise ValueError(f"cam must be (3,) or ({N}, 3), got {tuple(cam.shape)}")
+    for name, t, shape in (("pose48", pose48, (N, 48)), ("trans", trans, (N, 3)), ("weights", weights, (N, 21)),
+                           ("depth_weights", depth_weights, (N, 21)), ("prior", prior, (N, 45)), ("z_prior", z_prior, (N,))):
+        if t is not None and tuple(t.shape) != shape:
+            raise ValueError(f"{name} must be {shape}, got {tuple(t.shape)}")
+    iters, lambda0, pose_prior_weight, z_prior_weight, focal = int(iters), float(lambda0), float(pose_prior_weight), float(z_prior_weight), float(focal)
+    inf = float("inf")
+    if iters < 0 or not (0.0 <= lambda0 < inf) or not (0.0 <= pose_prior_weight < inf) or not (0.0 <= z_prior_weight < inf):
+        raise ValueError(f"iters >= 0 and finite lambda0, pose_prior_weight, z_prior_weight >= 0, got {iters}, {lambda0}, {pose_prior_weight}, "
+                         f"{z_prior_weight}")
+    if not (0.0 < focal < inf) or int(S) != S or int(S) <= 0:
+        raise ValueError(f"focal > 0 and an image size S >= 1, got {focal}, {S}")
+    if z_prior is None and z_prior_weight != 0.0:
+        raise ValueError("z_prior_weight needs z_prior")
+    if dm.v_template.device != targets.device:
+        raise ValueError(f"the model is on {dm.v_template.device}, the targets on {targets.device}")
+    dev = targets.device
+    want = ((N, 48), (N, 3), (N, 2), (N,), (N, 21, 3) if proj else None, (N, 63, 51) if jac else None)
+    if out is None:
+        out = ReprojIkResult(*[None if shape is None else torch.empty(shape, dtype=torch.int32 if name == "status" else torch.float32, device=dev)
+                               for name, shape in zip(ReprojIkResult._fields, want)])
+    else:
+        for name, t, shape in zip(ReprojIkResult._fields, out, want):
+            if (t is None) != (shape is None) or (t is not None and (tuple(t.shape) != shape or t.device != dev or not t.is_contiguous()
+                                                                      or t.dtype != (torch.int32 if name == "status" else torch.float32))):
+                raise ValueError(f"out.{name} does not fit this call")
+    out.pose48.copy_(pose48.detach())
+    out.trans.copy_(trans.detach())
+    c = lambda t: None if t is None else t.detach().contiguous()
+    betas, targets, cam, weights, depth_weights, prior, z_prior = c(betas), c(targets), c(cam), c(weights), c(depth_weights), c(prior), c(z_prior)
+    opt = _lib.ReprojIkOptions(iters, lambda0, pose_prior_weight, z_prior_weight, int(betas.dim() == 2), int(cam.dim() == 2), focal, int(S))
+    with torch.cuda.device(dev):
+        rc = _lib.lib().harp_mano_reproj_ik(ctypes.byref(dm.struct), _lib.ptr(betas), _lib.ptr(cam), _lib.ptr(targets), _lib.ptr(weights),
+                                            _lib.ptr(depth_weights), _lib.ptr(prior), _lib.ptr(z_prior), N, ctypes.byref(opt),
+                                            _lib.ptr(out.pose48), _lib.ptr(out.trans), _lib.ptr(out.cost), _lib.ptr(out.status),
+                                            _lib.ptr(out.proj), _lib.ptr(out.jac), _lib.stream())
+    _lib.check(rc, "harp_mano_reproj_ik")
+    return out

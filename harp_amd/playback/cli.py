@@ -18,6 +18,9 @@ def parse_args(argv=None):
                                                       "the 21 hand keypoints plus the elbow as row 21 (the wrist is solved) or (T,21,3) (the "
                                                       "wrist is held) [, weights (T,22) or (T,21), wrist_pose (3,) or (T,3)] "
                                                       "(Motion.from_arm_keypoints)")
+    ap.add_argument("--keypoints2d", default=None, help=".npz of keypoints (T,21,2) in pixels of the fit's img_size [, weights (T,21), depth (T,21) "
+                                                        "metres relative to the wrist, cam (3,) or (T,3)] instead of --motion: the motion is "
+                                                        "solved from them by reprojection (Motion.from_image_keypoints; the MANO hand only)")
     ap.add_argument("--vertices", default=None, help=".npz of vertices (T,778,3) in metres, MANO topology [, weights (T,778), cam (3,) or (T,3)] "
                                                      "instead of --motion: the motion is fitted to them (Motion.from_vertices); with a use_arm "
                                                      "config (T,778,3) or the arm's (T,1026,3) [, wrist_pose (3,) or (T,3) for 778] "
@@ -55,8 +58,8 @@ def parse_args(argv=None):
         raise SystemExit(f"--also at most {ops.COMPOSITE_MAX_LAYERS - 1} times")
     if args.fps_scale <= 0:
         raise SystemExit("--fps-scale must be positive")
-    if sum(v is not None for v in (args.motion, args.keypoints, args.vertices)) != 1:
-        raise SystemExit("exactly one of --motion, --keypoints and --vertices")
+    if sum(v is not None for v in (args.motion, args.keypoints, args.keypoints2d, args.vertices)) != 1:
+        raise SystemExit("exactly one of --motion, --keypoints, --keypoints2d and --vertices")
     return args
 
 
@@ -68,7 +71,7 @@ def main(argv=None):
     from ..utils import file_utils, hand_model_utils
     from ..utils.config_utils import get_config
 
-    def load(cfg_path, motion_path, keypoints_path=None, vertices_path=None):
+    def load(cfg_path, motion_path, keypoints_path=None, vertices_path=None, keypoints2d_path=None):
         with open(cfg_path) as f:
             configs = get_config(write_yaml=False, **yaml.safe_load(f))
         configs["device"] = args.device
@@ -84,6 +87,11 @@ def main(argv=None):
                 else:
                     motion = Motion.from_keypoints(z["keypoints"], params, hand_layer, cam=opt("cam"), weights=opt("weights"),
                                                    device=args.device, smooth=args.smooth_keypoints)
+        elif keypoints2d_path is not None:
+            with np.load(keypoints2d_path) as z:
+                opt = lambda k: z[k] if k in z.files else None            # noqa: E731
+                motion = Motion.from_image_keypoints(z["keypoints"], params, hand_layer, cam=opt("cam"), weights=opt("weights"),
+                                                     depth=opt("depth"), device=args.device, configs=configs)
         elif vertices_path is not None:
             with np.load(vertices_path) as z:
                 opt = lambda k: z[k] if k in z.files else None            # noqa: E731
@@ -108,19 +116,19 @@ def main(argv=None):
 
     fmt = "png" if args.alpha else "jpg"
     if not (args.flip or args.also or args.scene_depth or args.masks):
-        configs, params, hand_layer, motion = load(args.config, args.motion, args.keypoints, args.vertices)
+        configs, params, hand_layer, motion = load(args.config, args.motion, args.keypoints, args.vertices, args.keypoints2d)
         player = AvatarPlayer(configs, params, hand_layer, batch_size=args.batch_size, ss=args.ss, device=args.device)
         paths = player.play(motion, args.out, backgrounds=args.background, fmt=fmt, alpha=args.alpha)
     else:
-        specs = [(args.config, args.motion, args.flip, args.keypoints, args.vertices)]
+        specs = [(args.config, args.motion, args.flip, args.keypoints, args.vertices, args.keypoints2d)]
         for spec in args.also:
             part = spec.split(":")
             if len(part) not in (2, 3) or (len(part) == 3 and part[2] != "flip"):
                 raise SystemExit(f"--also takes CFG:MOTION or CFG:MOTION:flip, got {spec!r}")
-            specs.append((part[0], part[1], len(part) == 3, None, None))
+            specs.append((part[0], part[1], len(part) == 3, None, None, None))
         players, motions = [], []
-        for cfg_path, motion_path, _, keypoints_path, vertices_path in specs:
-            configs, params, hand_layer, motion = load(cfg_path, motion_path, keypoints_path, vertices_path)
+        for cfg_path, motion_path, _, keypoints_path, vertices_path, keypoints2d_path in specs:
+            configs, params, hand_layer, motion = load(cfg_path, motion_path, keypoints_path, vertices_path, keypoints2d_path)
             players.append(AvatarPlayer(configs, params, hand_layer, batch_size=args.batch_size, ss=args.ss, device=args.device, keep_depth=True))
             motions.append(motion)
         scene = ScenePlayer(players, flip=[spec[2] for spec in specs])

@@ -231,3 +231,119 @@ def arm_palm_start(keypoints, used, joints0):
     idx = np.array(PALM + ((ELBOW,) if kp.shape[1] > ELBOW else ()))
     j0 = np.asarray(joints0, np.float64)
     return vertex_start(kp[:, idx], np.asarray(used)[:, idx], j0[..., idx, :], np.zeros(3))
+
+
+def camera_tz(cam, focal, S):
+    """the camera's depth of the world origin, 2 focal / (S cam0 + 1e-9) (utils/visualize.py:268), for cam (..., 3)"""
+    return 2.0 * focal / (S * np.asarray(cam, np.float64)[..., 0] + 1e-9)
+
+
+def project_pixels(joints, cam, focal, S):
+    """joints (..., 21, 3) metres in the frame of the fit's `joints` -> (..., 21, 3) = (u, v, d) as csrc/reproj_ik.hip states them: the
+    player's camera (view = (-x - cam1, -y - cam2, z + t_z)) read at the rasteriser's pixel centres, so that the centre of column i is at
+    u = i + 0.5 and of row i at v = i + 0.5, and the depth relative to the wrist.  cam (3,) or (..., 3).  numpy float64."""
+    j = np.asarray(joints, np.float64)
+    cam = np.asarray(cam, np.float64)
+    Z = j[..., 2] + camera_tz(cam, focal, S)[..., None]
+    u = S / 2.0 + focal * (j[..., 0] + cam[..., 1, None]) / Z
+    v = S / 2.0 + focal * (j[..., 1] + cam[..., 2, None]) / Z
+    return np.stack([u, v, j[..., 2] - j[..., :1, 2]], -1)
+
+
+def planar_palm_starts(pixels, used, rest_joints, cam, focal, S):
+    """The two starts of the reprojection solve (Motion.from_image_keypoints) from the six palm pixels alone, host float64:
+    (rot (T,2,3) axis-angle, trans (T,2,3), depth (T,) = the palm centroid's distance along the view axis, metres).  pixels (T,21,2); used
+    (T,21) bool; rest_joints: rest_chain_joints; cam (3,) or (T,3).  The palm joints (PALM) move rigidly, R (J_k - J_0) + J_0 + trans, and
+    lie close to a plane, so under weak perspective their centred pixels are a 2 x 2 affine map A of their in-plane coordinates:
+    A = s B with s = sigma_1(A) = focal / Z and B the top 2 x 2 block of the rotated plane basis.  The basis' third row is
+    +-sqrt(lambda_max) v of I - B^T B: the two signs are the two poses (mirrored in depth) that the pixels of a plane cannot tell apart.
+    Each is re-orthonormalised, completed by the cross product and turned into an axis-angle (axis_angle_of); trans puts the palm
+    centroid on its pixel at depth Z — the root rotation turns about the wrist joint, not the origin.  A frame whose six palm pixels are
+    not all used takes the starts of the last frame that had them (none yet: no rotation, trans zero)."""
+    px = np.asarray(pixels, np.float64)
+    T = px.shape[0]
+    idx = np.array(PALM)
+    cam = np.broadcast_to(np.asarray(cam, np.float64), (T, 3))
+    tz = camera_tz(cam, focal, S)
+    r0, rbar = rest_joints[0], rest_joints[idx].mean(0)
+    q = rest_joints[idx] - rbar
+    _, _, Vt = np.linalg.svd(q, full_matrices=False)                # the palm's best plane: its two widest directions and the normal
+    e1, e2 = Vt[0], Vt[1]
+    E = np.stack([e1, e2, np.cross(e1, e2)], 1)                     # (3,3), columns: a right-handed basis
+    c = q @ E[:, :2]                                                # (6,2) in-plane coordinates
+    pinv = np.linalg.pinv(c)                                        # (2,6)
+    rot, trans, depth = np.zeros((T, 2, 3)), np.zeros((T, 2, 3)), np.zeros(T)
+    cur = (np.zeros((2, 3)), np.zeros((2, 3)), None)
+    for t in range(T):
+        if np.asarray(used)[t, idx].all():
+            p = px[t, idx]
+            pbar = p.mean(0)
+            A = (pinv @ (p - pbar)).T                               # (2,2): p - pbar ~ c A^T
+            s = np.linalg.svd(A, compute_uv=False)[0]
+            if s > 0 and np.isfinite(s):
+                B = A / s
+                lam, V = np.linalg.eigh(np.eye(2) - B.T @ B)
+                m = np.sqrt(max(lam[1], 0.0)) * V[:, 1]
+                Z = focal / s
+                pc = np.array([(pbar[0] - S / 2.0) * Z / focal - cam[t, 1], (pbar[1] - S / 2.0) * Z / focal - cam[t, 2], Z - tz[t]])
+                rots, trs = [], []
+                for sign in (1.0, -1.0):
+                    c1, c2 = np.append(B[:, 0], sign * m[0]), np.append(B[:, 1], sign * m[1])
+                    c1 = c1 / np.linalg.norm(c1)
+                    c2 = c2 - (c1 @ c2) * c1
+                    c2 = c2 / np.linalg.norm(c2)
+                    R = np.stack([c1, c2, np.cross(c1, c2)], 1) @ E.T
+                    rots.append(axis_angle_of(R))
+                    trs.append(pc - R @ (rbar - r0) - r0)
+                cur = (np.array(rots), np.array(trs), Z)
+        rot[t], trans[t] = cur[0], cur[1]
+        depth[t] = tz[t] if cur[2] is None else cur[2]
+    return rot, trans, depth
+
+
+def image_ik_inputs(keypoints, weights, depth, cam, init, params, model, focal, S, smooth=None):
+    """What Motion.from_image_keypoints passes to ops.mano_reproj_ik, checked and prepared on the host: dict(shape (10,), targets (T,21,3)
+    = (u, v, d) with NaN where there is no depth, weights (T,21) or None, pose48 (T,C,48), trans (T,C,3) for C candidate starts (2: the
+    planar starts; 1: init), depth (T,) = the start's palm depth, cam (T,3) float32), the others float64.  smooth: None or a function
+    (points (T,21,3), weights) -> (points, used (T,21)), which the pixels (as (u, v, 0)) and the depths (as (d, 0, 0)) go through; a joint
+    it filled then counts as used."""
+    kp = checked("keypoints", keypoints, (None, 21, 2), kind="f", split=True).astype(np.float64)
+    T = kp.shape[0]
+    w = None if weights is None else checked("weights", weights, (T, 21), kind="f", split=True).astype(np.float64)
+    d = None if depth is None else checked("depth", depth, (T, 21), kind="f", split=True).astype(np.float64)
+    if init is not None and (not all(hasattr(init, k) for k in ("rot", "trans", "pose")) or len(init) != T):
+        raise ValueError(f"init must be a Motion of {T} frames")
+    if smooth is not None:
+        p3, filled = smooth(np.concatenate([kp, np.zeros((T, 21, 1))], -1), w)
+        kp = np.asarray(p3, np.float64)[..., :2]
+        w = None if w is None else np.where((np.asarray(filled) > 0) & ~(w > 0), 1.0, w)
+        if d is not None:
+            d = np.asarray(smooth(np.concatenate([d[..., None], np.zeros((T, 21, 2))], -1), None)[0], np.float64)[..., 0]
+    cam = np.broadcast_to(checked("cam", params["cam"][0] if cam is None else cam, (3,), (T, 3)).astype(np.float32), (T, 3)).copy()
+    shape = params["shape"].detach().cpu().numpy().astype(np.float64).reshape(10)
+    used = np.isfinite(kp).all(-1) & (True if w is None else (w > 0))
+    rest = rest_chain_joints(model, shape)
+    rot, trans, zbar = planar_palm_starts(kp, used, rest, cam, focal, S)
+    if init is None:
+        pose48 = np.concatenate([rot, np.zeros((T, 2, 45))], -1)
+    else:
+        pose48 = np.concatenate([init.rot.cpu().numpy(), init.pose.cpu().numpy()], 1).astype(np.float64)[:, None]
+        trans = init.trans.cpu().numpy().astype(np.float64)[:, None]
+        palm = np.array(PALM)
+        # the warm start's own palm depth: the palm joints are rigid under the root rotation
+        for t in range(T):
+            R = _rotation_of(pose48[t, 0, :3])
+            zbar[t] = ((rest[palm] - rest[0]) @ R.T + rest[0] + trans[t, 0]).mean(0)[2] + camera_tz(cam[t], focal, S)
+    targets = np.concatenate([kp, np.full((T, 21, 1), np.nan) if d is None else d[..., None]], -1)
+    return dict(shape=shape, targets=targets, weights=w, pose48=pose48, trans=trans, depth=zbar, cam=cam)
+
+
+def _rotation_of(aa):
+    """axis-angle -> rotation matrix (Rodrigues), float64"""
+    aa = np.asarray(aa, np.float64)
+    th = np.linalg.norm(aa)
+    if th < 1e-300:
+        return np.eye(3)
+    k = aa / th
+    Kx = np.array([[0, -k[2], k[1]], [k[2], 0, -k[0]], [-k[1], k[0], 0]])
+    return np.eye(3) + np.sin(th) * Kx + (1 - np.cos(th)) * Kx @ Kx

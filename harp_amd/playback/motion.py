@@ -105,6 +105,63 @@ class Motion:
         return cls(res.pose48[:, 3:], res.pose48[:, :3], res.trans, a["cam"])
 
     @classmethod
+    def from_image_keypoints(cls, keypoints, params, hand_layer, cam=None, weights=None, depth=None, depth_weight=1.0, prior_weight=1e-5,
+                             depth_prior_weight=2.5e-5, iters=20, init=None, smooth=None, device=None, configs=None):
+        """A motion from IMAGE keypoints (a 2-D hand tracker run on a video) by batched reprojection inverse kinematics on the device
+        (ops.mano_reproj_ik, csrc/reproj_ik.hip).  keypoints (T,21,2) in pixels of the fit's img_size, in the model's
+        order — wrist, then thumb, index, middle, ring and little, each from root to tip — with the centre of column i at i + 0.5 and of
+        row i at i + 0.5 of the frames the player renders; a joint with a non-finite coordinate or a weight <= 0 (weights (T,21), default
+        ones) is ignored.  depth: None or (T,21) metres relative to the wrist along the view axis ("2.5-D"; NaN where there is none; the
+        wrist's own entry is not read).  params: the fit's parameter dict (its `shape` is the avatar's and is not solved; row 0 of its
+        `cam` is the default cam); cam: (3,) or (T,3); configs (required, by keyword): the fit's config, whose focal_length and img_size
+        are the camera's, as the player reads them — a Motion has no other way to know them.
+        The start (host, float64): pose zero and the TWO root rotations and translations that the palm's pixels allow
+        (planar_palm_starts: a plane seen under weak perspective has a mirror pose); both go through ONE solve of 2 T problems and the
+        one with the lower final cost is taken per frame on the device.  init= takes a Motion of equal length as the only candidate.
+        The three weights are dimensionless: each is multiplied by (focal / Z_t)^2 with Z_t the start's palm depth, so that a weight of 1
+        counts a metre (a radian) like focal / Z_t pixels: depth_weight on the depth rows, prior_weight on the pull of the finger pose
+        to the model's mean pose (what it means in from_keypoints), depth_prior_weight on the pull of trans_z to the start's (depth
+        along the view axis is what pixels determine worst).  The depth rows take their own frame's factor; the two priors are one
+        number per launch and take the median of the frames' factors.  The float32 normal equations need the two priors (§30).
+        There is no bone-length matching in 2-D: a larger hand simply reads as nearer.
+        THE LIMIT: without `depth`, every finger bone has a towards / away mirror pose that pixels cannot tell apart, and the prior
+        picks the one nearer the mean pose.  The reprojection is then right, but the 3-D pose is not unique (on the seeded
+        scenes the joints are off by 6 .. 8 mm in the median and up to 89 mm while 70 of 72 frames agree to 2.4 px and all to 3.6 px).
+        With depth rows the 3-D result is defined (0.9 .. 1.8 mm in the median, 8.9 mm at most).
+        smooth: None, or the sigma in frames of a Gaussian window that the pixels (and depths) go through first (smooth_keypoints, with
+        `weights` as the confidences); Motion.smooth filters the solved rows instead.  The result carries no light.  device: where the
+        solve runs (default: the device of params["shape"] when that is a HIP device, else "cuda").  The SMPL-X arm needs a solver for
+        its kinematic tree and raises NotImplementedError."""
+        if "pose_mean" in hand_layer._model_np:
+            raise NotImplementedError("Motion.from_image_keypoints solves the MANO hand; the SMPL-X arm needs a kinematic-tree solver, and "
+                                      "there is none for image keypoints yet")
+        if configs is None or "focal_length" not in configs or "img_size" not in configs:
+            raise ValueError("Motion.from_image_keypoints needs configs= with the fit's focal_length and img_size")
+        focal, S = float(configs["focal_length"]), int(configs["img_size"])
+        for name, v in (("depth_weight", depth_weight), ("prior_weight", prior_weight), ("depth_prior_weight", depth_prior_weight)):
+            if not (0.0 <= float(v) < float("inf")):
+                raise ValueError(f"{name} must be finite and >= 0, got {v}")
+        dev = torch.device(device if device is not None else (params["shape"].device if params["shape"].is_cuda else "cuda"))
+        host = lambda pair: tuple(t.cpu().numpy() for t in pair)      # noqa: E731
+        a = K.image_ik_inputs(keypoints, weights, depth, cam, init, params, hand_layer._model_np, focal, S,
+                              None if smooth is None else lambda kp, w: host(smooth_keypoints(kp, weights=w, sigma=smooth, device=dev)))
+        T, C = a["pose48"].shape[:2]
+        from ..manopth.manolayer import ManoDeviceModel
+        up = lambda x: None if x is None else torch.as_tensor(np.ascontiguousarray(x, dtype=np.float32)).to(dev)
+        rep = lambda x: None if x is None else np.repeat(x, C, axis=0)      # frame-major: problem t * C + c
+        scale = (focal / a["depth"]) ** 2                               # (T,) px^2 per squared metre (radian) at the start's palm depth
+        res = ops.mano_reproj_ik(ManoDeviceModel(hand_layer._model_np, dev), up(a["shape"]), up(rep(a["targets"])),
+                                 up(a["pose48"].reshape(T * C, 48)), up(a["trans"].reshape(T * C, 3)), up(rep(a["cam"])), focal, S,
+                                 weights=up(rep(a["weights"])),
+                                 depth_weights=None if depth is None else up(rep(np.broadcast_to((depth_weight * scale)[:, None], (T, 21)))),
+                                 z_prior=up(a["trans"].reshape(T * C, 3)[:, 2]), iters=iters,
+                                 pose_prior_weight=float(prior_weight * np.median(scale)), z_prior_weight=float(depth_prior_weight * np.median(scale)))
+        pick = res.cost[:, 1].reshape(T, C).argmin(1, keepdim=True)      # the candidate with the lower final cost, on the device
+        take = lambda rows: rows.reshape(T, C, -1).gather(1, pick[:, :, None].expand(T, 1, rows.shape[-1]))[:, 0]      # noqa: E731
+        pose48, trans = take(res.pose48), take(res.trans)
+        return cls(pose48[:, 3:], pose48[:, :3], trans, a["cam"])
+
+    @classmethod
     def from_vertices(cls, vertices, params, hand_layer, cam=None, weights=None, iters=10, pose_prior_weight=0.0, init=None, device=None):
         """A motion from per-frame mesh vertices in MANO topology (a mesh regressor's output, a dataset) by the batched vertex fit on the
         device (ops.mano_vertex_fit, csrc/vertex_fit.hip).  vertices (T,778,3) in metres, in the frame of the fit's

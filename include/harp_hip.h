@@ -1291,6 +1291,53 @@ int harp_arm_ik(const harp_tree_model* m, const float* betas, const float* targe
                 const float* wrist_prior, int T, const harp_arm_ik_options* opt, float* in_pose, float* trans, float* cost, int32_t* status,
                 float* joints, float* jac, hipStream_t stream);
 
+/* ---- batched 2.5-D reprojection IK: image keypoints -> MANO pose rows (csrc/reproj_ik.hip; playback Motion.from_image_keypoints;
+ * DESIGN.md §30) ----
+ * Nothing in the reference does this.  The model inverted is harp_lbs_mano_fwd's, seen through the player's camera (utils/visualize.py:
+ * 268-271: R = diag(-1,-1,1), T = (-cam1, -cam2, t_z)) and the rasteriser's pixel centres.  N independent Levenberg-Marquardt solves in
+ * one launch (one kernel node), forward only, no workspace, no allocation, no synchronisation, no atomics, fixed summation order
+ * (capturable; a repeated call gives the same bits).  Unknowns per problem x = [rot 3 | pose 45 | trans 3] = the rows of pose48 and trans
+ * as harp_lbs_mano_fwd takes them; the shape is given: betas (10,) for all problems, or (N,10) with betas_per_frame != 0; the camera is
+ * given: cam (3,), or (N,3) with cam_per_frame != 0, plus focal and S (the image is S x S pixels).
+ *   j(x) (21,3) metres = harp_lbs_mano_fwd's joints / 1000 (trans included).
+ *   Z_k = j_k.z + t_z, t_z = 2 focal / (S cam0 + 1e-9);   u_k = S/2 + focal (j_k.x + cam1) / Z_k;   v_k = S/2 + focal (j_k.y + cam2) / Z_k;
+ *   d_k = j_k.z - j_0.z.   u, v are continuous pixel coordinates: the centre of column i is at u = i + 0.5 and of row i at v = i + 0.5,
+ *   u grows with the column and v with the row of the rendered image (harp_project's x_ndc = 1 - 2u/S read at the rasteriser's pixel
+ *   centres -1 + (2 (S - 1 - i) + 1) / S).
+ *   C(x) = sum_k w_k [(u_k - U_k)^2 + (v_k - V_k)^2] + sum_{k>=1} wz_k (d_k - D_k)^2 + pose_prior_weight sum_i (pose_i - prior_i)^2
+ *          + z_prior_weight (trans_z - z_prior)^2;
+ *   targets (N,21,3) = (U, V, D): pixels, pixels, metres; weights (N,21) or NULL (ones); depth_weights (N,21) or NULL (no depth rows; the
+ *   wrist's own entry is never used); prior (N,45) or NULL (zeros: the model's mean pose); z_prior (N) or NULL (then z_prior_weight must
+ *   be 0).  The weights are in px^2 per squared unit of their residual.  A joint's PIXEL rows are used when w_k > 0 and U_k, V_k are finite;
+ *   its DEPTH row when k >= 1, wz_k > 0 and D_k is finite; an unused entry never enters arithmetic.
+ *   Iteration, exactly `iters` times, harp_mano_ik's: J = the exact 63 x 51 derivative of the rows (u, v, d) at x; A = J^T W J + P,
+ *   g = J^T W r + P (x - x_prior), P = pose_prior_weight on the 45 pose diagonals and z_prior_weight on trans_z's; (A + lambda diag A) d =
+ *   -g by a Cholesky factorisation of the matrix scaled from both sides by 1 / sqrt(A_ii (1 + lambda)); x' = x + d; C(x') < C(x): accept,
+ *   lambda = max(0.1 lambda, 1e-9); otherwise (a NaN included, a non-positive or non-finite pivot or diagonal, and a candidate with a
+ *   used pixel joint at Z_k <= 1e-3) keep x, lambda = min(10 lambda, 1e6).  lambda starts at lambda0.
+ * In/out: pose48 (N,48), trans (N,3).  Out: cost (N,2) = C at the input and at the result; status (N) int32 = accepted steps, or -1 for a
+ * problem with fewer than 4 used pixel joints, or -2 for one with a used pixel joint at Z_k <= 1e-3 at its input; neither is solved
+ * (their pose48 / trans rows are not written; with -2 cost is C as evaluated there).  Optional out (NULL allowed): proj (N,21,3) = (u, v, d)
+ * and jac (N,63,51) at the final x; a joint that is neither pixel-used nor in front (Z_k <= 1e-3) has u = v = 0 and zero u / v rows.
+ * iters == 0 evaluates cost, proj and jac at the input and writes neither pose48 nor trans.
+ * HARP_ERR_ARG before any launch: m, opt, betas, cam, targets, pose48, trans, cost or status NULL; N <= 0; iters < 0; lambda0,
+ * pose_prior_weight or z_prior_weight negative or not finite; focal not positive and finite; S <= 0; z_prior NULL with z_prior_weight != 0.
+ * harp_mano_reproj_ik_frames_per_block: the problems one workgroup solves (tests size their batches around it). */
+typedef struct harp_reproj_ik_options {
+  int iters;
+  float lambda0;            /* 1e-3 */
+  float pose_prior_weight;  /* px^2 / rad^2 */
+  float z_prior_weight;     /* px^2 / m^2 */
+  int betas_per_frame;      /* 0: betas (10,); otherwise betas (N,10) */
+  int cam_per_frame;        /* 0: cam (3,); otherwise cam (N,3) */
+  float focal;              /* pixels */
+  int S;                    /* image size, pixels */
+} harp_reproj_ik_options;
+int harp_mano_reproj_ik_frames_per_block(void);
+int harp_mano_reproj_ik(const harp_mano_model* m, const float* betas, const float* cam, const float* targets, const float* weights,
+                        const float* depth_weights, const float* prior, const float* z_prior, int N, const harp_reproj_ik_options* opt,
+                        float* pose48, float* trans, float* cost, int32_t* status, float* proj, float* jac, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
