@@ -1,9 +1,10 @@
 // Batched inverse kinematics of the SMPL-X right arm for gfx950 (ops.arm_ik; playback Motion.from_arm_keypoints): up to 22 3-D
 // keypoints per frame (the wrist, the five fingers root to tip, the elbow) -> the rows [rot | wrist | pose | trans] that harp_lbs_tree_fwd
 // turns back into those joints.  Nothing in the reference does this.  The keypoint counterpart of csrc/arm_vertex_fit.hip (§28) and the tree
-// counterpart of csrc/ik.hip (§24): the iteration and the in-place Cholesky are csrc/ik.hip's, the slot tables of the tree and the tangents
-// stored by structure are csrc/arm_vertex_fit.hip's (both repeated here: those two translation units stay as they are), the forward is
-// csrc/lbs_tree.hip's (lt::rod_fwd, the level-parallel chain), so the solver and the renderer cannot disagree.
+// counterpart of csrc/ik.hip (§24): the iteration is csrc/ik.hip's, the slot tables of the tree are tree_slots_body.h's and the solve is
+// lm_solve_body.h's, both written out here because this kernel measured slower through either shared routine, beyond its run-to-run
+// spread; the forward is csrc/lbs_tree.hip's (lt::rod_fwd, its tangent lt::rod_jvp, the level-parallel chain), so the
+// solver and the renderer cannot disagree.
 //
 // harp_arm_ik: T independent Levenberg-Marquardt solves in ONE launch, one wave (= one workgroup) per frame, 54 unknowns
 // x = [rot 3 | wrist 3 | pose 45 | trans 3] and 3 n_out <= 66 residuals (include/harp_hip.h states the contract).
@@ -27,10 +28,11 @@
 //                          centre) gets exactly 0.
 //                  trans   the identity.
 //                J (66 x 54, rows past 3 n_out zero, row stride 55: consecutive lanes and consecutive rows fall in different banks) in LDS.
-//   normal eqs., Cholesky, solves, accept: csrc/ik.hip's, lane i = row i; a frozen wrist column has A_ii = 1, zeros elsewhere, g_i = 0.
+//   normal eqs., solve, accept: csrc/ik.hip's (lm::jacobi_scale, lm::damped), lane i = row i; a frozen wrist column has A_ii = 1, zeros elsewhere, g_i = 0.
 // `iters` iterations whatever happens: no early exit, every branch that holds a barrier is uniform over the wave.  No workspace, no
 // allocation, no synchronisation, no atomics: the launch can be captured and a repeated call gives the same bits.
-#include "lbs_tree_body.h"
+#include "lm_solve_body.h"
+#include "tree_slots_body.h"                                           // (NIN, MAXSLOT, NOSLOT, UNSET; lbs_tree_body.h)
 
 #include <math.h>
 
@@ -42,11 +44,8 @@ constexpr int NX = 54;                  // unknowns per frame
 constexpr int NO = HARP_ARM_IK_MAX_JOINTS;
 constexpr int NR = 3 * NO;              // residual rows held (those past 3 n_joints_out stay zero)
 constexpr int LD = 55;                  // row stride of J and A in LDS (odd)
-constexpr int NIN = 17;                 // rows of in_pose
 constexpr int XW = 3, XP = 6, XT = 51;  // first wrist / finger / trans column
 constexpr int NSB = 10;                 // shape coefficients given (the model's other NB - 10 are zero)
-constexpr int MAXSLOT = 48;             // (column joint, joint at or below it) pairs: the arm has 16 + 5 x 6 = 46
-constexpr int NOSLOT = 255, UNSET = 254;
 constexpr int kAkFramesPerBlock = 1;    // one wave per workgroup, as csrc/ik.hip: LDS (48 KiB a frame: three on a CU) bounds the frames in flight on a CU
 
 struct AkLds {
@@ -80,28 +79,7 @@ struct AkLds {
     } e;
   } u;
 };
-
-// d R / d r[a] of lt::rod_fwd (same intermediate values, differentiated term by term)
-__device__ __forceinline__ void rod_jvp(const float r[3], int a, float dR[9]) {
-  const float e0 = r[0] + 1e-8f, e1 = r[1] + 1e-8f, e2 = r[2] + 1e-8f;
-  const float th = sqrtf(e0 * e0 + e1 * e1 + e2 * e2);
-  const float dx = r[0] / th, dy = r[1] / th, dz = r[2] / th;
-  const float s = sinf(th), cs = cosf(th), c = 1.0f - cs;
-  const float dth = (a == 0 ? e0 : (a == 1 ? e1 : e2)) / th;
-  const float k = dth / (th * th);
-  const float ddx = (a == 0 ? 1.0f : 0.0f) / th - r[0] * k;
-  const float ddy = (a == 1 ? 1.0f : 0.0f) / th - r[1] * k;
-  const float ddz = (a == 2 ? 1.0f : 0.0f) / th - r[2] * k;
-  const float ds = cs * dth, dc = s * dth;
-  const float n2 = dx * dx + dy * dy + dz * dz, dn2 = 2.0f * (dx * ddx + dy * ddy + dz * ddz);
-  const float ax = ds * dx + s * ddx, ay = ds * dy + s * ddy, az = ds * dz + s * ddz;
-  const float sxy = dc * dx * dy + c * (ddx * dy + dx * ddy);
-  const float sxz = dc * dx * dz + c * (ddx * dz + dx * ddz);
-  const float syz = dc * dy * dz + c * (ddy * dz + dy * ddz);
-  dR[0] = dc * (dx * dx - n2) + c * (2.0f * dx * ddx - dn2); dR[1] = -az + sxy; dR[2] = ay + sxz;
-  dR[3] = az + sxy; dR[4] = dc * (dy * dy - n2) + c * (2.0f * dy * ddy - dn2); dR[5] = -ax + syz;
-  dR[6] = -ay + sxz; dR[7] = ax + syz; dR[8] = dc * (dz * dz - n2) + c * (2.0f * dz * ddz - dn2);
-}
+static_assert(sizeof(AkLds) == 49216, "three frames on a CU rest on this size (DESIGN.md §29)");
 
 __device__ __forceinline__ void joint_aa(const harp_tree_model& M, const AkLds& S, int row, float aa[3]) {
   const int j = S.drv[row];
@@ -470,11 +448,11 @@ __global__ void __launch_bounds__(64) arm_ik_kernel(const harp_tree_model M, con
       }
       if (l < NX) S.u.A[l][j] = a;
     }
-    const float s = 1.0f / sqrtf(diag * (1.0f + lambda));             // Jacobi scaling: (A + lambda diag A) scaled has a unit diagonal
-    bool ok = __all(l >= NX || (diag > 0.f && isfinite(s)));
+    bool ok;
+    const float s = lm::jacobi_scale<NX>(l, diag, lambda, ok);
     __syncthreads();
 #pragma unroll 1
-    for (int j = 0; j < NX; ++j) {                                     // left-looking Cholesky, column j
+    for (int j = 0; j < NX; ++j) {                                     // lm::solve's factorisation, column j
       const float sj = __shfl(s, j, 64);
       float v = 0.f;
       if (l >= j && l < NX) {
@@ -506,11 +484,11 @@ __global__ void __launch_bounds__(64) arm_ik_kernel(const harp_tree_model M, con
     const bool accept = __builtin_amdgcn_readfirstlane((int)(ok && solve && (Cn < C))) != 0;       // (a NaN is not less)
     if (accept) {
       xl = xn;
-      lambda = fmaxf(0.1f * lambda, 1e-9f);
+      lambda = lm::damped(lambda, true);
       ++n_acc;
       fresh = true;
     } else {
-      lambda = fminf(10.0f * lambda, 1e6f);
+      lambda = lm::damped(lambda, false);
     }
   }
 

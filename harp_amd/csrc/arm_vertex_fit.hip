@@ -2,14 +2,15 @@
 // playback Motion.from_arm_vertices): n_t target vertices per frame (all 1026 of the arm, or the 778 of the hand through
 // right_mano_idx) -> the rows [rot | wrist | pose | betas | trans] that harp_lbs_tree_fwd turns back into those vertices.  The reference does
 // this with 500 + 700 Adam iterations (metro_modifications/hand_utils.py:134-240).  The sibling of csrc/vertex_fit.hip (MANO):
-// the iteration, the tile, the matrix-core product and the solve are that file's; the forward is csrc/lbs_tree.hip's (lt::rod_fwd, the
-// level-parallel chain), so the solver and the renderer cannot disagree.
+// the iteration and the tile are that file's, the solve is lm_solve_body.h's, the tree's slot tables are tree_slots_body.h's (shared with
+// csrc/arm_ik.hip); the forward is csrc/lbs_tree.hip's (lt::rod_fwd, lt::rod_jvp, the level-parallel chain), so the solver and the renderer
+// cannot disagree.
 //
 // harp_arm_vertex_fit: T independent Levenberg-Marquardt solves in ONE launch, one workgroup of four waves per frame, 64 unknowns
 // x = [rot 3 | wrist 3 | pose 45 | betas 10 | trans 3] (include/harp_hip.h states the contract).
 //
-//   prologue     once per workgroup, what no unknown moves: the tree (parents, depths, the joint each input row drives), for every driven
-//                joint but the root the list of joints below it ("slots": 16 for the wrist, 3 + 2 + 1 per finger = 46 in all), the ten
+//   prologue     once per workgroup, what no unknown moves: the tree and its slot tables (tree_slots_body.h: 16 slots for the wrist,
+//                3 + 2 + 1 per finger = 46 in all), the ten
 //                solved columns of J_dirs, the rotations of the joints nothing drives, and q0 = v_template + their pose correctives:
 //                constant rows (the real model's left hand: pose_src < 0 with a non-zero pose_mean) that are NOT zero, summed here once
 //                instead of in each of the 2 iters + 1 evaluations; a row whose R - I is exactly zero (rod_fwd(0) = I exactly) is skipped.
@@ -31,10 +32,12 @@
 //                accumulators (blocks (0,0), (1,0), (1,1)), live across the tiles, meeting in LDS wave after wave.
 //   g = J^T W r  64 unknowns leave the tile no column for the residual: thread (column c, wave p) adds J[k][c] w_k r_k over the wave's 48
 //                rows of every tile in a register, and the four partial sums meet in fixed order.
-//   solve        as csrc/vertex_fit.hip with all 64 lanes of wave 0.
+//   solve        lm_solve_body.h with all 64 lanes of wave 0.
 // `iters` iterations whatever happens; every branch is uniform over the workgroup.  No workspace, no allocation, no synchronisation, no
 // atomics: the launch can be captured and a repeated call gives the same bits.
-#include "lbs_tree_body.h"
+#include "lm_gram_body.h"
+#include "lm_solve_body.h"
+#include "tree_slots_body.h"
 
 #include <math.h>
 
@@ -42,26 +45,20 @@ namespace {
 
 using namespace lt;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using lm::f32x16;
 
 constexpr int NX = 64;                  // unknowns per frame = the matrix cores' 2 x 32
 constexpr int LD = 65;                  // row stride of the tile and of the normal matrix in LDS
 constexpr int TV = 64;                  // target vertices per tile
 constexpr int kThreads = 256;
 constexpr int kAfFramesPerBlock = 1;
-constexpr int NIN = 17;                 // rows of in_pose
 constexpr int XW = 3, XP = 6, XB = 51, XT = 61;       // first wrist / finger / shape / trans column
 constexpr int NSB = 10;                 // shape coefficients solved (the model's other NB - 10 are zero)
 constexpr int MAXV = HARP_ARM_VERTEX_FIT_MAX_VERTS;
-constexpr int MAXSLOT = 48;             // (column joint, joint below it) pairs: the arm has 16 + 5 x 6 = 46
 constexpr int MIN_USED = 22;            // 3 x 22 >= 64
 
-struct AfLds {                          // (the small tables first)
-  // the model's structure and what no unknown moves (prologue)
-  int par[MAXJ], depth[MAXJ], drv[NIN]; // drv[row] = the joint that row of in_pose drives
-  int soff[NIN + 1];                    // row's slots: soff[row] .. soff[row + 1] (row 0 has none)
-  int sj[MAXSLOT], sp[MAXSLOT];         // a slot's joint; its parent's slot, or -1 for the column's own joint
-  int maxd, bad, flag;
+struct AfLds : TreeTables {            // (the small tables first; the tree and its slot tables: the prologue's, tree_slots_body.h)
+  int flag;
   // the point and its chain (every evaluation)
   float x[NX];
   float prior[NX];                      // by column (zero outside the finger columns)
@@ -77,7 +74,6 @@ struct AfLds {                          // (the small tables first)
   float dAs[NSB][MAXJ][3];              // d t_j / d betas[k], then dt_j - G_j dJ_j
   float res[3 * TV], wt[TV];            // the tile's residual rows and vertex weights (0 = unused)
   float gp[4][NX];
-  unsigned char desc[NIN][MAXJ], driven[MAXJ];
   float sW[TV][MAXJ + 1];               // the tile's skin weights (odd stride: conflict-free rows)
   float q0[MAXV][3];                    // v_template + the constant correctives, by MODEL vertex
   float q[MAXV][3];                     // v_posed at the last evaluated point, by TARGET vertex
@@ -86,33 +82,12 @@ struct AfLds {                          // (the small tables first)
     float A[NX][LD];                    // the normal matrix (lower triangle), then its scaled Cholesky factor
   } u;
 };
-
-// d R / d r[a] of lt::rod_fwd (same intermediate values, differentiated term by term)
-__device__ __forceinline__ void rod_jvp(const float r[3], int a, float dR[9]) {
-  const float e0 = r[0] + 1e-8f, e1 = r[1] + 1e-8f, e2 = r[2] + 1e-8f;
-  const float th = sqrtf(e0 * e0 + e1 * e1 + e2 * e2);
-  const float dx = r[0] / th, dy = r[1] / th, dz = r[2] / th;
-  const float s = sinf(th), cs = cosf(th), c = 1.0f - cs;
-  const float dth = (a == 0 ? e0 : (a == 1 ? e1 : e2)) / th;
-  const float k = dth / (th * th);
-  const float ddx = (a == 0 ? 1.0f : 0.0f) / th - r[0] * k;
-  const float ddy = (a == 1 ? 1.0f : 0.0f) / th - r[1] * k;
-  const float ddz = (a == 2 ? 1.0f : 0.0f) / th - r[2] * k;
-  const float ds = cs * dth, dc = s * dth;
-  const float n2 = dx * dx + dy * dy + dz * dz, dn2 = 2.0f * (dx * ddx + dy * ddy + dz * ddz);
-  const float ax = ds * dx + s * ddx, ay = ds * dy + s * ddy, az = ds * dz + s * ddz;
-  const float sxy = dc * dx * dy + c * (ddx * dy + dx * ddy);
-  const float sxz = dc * dx * dz + c * (ddx * dz + dx * ddz);
-  const float syz = dc * dy * dz + c * (ddy * dz + dy * ddz);
-  dR[0] = dc * (dx * dx - n2) + c * (2.0f * dx * ddx - dn2); dR[1] = -az + sxy; dR[2] = ay + sxz;
-  dR[3] = az + sxy; dR[4] = dc * (dy * dy - n2) + c * (2.0f * dy * ddy - dn2); dR[5] = -ax + syz;
-  dR[6] = -ay + sxz; dR[7] = ax + syz; dR[8] = dc * (dz * dz - n2) + c * (2.0f * dz * ddz - dn2);
-}
+static_assert(sizeof(AfLds) == 132272, "the dynamic LDS of a workgroup (DESIGN.md §28)");
 
 __device__ __forceinline__ void joint_aa(const harp_tree_model& M, const AfLds& S, int row, float aa[3]) {
   const int j = S.drv[row];
 #pragma unroll
-  for (int c = 0; c < 3; ++c) aa[c] = M.pose_mean[3 * j + c] + S.x[3 * row + c];            // (lbs_tree_body.h:90)
+  for (int c = 0; c < 3; ++c) aa[c] = M.pose_mean[3 * j + c] + S.x[3 * row + c];            // (lbs_tree_body.h, joints_body)
 }
 
 __device__ __forceinline__ int target_vertex(const harp_tree_model& M, const int32_t* __restrict__ idx, int i) {
@@ -122,74 +97,13 @@ __device__ __forceinline__ int target_vertex(const harp_tree_model& M, const int
 // Once per workgroup.  Sets S.bad when the model is not of the shape this kernel's tables hold.
 __device__ void af_prologue(const harp_tree_model& M, AfLds& S, int tid) {
   const int NJ = M.NJ, NB = M.NB, NV = M.NV;
-  if (tid < NJ) S.par[tid] = M.parents[tid];
-  if (tid < NIN) S.drv[tid] = -1;
-  if (tid == 0) S.bad = 0;
-  __syncthreads();
-  if (tid < NJ) {
-    const int src = M.pose_src[tid];
-    S.driven[tid] = (src >= 0 && src < NIN) ? 1 : 0;
-    if (src >= 0 && src < NIN) S.drv[src] = tid;
-    int d = 0;
-    for (int q = S.par[tid]; q >= 0; q = S.par[q]) ++d;
-    S.depth[tid] = d;
-  }
   for (int i = tid; i < NSB * NJ * 3; i += kThreads) {
     const int k = i / (NJ * 3), l = i % (NJ * 3);
     S.dJ[k][l / 3][l % 3] = M.J_dirs[(size_t)l * NB + k];
   }
-  __syncthreads();
-  if (tid == 0) {
-    int md = 0, bad = (S.drv[0] != 0);
-    for (int j = 0; j < NJ; ++j) md = max(md, S.depth[j]);
-    for (int r = 1; r < NIN; ++r) bad |= (S.drv[r] <= 0);
-    S.maxd = md;
-    S.bad = bad;
-  }
-  __syncthreads();
+  tree_tables<kThreads>(M, S, tid);
   if (S.bad) return;
-  for (int i = tid; i < NIN * NJ; i += kThreads) {                     // is joint j the row's joint or below it
-    const int row = i / NJ, j = i % NJ, jq = S.drv[row];
-    int a = j;
-    while (a > jq) a = S.par[a];
-    S.desc[row][j] = (row > 0 && a == jq) ? 1 : 0;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    int n = 0;
-    S.soff[0] = 0;
-    for (int row = 0; row < NIN; ++row) {
-      for (int j = 0; j < NJ; ++j) n += S.desc[row][j];
-      S.soff[row + 1] = n;
-    }
-    if (n > MAXSLOT) S.bad = 1;
-  }
-  __syncthreads();
-  if (S.bad) return;
-  if (tid >= 1 && tid < NIN) {                                         // the row's slots, parents before children (parents[j] < j)
-    const int jq = S.drv[tid], s0 = S.soff[tid];
-    int s = s0;
-    for (int j = jq; j < NJ; ++j) {
-      if (!S.desc[tid][j]) continue;
-      int ps = -1;
-      if (j != jq)
-        for (int u = s0; u < s; ++u)
-          if (S.sj[u] == S.par[j]) ps = u;
-      S.sj[s] = j;
-      S.sp[s] = ps;
-      ++s;
-    }
-  }
-  if (tid >= 64 && tid < 64 + NJ) {                                    // the joints nothing drives: their rotation is the model's
-    const int j = tid - 64;
-    if (!S.driven[j]) {
-      const float aa[3] = {M.pose_mean[3 * j], M.pose_mean[3 * j + 1], M.pose_mean[3 * j + 2]};
-      float R[9];
-      rod_fwd(aa, R);
-#pragma unroll
-      for (int k = 0; k < 9; ++k) S.R[j][k] = R[k];
-    }
-  }
+  undriven_rotation(M, S, tid - 64, S.R);
   __syncthreads();
   for (int v = tid; v < NV; v += kThreads) {                           // q0: the template and the constant corrective rows
     float q[3] = {M.v_template[3 * v], M.v_template[3 * v + 1], M.v_template[3 * v + 2]};
@@ -221,7 +135,7 @@ __device__ void af_setup(const harp_tree_model& M, AfLds& S, int tid, bool JAC) 
       S.R[j][k] = R[k];
       S.pmv[tid][k] = R[k] - ((k == 0 || k == 4 || k == 8) ? 1.f : 0.f);
     }
-  } else if (tid >= 64 && tid < 64 + NJ * 3) {                         // rest joints at this shape (lbs_tree_body.h:100-112)
+  } else if (tid >= 64 && tid < 64 + NJ * 3) {                         // rest joints at this shape (lbs_tree_body.h, joints_body)
     const int l = tid - 64, j = l / 3, r = l % 3;
     float acc = M.J_template[l];
 #pragma unroll
@@ -243,7 +157,7 @@ __device__ void af_setup(const harp_tree_model& M, AfLds& S, int tid, bool JAC) 
   } else if (JAC && tid >= 64 && tid < 64 + NSB) {
     for (int r = 0; r < 3; ++r) S.dAs[tid - 64][0][r] = S.dJ[tid - 64][0][r];
   }
-  // batch_rigid_transform level by level (lbs_tree_body.h:114-139); beside it the shape tangents of the posed joint positions
+  // batch_rigid_transform level by level (lbs_tree_body.h, joints_body); beside it the shape tangents of the posed joint positions
   const int maxd = S.maxd;
   for (int d = 1; d <= maxd; ++d) {
     __syncthreads();
@@ -527,17 +441,8 @@ __device__ void af_normal(const harp_tree_model& M, AfLds& S, int tid, const int
       float* jo = jac + (size_t)tile * TV * 3 * NX;
       for (int i = tid; i < n; i += kThreads) jo[i] = S.u.J[i / NX][i % NX];
     }
+    lm::gram_accumulate(S.u.J, S.wt, wave, lane, acc00, acc10, acc11);
     {
-      const int col = lane & 31, kh = lane >> 5;
-#pragma unroll 4
-      for (int kk = 0; kk < 24; ++kk) {
-        const int k = 48 * wave + 2 * kk + kh;
-        const float wk = S.wt[k / 3], j0 = S.u.J[k][col], j1 = S.u.J[k][32 + col];
-        const float a0 = j0 * wk, a1 = j1 * wk;
-        acc00 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, j0, acc00, 0, 0, 0);
-        acc10 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, j0, acc10, 0, 0, 0);
-        acc11 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, j1, acc11, 0, 0, 0);
-      }
 #pragma unroll 4
       for (int kk = 0; kk < 48; ++kk) {                                // g: column `lane`, this wave's 48 rows, in order
         const int k = 48 * wave + kk;
@@ -620,14 +525,13 @@ arm_vertex_fit_kernel(const harp_tree_model M, const int32_t* __restrict__ vert_
     const float Ce = af_forward(M, S, tid, vert_idx, n_t, tg, wts, pose_w, wrist_w, shape_w,
                                 (last && verts) ? verts + (size_t)t * M.NV * 3 : nullptr);
     if (!at_x) {
-      if (ok && solve && (Ce < C)) {                                   // (a NaN is not less; uniform over the workgroup)
+      const bool accept = ok && solve && (Ce < C);                     // (a NaN is not less; uniform over the workgroup)
+      if (accept) {
         xl = xn;
         C = Ce;
-        lambda = fmaxf(0.1f * lambda, 1e-9f);
         ++n_acc;
-      } else {
-        lambda = fminf(10.0f * lambda, 1e6f);
       }
+      lambda = lm::damped(lambda, accept);
       continue;
     }
     if (e == 0) C0 = C = Ce;
@@ -656,39 +560,10 @@ arm_vertex_fit_kernel(const harp_tree_model M, const int32_t* __restrict__ vert_
       if (gout && tid < NX) gout[(size_t)t * NX + tid] = g;
       break;
     }
-    const float s = 1.0f / sqrtf(diag * (1.0f + lambda));             // Jacobi scaling: (A + lambda diag A) scaled has a unit diagonal
-    bool okw = __all(tid >= NX || (diag > 0.f && isfinite(s)));        // (wave 0's verdict counts)
-#pragma unroll 1
-    for (int j = 0; j < NX; ++j) {                                     // left-looking Cholesky, column j, on wave 0
-      if (wave == 0) {
-        const float sj = __shfl(s, j, 64);
-        float v = 0.f;
-        if (tid >= j) {
-          v = (tid == j) ? 1.0f : S.u.A[tid][j] * s * sj;
-#pragma unroll 8
-          for (int c = 0; c < j; ++c) v -= S.u.A[tid][c] * S.u.A[j][c];       // (eight pairs of LDS reads in flight, same order)
-        }
-        const float piv = __shfl(v, j, 64);
-        okw = okw && (piv > 0.f) && isfinite(piv);
-        const float ljj = sqrtf(piv);
-        if (tid >= j) S.u.A[tid][j] = (tid == j) ? ljj : v / ljj;
-      }
-      __syncthreads();
-    }
+    bool okw;                                                          // (wave 0's verdict counts)
+    const float s = lm::jacobi_scale<NX>(tid, diag, lambda, okw);
+    const float z = lm::solve<NX, LD, 1, 8>(S.u.A, tid, s, -g * s, wave == 0, okw);
     if (wave == 0) {
-      float b = -g * s, y = 0.f, z = 0.f;
-#pragma unroll 1
-      for (int j = 0; j < NX; ++j) {                                   // L y = b
-        const float yj = __shfl(b, j, 64) / S.u.A[j][j];
-        if (tid == j) y = yj;
-        if (tid > j) b -= S.u.A[tid][j] * yj;
-      }
-#pragma unroll 1
-      for (int j = NX - 1; j >= 0; --j) {                              // L^T z = y
-        const float zj = __shfl(y, j, 64) / S.u.A[j][j];
-        if (tid == j) z = zj;
-        if (tid < j) y -= S.u.A[j][tid] * zj;
-      }
       xn = xl + z * s;
       S.x[tid] = xn;
       if (tid == 0) S.flag = okw ? 1 : 0;

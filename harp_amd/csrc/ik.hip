@@ -5,7 +5,7 @@
 // harp_mano_ik: T independent Levenberg-Marquardt solves in ONE launch, one wave (= one workgroup) per frame.  Per frame 51 unknowns
 // x = [rot 3 | pose 45 | trans 3] and 63 residuals; cost C(x) = sum_k w_k |j_k(x) - t_k|^2 + w_prior sum_i (pose_i - prior_i)^2 with j(x)
 // the 21 joints of harp_lbs_mano_fwd in metres (16 chain joints, 5 tip vertices with shape blend, pose correctives and skinning, trans,
-// c_reorder's order; rodrigues_fwd, parent_of, c_tips, c_reorder from lbs_body.h).
+// c_reorder's order; rodrigues_fwd and its tangent rodrigues_jvp, parent_of, c_tips, c_reorder from lbs_body.h).
 //
 //   forward      lanes 0..15 one Rodrigues each, lanes 0..4 one finger chain each (as lbs_joints_kernel), lanes 0..14 the posed tip
 //                coordinates (135-long dot with the tips' posedirs rows), lanes 0..59 the tips' blended 3x4 transforms, lanes 0..62 one
@@ -15,16 +15,16 @@
 //                (the root: all five) and into ALL five tips: through the skinning weights of the joints it moves and through the tips'
 //                pose correctives.  Lanes 48..50: the identity columns of trans.  J (63 x 51) lives in LDS.
 //   normal eqs.  A = J^T W J + P (lane i: row i, its own weighted column in 63 registers, the other column a broadcast LDS read),
-//                g = J^T W r + P (x - prior); Jacobi scaling s_i = 1 / sqrt(A_ii (1 + lambda)): S = s (A + lambda diag A) s has a unit diagonal.
-//   Cholesky     left-looking, in place over A's lower triangle in LDS, lane i = row i, column by column (a dot of length j per lane, the
-//                pivot by a lane broadcast); a non-positive or non-finite pivot marks the step rejected.  Both triangular solves in
-//                registers with lane broadcasts, L read from LDS.  x' = x + s z.
-//   accept       C(x') < C(x) (a NaN is not less): x = x', lambda = max(0.1 lambda, 1e-9), J re-evaluated; else lambda = min(10 lambda, 1e6).
+//                g = J^T W r + P (x - prior); the Jacobi scale of lm_solve_body.h (lm::jacobi_scale).
+//   solve        the factorisation and both triangular solves of lm_solve_body.h, written out here: this kernel measured 0.3 % slower
+//                through lm::solve, beyond its run-to-run spread.  x' = x + s z.
+//   accept       C(x') < C(x) (a NaN is not less): x = x', lambda down, J re-evaluated; else lambda up (lm::damped).
 // `iters` iterations whatever happens: no early exit, every branch is uniform over the wave.  No workspace, no allocation, no
 // synchronisation, no atomics: the launch can be captured and a repeated call gives the same bits.
 // A frame with fewer than 3 used joints (w_k > 0 and a finite target) runs the same instructions and writes nothing back but cost, status
 // -1 and the optional joints / jac at its input.  An unused joint's target is tested for finiteness and never enters arithmetic.
 #include "lbs_body.h"
+#include "lm_solve_body.h"
 #include "harp_hip.h"
 
 #include <math.h>
@@ -47,34 +47,7 @@ struct IkLds {
   float w[21], res[NR], jnt[NR], tgt[NR], beta[NB], prior[48];
   int inv[21];                         // inverse of c_reorder: model joint / tip -> output joint
 };
-
-// d R / d aa[c] of lb::rodrigues_fwd (same intermediate values, differentiated term by term)
-__device__ __forceinline__ void rodrigues_jvp(const float aa[3], int c, float dR[9]) {
-  const float e[3] = {aa[0] + 1e-8f, aa[1] + 1e-8f, aa[2] + 1e-8f};
-  const float n = sqrtf(e[0] * e[0] + e[1] * e[1] + e[2] * e[2]);
-  const float a[3] = {aa[0] / n, aa[1] / n, aa[2] / n};
-  const float h = n * 0.5f, cs = cosf(h), s = sinf(h);
-  const float q[4] = {cs, s * a[0], s * a[1], s * a[2]};
-  const float qn = sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-  const float w = q[0] / qn, x = q[1] / qn, y = q[2] / qn, z = q[3] / qn;
-  const float dn = (c == 0 ? e[0] : (c == 1 ? e[1] : e[2])) / n;
-  const float dh = 0.5f * dn;
-  float dq[4];
-  dq[0] = -s * dh;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const float da = ((k == c) ? 1.0f : 0.0f) / n - aa[k] * dn / (n * n);
-    dq[k + 1] = cs * dh * a[k] + s * da;
-  }
-  const float dqn = (q[0] * dq[0] + q[1] * dq[1] + q[2] * dq[2] + q[3] * dq[3]) / qn;
-  const float dw = (dq[0] - w * dqn) / qn, dx = (dq[1] - x * dqn) / qn, dy = (dq[2] - y * dqn) / qn, dz = (dq[3] - z * dqn) / qn;
-  const float ww = w * dw, xx = x * dx, yy = y * dy, zz = z * dz;
-  const float dwx = dw * x + w * dx, dwy = dw * y + w * dy, dwz = dw * z + w * dz;
-  const float dxy = dx * y + x * dy, dxz = dx * z + x * dz, dyz = dy * z + y * dz;
-  dR[0] = 2 * (ww + xx - yy - zz); dR[1] = 2 * dxy - 2 * dwz;       dR[2] = 2 * dwy + 2 * dxz;
-  dR[3] = 2 * dwz + 2 * dxy;       dR[4] = 2 * (ww - xx + yy - zz); dR[5] = 2 * dyz - 2 * dwx;
-  dR[6] = 2 * dxz - 2 * dwy;       dR[7] = 2 * dwx + 2 * dyz;       dR[8] = 2 * (ww - xx - yy + zz);
-}
+static_assert(sizeof(IkLds) == 27056, "the frames in flight on a CU rest on this size (DESIGN.md §24)");
 
 __device__ __forceinline__ void joint_aa(const harp_mano_model& M, const IkLds& S, int j, float aa[3]) {
 #pragma unroll
@@ -319,10 +292,10 @@ __global__ void __launch_bounds__(64, 2) mano_ik_kernel(const harp_mano_model M,
       }
       if (l < NX) S.A[l][j] = a;
     }
-    const float s = 1.0f / sqrtf(diag * (1.0f + lambda));             // Jacobi scaling: (A + lambda diag A) scaled has a unit diagonal
-    bool ok = __all(l >= NX || (diag > 0.f && isfinite(s)));
+    bool ok;
+    const float s = lm::jacobi_scale<NX>(l, diag, lambda, ok);
     __syncthreads();
-    for (int j = 0; j < NX; ++j) {                                     // left-looking Cholesky, column j
+    for (int j = 0; j < NX; ++j) {                                     // lm::solve's factorisation, column j
       const float sj = __shfl(s, j, 64);
       float v = 0.f;
       if (l >= j && l < NX) {
@@ -351,11 +324,11 @@ __global__ void __launch_bounds__(64, 2) mano_ik_kernel(const harp_mano_model M,
     const bool accept = __builtin_amdgcn_readfirstlane((int)(ok && solve && (Cn < C))) != 0;       // (a NaN is not less)
     if (accept) {
       xl = xn;
-      lambda = fmaxf(0.1f * lambda, 1e-9f);
+      lambda = lm::damped(lambda, true);
       ++n_acc;
       C = ik_eval<true>(M, S, l, xl, prior_w);
     } else {
-      lambda = fminf(10.0f * lambda, 1e6f);
+      lambda = lm::damped(lambda, false);
     }
   }
 

@@ -56,6 +56,34 @@ __device__ __forceinline__ void rodrigues_bwd(const float aa[3], const float g[9
   gaa[2] = ga[2] / n + g_n * e2 / n;
 }
 
+// d R / d aa[c] of rodrigues_fwd (same intermediate values, differentiated term by term, the 1e-8 inside the norm included: it holds at
+// aa = 0): the forward-mode tangent of the pose solvers (ik.hip, reproj_ik.hip, vertex_fit.hip)
+__device__ __forceinline__ void rodrigues_jvp(const float aa[3], int c, float dR[9]) {
+  const float e[3] = {aa[0] + 1e-8f, aa[1] + 1e-8f, aa[2] + 1e-8f};
+  const float n = sqrtf(e[0] * e[0] + e[1] * e[1] + e[2] * e[2]);
+  const float a[3] = {aa[0] / n, aa[1] / n, aa[2] / n};
+  const float h = n * 0.5f, cs = cosf(h), s = sinf(h);
+  const float q[4] = {cs, s * a[0], s * a[1], s * a[2]};
+  const float qn = sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+  const float w = q[0] / qn, x = q[1] / qn, y = q[2] / qn, z = q[3] / qn;
+  const float dn = (c == 0 ? e[0] : (c == 1 ? e[1] : e[2])) / n;
+  const float dh = 0.5f * dn;
+  float dq[4];
+  dq[0] = -s * dh;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    const float da = ((k == c) ? 1.0f : 0.0f) / n - aa[k] * dn / (n * n);
+    dq[k + 1] = cs * dh * a[k] + s * da;
+  }
+  const float dqn = (q[0] * dq[0] + q[1] * dq[1] + q[2] * dq[2] + q[3] * dq[3]) / qn;
+  const float dw = (dq[0] - w * dqn) / qn, dx = (dq[1] - x * dqn) / qn, dy = (dq[2] - y * dqn) / qn, dz = (dq[3] - z * dqn) / qn;
+  const float ww = w * dw, xx = x * dx, yy = y * dy, zz = z * dz;
+  const float dwx = dw * x + w * dx, dwy = dw * y + w * dy, dwz = dw * z + w * dz;
+  const float dxy = dx * y + x * dy, dxz = dx * z + x * dz, dyz = dy * z + y * dz;
+  dR[0] = 2 * (ww + xx - yy - zz); dR[1] = 2 * dxy - 2 * dwz;       dR[2] = 2 * dwy + 2 * dxz;
+  dR[3] = 2 * dwz + 2 * dxy;       dR[4] = 2 * (ww - xx + yy - zz); dR[5] = 2 * dyz - 2 * dwx;
+  dR[6] = 2 * dxz - 2 * dwy;       dR[7] = 2 * dwx + 2 * dyz;       dR[8] = 2 * (ww - xx - yy + zz);
+}
 
 static __constant__ int c_tips[5] = {745, 317, 444, 556, 673};                                                  // manolayer.py:270
 static __constant__ int c_reorder[21] = {0, 13, 14, 15, 16, 1, 2, 3, 17, 4, 5, 6, 18, 10, 11, 12, 19, 7, 8, 9, 20};  // :279

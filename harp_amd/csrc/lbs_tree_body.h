@@ -49,6 +49,28 @@ __device__ __forceinline__ void rod_bwd(const float r[3], const float g[9], floa
   for (int k = 0; k < 3; ++k) gr[k] = gd[k] / th + g_th * e[k] / th;
 }
 
+// d R / d r[a] of rod_fwd (same intermediate values, differentiated term by term): the forward-mode tangent of the arm's pose solvers
+// (arm_ik.hip, arm_vertex_fit.hip)
+__device__ __forceinline__ void rod_jvp(const float r[3], int a, float dR[9]) {
+  const float e0 = r[0] + 1e-8f, e1 = r[1] + 1e-8f, e2 = r[2] + 1e-8f;
+  const float th = sqrtf(e0 * e0 + e1 * e1 + e2 * e2);
+  const float dx = r[0] / th, dy = r[1] / th, dz = r[2] / th;
+  const float s = sinf(th), cs = cosf(th), c = 1.0f - cs;
+  const float dth = (a == 0 ? e0 : (a == 1 ? e1 : e2)) / th;
+  const float k = dth / (th * th);
+  const float ddx = (a == 0 ? 1.0f : 0.0f) / th - r[0] * k;
+  const float ddy = (a == 1 ? 1.0f : 0.0f) / th - r[1] * k;
+  const float ddz = (a == 2 ? 1.0f : 0.0f) / th - r[2] * k;
+  const float ds = cs * dth, dc = s * dth;
+  const float n2 = dx * dx + dy * dy + dz * dz, dn2 = 2.0f * (dx * ddx + dy * ddy + dz * ddz);
+  const float ax = ds * dx + s * ddx, ay = ds * dy + s * ddy, az = ds * dz + s * ddz;
+  const float sxy = dc * dx * dy + c * (ddx * dy + dx * ddy);
+  const float sxz = dc * dx * dz + c * (ddx * dz + dx * ddz);
+  const float syz = dc * dy * dz + c * (ddy * dz + dy * ddz);
+  dR[0] = dc * (dx * dx - n2) + c * (2.0f * dx * ddx - dn2); dR[1] = -az + sxy; dR[2] = ay + sxz;
+  dR[3] = az + sxy; dR[4] = dc * (dy * dy - n2) + c * (2.0f * dy * ddy - dn2); dR[5] = -ax + syz;
+  dR[6] = -ay + sxz; dR[7] = ax + syz; dR[8] = dc * (dz * dz - n2) + c * (2.0f * dz * ddz - dn2);
+}
 
 // workspace of harp_lbs_tree_fwd / bwd (harp_lbs_tree_ws_floats)
 struct TreeWs { float *pm, *A, *G, *Jrest, *Rloc, *vp, *g_vp, *g_A, *g_pm, *g_Gt; };

@@ -6,10 +6,11 @@
 // rasteriser's pixel centres (column i has its centre at u = i + 0.5).
 //
 // harp_mano_reproj_ik: N independent Levenberg-Marquardt solves in ONE launch, one wave (= one workgroup) per problem; the iteration is
-// harp_mano_ik's (csrc/ik.hip), whose tangent push and Cholesky are repeated here on purpose: that file stays as it is.  Per problem 51
+// harp_mano_ik's (csrc/ik.hip): the same joints forward and tangent push, and lm_solve_body.h's solve, written out in both files because
+// either kernel measured slower through shared routines, beyond its run-to-run spread.  Per problem 51
 // unknowns x = [rot 3 | pose 45 | trans 3] and 63 rows (u_k, v_k, d_k):
 //   Z_k = j_k.z + t_z, u_k = S/2 + focal (j_k.x + cam1) / Z_k, v_k = S/2 + focal (j_k.y + cam2) / Z_k, d_k = j_k.z - j_0.z
-// with j(x) the 21 joints of harp_lbs_mano_fwd in metres (rodrigues_fwd, parent_of, c_tips, c_reorder from lbs_body.h), and the cost
+// with j(x) the 21 joints of harp_lbs_mano_fwd in metres (rodrigues_fwd, rodrigues_jvp, parent_of, c_tips, c_reorder from lbs_body.h), and the cost
 //   C = sum_k w_k [(u_k - u^_k)^2 + (v_k - v^_k)^2] + sum_{k>=1} wz_k (d_k - d^_k)^2 + w_pose sum_i (pose_i - prior_i)^2 + w_z (trans_z - z_prior)^2.
 //
 //   forward      as csrc/ik.hip up to the 63 joint coordinates; then lane k < 21 projects joint k: its Z, its three rows, their residuals
@@ -18,7 +19,7 @@
 //   Jacobian     lane i < 48 pushes the tangent of ITS axis-angle component into all 21 joints (as csrc/ik.hip; dense in the tips), lanes
 //                48..50 hold the identity columns of trans; every lane then turns the 63 3-D entries of its own column into (u, v, d) rows
 //                — du = focal/Z dj.x - focal (j.x + cam1)/Z^2 dj.z, dd = dj_k.z - dj_0.z with its own wrist entry — in place in LDS.
-//   normal eqs., Cholesky, accept: csrc/ik.hip's, with the row weights (w_k, w_k, wz_k) and the two priors on the diagonal; a candidate
+//   normal eqs., solve, accept: csrc/ik.hip's (lm::jacobi_scale, lm::damped), with the row weights (w_k, w_k, wz_k) and the two priors on the diagonal; a candidate
 //                behind the camera is a rejection.
 // `iters` iterations whatever happens: no early exit, every branch is uniform over the wave.  No workspace, no allocation, no
 // synchronisation, no atomics: the launch can be captured and a repeated call gives the same bits.
@@ -26,6 +27,7 @@
 // instructions and writes nothing back but cost, status and the optional proj / jac at its input.  An unused target is tested and never
 // enters arithmetic; a joint that is not pixel-used AND at Z_k <= 1e-3 gets u = v = 0 and zero u / v rows in jac (nothing to divide by).
 #include "lbs_body.h"
+#include "lm_solve_body.h"
 #include "harp_hip.h"
 
 #include <math.h>
@@ -56,34 +58,7 @@ struct RpLds {
   __device__ float* px() { return &A[0][0] + 21; }         // [21] focal (j_k.x + cam1) / Z_k^2
   __device__ float* py() { return &A[0][0] + 42; }         // [21] focal (j_k.y + cam2) / Z_k^2
 };
-
-// d R / d aa[c] of lb::rodrigues_fwd (same intermediate values, differentiated term by term)
-__device__ __forceinline__ void rodrigues_jvp(const float aa[3], int c, float dR[9]) {
-  const float e[3] = {aa[0] + 1e-8f, aa[1] + 1e-8f, aa[2] + 1e-8f};
-  const float n = sqrtf(e[0] * e[0] + e[1] * e[1] + e[2] * e[2]);
-  const float a[3] = {aa[0] / n, aa[1] / n, aa[2] / n};
-  const float h = n * 0.5f, cs = cosf(h), s = sinf(h);
-  const float q[4] = {cs, s * a[0], s * a[1], s * a[2]};
-  const float qn = sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-  const float w = q[0] / qn, x = q[1] / qn, y = q[2] / qn, z = q[3] / qn;
-  const float dn = (c == 0 ? e[0] : (c == 1 ? e[1] : e[2])) / n;
-  const float dh = 0.5f * dn;
-  float dq[4];
-  dq[0] = -s * dh;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const float da = ((k == c) ? 1.0f : 0.0f) / n - aa[k] * dn / (n * n);
-    dq[k + 1] = cs * dh * a[k] + s * da;
-  }
-  const float dqn = (q[0] * dq[0] + q[1] * dq[1] + q[2] * dq[2] + q[3] * dq[3]) / qn;
-  const float dw = (dq[0] - w * dqn) / qn, dx = (dq[1] - x * dqn) / qn, dy = (dq[2] - y * dqn) / qn, dz = (dq[3] - z * dqn) / qn;
-  const float ww = w * dw, xx = x * dx, yy = y * dy, zz = z * dz;
-  const float dwx = dw * x + w * dx, dwy = dw * y + w * dy, dwz = dw * z + w * dz;
-  const float dxy = dx * y + x * dy, dxz = dx * z + x * dz, dyz = dy * z + y * dz;
-  dR[0] = 2 * (ww + xx - yy - zz); dR[1] = 2 * dxy - 2 * dwz;       dR[2] = 2 * dwy + 2 * dxz;
-  dR[3] = 2 * dwz + 2 * dxy;       dR[4] = 2 * (ww - xx + yy - zz); dR[5] = 2 * dyz - 2 * dwx;
-  dR[6] = 2 * dxz - 2 * dwy;       dR[7] = 2 * dwx + 2 * dyz;       dR[8] = 2 * (ww - xx - yy + zz);
-}
+static_assert(sizeof(RpLds) == 27296, "six problems within a CU's 160 KiB rest on this size (DESIGN.md §30)");
 
 __device__ __forceinline__ void joint_aa(const harp_mano_model& M, const RpLds& S, int j, float aa[3]) {
 #pragma unroll
@@ -372,10 +347,10 @@ __global__ void __launch_bounds__(64, 2) mano_reproj_ik_kernel(const harp_mano_m
       }
       if (l < NX) S.A[l][j] = a;
     }
-    const float s = 1.0f / sqrtf(diag * (1.0f + lambda));             // Jacobi scaling: (A + lambda diag A) scaled has a unit diagonal
-    bool ok = __all(l >= NX || (diag > 0.f && isfinite(s)));
+    bool ok;
+    const float s = lm::jacobi_scale<NX>(l, diag, lambda, ok);
     __syncthreads();
-    for (int j = 0; j < NX; ++j) {                                     // left-looking Cholesky, column j
+    for (int j = 0; j < NX; ++j) {                                     // lm::solve's factorisation, column j
       const float sj = __shfl(s, j, 64);
       float v = 0.f;
       if (l >= j && l < NX) {
@@ -404,11 +379,11 @@ __global__ void __launch_bounds__(64, 2) mano_reproj_ik_kernel(const harp_mano_m
     const bool accept = __builtin_amdgcn_readfirstlane((int)(ok && solve && !behind && (Cn < C))) != 0;       // (a NaN is not less)
     if (accept) {
       xl = xn;
-      lambda = fmaxf(0.1f * lambda, 1e-9f);
+      lambda = lm::damped(lambda, true);
       ++n_acc;
       C = rp_eval<true>(M, S, l, xl, pw, pc, focal, half, behind);
     } else {
-      lambda = fminf(10.0f * lambda, 1e6f);
+      lambda = lm::damped(lambda, false);
     }
   }
 

@@ -1,8 +1,8 @@
 // Batched fit of the MANO hand to mesh vertices for gfx950 (ops.mano_vertex_fit; hand_utils.optimize_for_mano_param(method="lm");
 // playback Motion.from_vertices): 778 target vertices per frame -> the rows [rot | pose | betas | trans] that
 // harp_lbs_mano_fwd turns back into those vertices.  The reference does this with 500 + 700 Adam iterations
-// (metro_modifications/hand_utils.py:16-131); the model inverted is csrc/lbs.hip's, with rodrigues_fwd, parent_of, skin_weights and skin_T
-// of lbs_body.h, so the solver and the renderer cannot disagree.
+// (metro_modifications/hand_utils.py:16-131); the model inverted is csrc/lbs.hip's, with rodrigues_fwd, rodrigues_jvp, parent_of, skin_weights
+// and skin_T of lbs_body.h, so the solver and the renderer cannot disagree.
 //
 // harp_mano_vertex_fit: T independent Levenberg-Marquardt solves in ONE launch, one workgroup of four waves per frame.  Per frame 61
 // unknowns x = [rot 3 | pose 45 | betas 10 | trans 3] and 2334 residuals (include/harp_hip.h states the contract).
@@ -24,11 +24,13 @@
 //                accumulators - blocks (0,0), (1,0), (1,1) of the 64 x 64 product; the lower triangle is all Cholesky reads - that
 //                live in registers across the 13 tiles and meet in LDS at the end, wave after wave (fixed order).  Row 61 of the
 //                product is g = J^T W r.
-//   solve        as csrc/ik.hip: Jacobi scaling, left-looking Cholesky in place over the lower triangle in LDS with lane i = row i on
-//                wave 0, both triangular solves in registers with lane broadcasts, accept iff C(x') < C(x).
+//   solve        lm_solve_body.h on wave 0 (Jacobi scaling, the in-place Cholesky of the scaled system in LDS with lane i = row i, both
+//                triangular solves in registers), accept iff C(x') < C(x).
 // `iters` iterations whatever happens; every branch is uniform over the workgroup.  No workspace, no allocation, no synchronisation, no
 // atomics: the launch can be captured and a repeated call gives the same bits.
 #include "lbs_body.h"
+#include "lm_gram_body.h"
+#include "lm_solve_body.h"
 #include "harp_hip.h"
 
 #include <math.h>
@@ -37,7 +39,7 @@ namespace {
 
 using namespace lb;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using lm::f32x16;
 
 constexpr int NX = 61;                  // unknowns per frame
 constexpr int NXP = 64;                 // ... padded to the matrix cores' 2 x 32; column 61 carries the residual
@@ -65,34 +67,7 @@ struct VfLds {                          // (the small tables first: their addres
     float A[NXP][LD];                   // the normal matrix (lower triangle; row 61 = g), then its scaled Cholesky factor
   } u;
 };
-
-// d R / d aa[c] of lb::rodrigues_fwd (same intermediate values, differentiated term by term; csrc/ik.hip has its own copy)
-__device__ __forceinline__ void rodrigues_jvp(const float aa[3], int c, float dR[9]) {
-  const float e[3] = {aa[0] + 1e-8f, aa[1] + 1e-8f, aa[2] + 1e-8f};
-  const float n = sqrtf(e[0] * e[0] + e[1] * e[1] + e[2] * e[2]);
-  const float a[3] = {aa[0] / n, aa[1] / n, aa[2] / n};
-  const float h = n * 0.5f, cs = cosf(h), s = sinf(h);
-  const float q[4] = {cs, s * a[0], s * a[1], s * a[2]};
-  const float qn = sqrtf(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-  const float w = q[0] / qn, x = q[1] / qn, y = q[2] / qn, z = q[3] / qn;
-  const float dn = (c == 0 ? e[0] : (c == 1 ? e[1] : e[2])) / n;
-  const float dh = 0.5f * dn;
-  float dq[4];
-  dq[0] = -s * dh;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const float da = ((k == c) ? 1.0f : 0.0f) / n - aa[k] * dn / (n * n);
-    dq[k + 1] = cs * dh * a[k] + s * da;
-  }
-  const float dqn = (q[0] * dq[0] + q[1] * dq[1] + q[2] * dq[2] + q[3] * dq[3]) / qn;
-  const float dw = (dq[0] - w * dqn) / qn, dx = (dq[1] - x * dqn) / qn, dy = (dq[2] - y * dqn) / qn, dz = (dq[3] - z * dqn) / qn;
-  const float ww = w * dw, xx = x * dx, yy = y * dy, zz = z * dz;
-  const float dwx = dw * x + w * dx, dwy = dw * y + w * dy, dwz = dw * z + w * dz;
-  const float dxy = dx * y + x * dy, dxz = dx * z + x * dz, dyz = dy * z + y * dz;
-  dR[0] = 2 * (ww + xx - yy - zz); dR[1] = 2 * dxy - 2 * dwz;       dR[2] = 2 * dwy + 2 * dxz;
-  dR[3] = 2 * dwz + 2 * dxy;       dR[4] = 2 * (ww - xx + yy - zz); dR[5] = 2 * dyz - 2 * dwx;
-  dR[6] = 2 * dxz - 2 * dwy;       dR[7] = 2 * dwx + 2 * dyz;       dR[8] = 2 * (ww - xx - yy + zz);
-}
+static_assert(sizeof(VfLds) == 75148, "two workgroups on a CU rest on this size (DESIGN.md §27)");
 
 __device__ __forceinline__ void joint_aa(const harp_mano_model& M, const VfLds& S, int j, float aa[3]) {
 #pragma unroll
@@ -408,18 +383,7 @@ __device__ void vf_normal(const harp_mano_model& M, VfLds& S, int tid, const flo
       float* jo = jac + (size_t)tile * TV * 3 * NX;
       for (int i = tid; i < n; i += kThreads) jo[i] = S.u.J[i / NX][i % NX];
     }
-    {
-      const int col = lane & 31, kh = lane >> 5;
-#pragma unroll 4
-      for (int kk = 0; kk < 24; ++kk) {
-        const int k = 48 * wave + 2 * kk + kh;
-        const float wk = S.wt[k / 3], j0 = S.u.J[k][col], j1 = S.u.J[k][32 + col];
-        const float a0 = j0 * wk, a1 = j1 * wk;
-        acc00 = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, j0, acc00, 0, 0, 0);
-        acc10 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, j0, acc10, 0, 0, 0);
-        acc11 = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, j1, acc11, 0, 0, 0);
-      }
-    }
+    lm::gram_accumulate(S.u.J, S.wt, wave, lane, acc00, acc10, acc11);
     __syncthreads();
   }
   for (int w = 0; w < 4; ++w) {                                        // the four K slices meet, wave after wave
@@ -451,7 +415,6 @@ __global__ void __launch_bounds__(kThreads, 2) mano_vertex_fit_kernel(const harp
   const float* tg = targets + (size_t)t * NV * 3;
   const float* wts = weights ? weights + (size_t)t * NV : nullptr;
   const size_t brow = (solve_shape || betas_per_frame) ? (size_t)t * NB : 0;
-  const int lc = min(tid, NX - 1);
   float xl = 0.f;                                                      // wave 0, lane l: unknown l
   if (tid < 48) xl = pose48[(size_t)t * 48 + tid];
   else if (tid < XT) xl = betas[brow + (tid - XB)];
@@ -487,14 +450,13 @@ __global__ void __launch_bounds__(kThreads, 2) mano_vertex_fit_kernel(const harp
     vf_setup(M, S, tid, at_x);
     const float Ce = vf_forward(M, S, tid, tg, wts, pose_w, shape_w, (last && verts) ? verts + (size_t)t * NV * 3 : nullptr);
     if (!at_x) {
-      if (ok && solve && (Ce < C)) {                                   // (a NaN is not less; uniform over the workgroup)
+      const bool accept = ok && solve && (Ce < C);                     // (a NaN is not less; uniform over the workgroup)
+      if (accept) {
         xl = xn;
         C = Ce;
-        lambda = fmaxf(0.1f * lambda, 1e-9f);
         ++n_acc;
-      } else {
-        lambda = fminf(10.0f * lambda, 1e6f);
       }
+      lambda = lm::damped(lambda, accept);
       continue;
     }
     if (e == 0) C0 = C = Ce;
@@ -522,39 +484,10 @@ __global__ void __launch_bounds__(kThreads, 2) mano_vertex_fit_kernel(const harp
       if (gout && tid < NX) gout[(size_t)t * NX + tid] = g;
       break;
     }
-    const float s = 1.0f / sqrtf(diag * (1.0f + lambda));             // Jacobi scaling: (A + lambda diag A) scaled has a unit diagonal
-    bool okw = __all(tid >= NX || (diag > 0.f && isfinite(s)));        // (wave 0's verdict counts)
-#pragma unroll 1
-    for (int j = 0; j < NX; ++j) {                                     // left-looking Cholesky, column j, on wave 0
-      if (wave == 0) {
-        const float sj = __shfl(s, j, 64);
-        float v = 0.f;
-        if (tid >= j && tid < NX) {
-          v = (tid == j) ? 1.0f : S.u.A[tid][j] * s * sj;
-#pragma unroll 8
-          for (int c = 0; c < j; ++c) v -= S.u.A[tid][c] * S.u.A[j][c];       // (eight pairs of LDS reads in flight, same order)
-        }
-        const float piv = __shfl(v, j, 64);
-        okw = okw && (piv > 0.f) && isfinite(piv);
-        const float ljj = sqrtf(piv);
-        if (tid >= j && tid < NX) S.u.A[tid][j] = (tid == j) ? ljj : v / ljj;
-      }
-      __syncthreads();
-    }
+    bool okw;                                                          // (wave 0's verdict counts)
+    const float s = lm::jacobi_scale<NX>(tid, diag, lambda, okw);
+    const float z = lm::solve<NX, LD, 1, 8>(S.u.A, tid, s, -g * s, wave == 0, okw);
     if (wave == 0) {
-      float b = (tid < NX) ? -g * s : 0.f, y = 0.f, z = 0.f;
-#pragma unroll 1
-      for (int j = 0; j < NX; ++j) {                                   // L y = b
-        const float yj = __shfl(b, j, 64) / S.u.A[j][j];
-        if (tid == j) y = yj;
-        if (tid > j && tid < NX) b -= S.u.A[tid][j] * yj;
-      }
-#pragma unroll 1
-      for (int j = NX - 1; j >= 0; --j) {                              // L^T z = y
-        const float zj = __shfl(y, j, 64) / S.u.A[j][j];
-        if (tid == j) z = zj;
-        if (tid < j) y -= S.u.A[j][lc] * zj;
-      }
       xn = (tid < NX) ? xl + z * s : 0.f;
       S.x[tid] = xn;
       if (tid == 0) S.flag = okw ? 1 : 0;

@@ -1,0 +1,161 @@
+"""The bits of the five batched Levenberg-Marquardt solvers (csrc/ik.hip, reproj_ik.hip, arm_ik.hip, vertex_fit.hip, arm_vertex_fit.hip;
+DESIGN.md §31): a SHA-256 of the raw bytes of every output tensor of one small deterministic batch per solver and per setting of
+solve_shape / solve_wrist.  Two builds of the library that print the same digests compute the same thing; the file touches nothing but
+harp_amd.ops and the synthetic hand and arm models, so it runs unchanged against an older checkout.
+
+Each batch: 4 problems from a start near the truth (the targets are the solver's own forward at iters = 0 of a true point), 3 iterations,
+every optional output; problem 3 has fewer used targets than the solver asks for (status -1), one unused target is NaN, and problem 2 of
+the reprojection solve starts with its used joints behind the camera (status -2).
+
+    python tools/dev/gpu_solver_bits.py [--out profiles/lm_core_bits_new.json]"""
+import argparse
+import hashlib
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
+
+T, ITERS = 4, 3
+CAM, FOCAL, S = (8.9, 0.01, -0.02), 2000.0, 448
+DEV = "cuda"
+
+
+def up(x):
+    return torch.as_tensor(np.ascontiguousarray(x, dtype=np.float32), device=DEV)
+
+
+def digest(t):
+    return hashlib.sha256(t.detach().cpu().contiguous().numpy().tobytes()).hexdigest()
+
+
+def record(res, name, out, inputs):
+    res[name + "/inputs"] = hashlib.sha256("".join(digest(t) for t in inputs if t is not None).encode()).hexdigest()
+    for f in out._fields:
+        t = getattr(out, f)
+        if t is not None:
+            res[f"{name}/{f}"] = digest(t)
+    res[name + "/status_values"] = out.status.cpu().tolist()
+
+
+def weights_with_few(n, few, rng):
+    """(T, n) weights in [0.5, 1.5], some zero; the last problem keeps only `few` targets"""
+    w = rng.uniform(0.5, 1.5, size=(T, n))
+    w[0, 1] = 0.0
+    w[T - 1, few:] = 0.0
+    return w
+
+
+def hand(res):
+    from harp_amd import ops, synth
+    from harp_amd.manopth.manolayer import ManoLayer
+    dm = ManoLayer(flat_hand_mean=False, use_pca=False, model=synth.make_mano_model(), device=DEV).device_model
+    rng = np.random.default_rng(31)
+    pose = np.concatenate([rng.normal(size=(T, 3)) * 0.8, rng.normal(size=(T, 45)) * 0.3], 1)
+    trans = rng.uniform(-0.05, 0.05, size=(T, 3))
+    betas = rng.normal(size=(T, 10)) * 0.5
+    x0, t0 = up(pose + rng.normal(size=pose.shape) * 0.05), up(trans + rng.normal(size=trans.shape) * 0.01)
+    prior = up(rng.normal(size=(T, 45)) * 0.1)
+
+    # 3-D keypoints
+    kp = ops.mano_ik(dm, up(betas), torch.zeros(T, 21, 3, device=DEV), up(pose), up(trans), iters=0, joints=True).joints / 1000.0
+    w = weights_with_few(21, 2, rng)
+    tg = kp.clone()
+    tg[0, 1] = float("nan")
+    args = (up(betas), tg.contiguous(), x0, t0)
+    kw = dict(weights=up(w), prior=prior, prior_weight=1e-4, iters=ITERS, joints=True, jac=True)
+    record(res, "mano_ik", ops.mano_ik(dm, *args, **kw), args + (kw["weights"], prior))
+
+    # image keypoints: the camera of csrc/reproj_ik.hip's header
+    j = kp.cpu().double().numpy()
+    Z = j[..., 2] + 2.0 * FOCAL / (S * CAM[0] + 1e-9)
+    rows = np.stack([S / 2 + FOCAL * (j[..., 0] + CAM[1]) / Z, S / 2 + FOCAL * (j[..., 1] + CAM[2]) / Z, j[..., 2] - j[:, :1, 2]], -1)
+    rows[0, 1] = np.nan
+    w = weights_with_few(21, 3, rng)
+    wz = rng.uniform(0.5, 1.5, size=(T, 21)) * 1e6
+    t0r = t0.clone()
+    t0r[2, 2] = -2.0                                       # every joint of problem 2 behind the camera at the input
+    args = (up(betas), up(rows), x0, t0r, up(CAM), FOCAL, S)
+    kw = dict(weights=up(w), depth_weights=up(wz), prior=prior, z_prior=up(trans[:, 2]), pose_prior_weight=1e-2, z_prior_weight=1.0,
+              iters=ITERS, proj=True, jac=True)
+    record(res, "mano_reproj_ik", ops.mano_reproj_ik(dm, *args, **kw),
+           (args[0], args[1], x0, t0r, args[4], kw["weights"], kw["depth_weights"], prior, kw["z_prior"]))
+
+    # mesh vertices
+    z = torch.zeros(T, 10, device=DEV)
+    verts = ops.mano_vertex_fit(dm, torch.zeros(T, 778, 3, device=DEV), up(pose), up(betas), up(trans), iters=0, verts=True).verts / 1000.0
+    w = weights_with_few(778, 20, rng)
+    tg = verts.clone()
+    tg[0, 1] = float("nan")
+    for solve_shape in (True, False):
+        b0 = z if solve_shape else up(betas)
+        args = (tg.contiguous(), x0, b0, t0)
+        kw = dict(weights=up(w), prior=prior, solve_shape=solve_shape, pose_prior_weight=1e-4, shape_prior_weight=1e-5, iters=ITERS,
+                  verts=True, jac=True, normal=True)
+        record(res, f"mano_vertex_fit/shape{int(solve_shape)}", ops.mano_vertex_fit(dm, *args, **kw), args + (kw["weights"], prior))
+
+
+def arm(res):
+    from harp_amd import ops, synth
+    from harp_amd.hand_models_harp.body_models import SMPLXARM
+    import harp_amd
+    model = synth.make_smplx_arm_model(seed=0)
+    corr = np.load(os.path.join(os.path.dirname(os.path.abspath(harp_amd.__file__)), "assets", "arm_corr.npz"))
+    dm = SMPLXARM(model, model["faces"], corr["mano_vert_from_arm"], device=DEV).device_model
+    rng = np.random.default_rng(37)
+    rows = np.concatenate([rng.normal(size=(T, 1, 3)) * 0.8, rng.normal(size=(T, 16, 3)) * 0.3], 1)
+    trans = rng.uniform(-0.3, 0.3, size=(T, 3))
+    betas = rng.normal(size=(T, 10)) * 0.5
+    x0, t0 = up(rows + rng.normal(size=rows.shape) * 0.05), up(trans + rng.normal(size=trans.shape) * 0.01)
+    prior, wprior = up(rng.normal(size=(T, 45)) * 0.1), up(rng.normal(size=(T, 3)) * 0.1)
+
+    # 3-D keypoints
+    n = int(dm.struct.n_joints_out)
+    kp = ops.arm_ik(dm, up(betas), torch.zeros(T, n, 3, device=DEV), up(rows), up(trans), iters=0, joints=True).joints / 1000.0
+    w = weights_with_few(n, 2, rng)
+    tg = kp.clone()
+    tg[0, 1] = float("nan")
+    for solve_wrist in (True, False):
+        args = (up(betas), tg.contiguous(), x0, t0)
+        kw = dict(weights=up(w), prior=prior, wrist_prior=wprior, solve_wrist=solve_wrist, pose_prior_weight=1e-4, wrist_prior_weight=1e-3,
+                  iters=ITERS, joints=True, jac=True)
+        record(res, f"arm_ik/wrist{int(solve_wrist)}", ops.arm_ik(dm, *args, **kw), args + (kw["weights"], prior, wprior))
+
+    # mesh vertices, all of the arm's
+    NV = int(model["v_template"].shape[0])
+    z = torch.zeros(T, 10, device=DEV)
+    verts = ops.arm_vertex_fit(dm, torch.zeros(T, NV, 3, device=DEV), up(rows), up(betas), up(trans), iters=0, verts=True).verts / 1000.0
+    w = weights_with_few(NV, 21, rng)
+    tg = verts.clone()
+    tg[0, 1] = float("nan")
+    for solve_shape in (True, False):
+        for solve_wrist in (True, False):
+            b0 = z if solve_shape else up(betas)
+            args = (tg.contiguous(), x0, b0, t0)
+            kw = dict(weights=up(w), prior=prior, solve_shape=solve_shape, solve_wrist=solve_wrist, pose_prior_weight=1e-4,
+                      wrist_prior_weight=1e-3, shape_prior_weight=1e-5, iters=ITERS, verts=True, jac=True, normal=True)
+            record(res, f"arm_vertex_fit/shape{int(solve_shape)}_wrist{int(solve_wrist)}", ops.arm_vertex_fit(dm, *args, **kw),
+                   args + (kw["weights"], prior))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    res = {}
+    hand(res)
+    arm(res)
+    torch.cuda.synchronize()
+    print(json.dumps(res, indent=1))
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(res, f, indent=1)
+            f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
