@@ -3,7 +3,8 @@ per frame, csrc/chain.hip + chain_body.h) and harp_mesh_chain_fwd_wide / _bwd_wi
 against the float64 reference tests/_chain_ref.py, on synthetic meshes that are each the smallest to reach one path the two production
 templates never reach: a wide part that owns no vertex, V % 4 != 0, E0 = 0, E0 > 3 * 1024, valence above kPre = 8, both il == 0 clamp
 branches, V = harp_mesh_chain_max_vertices() exactly; with a general camera rotation and a light exactly on the vertical through the
-centroid (look_at_rotation's degenerate branch).
+centroid (look_at_rotation's degenerate branch).  The two production templates are cases as well: `mano` (3093 vertices) and `arm` (the
+SMPL-X arm: 1026 + 3057 = 4083 vertices, 1021 per wide part, 0.8 m in front of the camera because it reaches 0.34 m from its centroid).
 
 Forward: stage by stage, each stage against the reference evaluated on the kernel's OWN float32 output of the stage before, so that every
 stage carries the bound derived for its stand-alone building block in tests/test_gpu_building_blocks.py (U = 2^-24).
@@ -137,14 +138,15 @@ def _mesh_tables(name):
                     t = (t + 1) % n
                 f.append([i, j, t])
         return np.array(f), P, True, False
-    assert name == "mano"
+    assert name in ("mano", "arm")
     from harp_amd import synth
-    tpl = synth.load_template("hand")
+    tpl = synth.load_template("hand" if name == "mano" else "arm")
     P = tpl["base_verts"].astype(np.float64) * 1000.0
     return tpl["faces0"], P - P.mean(0), True, True
 
 
 NJ_OF = dict(tri=1, hub=341)      # every other mesh: 21
+CAM_DIST = dict(arm=0.8)          # every other mesh: 0.5 m in front of the camera
 
 
 @functools.lru_cache(maxsize=None)
@@ -173,7 +175,8 @@ def _case(name, B):
         cam_R[0] = torch.diag(torch.tensor([-1.0, -1.0, 1.0]))
     centre = verts_mm.double().mean(1) * 1e-3
     # the mesh 0.5 m in front of the camera whatever the rotation: view z within 0.5 +- 0.15
-    cam_T = (torch.tensor([0.01, -0.02, 0.5], dtype=torch.float64) - torch.bmm(centre[:, None], cam_R.double())[:, 0]).float()
+    # (the arm reaches 0.34 m from its centroid: 0.8 m)
+    cam_T = (torch.tensor([0.01, -0.02, CAM_DIST.get(name, 0.5)], dtype=torch.float64) - torch.bmm(centre[:, None], cam_R.double())[:, 0]).float()
     light = (centre + torch.tensor([[0.4, -0.8, -0.3], [-0.5, 0.6, 0.4], [0.3, 0.7, -0.6]], dtype=torch.float64)[:B]).float()
     disp = (torch.randn(V, generator=g) * DISP_SCALE).float()
     i32 = lambda a: torch.from_numpy(np.ascontiguousarray(np.asarray(a, np.int32)))
@@ -203,11 +206,13 @@ def _assert_property(cs):
         assert (V0, E0) == (1054 + 4, 3033 + 5) and V == 4096 == _L()[0].harp_mesh_chain_max_vertices() and len(cs["comps"]) == 2
     elif name == "dense":
         assert V0 == 80 and E0 == 80 * 79 // 2 == 3160 and E0 > 3 * 1024 and V == 3240
+    elif name == "arm":
+        assert (V0, E0, V) == (1026, 3057, 4083) and per == 1021 and V % 4 == 3   # the SMPL-X arm template: the largest production mesh
     else:
         assert (V0, V) == (778, 3093)
 
 
-CASES = [(m, B) for m in ("tri", "five", "hub", "hub_raw", "clamp") for B in (1, 3)] + [("full", 1), ("dense", 1), ("mano", 1)]
+CASES = [(m, B) for m in ("tri", "five", "hub", "hub_raw", "clamp") for B in (1, 3)] + [("full", 1), ("dense", 1), ("mano", 1), ("arm", 1)]
 
 
 # ----------------------------------------------------------------------------------------------------------------------------------
