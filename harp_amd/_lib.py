@@ -338,6 +338,18 @@ class Layer(ctypes.Structure):
 SIGNATURES["harp_composite_layers_u8"] = (_i, [ctypes.POINTER(Layer), _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp])
 
 
+class LabelLayer(ctypes.Structure):
+    """mirror of `harp_label_layer` (include/harp_hip.h)"""
+    _fields_ = ([(n, _vp) for n in ("face_id", "zbuf", "face_label", "ndc", "faces", "verts_uvs", "faces_uvs")] +
+                [(n, ctypes.c_int32) for n in ("V", "F", "Vt", "flip_x", "reserved")])
+
+
+# what the frames show (csrc/annotate.hip)
+_llp = ctypes.POINTER(LabelLayer)
+SIGNATURES["harp_annotate_layers"] = (_i, [_llp, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp])
+SIGNATURES["harp_keypoint_visibility"] = (_i, [_vp, _vp, _vp, _i, _i, _f, _i, _i, _i, _llp, _i, _vp, _i, _vp, _f, _vp, _vp, _vp])
+
+
 class IkOptions(ctypes.Structure):
     """mirror of `harp_ik_options` (include/harp_hip.h)"""
     _fields_ = [("iters", _i), ("lambda0", _f), ("prior_weight", _f), ("betas_per_frame", _i)]

@@ -1303,6 +1303,152 @@ def composite_layers_u8(layers, ss=1, scene_depth=None, scene_rows=None, backgro
     return (out, own) if owner else out
 
 
+# ---- what the frames show (csrc/annotate.hip) ------------------------------------------------------------------------
+LayerLabels = collections.namedtuple("LayerLabels", "owner part depth face uv bbox")
+KeypointVisibility = collections.namedtuple("KeypointVisibility", "uvz vis")
+LABEL_OCCLUDER_SCENE = 255                             # vis[..., 1] of a joint hidden by the scene depth
+
+
+def _scene_depth_input(name, scene_depth, scene_rows, B, S):
+    """composite_layers_u8's checks of (scene_depth, scene_rows) -> (scene_depth, scene_rows, n_scene), contiguous"""
+    n_scene = 0
+    if scene_depth is not None:
+        if scene_depth.dtype != torch.float32 or scene_depth.dim() != 3 or tuple(scene_depth.shape[1:]) != (S, S) or scene_depth.shape[0] < 1:
+            raise TypeError(f"scene_depth must be float32 (n_scene, {S}, {S}), got {scene_depth.dtype} {tuple(scene_depth.shape)}")
+        n_scene = scene_depth.shape[0]
+        if scene_rows is None and n_scene not in (1, B):
+            raise ValueError(f"{n_scene} scene depths for {B} frames: pass scene_rows")
+        scene_depth = scene_depth.detach().contiguous()
+    if scene_rows is not None:
+        if scene_depth is None:
+            raise ValueError("scene_rows without a scene_depth")
+        if scene_rows.dtype != torch.int32 or tuple(scene_rows.shape) != (B,):
+            raise TypeError(f"scene_rows must be int32 ({B},), got {scene_rows.dtype} {tuple(scene_rows.shape)}")
+        scene_rows = scene_rows.contiguous()
+    return scene_depth, scene_rows, n_scene
+
+
+_LABEL_LAYER_KEYS = ("face_id", "zbuf", "face_label", "flip", "ndc", "faces", "verts_uvs", "faces_uvs")
+
+
+def _label_layers(name, layers, ss, with_uv, depth_only=False):
+    """layers: 1..4 dicts (face_id, zbuf, face_label, flip [, ndc, faces, verts_uvs, faces_uvs]) checked -> (the C array, the tensors
+    it points at, B, S)"""
+    layers = list(layers)
+    if not 1 <= len(layers) <= COMPOSITE_MAX_LAYERS or any(not isinstance(l, dict) or set(l) - set(_LABEL_LAYER_KEYS) for l in layers):
+        raise ValueError(f"{name} takes 1..{COMPOSITE_MAX_LAYERS} layers, dicts with keys of {_LABEL_LAYER_KEYS}, got {len(layers)}")
+    _playback_input(name, *[l.get(k) for l in layers for k in _LABEL_LAYER_KEYS if k != "flip"])
+    if not 1 <= ss <= RESOLVE_MAX_SS:
+        raise ValueError(f"ss in 1..{RESOLVE_MAX_SS}, got {ss}")
+    z0 = layers[0].get("zbuf")
+    if z0 is None or z0.dtype != torch.float32 or z0.dim() != 3 or z0.shape[1] != z0.shape[2] or z0.shape[1] % ss or z0.shape[0] < 1 or z0.shape[1] < 1:
+        raise TypeError(f"{name} takes float32 (B, S ss, S ss) depths, got {None if z0 is None else (z0.dtype, tuple(z0.shape))} with ss = {ss}")
+    B, S = z0.shape[0], z0.shape[1] // ss
+    keep, arr = [], (_lib.LabelLayer * len(layers))()
+    c = lambda t: t.detach().contiguous()               # noqa: E731
+    for i, l in enumerate(layers):
+        z = l.get("zbuf")
+        if z is None or z.dtype != torch.float32:
+            raise TypeError(f"layer {i}: zbuf must be float32, got {None if z is None else z.dtype}")
+        if tuple(z.shape) != tuple(z0.shape):
+            raise ValueError(f"layer {i}: zbuf {tuple(z.shape)} must be {tuple(z0.shape)}")
+        a = arr[i]
+        ts = [c(z)]
+        a.zbuf, a.flip_x, a.reserved = _lib.ptr(ts[0]), int(bool(l.get("flip", False))), 0
+        if not depth_only:
+            fid, lab = l.get("face_id"), l.get("face_label")
+            if fid is None or fid.dtype != torch.int32 or lab is None or lab.dtype != torch.uint8:
+                raise TypeError(f"layer {i}: face_id must be int32 and face_label uint8")
+            if tuple(fid.shape) != tuple(z0.shape) or lab.dim() != 1 or lab.shape[0] < 1:
+                raise ValueError(f"layer {i}: face_id {tuple(fid.shape)} must be {tuple(z0.shape)} and face_label (F,), got {tuple(lab.shape)}")
+            ts += [c(fid), c(lab)]
+            a.face_id, a.face_label, a.F = _lib.ptr(ts[1]), _lib.ptr(ts[2]), lab.shape[0]
+            if with_uv:
+                ndc, faces, vuv, fuv = (l.get(k) for k in ("ndc", "faces", "verts_uvs", "faces_uvs"))
+                if any(t is None for t in (ndc, faces, vuv, fuv)):
+                    raise ValueError(f"layer {i}: the uv output needs ndc, faces, verts_uvs and faces_uvs")
+                if ndc.dtype != torch.float32 or vuv.dtype != torch.float32 or faces.dtype != torch.int32 or fuv.dtype != torch.int32:
+                    raise TypeError(f"layer {i}: ndc and verts_uvs must be float32, faces and faces_uvs int32")
+                F = lab.shape[0]
+                if (ndc.dim() != 3 or ndc.shape[0] != B or ndc.shape[1] < 1 or ndc.shape[2] != 3 or tuple(faces.shape) != (F, 3)
+                        or tuple(fuv.shape) != (F, 3) or vuv.dim() != 2 or vuv.shape[0] < 1 or vuv.shape[1] != 2):
+                    raise ValueError(f"layer {i}: ndc ({B}, V, 3), faces ({F}, 3), verts_uvs (Vt, 2), faces_uvs ({F}, 3), got {tuple(ndc.shape)}, "
+                                     f"{tuple(faces.shape)}, {tuple(vuv.shape)}, {tuple(fuv.shape)}")
+                ts += [c(ndc), c(faces), c(vuv), c(fuv)]
+                a.ndc, a.faces, a.verts_uvs, a.faces_uvs = (_lib.ptr(t) for t in ts[3:])
+                a.V, a.Vt = ndc.shape[1], vuv.shape[0]
+        keep.append(ts)
+    return arr, keep, B, S
+
+
+def annotate_layers(layers, ss=1, scene_depth=None, scene_rows=None, owner=True, part=True, depth=True, face=True, uv=False, bbox=True):
+    """What the frame of composite_layers_u8 on the same layers SHOWS (csrc/annotate.hip: harp_annotate_layers, whose contract
+    include/harp_hip.h states), forward only.  layers: 1..4 dicts of face_id (B, S ss, S ss) int32 and zbuf (B, S ss, S ss) float32 as the
+    camera-view rasteriser leaves them, face_label (F,) uint8 (playback.labels.face_part_labels), flip, and for uv=True ndc (B,V,3)
+    float32, faces (F,3) int32, verts_uvs (Vt,2) float32, faces_uvs (F,3) int32.  scene_depth, scene_rows: as composite_layers_u8.
+    Returns LayerLabels(owner (B,S,S) uint8 — bit for bit the composite's —, part (B,S,S) uint8, depth (B,S,S) float32 view depth, face
+    (B,S,S) int32, uv (B,S,S,2) float32, bbox (B, len(layers), 4) int32 as (xmin, ymin, xmax, ymax), -1 for a layer that owns no pixel),
+    None for an output that was not asked for."""
+    ss, want_uv = int(ss), bool(uv)
+    arr, keep, B, S = _label_layers("annotate_layers", layers, ss, want_uv)
+    _playback_input("annotate_layers", keep[0][0], scene_depth, scene_rows)
+    scene_depth, scene_rows, n_scene = _scene_depth_input("annotate_layers", scene_depth, scene_rows, B, S)
+    if not any((owner, part, depth, face, uv, bbox)):
+        raise ValueError("annotate_layers: no output asked for")
+    dev = keep[0][0].device
+    new = lambda on, shape, dt: torch.empty(*shape, dtype=dt, device=dev) if on else None      # noqa: E731
+    o = LayerLabels(new(owner, (B, S, S), torch.uint8), new(part, (B, S, S), torch.uint8), new(depth, (B, S, S), torch.float32),
+                    new(face, (B, S, S), torch.int32), new(uv, (B, S, S, 2), torch.float32),
+                    torch.zeros(B, len(keep), 4, dtype=torch.int32, device=dev) if bbox else None)
+    with torch.cuda.device(dev):
+        rc = _lib.lib().harp_annotate_layers(arr, len(keep), B, S, ss, _lib.ptr(scene_depth), n_scene, _lib.ptr(scene_rows), *[_lib.ptr(t) for t in o],
+                                             _lib.stream())
+    _lib.check(rc, "harp_annotate_layers")
+    return o._replace(bbox=bbox_from_extents(o.bbox, S)) if bbox else o
+
+
+def bbox_from_extents(ext, S):
+    """harp_annotate_layers' accumulated (S - xmin, S - ymin, xmax + 1, ymax + 1), all zeros for nothing -> (xmin, ymin, xmax, ymax), -1
+    for nothing (device arithmetic, no synchronisation)"""
+    box = torch.stack([S - ext[..., 0], S - ext[..., 1], ext[..., 2] - 1, ext[..., 3] - 1], -1)
+    return torch.where((ext[..., 2:3] > 0).expand_as(box), box, torch.full_like(box, -1))
+
+
+def keypoint_visibility(joints, cam_R, cam_T, focal, S, layers, self_layer=0, ss=1, scene_depth=None, scene_rows=None, tol=0.02):
+    """The joints of layer `self_layer` in the image, and whether each is seen (csrc/annotate.hip: harp_keypoint_visibility, whose contract
+    include/harp_hip.h states), forward only.  joints (B,NJ,3) float32 metres, cam_R (B,9), cam_T (B,3) float32 as the fused front leaves
+    them; focal and S of the output image; layers: 1..4 dicts of zbuf (B, S ss, S ss) float32 and flip (other keys are ignored);
+    scene_depth, scene_rows: as composite_layers_u8; tol metres: a joint lies under its own skin, so it counts as visible when the nearest
+    surface is no nearer than Z - tol.  Returns KeypointVisibility(uvz (B,NJ,3) float32 = (u, v, view depth), vis (B,NJ,2) uint8 =
+    (0 not in the image | 1 hidden | 2 visible, what hides it: 0 nothing, 1 + the layer, 255 the scene depth))."""
+    import math
+    ss, S, self_layer, focal, tol = int(ss), int(S), int(self_layer), float(focal), float(tol)
+    _playback_input("keypoint_visibility", joints, cam_R, cam_T, scene_depth, scene_rows)
+    arr, keep, B, S_l = _label_layers("keypoint_visibility", layers, ss, False, depth_only=True)
+    _playback_input("keypoint_visibility", joints, keep[0][0])
+    if any(t.dtype != torch.float32 for t in (joints, cam_R, cam_T)):
+        raise TypeError("keypoint_visibility takes float32 joints, cam_R and cam_T")
+    if joints.dim() != 3 or joints.shape[0] != B or joints.shape[1] < 1 or joints.shape[2] != 3 or tuple(cam_R.shape) != (B, 9) or tuple(cam_T.shape) != (B, 3):
+        raise ValueError(f"keypoint_visibility takes joints ({B}, NJ, 3), cam_R ({B}, 9) and cam_T ({B}, 3), got {tuple(joints.shape)}, "
+                         f"{tuple(cam_R.shape)}, {tuple(cam_T.shape)}")
+    if S != S_l:
+        raise ValueError(f"the layers are {S_l * ss} wide: S = {S_l} at ss = {ss}, got S = {S}")
+    if not 0 <= self_layer < len(keep):
+        raise ValueError(f"self_layer in 0..{len(keep) - 1}, got {self_layer}")
+    if not (focal > 0 and math.isfinite(focal)) or not (tol >= 0 and math.isfinite(tol)):
+        raise ValueError(f"focal must be positive and tol non-negative, both finite; got {focal}, {tol}")
+    scene_depth, scene_rows, n_scene = _scene_depth_input("keypoint_visibility", scene_depth, scene_rows, B, S)
+    NJ = joints.shape[1]
+    j, R, T = joints.detach().contiguous(), cam_R.detach().contiguous(), cam_T.detach().contiguous()
+    o = KeypointVisibility(torch.empty(B, NJ, 3, dtype=torch.float32, device=j.device), torch.empty(B, NJ, 2, dtype=torch.uint8, device=j.device))
+    with torch.cuda.device(j.device):
+        rc = _lib.lib().harp_keypoint_visibility(_lib.ptr(j), _lib.ptr(R), _lib.ptr(T), B, NJ, focal, S, ss, self_layer, arr, len(keep),
+                                                 _lib.ptr(scene_depth), n_scene, _lib.ptr(scene_rows), tol, _lib.ptr(o.uvz), _lib.ptr(o.vis),
+                                                 _lib.stream())
+    _lib.check(rc, "harp_keypoint_visibility")
+    return o
+
+
 # ---- batched MANO inverse kinematics (csrc/ik.hip, DESIGN.md §24) -----------------------------------------------------------------
 IkResult = collections.namedtuple("IkResult", "pose48 trans cost status joints jac")
 

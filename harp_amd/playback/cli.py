@@ -3,7 +3,7 @@ import numpy as np
 
 from .. import ops
 from .motion import Motion, motion_jitter
-from .player import AvatarPlayer, ScenePlayer
+from .player import LABEL_TOL, AvatarPlayer, ScenePlayer
 
 
 def parse_args(argv=None):
@@ -38,6 +38,12 @@ def parse_args(argv=None):
     ap.add_argument("--scene-depth", default=None, help="directory of .npy float32 (img_size, img_size) depth maps in metres or 16-bit PNGs in "
                                                         "millimetres, 0 = no measurement (cycled): what is nearer hides the avatars")
     ap.add_argument("--masks", action="store_true", help="also write mask_%%04d.png: 0 background, 1 + the avatar that owns the pixel")
+    ap.add_argument("--labels", action="store_true",
+                    help="also write part_%%04d.png (the part of the hand), depth_%%04d.png (16-bit millimetres, what --scene-depth reads), "
+                         "iuv_%%04d.png (part, u, v) and keypoints.npz per avatar (pixels, visibility, occluder, box: what --keypoints2d reads)")
+    ap.add_argument("--label-tol", type=float, default=LABEL_TOL, metavar="M",
+                    help="with --labels: a joint counts as visible when the nearest surface is no nearer than its depth minus M metres "
+                         "(a joint lies under the skin)")
     ap.add_argument("--smooth", type=float, default=None, metavar="SIGMA",
                     help="filter the loaded or solved motion with a Gaussian window of SIGMA frames before --fps-scale (Motion.smooth); prints the "
                          "joint jitter before and after")
@@ -50,6 +56,8 @@ def parse_args(argv=None):
         v = getattr(args, name)
         if v is not None and not v > 0:
             raise SystemExit(f"--{name.replace('_', '-')} must be positive")
+    if not args.label_tol >= 0:
+        raise SystemExit("--label-tol must not be negative")
     if args.smooth_trim is not None and args.smooth is None:
         raise SystemExit("--smooth-trim needs --smooth")
     if args.smooth_keypoints is not None and args.keypoints is None:
@@ -117,8 +125,8 @@ def main(argv=None):
     fmt = "png" if args.alpha else "jpg"
     if not (args.flip or args.also or args.scene_depth or args.masks):
         configs, params, hand_layer, motion = load(args.config, args.motion, args.keypoints, args.vertices, args.keypoints2d)
-        player = AvatarPlayer(configs, params, hand_layer, batch_size=args.batch_size, ss=args.ss, device=args.device)
-        paths = player.play(motion, args.out, backgrounds=args.background, fmt=fmt, alpha=args.alpha)
+        player = AvatarPlayer(configs, params, hand_layer, batch_size=args.batch_size, ss=args.ss, device=args.device, keep_depth=args.labels)
+        paths = player.play(motion, args.out, backgrounds=args.background, fmt=fmt, alpha=args.alpha, labels=args.labels, label_tol=args.label_tol)
     else:
         specs = [(args.config, args.motion, args.flip, args.keypoints, args.vertices, args.keypoints2d)]
         for spec in args.also:
@@ -132,6 +140,7 @@ def main(argv=None):
             players.append(AvatarPlayer(configs, params, hand_layer, batch_size=args.batch_size, ss=args.ss, device=args.device, keep_depth=True))
             motions.append(motion)
         scene = ScenePlayer(players, flip=[spec[2] for spec in specs])
-        paths = scene.play(motions, args.out, backgrounds=args.background, scene_depth=args.scene_depth, fmt=fmt, alpha=args.alpha, masks=args.masks)
+        paths = scene.play(motions, args.out, backgrounds=args.background, scene_depth=args.scene_depth, fmt=fmt, alpha=args.alpha, masks=args.masks,
+                           labels=args.labels, label_tol=args.label_tol)
     print(f"wrote {len(paths)} frames to {args.out}")
     return paths

@@ -1,6 +1,7 @@
 """The two forward-only renderers on one base.  `_Player` owns what a render call and a play loop need whatever is drawn:
 the index stage, the copies of the caller's tensors, the output buffer, the graphs and the double-buffered way to disk.  `AvatarPlayer`
 adds one avatar's launches and the resolve (§22), `ScenePlayer` several avatars and the composite (§23)."""
+import collections
 import ctypes
 import os
 
@@ -11,6 +12,13 @@ from .. import _lib, ops
 from .keypoints import checked
 
 BG_WHITE = (1.0, 1.0, 1.0)                             # the reference's BlendParams background (renderer_helper.py:49)
+LABEL_TOL = 0.02                                       # metres: how far under the nearest surface a joint still counts as visible
+# what annotate() returns: device tensors over the rows asked for, views of the player's buffers that the next annotate
+# overwrites (bbox is computed from one); None for a map that was not asked for.  owner, part (n,S,S) uint8; depth (n,S,S) float32 view
+# depth in metres, 0 = empty; face (n,S,S) int32, -1 = empty; uv (n,S,S,2) float32; bbox (xmin, ymin, xmax, ymax) int32, -1 = nothing:
+# (n,4) of an AvatarPlayer, (n,P,4) of a scene of P players; uvz (n,NJ,3) float32 = (u, v, view depth) and vis (n,NJ,2) uint8 =
+# (0 not in the image | 1 hidden | 2 visible, the occluder: 0 nothing, 1 + the player, 255 the scene depth) — of a scene, one per player
+Annotation = collections.namedtuple("Annotation", "owner part depth face uv bbox uvz vis")
 
 
 def _ck(rc, what):
@@ -235,6 +243,8 @@ class AvatarPlayer(_Player):
                                                 _lib.ptr(self.nmap_n), _lib.ptr(self.texnm), _lib.stream()), "normalize3_pack")
         self._cap = 0
         self.tab = self.tables = None
+        self._skin_weights = np.asarray(hand_layer._model_np["weights"])      # (V0, NJ): the part table is made from it on first use
+        self._face_label, self._labels_wanted, self.lab, self.kp = None, False, None, None
 
     def _alloc_scratch(self):
         """per-batch buffers for B frames at S * ss: what FitEngine keeps for a step's forward half, nothing of its backward"""
@@ -324,9 +334,9 @@ class AvatarPlayer(_Player):
         a.rgb, a.texnm = _lib.ptr(s["rgb"]), _lib.ptr(self.texnm)
         return a
 
-    def _render_batch(self, fid):
+    def _render_batch(self, fid, shade=True):
         """front, rasterisers and shader of one batch of B frames, in order on the current stream: s["rgb"], s["face_c"] (and s["z_c"]
-        with keep_depth) at S * ss, everything in front of the resolve"""
+        with keep_depth) at S * ss, everything in front of the resolve; shade=False stops before the shader (labels need no colour)"""
         L, s, p, tp, st = _lib.lib(), self.s, _lib.ptr, self.topo, _lib.stream()
         B, V, F, Sh = self.B, tp.V, tp.F, self.Sh
         z_c = p(s["z_c"]) if self.keep_depth else None
@@ -340,12 +350,62 @@ class AvatarPlayer(_Player):
                 "raster_light")
         else:                                            # one view: the rasteriser's own set-up
             _ck(L.harp_rasterize_fwd(p(s["ndc_c"]), p(tp.faces), B, V, F, Sh, 0, 0.0, 1.0, p(s["ws_c"]), p(s["face_c"]), z_c, None, st), "raster_cam")
-        _ck(L.harp_shade_fwd(ctypes.byref(self._shade_struct()), st), "shade_fwd")
+        if shade:
+            _ck(L.harp_shade_fwd(ctypes.byref(self._shade_struct()), st), "shade_fwd")
 
-    def _enqueue(self, n_pad, channels, with_bg):
-        """per batch of B frames: its launches up to the shader, then the resolve"""
+    # ---- labels ---------------------------------------------------------------------------------------------------
+    def _part_table(self):
+        """the part of every face on the device, made on first use (host integer work, once per player)"""
+        if self._face_label is None:
+            from .labels import face_part_labels
+            tab = face_part_labels(self._skin_weights, self.topo.faces0.cpu().numpy(), self.topo.V0)
+            if tab.shape[0] != self.topo.F:
+                raise RuntimeError(f"{tab.shape[0]} part labels for {self.topo.F} faces")
+            self._face_label = torch.from_numpy(tab).to(self.dev)
+        return self._face_label
+
+    def _label_layer(self, flip, uv):
+        """this player's harp_label_layer over its batch buffers (annotate() has made the part table)"""
+        s, p, tp = self.s, _lib.ptr, self.topo
+        a = _lib.LabelLayer(face_id=p(s["face_c"]), zbuf=p(s["z_c"]), face_label=p(self._face_label), F=tp.F, flip_x=int(flip), reserved=0)
+        if uv:
+            a.ndc, a.faces, a.verts_uvs, a.faces_uvs, a.V, a.Vt = p(s["ndc_c"]), p(tp.faces), p(tp.verts_uvs), p(tp.faces_uvs), tp.V, tp.verts_uvs.shape[0]
+        return a
+
+    def _keypoint_buffers(self, n):
+        """(uvz, vis) for n frames of this player's joints; whoever runs the launches owns them (the player itself, or its scene)"""
+        return dict(uvz=torch.empty(n, self.n_joints, 3, dtype=torch.float32, device=self.dev),
+                    vis=torch.empty(n, self.n_joints, 2, dtype=torch.uint8, device=self.dev))
+
+    def _enqueue_keypoints(self, kp, lo, layers, n_layers, self_layer, scene, tol):
+        """harp_keypoint_visibility of this player's batch into rows lo.. of the buffers kp; scene: _staged_args of the scene depth"""
+        s, p = self.s, _lib.ptr
+        _ck(_lib.lib().harp_keypoint_visibility(p(s["joints_m"]), p(s["cam_R"]), p(s["cam_T"]), self.B, self.n_joints, self.focal_h / self.ss, self.S,
+                                                self.ss, self_layer, layers, n_layers, *scene, tol, kp["uvz"][lo:].data_ptr(),
+                                                kp["vis"][lo:].data_ptr(), _lib.stream()), "keypoint_visibility")
+
+    def _grow(self, n_pad, used):
+        grew = n_pad > self._n_cap
+        super()._grow(n_pad, used)
+        if grew:
+            self.lab = None
+        if self._labels_wanted and self.lab is None:
+            self.lab = _label_buffers(self._n_cap, self.S, 1, self.dev)
+            self.kp = self._keypoint_buffers(self._n_cap)
+
+    def _enqueue(self, n_pad, channels, with_bg, labels=None):
+        """per batch of B frames: its launches up to the shader, then the resolve; with labels = (part, depth, uv, keypoints, tol) the
+        launches up to the rasterisers, then the labels of the batch"""
         L, s, p = _lib.lib(), self.s, _lib.ptr
         per = self.S * self.S * channels
+        if labels is not None:
+            layer = (_lib.LabelLayer * 1)(self._label_layer(False, labels[2]))
+            for lo in range(0, n_pad, self.B):
+                self._render_batch(self.idx_dev[0, lo:lo + self.B], shade=False)
+                _enqueue_labels(self.lab, lo, layer, 1, self.B, self.S, self.ss, (None, 0, None), labels)
+                if labels[3]:
+                    self._enqueue_keypoints(self.kp, lo, layer, 1, 0, (None, 0, None), labels[4])
+            return
         for lo in range(0, n_pad, self.B):
             self._render_batch(self.idx_dev[0, lo:lo + self.B])
             _ck(L.harp_resolve_u8(p(s["rgb"]), p(s["face_c"]), self.B, self.S, self.ss, *self._staged_args(0, lo, with_bg), p(self.bg_color_dev),
@@ -362,17 +422,39 @@ class AvatarPlayer(_Player):
             raise RuntimeError("load_motion() first")
         return self._render(rows, alpha, [(background, bg_rows)])[0]
 
+    @torch.no_grad()
+    def annotate(self, rows, parts=True, depth=True, uv=False, keypoints=True, tol=LABEL_TOL):
+        """What the frames `rows` of the loaded motion show -> Annotation (above) of device tensors: always owner (1 where the avatar
+        is), face and bbox; part with parts=True, depth with depth=True, uv with uv=True, uvz and vis with keypoints=True.  Needs
+        keep_depth=True.  The batch's front and rasterisers run as in render (the shader does not: labels need no colour), then
+        harp_annotate_layers and harp_keypoint_visibility, under the same graph path.  tol: a joint lies INSIDE the hand, a finger's
+        radius or half the palm's thickness under the skin, so a joint counts as visible when the nearest surface at its pixel is no
+        nearer than its own depth minus tol metres; 0.02 is that convention, not a tuned value."""
+        if not self.keep_depth:
+            raise ValueError("annotate needs a player built with keep_depth=True")
+        if self.tables is None:
+            raise RuntimeError("load_motion() first")
+        labels = _label_flags(parts, depth, uv, keypoints, tol)
+        self._part_table()
+        self._labels_wanted = True
+        n = self._render(rows, False, [(None, None)], labels)[1]
+        return _annotation(self.lab, n, self.S, labels, self.kp["uvz"][:n] if labels[3] else None, self.kp["vis"][:n] if labels[3] else None, one=True)
+
     # ---- a whole motion to files ------------------------------------------------------------------------------------------------
-    def play(self, motion, out_dir, backgrounds=None, fmt="jpg", alpha=False):
+    def play(self, motion, out_dir, backgrounds=None, fmt="jpg", alpha=False, labels=False, label_tol=LABEL_TOL):
         """load_motion(motion), render it batch by batch and write out_dir/%04d.<fmt> (fmt "jpg" or "png"; alpha=True needs "png" and
         writes RGBA).  backgrounds: None, a (N,S,S,3) uint8 tensor or a directory of images of that size (sorted by name); frame i is
         composited over background i mod N.  The frames leave through two pinned host buffers, one per batch in flight, and are encoded on
-        a thread pool while the next batch renders.  Returns the list of paths."""
+        a thread pool while the next batch renders.  labels=True (needs keep_depth=True) also writes part_%04d.png, depth_%04d.png,
+        iuv_%04d.png and keypoints.npz (write_labels).  Returns the list of paths."""
         def prepare():
             self.load_motion(motion)
             bgs = load_backgrounds(backgrounds, self.S, self.dev)
             return lambda rows: self.render(rows, bgs, None if bgs is None else rows % bgs.shape[0], alpha)
-        return self._play(out_dir, fmt, alpha, prepare)
+        paths = self._play(out_dir, fmt, alpha, prepare)
+        if labels:
+            write_labels(out_dir, self.T, self.B, lambda rows: self.annotate(rows, uv=True, tol=label_tol), [part_names_of(self)])
+        return paths
 
 
 class ScenePlayer(_Player):
@@ -402,6 +484,7 @@ class ScenePlayer(_Player):
         self.players = players
         super().__init__(p0.dev, p0.S, p0.ss, p0.B, all(p.use_graph for p in players),
                          (("background", (p0.S, p0.S, 3), torch.uint8), ("scene_depth", (p0.S, p0.S), torch.float32)))
+        self._labels_wanted, self.lab, self.kp = False, None, None
 
     def load_motions(self, motions):
         """one motion per player, of equal length: scene row i is row i of every motion (AvatarPlayer.load_motion each)"""
@@ -420,12 +503,29 @@ class ScenePlayer(_Player):
     def _grow(self, n_pad, used):
         if n_pad > self._n_cap:
             self.owner = torch.empty(n_pad, self.S, self.S, dtype=torch.uint8, device=self.dev)
+            self.lab = None
         super()._grow(n_pad, used)
+        if self._labels_wanted and self.lab is None:
+            self.lab = _label_buffers(self._n_cap, self.S, len(self.players), self.dev)
+            self.kp = [pl._keypoint_buffers(self._n_cap) for pl in self.players]
 
-    def _enqueue(self, n_pad, channels, with_bg, with_depth, with_owner):
-        """per batch: every player's front / rasterisers / shader, then one composite"""
+    def _enqueue(self, n_pad, channels, with_bg, with_depth, with_owner, labels=None):
+        """per batch: every player's front / rasterisers / shader, then one composite; with labels = (part, depth, uv, keypoints, tol)
+        every player's front / rasterisers, then the labels of the batch and every player's keypoints"""
         L, p, B = _lib.lib(), _lib.ptr, self.B
         per = self.S * self.S
+        if labels is not None:
+            P = len(self.players)
+            layers = (_lib.LabelLayer * P)(*[pl._label_layer(f, labels[2]) for pl, f in zip(self.players, self.flip)])
+            for lo in range(0, n_pad, B):
+                scene = self._staged_args(1, lo, with_depth)
+                for pl in self.players:
+                    pl._render_batch(self.idx_dev[0, lo:lo + B], shade=False)
+                _enqueue_labels(self.lab, lo, layers, P, B, self.S, self.ss, scene, labels)
+                if labels[3]:
+                    for k, pl in enumerate(self.players):
+                        pl._enqueue_keypoints(self.kp[k], lo, layers, P, k, scene, labels[4])
+            return
         layers = (_lib.Layer * len(self.players))(*[_lib.Layer(p(pl.s["rgb"]), p(pl.s["z_c"]), int(f), 0) for pl, f in zip(self.players, self.flip)])
         for lo in range(0, n_pad, B):
             for pl in self.players:
@@ -449,17 +549,110 @@ class ScenePlayer(_Player):
         frames, n = self._render(rows, alpha, [(background, bg_rows), (scene_depth, depth_rows)], bool(owner))
         return (frames, self.owner[:n]) if owner else frames
 
-    def play(self, motions, out_dir, backgrounds=None, scene_depth=None, fmt="jpg", alpha=False, masks=False):
+    @torch.no_grad()
+    def annotate(self, rows, parts=True, depth=True, uv=False, keypoints=True, tol=LABEL_TOL, scene_depth=None, depth_rows=None):
+        """What the scene's frames `rows` show -> Annotation, as AvatarPlayer.annotate: owner is bit for bit render(owner=True)'s, bbox is
+        (n, players, 4), and uvz and vis are tuples with one tensor per player (its own joints; the occluder 1 + k is player k, 255 the
+        scene depth).  scene_depth, depth_rows: as render."""
+        if self.T < 1 or any(p.tables is None for p in self.players):
+            raise RuntimeError("load_motions() first")
+        labels = _label_flags(parts, depth, uv, keypoints, tol)
+        for pl in self.players:
+            pl._part_table()
+        self._labels_wanted = True
+        n = self._render(rows, False, [(None, None), (scene_depth, depth_rows)], False, labels)[1]
+        kp = lambda key: tuple(b[key][:n] for b in self.kp) if labels[3] else None      # noqa: E731
+        return _annotation(self.lab, n, self.S, labels, kp("uvz"), kp("vis"), one=False)
+
+    def play(self, motions, out_dir, backgrounds=None, scene_depth=None, fmt="jpg", alpha=False, masks=False, labels=False, label_tol=LABEL_TOL):
         """load_motions(motions), render the scene batch by batch and write out_dir/%04d.<fmt> as AvatarPlayer.play does; with masks=True
         also out_dir/mask_%04d.png, the owner map (8-bit grey: 0 background, 1 + the player).  backgrounds: as AvatarPlayer.play;
-        scene_depth: None, a float32 (N,S,S) tensor or a directory (load_scene_depth), frame i tested against depth i mod N.  Returns the
-        list of the frames' paths."""
+        scene_depth: None, a float32 (N,S,S) tensor or a directory (load_scene_depth), frame i tested against depth i mod N.  labels=True
+        also writes the label files (write_labels), one keypoints_<k>.npz per player k when there are several.  Returns the list of the
+        frames' paths."""
         def prepare():
             self.load_motions(motions)
             bgs, depth = load_backgrounds(backgrounds, self.S, self.dev), load_scene_depth(scene_depth, self.S, self.dev)
+            prepare.depth = depth
             return lambda rows: self.render(rows, bgs, None if bgs is None else rows % bgs.shape[0], alpha, depth,
                                             None if depth is None else rows % depth.shape[0], owner=masks)
-        return self._play(out_dir, fmt, alpha, prepare, masks)
+        paths = self._play(out_dir, fmt, alpha, prepare, masks)
+        if labels:
+            d = prepare.depth
+            write_labels(out_dir, self.T, self.B, lambda rows: self.annotate(rows, uv=True, tol=label_tol, scene_depth=d,
+                                                                             depth_rows=None if d is None else rows % d.shape[0]),
+                         [part_names_of(pl) for pl in self.players])
+        return paths
+
+
+def part_names_of(player):
+    """the label names of an AvatarPlayer's model, index = label (labels.part_names of its hand layer)"""
+    from .labels import joint_part_names
+    return joint_part_names(player._skin_weights.shape[1])
+
+
+def _label_flags(parts, depth, uv, keypoints, tol):
+    import math
+    tol = float(tol)
+    if not (tol >= 0 and math.isfinite(tol)):
+        raise ValueError(f"tol must be non-negative and finite, got {tol}")
+    return (bool(parts), bool(depth), bool(uv), bool(keypoints), tol)
+
+
+def _label_buffers(n, S, P, dev):
+    new = lambda dt, *shape: torch.empty(n, *shape, dtype=dt, device=dev)      # noqa: E731
+    return dict(owner=new(torch.uint8, S, S), part=new(torch.uint8, S, S), depth=new(torch.float32, S, S), face=new(torch.int32, S, S),
+                uv=new(torch.float32, S, S, 2), bbox=new(torch.int32, P, 4))
+
+
+def _enqueue_labels(lab, lo, layers, n_layers, B, S, ss, scene, labels):
+    """the clear of the batch's boxes and harp_annotate_layers into rows lo.. of the label buffers, on the current stream"""
+    at = lambda k, on=True: lab[k][lo:].data_ptr() if on else None      # noqa: E731
+    lab["bbox"][lo:lo + B].zero_()                       # (inside the captured sequence: the boxes are accumulated by atomic max)
+    _ck(_lib.lib().harp_annotate_layers(layers, n_layers, B, S, ss, *scene, at("owner"), at("part", labels[0]), at("depth", labels[1]), at("face"),
+                                        at("uv", labels[2]), at("bbox"), _lib.stream()), "annotate_layers")
+
+
+def _annotation(lab, n, S, labels, uvz, vis, one):
+    bbox = ops.bbox_from_extents(lab["bbox"][:n], S)
+    view = lambda k, on=True: lab[k][:n] if on else None      # noqa: E731
+    return Annotation(view("owner"), view("part", labels[0]), view("depth", labels[1]), view("face"), view("uv", labels[2]),
+                      bbox[:, 0] if one else bbox, uvz, vis)
+
+
+def write_labels(out_dir, T, B, annotate, names):
+    """The label files of a played motion beside its frames, batch by batch: part_%04d.png (8-bit grey, the part), depth_%04d.png (16-bit,
+    millimetres (int)(1000 z + 0.5) clamped to 65535, 0 = empty: what load_scene_depth reads), iuv_%04d.png (8-bit RGB (part,
+    floor(255 u + 0.5), floor(255 v + 0.5)), the DensePose convention) and per player keypoints.npz (keypoints_<k>.npz when there are
+    several): keypoints (T,NJ,2) pixels, weights (T,NJ) = 1 for a visible joint and 0 otherwise, depth (T,NJ) = Z_k - Z_0 metres, z (T,NJ),
+    visible, occluder (T,NJ) uint8, bbox (T,4) = (xmin, ymin, xmax, ymax) or -1, part_names.  The file of a MANO hand is what
+    --keypoints2d reads.  annotate(rows) -> Annotation with every map; names: one list of part names per player."""
+    from concurrent.futures import ThreadPoolExecutor
+    from ..utils.data_util import default_workers
+    P = len(names)
+    kp = [dict(uvz=[], vis=[], bbox=[]) for _ in range(P)]
+    pool, pending = ThreadPoolExecutor(max(1, min(8, default_workers()))), []
+    for lo in range(0, T, B):
+        rows = np.arange(lo, min(T, lo + B))
+        a = annotate(rows)
+        part, depth, uv = a.part.cpu().numpy(), a.depth.cpu().numpy(), a.uv.cpu().numpy()
+        single = torch.is_tensor(a.uvz)                   # an AvatarPlayer's: one player, bbox (n,4)
+        uvz, vis, bbox = ((a.uvz,), (a.vis,), a.bbox[:, None]) if single else (a.uvz, a.vis, a.bbox)
+        for k in range(P):
+            kp[k]["uvz"].append(uvz[k].cpu().numpy()); kp[k]["vis"].append(vis[k].cpu().numpy()); kp[k]["bbox"].append(bbox[:, k].cpu().numpy())
+        mm = np.clip((1000.0 * depth.astype(np.float64) + 0.5).astype(np.int64), 0, 65535).astype(np.uint16)
+        q = np.clip(np.floor(255.0 * uv.astype(np.float64) + 0.5), 0, 255).astype(np.uint8)
+        for i, r in enumerate(rows):                     # (host copies of this batch: encoded while the next batch is labelled)
+            pending += [pool.submit(_encode, os.path.join(out_dir, "part_%04d.png" % r), part[i], "png"),
+                        pool.submit(_encode, os.path.join(out_dir, "depth_%04d.png" % r), mm[i], "png"),
+                        pool.submit(_encode, os.path.join(out_dir, "iuv_%04d.png" % r), np.concatenate([part[i][..., None], q[i]], -1), "png")]
+    with pool:
+        for fut in pending:
+            fut.result()
+    for k in range(P):
+        uvz, vis, bbox = (np.concatenate(kp[k][key]) for key in ("uvz", "vis", "bbox"))
+        np.savez(os.path.join(out_dir, "keypoints.npz" if P == 1 else "keypoints_%d.npz" % k), keypoints=uvz[..., :2], weights=(vis[..., 0] == 2).astype(np.float32),
+                 depth=uvz[..., 2] - uvz[:, :1, 2], z=uvz[..., 2], visible=vis[..., 0], occluder=vis[..., 1], bbox=bbox, part_names=np.array(names[k]))
 
 
 def _encode(path, u8, fmt):

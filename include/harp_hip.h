@@ -1091,6 +1091,61 @@ int harp_composite_layers_u8(const harp_layer* layers, int n_layers, int B, int 
                              const int32_t* scene_rows, const unsigned char* bg, int n_bg, const int32_t* bg_rows, const float* bg_color,
                              int channels, unsigned char* out, unsigned char* owner, hipStream_t stream);
 
+/* ---- labelled playback: what the frames show (csrc/annotate.hip; playback/player.py annotate) ----
+ * Nothing in the reference does this.  Both entries read what a player's batch leaves on the device, allocate nothing, only enqueue on
+ * `stream` and are capturable; the layer array is a HOST array read during the call and passed to the kernel by value, as harp_layer. */
+typedef struct harp_label_layer {
+  const int32_t* face_id;          /* (B, S ss, S ss) as the camera-view harp_rasterize_fwd leaves it */
+  const float* zbuf;               /* (B, S ss, S ss) view depth, as harp_layer's */
+  const unsigned char* face_label; /* (F,) the part of every face, 1..255 (playback/labels.py face_part_labels) */
+  const float* ndc;                /* (B,V,3) as harp_project_fwd leaves it        \                                       */
+  const int32_t* faces;            /* (F,3)                                         | read for the uv output only: all four */
+  const float* verts_uvs;          /* (Vt,2)                                        | may be NULL without it                */
+  const int32_t* faces_uvs;        /* (F,3)                                        /                                       */
+  int32_t V, F, Vt;                /* F > 0 always; V, Vt > 0 with the uv output */
+  int32_t flip_x;                  /* != 0: the layer is read mirrored, sub-column S ss - 1 - X */
+  int32_t reserved;                /* 0 */
+} harp_label_layer;
+/* harp_annotate_layers: n_layers in 1..4, ss in 1..4, scene_z / n_scene / scene_rows exactly as harp_composite_layers_u8 -> any of
+ * owner (B,S,S) u8, part (B,S,S) u8, depth (B,S,S) f32, face (B,S,S) i32, uv (B,S,S,2) f32, bbox (B,n_layers,4) i32 (each may be NULL, not
+ * all).  Output pixel (b, y, x), sub-sample (sy, sx) in [0, ss)^2:
+ *   winner per sub-sample: harp_composite_layers_u8's rule, word for word (candidate when z_l > 0, in front of a valid scene depth, the
+ *     smallest z, ties to the lower layer; a flipped layer is read at column S ss - 1 - X).  The winner's LABEL is face_label[face_id] of
+ *     that layer there, and 0 for a face_id outside [0, F) (nothing is read out of bounds).
+ *   owner: 0 when no sub-sample has a winner, otherwise 1 + the layer that won the most sub-samples, a tie to the lower index: bit for
+ *     bit harp_composite_layers_u8's owner for the same inputs.
+ *   part: among the sub-samples the owner layer won the most frequent label, a tie to the lower label; 0 when owner is 0.
+ *   representative sub-sample: among the owner's sub-samples with that label the one with the smallest z, a tie to the first in row-major
+ *     order (sy outer, sx inner).  depth = its z (0 when owner is 0); face = its face_id (-1 when owner is 0);
+ *     uv = sum_k b_k verts_uvs[faces_uvs[face, k]], and (0, 0) when owner is 0, when face is outside [0, F) or when one of the face's six
+ *     table entries is outside [0, V) / [0, Vt).  b = the perspective-corrected barycentrics of csrc/shade_common.h bary_fwd (the same
+ *     formula, kEps included) on the face's three ndc rows, at the centre of the SOURCE sub-pixel the layer was read at — the mirrored
+ *     column for a flipped layer, the UV belongs to the surface point — in the rasteriser's convention, 1 - 2 (i + 0.5) / (S ss).
+ *   bbox (+= by integer atomic max; the caller zeroes it): (S - xmin, S - ymin, xmax + 1, ymax + 1) over the pixels whose owner is
+ *     1 + l; all zeros: layer l owns no pixel.
+ * HARP_ERR_ARG before any launch: layers NULL; every output NULL; n_layers outside 1..4; a layer with a NULL face_id, zbuf or face_label,
+ * F <= 0 or a non-zero reserved; with uv, a layer with a NULL ndc, faces, verts_uvs or faces_uvs or V, Vt <= 0; B, S <= 0; ss outside
+ * 1..4; S ss > 46340; n_scene as harp_composite_layers_u8. */
+int harp_annotate_layers(const harp_label_layer* layers, int n_layers, int B, int S, int ss, const float* scene_z, int n_scene,
+                         const int32_t* scene_rows, unsigned char* owner, unsigned char* part, float* depth, int32_t* face, float* uv,
+                         int32_t* bbox, hipStream_t stream);
+/* harp_keypoint_visibility: the joints of layer `self_layer` projected and tested against the scene.  joints (B,NJ,3) metres, as the fused
+ * front leaves joints_m; cam_R (B,9), cam_T (B,3); focal and S of the OUTPUT image; of the layers only zbuf (B, S ss, S ss) and flip_x are
+ * read; tol metres -> uvz (B,NJ,3) f32 and vis (B,NJ,2) u8.  Per joint, with view = harp_project_fwd's transform of j (for its R =
+ * diag(-1,-1,1) and T = (-cam1, -cam2, t_z) this is playback/keypoints.py project_pixels): Z = view.z, u = S/2 - focal view.x / Z,
+ * v = S/2 - focal view.y / Z, and u becomes S - u when self_layer is flipped.  uvz = (u, v, Z), or zeros when not Z > 1e-3 (a NaN too).
+ *   vis[0]: 0 = not in the image (not Z > 1e-3, Z infinite, u or v outside [0, S) or NaN); 1 = hidden; 2 = visible.
+ *   vis[1]: what hides it: 0 nothing, 1 + the layer, 255 the scene depth.
+ * The test is made at sub-pixel (Y, X) = (min((int)(v ss), S ss - 1), min((int)(u ss), S ss - 1)) of the output frame: the nearest surface
+ * there is harp_composite_layers_u8's winner when there is one, otherwise the scene depth at (Y / ss, X / ss) when valid, otherwise
+ * nothing.  The joint is visible when there is nothing or z_near >= Z - tol; a joint behind its own skin by more than tol reports its
+ * own layer.  HARP_ERR_ARG before any launch: a NULL joints, cam_R, cam_T, layers, uvz or vis; n_layers outside 1..4; self_layer outside
+ * [0, n_layers); a layer with a NULL zbuf or a non-zero reserved; B, NJ, S <= 0; ss outside 1..4; S ss > 46340; focal not > 0; tol not
+ * >= 0; n_scene as harp_composite_layers_u8. */
+int harp_keypoint_visibility(const float* joints, const float* cam_R, const float* cam_T, int B, int NJ, float focal, int S, int ss,
+                             int self_layer, const harp_label_layer* layers, int n_layers, const float* scene_z, int n_scene,
+                             const int32_t* scene_rows, float tol, float* uvz, unsigned char* vis, hipStream_t stream);
+
 /* ---- batched MANO inverse kinematics: 3-D keypoints -> pose rows (csrc/ik.hip; playback.py Motion.from_keypoints) ----
  * Nothing in the reference does this: its change_pose takes another sequence's parameters.  The model inverted is harp_lbs_mano_fwd's.
  * T independent Levenberg-Marquardt solves in one launch, forward only, no workspace, no allocation, no synchronisation, no atomics
