@@ -350,6 +350,16 @@ SIGNATURES["harp_annotate_layers"] = (_i, [_llp, _i, _i, _i, _i, _vp, _i, _vp, _
 SIGNATURES["harp_keypoint_visibility"] = (_i, [_vp, _vp, _vp, _i, _i, _f, _i, _i, _i, _llp, _i, _vp, _i, _vp, _f, _vp, _vp, _vp])
 
 
+class FlowLayer(ctypes.Structure):
+    """mirror of `harp_flow_layer` (include/harp_hip.h)"""
+    _fields_ = ([(n, _vp) for n in ("face_id", "zbuf", "face_label", "ndc", "faces", "ndc_to", "zbuf_to")] +
+                [(n, ctypes.c_int32) for n in ("V", "F", "flip_x", "reserved")])
+
+
+# where the surface points of a frame are in another frame (csrc/flow.hip)
+SIGNATURES["harp_flow_layers"] = (_i, [ctypes.POINTER(FlowLayer), _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _f, _vp, _vp, _vp, _vp])
+
+
 class IkOptions(ctypes.Structure):
     """mirror of `harp_ik_options` (include/harp_hip.h)"""
     _fields_ = [("iters", _i), ("lambda0", _f), ("prior_weight", _f), ("betas_per_frame", _i)]

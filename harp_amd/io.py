@@ -83,3 +83,36 @@ def save_obj(f, verts, faces, decimal_places=None, *, verts_uvs=None, faces_uvs=
             out.write(f"newmtl mesh\nmap_Kd {name}.png\n")
         with open(stem + ".png", "wb") as out:
             out.write(texture_png if texture_png is not None else encode_png(texture_map))
+
+
+FLO_MAGIC = 202021.25                                  # the Middlebury .flo tag, the float32 whose bytes read "PIEH"
+FLO_UNKNOWN = 1e9                                      # that format's value for a pixel without flow, in both channels
+
+
+def save_flo(path, flow, known=None):
+    """Optical flow (H,W,2) in pixels as a Middlebury .flo file: float32 FLO_MAGIC, int32 width, int32 height, then (H,W,2) float32 (u, v),
+    little endian.  known: None or (H,W) bool; a pixel where it is False is written as FLO_UNKNOWN in both channels."""
+    f = np.array(flow, dtype="<f4")
+    if f.ndim != 3 or f.shape[2] != 2:
+        raise ValueError(f"flow must be (H, W, 2), got {f.shape}")
+    if known is not None:
+        known = np.asarray(known, bool)
+        if known.shape != f.shape[:2]:
+            raise ValueError(f"known must be {f.shape[:2]}, got {known.shape}")
+        f[~known] = FLO_UNKNOWN
+    with open(path, "wb") as fh:
+        fh.write(np.array(FLO_MAGIC, "<f4").tobytes() + np.array([f.shape[1], f.shape[0]], "<i4").tobytes() + f.tobytes())
+
+
+def load_flo(path):
+    """A Middlebury .flo file -> (flow (H,W,2) float32 as stored, known (H,W) bool: False where a channel's magnitude is FLO_UNKNOWN or
+    more, which is what save_flo writes for a pixel without flow)"""
+    with open(path, "rb") as fh:
+        raw = fh.read()
+    if len(raw) < 12 or np.frombuffer(raw[:4], "<f4")[0] != np.float32(FLO_MAGIC):
+        raise ValueError(f"{path} is not a .flo file")
+    w, h = (int(v) for v in np.frombuffer(raw[4:12], "<i4"))
+    if w < 1 or h < 1 or len(raw) != 12 + 8 * w * h:
+        raise ValueError(f"{path}: {len(raw)} bytes for {w} x {h} pixels")
+    f = np.frombuffer(raw[12:], "<f4").reshape(h, w, 2).copy()
+    return f, ~(np.abs(f) >= np.float32(FLO_UNKNOWN)).any(-1)

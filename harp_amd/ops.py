@@ -1449,6 +1449,68 @@ def keypoint_visibility(joints, cam_R, cam_T, focal, S, layers, self_layer=0, ss
     return o
 
 
+# ---- where the surface points of a frame are in another frame (csrc/flow.hip) ----------------------------------------
+LayerFlow = collections.namedtuple("LayerFlow", "flow dz status")
+# metres: a convention, not a tuned value.  The tracked point lies ON the surface (a joint lies under it: LABEL_TOL is 0.02), so the
+# tolerance only absorbs the depth difference between the point where it lands and the centre of the sub-pixel it is tested at
+FLOW_TOL = 0.005
+FLOW_STATUS = ("none", "untrackable", "outside", "hidden", "visible")      # status[..., 0]
+_FLOW_LAYER_KEYS = ("face_id", "zbuf", "face_label", "flip", "ndc", "faces")
+
+
+def flow_layers(layers, to, ss=1, scene_depth=None, scene_rows=None, scene_depth_to=None, scene_rows_to=None, tol=FLOW_TOL):
+    """Where the surface point that each output pixel of composite_layers_u8 on `layers` shows lies in the TARGET frames (csrc/flow.hip:
+    harp_flow_layers, whose contract include/harp_hip.h states), forward only.  layers: annotate_layers' 1..4 dicts of the SOURCE frames
+    with face_id, zbuf, face_label, flip, ndc (B,V,3) float32 and faces (F,3) int32 (verts_uvs and faces_uvs are ignored); to: per layer a
+    dict of the same mesh in the target frames, ndc (B,V,3) float32 and zbuf (B, S ss, S ss) float32.  scene_depth, scene_rows: the scene
+    depth of the source frames, scene_depth_to, scene_rows_to: of the target frames, each as composite_layers_u8.  tol metres: the point is
+    visible when the nearest target surface where it lands is no nearer than its own depth minus tol (FLOW_TOL).  Returns LayerFlow(flow
+    (B,S,S,2) float32 in output pixels, dz (B,S,S) float32 metres, status (B,S,S,2) uint8 = (0 no owner | 1 not trackable | 2 lands
+    outside the image | 3 hidden | 4 visible, what hides it: 0 nothing, 1 + the layer, 255 the scene depth)); flow and dz are zero
+    where status is 0 or 1."""
+    import math
+    ss, tol = int(ss), float(tol)
+    layers, to = list(layers), list(to)
+    src = [{k: v for k, v in l.items() if k not in ("verts_uvs", "faces_uvs")} if isinstance(l, dict) else l for l in layers]
+    arr_l, keep, B, S = _label_layers("flow_layers", src, ss, False)
+    if len(to) != len(src) or any(not isinstance(t, dict) or set(t) != {"ndc", "zbuf"} for t in to):
+        raise ValueError(f"flow_layers takes one dict (ndc, zbuf) of the target frames per layer, got {len(to)} for {len(src)} layers")
+    _playback_input("flow_layers", keep[0][0], *[l.get(k) for l in src for k in ("ndc", "faces")], *[t[k] for t in to for k in ("ndc", "zbuf")],
+                    scene_depth, scene_rows, scene_depth_to, scene_rows_to)
+    if not (tol >= 0 and math.isfinite(tol)):
+        raise ValueError(f"tol must be non-negative and finite, got {tol}")
+    z0 = keep[0][0]
+    c = lambda t: t.detach().contiguous()               # noqa: E731
+    arr = (_lib.FlowLayer * len(src))()
+    for i, (l, t) in enumerate(zip(src, to)):
+        ndc, faces, ndc_to, z_to = l.get("ndc"), l.get("faces"), t["ndc"], t["zbuf"]
+        if ndc is None or faces is None:
+            raise ValueError(f"layer {i}: the flow needs ndc and faces")
+        if ndc.dtype != torch.float32 or ndc_to.dtype != torch.float32 or z_to.dtype != torch.float32 or faces.dtype != torch.int32:
+            raise TypeError(f"layer {i}: ndc and the target's ndc and zbuf must be float32, faces int32")
+        F = arr_l[i].F
+        if (ndc.dim() != 3 or ndc.shape[0] != B or ndc.shape[1] < 1 or ndc.shape[2] != 3 or tuple(faces.shape) != (F, 3)
+                or tuple(ndc_to.shape) != tuple(ndc.shape) or tuple(z_to.shape) != tuple(z0.shape)):
+            raise ValueError(f"layer {i}: ndc ({B}, V, 3), faces ({F}, 3), the target's ndc as the source's and its zbuf {tuple(z0.shape)}, got "
+                             f"{tuple(ndc.shape)}, {tuple(faces.shape)}, {tuple(ndc_to.shape)}, {tuple(z_to.shape)}")
+        ts = [c(ndc), c(faces), c(ndc_to), c(z_to)]
+        keep.append(ts)
+        a = arr[i]
+        a.face_id, a.zbuf, a.face_label, a.F, a.flip_x, a.reserved = arr_l[i].face_id, arr_l[i].zbuf, arr_l[i].face_label, F, arr_l[i].flip_x, 0
+        a.ndc, a.faces, a.ndc_to, a.zbuf_to = (_lib.ptr(x) for x in ts)
+        a.V = ndc.shape[1]
+    scene_depth, scene_rows, n_scene = _scene_depth_input("flow_layers", scene_depth, scene_rows, B, S)
+    scene_depth_to, scene_rows_to, n_scene_to = _scene_depth_input("flow_layers", scene_depth_to, scene_rows_to, B, S)
+    dev = z0.device
+    o = LayerFlow(torch.empty(B, S, S, 2, dtype=torch.float32, device=dev), torch.empty(B, S, S, dtype=torch.float32, device=dev),
+                  torch.empty(B, S, S, 2, dtype=torch.uint8, device=dev))
+    with torch.cuda.device(dev):
+        rc = _lib.lib().harp_flow_layers(arr, len(src), B, S, ss, _lib.ptr(scene_depth), n_scene, _lib.ptr(scene_rows), _lib.ptr(scene_depth_to),
+                                         n_scene_to, _lib.ptr(scene_rows_to), tol, *[_lib.ptr(t) for t in o], _lib.stream())
+    _lib.check(rc, "harp_flow_layers")
+    return o
+
+
 # ---- batched MANO inverse kinematics (csrc/ik.hip, DESIGN.md §24) -----------------------------------------------------------------
 IkResult = collections.namedtuple("IkResult", "pose48 trans cost status joints jac")
 

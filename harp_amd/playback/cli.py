@@ -3,7 +3,7 @@ import numpy as np
 
 from .. import ops
 from .motion import Motion, motion_jitter
-from .player import LABEL_TOL, AvatarPlayer, ScenePlayer
+from .player import FLOW_TOL, LABEL_TOL, AvatarPlayer, ScenePlayer
 
 
 def parse_args(argv=None):
@@ -44,6 +44,13 @@ def parse_args(argv=None):
     ap.add_argument("--label-tol", type=float, default=LABEL_TOL, metavar="M",
                     help="with --labels: a joint counts as visible when the nearest surface is no nearer than its depth minus M metres "
                          "(a joint lies under the skin)")
+    ap.add_argument("--flow", choices=("fw", "bw", "both"), default=None,
+                    help="also write the optical flow of every pixel's surface point to the next frame (fw: flow_%%04d.flo, Middlebury format), "
+                         "to the previous frame (bw: flow_bw_%%04d.flo) or both, with flow_status_%%04d.png / flow_bw_status_%%04d.png (0 nothing, "
+                         "1 not trackable, 2 leaves the image, 3 hidden in the other frame, 4 visible there)")
+    ap.add_argument("--flow-tol", type=float, default=FLOW_TOL, metavar="M",
+                    help="with --flow: a point counts as visible in the other frame when the nearest surface where it lands is no nearer than "
+                         "its depth minus M metres")
     ap.add_argument("--smooth", type=float, default=None, metavar="SIGMA",
                     help="filter the loaded or solved motion with a Gaussian window of SIGMA frames before --fps-scale (Motion.smooth); prints the "
                          "joint jitter before and after")
@@ -58,6 +65,8 @@ def parse_args(argv=None):
             raise SystemExit(f"--{name.replace('_', '-')} must be positive")
     if not args.label_tol >= 0:
         raise SystemExit("--label-tol must not be negative")
+    if not (args.flow_tol >= 0 and np.isfinite(args.flow_tol)):
+        raise SystemExit("--flow-tol must not be negative and must be finite")
     if args.smooth_trim is not None and args.smooth is None:
         raise SystemExit("--smooth-trim needs --smooth")
     if args.smooth_keypoints is not None and args.keypoints is None:
@@ -125,8 +134,9 @@ def main(argv=None):
     fmt = "png" if args.alpha else "jpg"
     if not (args.flip or args.also or args.scene_depth or args.masks):
         configs, params, hand_layer, motion = load(args.config, args.motion, args.keypoints, args.vertices, args.keypoints2d)
-        player = AvatarPlayer(configs, params, hand_layer, batch_size=args.batch_size, ss=args.ss, device=args.device, keep_depth=args.labels)
-        paths = player.play(motion, args.out, backgrounds=args.background, fmt=fmt, alpha=args.alpha, labels=args.labels, label_tol=args.label_tol)
+        player = AvatarPlayer(configs, params, hand_layer, batch_size=args.batch_size, ss=args.ss, device=args.device, keep_depth=args.labels or args.flow is not None)
+        paths = player.play(motion, args.out, backgrounds=args.background, fmt=fmt, alpha=args.alpha, labels=args.labels, label_tol=args.label_tol,
+                            flow=args.flow, flow_tol=args.flow_tol)
     else:
         specs = [(args.config, args.motion, args.flip, args.keypoints, args.vertices, args.keypoints2d)]
         for spec in args.also:
@@ -141,6 +151,6 @@ def main(argv=None):
             motions.append(motion)
         scene = ScenePlayer(players, flip=[spec[2] for spec in specs])
         paths = scene.play(motions, args.out, backgrounds=args.background, scene_depth=args.scene_depth, fmt=fmt, alpha=args.alpha, masks=args.masks,
-                           labels=args.labels, label_tol=args.label_tol)
+                           labels=args.labels, label_tol=args.label_tol, flow=args.flow, flow_tol=args.flow_tol)
     print(f"wrote {len(paths)} frames to {args.out}")
     return paths

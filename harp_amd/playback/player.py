@@ -19,6 +19,12 @@ LABEL_TOL = 0.02                                       # metres: how far under t
 # (n,4) of an AvatarPlayer, (n,P,4) of a scene of P players; uvz (n,NJ,3) float32 = (u, v, view depth) and vis (n,NJ,2) uint8 =
 # (0 not in the image | 1 hidden | 2 visible, the occluder: 0 nothing, 1 + the player, 255 the scene depth) — of a scene, one per player
 Annotation = collections.namedtuple("Annotation", "owner part depth face uv bbox uvz vis")
+FLOW_TOL = ops.FLOW_TOL                                # metres: how far under the nearest target surface a tracked surface point still counts as visible
+# what flow() returns: device tensors over the rows asked for, views of the player's buffers that the next flow overwrites.
+# flow (n,S,S,2) float32: where the surface point a pixel shows lies in the target frame, minus the pixel's own place, in output pixels
+# (x, y); dz (n,S,S) float32: its view depth there minus its depth here, metres; status (n,S,S,2) uint8 = (0 nothing | 1 not trackable |
+# 2 lands outside the image | 3 hidden at the target | 4 visible there, what hides it: 0 nothing, 1 + the player, 255 the scene depth)
+Flow = collections.namedtuple("Flow", "flow dz status")
 
 
 def _ck(rc, what):
@@ -61,6 +67,7 @@ class _Player:
         self._inputs = inputs
         self.T = self._n_cap = 0
         self.idx_done, self._bufs, self._graphs = None, {}, {}
+        self._flow = None                                # what flow() adds, allocated on its first call (_grow_flow)
         self.bg_color_dev = torch.empty(3, dtype=torch.float32, device=self.dev)
         self.bg_color = BG_WHITE
 
@@ -121,6 +128,40 @@ class _Player:
             if t is not None:
                 torch.index_select(t, 0, self.idx_dev[2 + 2 * k, :n], out=self._bufs[name][:n])
 
+    def _grow_flow(self, n_inputs, used):
+        """What flow() needs beside render's buffers, allocated on its first call and again when a longer `rows` has grown the player: the
+        index table of the TARGET rows (stage_table's layout over n_inputs staged inputs, beside idx_dev, which keeps its own) with its
+        pinned stage, the three outputs, and a copy of its own for every staged input the target rows use"""
+        if self._flow is None or self._flow["cap"] != self._n_cap:
+            n, S, rows = self._n_cap, self.S, 1 + 2 * n_inputs
+            new = lambda dt, *shape: torch.empty(n, *shape, dtype=dt, device=self.dev)      # noqa: E731
+            self._flow = dict(cap=n, idx_dev=torch.zeros(rows, n, dtype=torch.int32, device=self.dev),
+                              idx_pin=torch.zeros(rows, n, dtype=torch.int32).pin_memory(), flow=new(torch.float32, S, S, 2),
+                              dz=new(torch.float32, S, S), status=new(torch.uint8, S, S, 2), bufs={})
+        for (name, shape, dtype), u in zip(self._inputs[len(self._inputs) - n_inputs:], used):
+            if u and name not in self._flow["bufs"]:     # (no graph reads it yet)
+                self._flow["bufs"][name] = torch.empty(self._n_cap, *shape, dtype=dtype, device=self.dev)
+
+    def _upload_to(self, table, tensors, n):
+        """_upload for the target rows' table, enqueued in front of it: the event that _upload records covers both copies"""
+        fl = self._flow
+        if self.idx_done is not None:
+            self.idx_done.synchronize()
+        fl["idx_pin"].numpy()[:, :table.shape[1]] = table
+        fl["idx_dev"].copy_(fl["idx_pin"], non_blocking=True)
+        for k, ((name, _, _), t) in enumerate(zip(self._inputs[len(self._inputs) - len(tensors):], tensors)):
+            if t is not None:
+                torch.index_select(t, 0, fl["idx_dev"][2 + 2 * k, :n], out=fl["bufs"][name][:n])
+
+    def _staged_to_args(self, k, name, lo, used):
+        """_staged_args of the target rows' copy of staged input `name`, k-th of the target table"""
+        if not used:
+            return None, 0, None
+        return self._flow["bufs"][name].data_ptr(), self._n_cap, self._flow["idx_dev"][1 + 2 * k, lo:lo + self.B].data_ptr()
+
+    def _flow_view(self, n):
+        return Flow(self._flow["flow"][:n], self._flow["dz"][:n], self._flow["status"][:n])
+
     def _run(self, key):
         """_enqueue(*key) as it is, or as the replay of its graph, captured when the key is first seen"""
         if not self.use_graph:
@@ -143,10 +184,11 @@ class _Player:
             return None, 0, None
         return self._bufs[self._inputs[k][0]].data_ptr(), self._n_cap, self.idx_dev[1 + 2 * k, lo:lo + self.B].data_ptr()
 
-    def _render(self, rows, alpha, inputs, *flags):
+    def _render(self, rows, alpha, inputs, *flags, to=None):
         """The render path of both players: `rows` checked on the host, padded to whole batches, staged with `inputs` (per declared input
         the caller's (tensor, rows)), and enqueued or replayed under the key (padded length, channels, input used?..., *flags)
-        -> (frames (n, S, S, channels), n)."""
+        -> (frames (n, S, S, channels), n).  to (flow only): (the target rows, [the caller's (tensor, rows) of the staged inputs the target
+        frames use, the last of the declared ones]); they travel in a table of their own (_grow_flow)."""
         r = _host_rows("rows", rows)
         n = r.shape[0]
         if n < 1:
@@ -157,8 +199,17 @@ class _Player:
         staged = [self._staged(name, t, rr, n, shape, dtype) for (name, shape, dtype), (t, rr) in zip(self._inputs, inputs)]
         used = tuple(rr is not None for rr, _ in staged)
         n_pad = -(-n // self.B) * self.B
+        if to is not None:
+            r_to = _host_rows("to_rows", to[0], n)
+            if r_to.min() < 0 or r_to.max() >= self.T:
+                raise IndexError(f"to_rows span [{r_to.min()}, {r_to.max()}] but {self._holds} {self.T} frames")
+            decl = self._inputs[len(self._inputs) - len(to[1]):]
+            staged_to = [self._staged(name, t, rr, n, shape, dtype) for (name, shape, dtype), (t, rr) in zip(decl, to[1])]
         with torch.cuda.device(self.dev):
             self._grow(n_pad, used)
+            if to is not None:
+                self._grow_flow(len(staged_to), [rr is not None for rr, _ in staged_to])
+                self._upload_to(stage_table(r_to, n_pad, staged_to), [t for t, _ in to[1]], n)
             self._upload(stage_table(r, n_pad, staged), [t for t, _ in inputs], n)
             self._run((n_pad, C) + used + flags)
         return self.out[:n * self.S * self.S * C].view(n, self.S, self.S, C), n
@@ -245,6 +296,7 @@ class AvatarPlayer(_Player):
         self.tab = self.tables = None
         self._skin_weights = np.asarray(hand_layer._model_np["weights"])      # (V0, NJ): the part table is made from it on first use
         self._face_label, self._labels_wanted, self.lab, self.kp = None, False, None, None
+        self.s_to = None                                 # the target frames' ndc_c and z_c of a batch, allocated on the first flow()
 
     def _alloc_scratch(self):
         """per-batch buffers for B frames at S * ss: what FitEngine keeps for a step's forward half, nothing of its backward"""
@@ -372,6 +424,23 @@ class AvatarPlayer(_Player):
             a.ndc, a.faces, a.verts_uvs, a.faces_uvs, a.V, a.Vt = p(s["ndc_c"]), p(tp.faces), p(tp.verts_uvs), p(tp.faces_uvs), tp.V, tp.verts_uvs.shape[0]
         return a
 
+    def _flow_layer(self, flip):
+        """this player's harp_flow_layer over its batch buffers and its copies of the target frames' (flow() has made them)"""
+        s, p, tp = self.s, _lib.ptr, self.topo
+        return _lib.FlowLayer(face_id=p(s["face_c"]), zbuf=p(s["z_c"]), face_label=p(self._face_label), ndc=p(s["ndc_c"]), faces=p(tp.faces),
+                              ndc_to=p(self.s_to["ndc"]), zbuf_to=p(self.s_to["z"]), V=tp.V, F=tp.F, flip_x=int(flip), reserved=0)
+
+    def _flow_targets(self):
+        """the copies of a batch's ndc_c and z_c that hold the target frames while the source frames are rendered, made once"""
+        if self.s_to is None:
+            self.s_to = dict(ndc=torch.empty_like(self.s["ndc_c"]), z=torch.empty_like(self.s["z_c"]))
+        self._part_table()
+
+    def _keep_targets(self):
+        """the batch just rendered is the flow's target: device copies of its ndc_c and z_c, in stream order"""
+        self.s_to["ndc"].copy_(self.s["ndc_c"])
+        self.s_to["z"].copy_(self.s["z_c"])
+
     def _keypoint_buffers(self, n):
         """(uvz, vis) for n frames of this player's joints; whoever runs the launches owns them (the player itself, or its scene)"""
         return dict(uvz=torch.empty(n, self.n_joints, 3, dtype=torch.float32, device=self.dev),
@@ -393,11 +462,20 @@ class AvatarPlayer(_Player):
             self.lab = _label_buffers(self._n_cap, self.S, 1, self.dev)
             self.kp = self._keypoint_buffers(self._n_cap)
 
-    def _enqueue(self, n_pad, channels, with_bg, labels=None):
+    def _enqueue(self, n_pad, channels, with_bg, labels=None, flow=None):
         """per batch of B frames: its launches up to the shader, then the resolve; with labels = (part, depth, uv, keypoints, tol) the
-        launches up to the rasterisers, then the labels of the batch"""
+        launches up to the rasterisers, then the labels of the batch; with flow = ("flow", tol) the launches up to the rasterisers of the
+        TARGET rows, copies of their ndc_c and z_c, the same of the source rows, then the flow of the batch"""
         L, s, p = _lib.lib(), self.s, _lib.ptr
         per = self.S * self.S * channels
+        if flow is not None:
+            layer = (_lib.FlowLayer * 1)(self._flow_layer(False))
+            for lo in range(0, n_pad, self.B):
+                self._render_batch(self._flow["idx_dev"][0, lo:lo + self.B], shade=False)
+                self._keep_targets()
+                self._render_batch(self.idx_dev[0, lo:lo + self.B], shade=False)
+                _enqueue_flow(self._flow, lo, layer, 1, self.B, self.S, self.ss, (None, 0, None), (None, 0, None), flow[1])
+            return
         if labels is not None:
             layer = (_lib.LabelLayer * 1)(self._label_layer(False, labels[2]))
             for lo in range(0, n_pad, self.B):
@@ -440,13 +518,32 @@ class AvatarPlayer(_Player):
         n = self._render(rows, False, [(None, None)], labels)[1]
         return _annotation(self.lab, n, self.S, labels, self.kp["uvz"][:n] if labels[3] else None, self.kp["vis"][:n] if labels[3] else None, one=True)
 
+    @torch.no_grad()
+    def flow(self, rows, to_rows, tol=FLOW_TOL):
+        """Where the surface point that each pixel of frame rows[i] shows lies in frame to_rows[i] of the loaded motion -> Flow (above) of
+        device tensors.  Needs keep_depth=True.  Per batch the front and the rasterisers of the target rows, device copies of their ndc_c
+        and z_c, the front and the rasterisers of the source rows and one harp_flow_layers, under a graph key of its own.  tol: the point
+        lies on the surface, so the tolerance only absorbs the depth difference between where it lands and the centre of the sub-pixel
+        it is tested at; 0.005 is that convention, not a tuned value."""
+        if not self.keep_depth:
+            raise ValueError("flow needs a player built with keep_depth=True")
+        if self.tables is None:
+            raise RuntimeError("load_motion() first")
+        tol = _flow_tol(tol)
+        self._flow_targets()
+        n = self._render(rows, False, [(None, None)], None, ("flow", tol), to=(to_rows, []))[1]
+        return self._flow_view(n)
+
     # ---- a whole motion to files ------------------------------------------------------------------------------------------------
-    def play(self, motion, out_dir, backgrounds=None, fmt="jpg", alpha=False, labels=False, label_tol=LABEL_TOL):
+    def play(self, motion, out_dir, backgrounds=None, fmt="jpg", alpha=False, labels=False, label_tol=LABEL_TOL, flow=None, flow_tol=FLOW_TOL):
         """load_motion(motion), render it batch by batch and write out_dir/%04d.<fmt> (fmt "jpg" or "png"; alpha=True needs "png" and
         writes RGBA).  backgrounds: None, a (N,S,S,3) uint8 tensor or a directory of images of that size (sorted by name); frame i is
         composited over background i mod N.  The frames leave through two pinned host buffers, one per batch in flight, and are encoded on
         a thread pool while the next batch renders.  labels=True (needs keep_depth=True) also writes part_%04d.png, depth_%04d.png,
-        iuv_%04d.png and keypoints.npz (write_labels).  Returns the list of paths."""
+        iuv_%04d.png and keypoints.npz (write_labels).  flow="fw" | "bw" | "both" (needs keep_depth=True) also writes flow_%04d.flo and /
+        or flow_bw_%04d.flo with their status PNGs (write_flow).  Returns the list of paths."""
+        _flow_mode(flow), _flow_tol(flow_tol)
+
         def prepare():
             self.load_motion(motion)
             bgs = load_backgrounds(backgrounds, self.S, self.dev)
@@ -454,6 +551,8 @@ class AvatarPlayer(_Player):
         paths = self._play(out_dir, fmt, alpha, prepare)
         if labels:
             write_labels(out_dir, self.T, self.B, lambda rows: self.annotate(rows, uv=True, tol=label_tol), [part_names_of(self)])
+        if flow:
+            write_flow(out_dir, self.T, self.B, lambda rows, to: self.flow(rows, to, tol=flow_tol), flow)
         return paths
 
 
@@ -509,11 +608,25 @@ class ScenePlayer(_Player):
             self.lab = _label_buffers(self._n_cap, self.S, len(self.players), self.dev)
             self.kp = [pl._keypoint_buffers(self._n_cap) for pl in self.players]
 
-    def _enqueue(self, n_pad, channels, with_bg, with_depth, with_owner, labels=None):
+    def _enqueue(self, n_pad, channels, with_bg, with_depth, with_owner, labels=None, flow=None):
         """per batch: every player's front / rasterisers / shader, then one composite; with labels = (part, depth, uv, keypoints, tol)
-        every player's front / rasterisers, then the labels of the batch and every player's keypoints"""
+        every player's front / rasterisers, then the labels of the batch and every player's keypoints; with flow = ("flow", tol)
+        every player's front / rasterisers of the TARGET rows and copies of their ndc_c and z_c, the same of the source rows, then
+        the flow of the batch"""
         L, p, B = _lib.lib(), _lib.ptr, self.B
         per = self.S * self.S
+        if flow is not None:
+            P = len(self.players)
+            layers = (_lib.FlowLayer * P)(*[pl._flow_layer(f) for pl, f in zip(self.players, self.flip)])
+            for lo in range(0, n_pad, B):
+                for pl in self.players:
+                    pl._render_batch(self._flow["idx_dev"][0, lo:lo + B], shade=False)
+                    pl._keep_targets()
+                for pl in self.players:
+                    pl._render_batch(self.idx_dev[0, lo:lo + B], shade=False)
+                _enqueue_flow(self._flow, lo, layers, P, B, self.S, self.ss, self._staged_args(1, lo, with_depth),
+                              self._staged_to_args(0, "scene_depth", lo, with_depth), flow[1])
+            return
         if labels is not None:
             P = len(self.players)
             layers = (_lib.LabelLayer * P)(*[pl._label_layer(f, labels[2]) for pl, f in zip(self.players, self.flip)])
@@ -564,12 +677,30 @@ class ScenePlayer(_Player):
         kp = lambda key: tuple(b[key][:n] for b in self.kp) if labels[3] else None      # noqa: E731
         return _annotation(self.lab, n, self.S, labels, kp("uvz"), kp("vis"), one=False)
 
-    def play(self, motions, out_dir, backgrounds=None, scene_depth=None, fmt="jpg", alpha=False, masks=False, labels=False, label_tol=LABEL_TOL):
+    @torch.no_grad()
+    def flow(self, rows, to_rows, tol=FLOW_TOL, scene_depth=None, depth_rows=None, depth_to_rows=None):
+        """Where the surface point that each pixel of scene frame rows[i] shows lies in scene frame to_rows[i] -> Flow, as
+        AvatarPlayer.flow: the source point is annotate's (the same owner, face and uv), the occluder 1 + k is player k, 255 the scene
+        depth.  scene_depth: as render; frame rows[i] is composited against its row depth_rows[i] and the point is tested at the target
+        against its row depth_to_rows[i] (each without its rows: row i when N == len(rows), row 0 when N == 1)."""
+        if self.T < 1 or any(p.tables is None for p in self.players):
+            raise RuntimeError("load_motions() first")
+        tol = _flow_tol(tol)
+        for pl in self.players:
+            pl._flow_targets()
+        n = self._render(rows, False, [(None, None), (scene_depth, depth_rows)], False, None, ("flow", tol),
+                         to=(to_rows, [(scene_depth, depth_to_rows)]))[1]
+        return self._flow_view(n)
+
+    def play(self, motions, out_dir, backgrounds=None, scene_depth=None, fmt="jpg", alpha=False, masks=False, labels=False, label_tol=LABEL_TOL,
+             flow=None, flow_tol=FLOW_TOL):
         """load_motions(motions), render the scene batch by batch and write out_dir/%04d.<fmt> as AvatarPlayer.play does; with masks=True
         also out_dir/mask_%04d.png, the owner map (8-bit grey: 0 background, 1 + the player).  backgrounds: as AvatarPlayer.play;
         scene_depth: None, a float32 (N,S,S) tensor or a directory (load_scene_depth), frame i tested against depth i mod N.  labels=True
         also writes the label files (write_labels), one keypoints_<k>.npz per player k when there are several.  Returns the list of the
-        frames' paths."""
+        frames' paths.  flow="fw" | "bw" | "both" also writes the flow files (write_flow)."""
+        _flow_mode(flow), _flow_tol(flow_tol)
+
         def prepare():
             self.load_motions(motions)
             bgs, depth = load_backgrounds(backgrounds, self.S, self.dev), load_scene_depth(scene_depth, self.S, self.dev)
@@ -582,6 +713,11 @@ class ScenePlayer(_Player):
             write_labels(out_dir, self.T, self.B, lambda rows: self.annotate(rows, uv=True, tol=label_tol, scene_depth=d,
                                                                              depth_rows=None if d is None else rows % d.shape[0]),
                          [part_names_of(pl) for pl in self.players])
+        if flow:
+            d = prepare.depth
+            dr = lambda rows: None if d is None else rows % d.shape[0]      # noqa: E731
+            write_flow(out_dir, self.T, self.B, lambda rows, to: self.flow(rows, to, tol=flow_tol, scene_depth=d, depth_rows=dr(rows),
+                                                                          depth_to_rows=dr(to)), flow)
         return paths
 
 
@@ -611,6 +747,26 @@ def _enqueue_labels(lab, lo, layers, n_layers, B, S, ss, scene, labels):
     lab["bbox"][lo:lo + B].zero_()                       # (inside the captured sequence: the boxes are accumulated by atomic max)
     _ck(_lib.lib().harp_annotate_layers(layers, n_layers, B, S, ss, *scene, at("owner"), at("part", labels[0]), at("depth", labels[1]), at("face"),
                                         at("uv", labels[2]), at("bbox"), _lib.stream()), "annotate_layers")
+
+
+def _flow_tol(tol):
+    import math
+    tol = float(tol)
+    if not (tol >= 0 and math.isfinite(tol)):
+        raise ValueError(f"tol must be non-negative and finite, got {tol}")
+    return tol
+
+
+def _flow_mode(flow):
+    if flow not in (None, "fw", "bw", "both"):
+        raise ValueError(f'flow is None, "fw", "bw" or "both", got {flow!r}')
+    return flow
+
+
+def _enqueue_flow(fl, lo, layers, n_layers, B, S, ss, scene, scene_to, tol):
+    """harp_flow_layers into rows lo.. of the flow buffers, on the current stream"""
+    _ck(_lib.lib().harp_flow_layers(layers, n_layers, B, S, ss, *scene, *scene_to, tol, fl["flow"][lo:].data_ptr(), fl["dz"][lo:].data_ptr(),
+                                    fl["status"][lo:].data_ptr(), _lib.stream()), "flow_layers")
 
 
 def _annotation(lab, n, S, labels, uvz, vis, one):
@@ -653,6 +809,30 @@ def write_labels(out_dir, T, B, annotate, names):
         uvz, vis, bbox = (np.concatenate(kp[k][key]) for key in ("uvz", "vis", "bbox"))
         np.savez(os.path.join(out_dir, "keypoints.npz" if P == 1 else "keypoints_%d.npz" % k), keypoints=uvz[..., :2], weights=(vis[..., 0] == 2).astype(np.float32),
                  depth=uvz[..., 2] - uvz[:, :1, 2], z=uvz[..., 2], visible=vis[..., 0], occluder=vis[..., 1], bbox=bbox, part_names=np.array(names[k]))
+
+
+def write_flow(out_dir, T, B, flow, mode):
+    """The motion labels of a played motion beside its frames, batch by batch.  mode "fw" or "both": flow_%04d.flo, frame t -> t + 1, for
+    t = 0 .. T - 2; "bw" or "both": flow_bw_%04d.flo, frame t -> t - 1, for t = 1 .. T - 1; with each flow_status_%04d.png /
+    flow_bw_status_%04d.png, 8-bit grey of status[0].  .flo is the Middlebury format in output pixels (harp_amd.io.save_flo); a pixel
+    with status 0 or 1 carries that format's unknown value.  flow(rows, to_rows) -> Flow."""
+    from concurrent.futures import ThreadPoolExecutor
+    from ..io import save_flo
+    from ..utils.data_util import default_workers
+    pool, pending = ThreadPoolExecutor(max(1, min(8, default_workers()))), []
+    for stem, step, first, last in (("flow", 1, 0, T - 1), ("flow_bw", -1, 1, T)):
+        if mode not in ("both", "fw" if step > 0 else "bw"):
+            continue
+        for lo in range(first, last, B):
+            rows = np.arange(lo, min(last, lo + B))
+            got = flow(rows, rows + step)
+            fl, st = got.flow.cpu().numpy(), got.status[..., 0].cpu().numpy()      # (host copies of this batch: encoded while the next runs)
+            for i, r in enumerate(rows):
+                pending += [pool.submit(save_flo, os.path.join(out_dir, "%s_%04d.flo" % (stem, r)), fl[i], st[i] >= 2),
+                            pool.submit(_encode, os.path.join(out_dir, "%s_status_%04d.png" % (stem, r)), st[i], "png")]
+    with pool:
+        for fut in pending:
+            fut.result()
 
 
 def _encode(path, u8, fmt):

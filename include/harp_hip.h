@@ -1146,6 +1146,47 @@ int harp_keypoint_visibility(const float* joints, const float* cam_R, const floa
                              int self_layer, const harp_label_layer* layers, int n_layers, const float* scene_z, int n_scene,
                              const int32_t* scene_rows, float tol, float* uvz, unsigned char* vis, hipStream_t stream);
 
+/* ---- motion labels: per-pixel optical flow and occlusion between frames (csrc/flow.hip; playback/player.py flow) ----
+ * Nothing in the reference does this.  The entry reads what a player's batch leaves on the device for the SOURCE frames and copies of ndc
+ * and zbuf of the TARGET frames (the same meshes in the other pose / camera); it allocates nothing, only enqueues on `stream`, is
+ * capturable and uses no atomics: a repeated call gives the same bits.  The layer array is a HOST array read during the call and passed
+ * to the kernel by value, as harp_label_layer. */
+typedef struct harp_flow_layer {
+  const int32_t* face_id;          /* SOURCE frames (B, S ss, S ss), as harp_label_layer's */
+  const float* zbuf;               /* SOURCE (B, S ss, S ss) */
+  const unsigned char* face_label; /* (F,) */
+  const float* ndc;                /* SOURCE (B,V,3) (x_ndc, y_ndc, z_view) */
+  const int32_t* faces;            /* (F,3) */
+  const float* ndc_to;             /* TARGET frames (B,V,3): the same mesh, the other pose / camera */
+  const float* zbuf_to;            /* TARGET (B, S ss, S ss) view depth of this layer */
+  int32_t V, F, flip_x, reserved;  /* reserved 0 */
+} harp_flow_layer;
+/* harp_flow_layers: n_layers in 1..4, ss in 1..4; scene_z / n_scene / scene_rows (the scene depth of the source frames) and scene_z_to /
+ * n_scene_to / scene_rows_to (of the target frames) each exactly as harp_composite_layers_u8; tol metres -> flow (B,S,S,2) f32 output
+ * pixels, dz (B,S,S) f32 metres, status (B,S,S,2) u8.  Output pixel (b, y, x):
+ *   source point: harp_annotate_layers' winner rule, owner, part and representative sub-sample, word for word, on the source layers and
+ *     the source scene depth.  Layer l = owner - 1; face f and depth z are the representative sub-sample's, at output sub-pixel (Y, X);
+ *     Xs = the source column the layer was read at (S ss - 1 - X for a flipped layer); b_k = csrc/shade_common.h bary_fwd (kEps included)
+ *     on the face's three source ndc rows at the centre of (Y, Xs), 1 - 2 (i + 0.5) / (S ss): exactly the point `uv` is taken at.
+ *   target point, (x'_k, y'_k, z'_k) = the face's rows of ndc_to (harp_texture_bake_accum's projection of a barycentric point):
+ *     Z' = sum_k b_k z'_k, x' = sum_k b_k x'_k z'_k / Z', y' likewise; cx = (1 - x') S ss / 2, cy = (1 - y') S ss / 2: continuous sub-pixel
+ *     coordinates, the centre of sub-pixel i at i + 0.5; for a flipped layer cx := S ss - cx.
+ *   flow = ((cx - (X + 0.5)) / ss, (cy - (Y + 0.5)) / ss), dz = Z' - z.
+ *   status[0]: 0 = no owner (flow, dz zero); 1 = not trackable: f outside [0, F), a vertex index of the face outside [0, V), not
+ *     Z' > 1e-3, or Z', cx or cy not finite (nothing is read out of bounds; flow, dz zero); 2 = lands outside the image, cx or cy outside
+ *     [0, S ss) (flow and dz are written); 3 = hidden at the target; 4 = visible at the target.
+ *   3 / 4 is harp_keypoint_visibility's test at target sub-pixel (Yt, Xt) = (min((int)cy, S ss - 1), min((int)cx, S ss - 1)): the nearest
+ *     surface is the composite's winner over the layers' zbuf_to (a flipped layer read at column S ss - 1 - Xt) in front of the target
+ *     scene depth at (Yt / ss, Xt / ss) when there is one, otherwise that scene depth when valid, otherwise nothing; visible when there
+ *     is nothing or z_near >= Z' - tol.
+ *   status[1]: what hides the point: 0 nothing, 1 + the layer (the point's own layer for self-occlusion), 255 the scene depth.
+ * HARP_ERR_ARG before any launch: a NULL layers, flow, dz or status; n_layers outside 1..4; a layer with any NULL pointer, V <= 0, F <= 0
+ * or a non-zero reserved; B, S <= 0; ss outside 1..4; S ss > 46340; tol not >= 0 or not finite; n_scene or n_scene_to as
+ * harp_composite_layers_u8. */
+int harp_flow_layers(const harp_flow_layer* layers, int n_layers, int B, int S, int ss, const float* scene_z, int n_scene,
+                     const int32_t* scene_rows, const float* scene_z_to, int n_scene_to, const int32_t* scene_rows_to, float tol, float* flow,
+                     float* dz, unsigned char* status, hipStream_t stream);
+
 /* ---- batched MANO inverse kinematics: 3-D keypoints -> pose rows (csrc/ik.hip; playback.py Motion.from_keypoints) ----
  * Nothing in the reference does this: its change_pose takes another sequence's parameters.  The model inverted is harp_lbs_mano_fwd's.
  * T independent Levenberg-Marquardt solves in one launch, forward only, no workspace, no allocation, no synchronisation, no atomics
