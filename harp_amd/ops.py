@@ -1511,6 +1511,62 @@ def flow_layers(layers, to, ss=1, scene_depth=None, scene_rows=None, scene_depth
     return o
 
 
+# ---- the front that the five batched Levenberg-Marquardt solvers below share --------------------------------------------
+# A wrapper runs, in this order: _playback_input (device tensors, forward only), _lm_float32, its own check of `targets`, _lm_shapes,
+# _lm_scalars, its own checks, _lm_model_device, _lm_result, _lm_start, _lm_input, then its options struct and its one call.
+def _lm_float32(fn, **named):
+    """every tensor of `named` that is not None is float32, else a TypeError that names the field"""
+    for name, t in named.items():
+        if t is not None and t.dtype != torch.float32:
+            raise TypeError(f"{fn} takes float32 tensors, {name} is {t.dtype}")
+
+
+def _lm_shapes(*named):
+    """named: (name, tensor or None, shape) or, for a field with a choice such as betas and cam, (name, tensor, [shape, ...]); a tensor of
+    another shape raises a ValueError that names the field and both shapes"""
+    for name, t, want in named:
+        if t is not None and tuple(t.shape) != want and not (isinstance(want, list) and tuple(t.shape) in want):
+            want = " or ".join(map(str, want)) if isinstance(want, list) else want
+            raise ValueError(f"{name} must be {want}, got {tuple(t.shape)}")
+
+
+def _lm_scalars(iters, **weights):
+    """iters >= 0 and every weight (already a float) finite and >= 0, else a ValueError that lists the names and the values"""
+    if iters < 0 or any(not (0.0 <= v < float("inf")) for v in weights.values()):
+        raise ValueError(f"iters >= 0 and finite {', '.join(weights)} >= 0, got {iters}, {', '.join(map(str, weights.values()))}")
+
+
+def _lm_model_device(dm, targets):
+    if dm.v_template.device != targets.device:
+        raise ValueError(f"the model is on {dm.v_template.device}, the targets on {targets.device}")
+
+
+def _lm_result(kind, want, out, dev):
+    """The result namedtuple `kind` on `dev`.  want: one shape per field, None for an output that was not asked for; status is the one
+    int32 field, the rest are float32.  out=None: new tensors.  Else `out` itself, once every field fits: None exactly where want is, and
+    otherwise of that shape, on dev, contiguous and of the field's dtype — nothing is allocated then."""
+    if out is None:
+        return kind(*[None if shape is None else torch.empty(shape, dtype=torch.int32 if name == "status" else torch.float32, device=dev)
+                      for name, shape in zip(kind._fields, want)])
+    for name, t, shape in zip(kind._fields, out, want):
+        if (t is None) != (shape is None) or (t is not None and (tuple(t.shape) != shape or t.device != dev or not t.is_contiguous()
+                                                                  or t.dtype != (torch.int32 if name == "status" else torch.float32))):
+            raise ValueError(f"out.{name} does not fit this call")
+    return out
+
+
+def _lm_start(out, **start):
+    """the start rows into the result's fields of the same names: the kernel iterates in place, the caller's tensors stay untouched"""
+    for name, t in start.items():
+        getattr(out, name).copy_(t.detach())
+
+
+def _lm_input(t):
+    """an input as the kernel reads it, which is by its pointer alone: contiguous — the tensor itself when it already is, without a new
+    tensor object — else a detached contiguous copy; None as None"""
+    return t if t is None or t.is_contiguous() else t.detach().contiguous()
+
+
 # ---- batched MANO inverse kinematics (csrc/ik.hip, DESIGN.md §24) -----------------------------------------------------------------
 IkResult = collections.namedtuple("IkResult", "pose48 trans cost status joints jac")
 
@@ -1531,38 +1587,20 @@ def mano_ik(dm, betas, targets, pose48, trans, weights=None, prior=None, iters=1
     iters = 0 evaluates at the start.  out: an earlier IkResult of the same shapes whose tensors are written instead of new ones — the
     call then allocates nothing and can be captured into a graph."""
     _playback_input("mano_ik", betas, targets, pose48, trans, weights, prior)
-    for name, t in (("betas", betas), ("targets", targets), ("pose48", pose48), ("trans", trans), ("weights", weights), ("prior", prior)):
-        if t is not None and t.dtype != torch.float32:
-            raise TypeError(f"mano_ik takes float32 tensors, {name} is {t.dtype}")
+    _lm_float32("mano_ik", betas=betas, targets=targets, pose48=pose48, trans=trans, weights=weights, prior=prior)
     if targets.dim() != 3 or tuple(targets.shape[1:]) != (21, 3) or targets.shape[0] < 1:
         raise ValueError(f"targets must be (T, 21, 3), got {tuple(targets.shape)}")
     T = targets.shape[0]
-    if tuple(betas.shape) not in ((10,), (T, 10)):
-        raise ValueError(f"betas must be (10,) or ({T}, 10), got {tuple(betas.shape)}")
-    for name, t, shape in (("pose48", pose48, (T, 48)), ("trans", trans, (T, 3)), ("weights", weights, (T, 21)), ("prior", prior, (T, 45))):
-        if t is not None and tuple(t.shape) != shape:
-            raise ValueError(f"{name} must be {shape}, got {tuple(t.shape)}")
+    _lm_shapes(("betas", betas, [(10,), (T, 10)]), ("pose48", pose48, (T, 48)), ("trans", trans, (T, 3)), ("weights", weights, (T, 21)),
+               ("prior", prior, (T, 45)))
     iters, lambda0, prior_weight = int(iters), float(lambda0), float(prior_weight)
-    if iters < 0 or not (0.0 <= lambda0 < float("inf")) or not (0.0 <= prior_weight < float("inf")):
-        raise ValueError(f"iters >= 0 and finite lambda0, prior_weight >= 0, got {iters}, {lambda0}, {prior_weight}")
-    if dm.v_template.device != targets.device:
-        raise ValueError(f"the model is on {dm.v_template.device}, the targets on {targets.device}")
-    dev = targets.device
-    if out is None:
-        e = lambda shape, dt=torch.float32: torch.empty(shape, dtype=dt, device=dev)
-        out = IkResult(e((T, 48)), e((T, 3)), e((T, 2)), e((T,), torch.int32), e((T, 21, 3)) if joints else None, e((T, 63, 51)) if jac else None)
-    else:
-        want = ((T, 48), (T, 3), (T, 2), (T,), (T, 21, 3) if joints else None, (T, 63, 51) if jac else None)
-        for name, t, shape in zip(IkResult._fields, out, want):
-            if (t is None) != (shape is None) or (t is not None and (tuple(t.shape) != shape or t.device != dev or not t.is_contiguous()
-                                                                      or t.dtype != (torch.int32 if name == "status" else torch.float32))):
-                raise ValueError(f"out.{name} does not fit this call")
-    out.pose48.copy_(pose48.detach())
-    out.trans.copy_(trans.detach())
-    c = lambda t: None if t is None else t.detach().contiguous()
-    betas, targets, weights, prior = c(betas), c(targets), c(weights), c(prior)
+    _lm_scalars(iters, lambda0=lambda0, prior_weight=prior_weight)
+    _lm_model_device(dm, targets)
+    out = _lm_result(IkResult, ((T, 48), (T, 3), (T, 2), (T,), (T, 21, 3) if joints else None, (T, 63, 51) if jac else None), out, targets.device)
+    _lm_start(out, pose48=pose48, trans=trans)
+    betas, targets, weights, prior = map(_lm_input, (betas, targets, weights, prior))
     opt = _lib.IkOptions(iters, lambda0, prior_weight, int(betas.dim() == 2))
-    with torch.cuda.device(dev):
+    with torch.cuda.device(targets.device):
         rc = _lib.lib().harp_mano_ik(ctypes.byref(dm.struct), _lib.ptr(betas), _lib.ptr(targets), _lib.ptr(weights), _lib.ptr(prior), T,
                                      ctypes.byref(opt), _lib.ptr(out.pose48), _lib.ptr(out.trans), _lib.ptr(out.cost), _lib.ptr(out.status),
                                      _lib.ptr(out.joints), _lib.ptr(out.jac), _lib.stream())
@@ -1592,42 +1630,23 @@ def mano_vertex_fit(dm, targets, pose48, betas, trans, weights=None, prior=None,
     earlier VertexFitResult of the same shapes whose tensors are written instead of new ones — the call then allocates nothing and can be
     captured into a graph."""
     _playback_input("mano_vertex_fit", targets, pose48, betas, trans, weights, prior)
-    for name, t in (("targets", targets), ("pose48", pose48), ("betas", betas), ("trans", trans), ("weights", weights), ("prior", prior)):
-        if t is not None and t.dtype != torch.float32:
-            raise TypeError(f"mano_vertex_fit takes float32 tensors, {name} is {t.dtype}")
+    _lm_float32("mano_vertex_fit", targets=targets, pose48=pose48, betas=betas, trans=trans, weights=weights, prior=prior)
     if targets.dim() != 3 or tuple(targets.shape[1:]) != (778, 3) or targets.shape[0] < 1:
         raise ValueError(f"targets must be (T, 778, 3), got {tuple(targets.shape)}")
     T = targets.shape[0]
     solve_shape = bool(solve_shape)
-    if tuple(betas.shape) not in (((T, 10),) if solve_shape else ((10,), (T, 10))):
-        raise ValueError(f"betas must be ({T}, 10)" + ("" if solve_shape else " or (10,)") + f", got {tuple(betas.shape)}")
-    for name, t, shape in (("pose48", pose48, (T, 48)), ("trans", trans, (T, 3)), ("weights", weights, (T, 778)), ("prior", prior, (T, 45))):
-        if t is not None and tuple(t.shape) != shape:
-            raise ValueError(f"{name} must be {shape}, got {tuple(t.shape)}")
+    _lm_shapes(("betas", betas, [(T, 10)] if solve_shape else [(T, 10), (10,)]), ("pose48", pose48, (T, 48)), ("trans", trans, (T, 3)),
+               ("weights", weights, (T, 778)), ("prior", prior, (T, 45)))
     iters, lambda0, pose_prior_weight, shape_prior_weight = int(iters), float(lambda0), float(pose_prior_weight), float(shape_prior_weight)
-    if iters < 0 or any(not (0.0 <= v < float("inf")) for v in (lambda0, pose_prior_weight, shape_prior_weight)):
-        raise ValueError(f"iters >= 0 and finite lambda0, pose_prior_weight, shape_prior_weight >= 0, got {iters}, {lambda0}, "
-                         f"{pose_prior_weight}, {shape_prior_weight}")
-    if dm.v_template.device != targets.device:
-        raise ValueError(f"the model is on {dm.v_template.device}, the targets on {targets.device}")
-    dev = targets.device
+    _lm_scalars(iters, lambda0=lambda0, pose_prior_weight=pose_prior_weight, shape_prior_weight=shape_prior_weight)
+    _lm_model_device(dm, targets)
     want = ((T, 48), tuple(betas.shape), (T, 3), (T, 2), (T,), (T, 778, 3) if verts else None, (T, 2334, 61) if jac else None,
             (T, 61, 61) if normal else None, (T, 61) if normal else None)
-    if out is None:
-        out = VertexFitResult(*[None if shape is None else torch.empty(shape, dtype=torch.int32 if name == "status" else torch.float32, device=dev)
-                                for name, shape in zip(VertexFitResult._fields, want)])
-    else:
-        for name, t, shape in zip(VertexFitResult._fields, out, want):
-            if (t is None) != (shape is None) or (t is not None and (tuple(t.shape) != shape or t.device != dev or not t.is_contiguous()
-                                                                      or t.dtype != (torch.int32 if name == "status" else torch.float32))):
-                raise ValueError(f"out.{name} does not fit this call")
-    out.pose48.copy_(pose48.detach())
-    out.betas.copy_(betas.detach())
-    out.trans.copy_(trans.detach())
-    c = lambda t: None if t is None else t.detach().contiguous()
-    targets, weights, prior = c(targets), c(weights), c(prior)
+    out = _lm_result(VertexFitResult, want, out, targets.device)
+    _lm_start(out, pose48=pose48, betas=betas, trans=trans)
+    targets, weights, prior = map(_lm_input, (targets, weights, prior))
     opt = _lib.VertexFitOptions(iters, lambda0, pose_prior_weight, shape_prior_weight, int(solve_shape), int(betas.dim() == 2))
-    with torch.cuda.device(dev):
+    with torch.cuda.device(targets.device):
         rc = _lib.lib().harp_mano_vertex_fit(ctypes.byref(dm.struct), _lib.ptr(targets), _lib.ptr(weights), _lib.ptr(prior), T, ctypes.byref(opt),
                                              _lib.ptr(out.pose48), _lib.ptr(out.betas), _lib.ptr(out.trans), _lib.ptr(out.cost),
                                              _lib.ptr(out.status), _lib.ptr(out.verts), _lib.ptr(out.jac), _lib.ptr(out.A), _lib.ptr(out.g),
@@ -1661,9 +1680,7 @@ def arm_vertex_fit(dm, targets, in_pose, betas, trans, vert_idx=None, weights=No
     result.  iters = 0 evaluates at the start.  out: an earlier ArmVertexFitResult of the same shapes whose tensors are written instead of
     new ones — the call then allocates nothing (pass an int32 vert_idx) and can be captured into a graph."""
     _playback_input("arm_vertex_fit", targets, in_pose, betas, trans, weights, prior, vert_idx)
-    for name, t in (("targets", targets), ("in_pose", in_pose), ("betas", betas), ("trans", trans), ("weights", weights), ("prior", prior)):
-        if t is not None and t.dtype != torch.float32:
-            raise TypeError(f"arm_vertex_fit takes float32 tensors, {name} is {t.dtype}")
+    _lm_float32("arm_vertex_fit", targets=targets, in_pose=in_pose, betas=betas, trans=trans, weights=weights, prior=prior)
     NV = int(dm.NV)
     if targets.dim() != 3 or targets.shape[2] != 3 or targets.shape[0] < 1 or not 1 <= targets.shape[1] <= NV:
         raise ValueError(f"targets must be (T, n_t <= {NV}, 3), got {tuple(targets.shape)}")
@@ -1678,37 +1695,21 @@ def arm_vertex_fit(dm, targets, in_pose, betas, trans, vert_idx=None, weights=No
             raise ValueError(f"vert_idx must lie in [0, {NV})")
         vert_idx = vert_idx.to(torch.int32).contiguous()
     solve_shape, solve_wrist = bool(solve_shape), bool(solve_wrist)
-    if tuple(betas.shape) not in (((T, 10),) if solve_shape else ((10,), (T, 10))):
-        raise ValueError(f"betas must be ({T}, 10)" + ("" if solve_shape else " or (10,)") + f", got {tuple(betas.shape)}")
-    for name, t, shape in (("in_pose", in_pose, (T, 17, 3)), ("trans", trans, (T, 3)), ("weights", weights, (T, n_t)), ("prior", prior, (T, 45))):
-        if t is not None and tuple(t.shape) != shape:
-            raise ValueError(f"{name} must be {shape}, got {tuple(t.shape)}")
+    _lm_shapes(("betas", betas, [(T, 10)] if solve_shape else [(T, 10), (10,)]), ("in_pose", in_pose, (T, 17, 3)), ("trans", trans, (T, 3)),
+               ("weights", weights, (T, n_t)), ("prior", prior, (T, 45)))
     iters, lambda0 = int(iters), float(lambda0)
     pose_prior_weight, wrist_prior_weight, shape_prior_weight = float(pose_prior_weight), float(wrist_prior_weight), float(shape_prior_weight)
-    if iters < 0 or any(not (0.0 <= v < float("inf")) for v in (lambda0, pose_prior_weight, wrist_prior_weight, shape_prior_weight)):
-        raise ValueError(f"iters >= 0 and finite lambda0, pose_prior_weight, wrist_prior_weight, shape_prior_weight >= 0, got {iters}, {lambda0}, "
-                         f"{pose_prior_weight}, {wrist_prior_weight}, {shape_prior_weight}")
-    if dm.v_template.device != targets.device:
-        raise ValueError(f"the model is on {dm.v_template.device}, the targets on {targets.device}")
-    dev = targets.device
+    _lm_scalars(iters, lambda0=lambda0, pose_prior_weight=pose_prior_weight, wrist_prior_weight=wrist_prior_weight,
+                shape_prior_weight=shape_prior_weight)
+    _lm_model_device(dm, targets)
     want = ((T, 17, 3), tuple(betas.shape), (T, 3), (T, 2), (T,), (T, NV, 3) if verts else None, (T, 3 * n_t, 64) if jac else None,
             (T, 64, 64) if normal else None, (T, 64) if normal else None)
-    if out is None:
-        out = ArmVertexFitResult(*[None if shape is None else torch.empty(shape, dtype=torch.int32 if name == "status" else torch.float32, device=dev)
-                                   for name, shape in zip(ArmVertexFitResult._fields, want)])
-    else:
-        for name, t, shape in zip(ArmVertexFitResult._fields, out, want):
-            if (t is None) != (shape is None) or (t is not None and (tuple(t.shape) != shape or t.device != dev or not t.is_contiguous()
-                                                                      or t.dtype != (torch.int32 if name == "status" else torch.float32))):
-                raise ValueError(f"out.{name} does not fit this call")
-    out.in_pose.copy_(in_pose.detach())
-    out.betas.copy_(betas.detach())
-    out.trans.copy_(trans.detach())
-    c = lambda t: None if t is None else t.detach().contiguous()
-    targets, weights, prior = c(targets), c(weights), c(prior)
+    out = _lm_result(ArmVertexFitResult, want, out, targets.device)
+    _lm_start(out, in_pose=in_pose, betas=betas, trans=trans)
+    targets, weights, prior = map(_lm_input, (targets, weights, prior))
     opt = _lib.ArmVertexFitOptions(iters, lambda0, pose_prior_weight, wrist_prior_weight, shape_prior_weight, int(solve_shape), int(solve_wrist),
                                    int(betas.dim() == 2))
-    with torch.cuda.device(dev):
+    with torch.cuda.device(targets.device):
         rc = _lib.lib().harp_arm_vertex_fit(ctypes.byref(dm.struct), _lib.ptr(vert_idx), n_t, _lib.ptr(targets), _lib.ptr(weights), _lib.ptr(prior),
                                             T, ctypes.byref(opt), _lib.ptr(out.in_pose), _lib.ptr(out.betas), _lib.ptr(out.trans),
                                             _lib.ptr(out.cost), _lib.ptr(out.status), _lib.ptr(out.verts), _lib.ptr(out.jac), _lib.ptr(out.A),
@@ -1739,42 +1740,22 @@ def arm_ik(dm, betas, targets, in_pose, trans, weights=None, prior=None, wrist_p
     jac (T,3 n,54) or None), the optional ones at the result.  iters = 0 evaluates at the start.  out: an earlier ArmIkResult of the same
     shapes whose tensors are written instead of new ones — the call then allocates nothing and can be captured into a graph."""
     _playback_input("arm_ik", betas, targets, in_pose, trans, weights, prior, wrist_prior)
-    for name, t in (("betas", betas), ("targets", targets), ("in_pose", in_pose), ("trans", trans), ("weights", weights), ("prior", prior),
-                    ("wrist_prior", wrist_prior)):
-        if t is not None and t.dtype != torch.float32:
-            raise TypeError(f"arm_ik takes float32 tensors, {name} is {t.dtype}")
+    _lm_float32("arm_ik", betas=betas, targets=targets, in_pose=in_pose, trans=trans, weights=weights, prior=prior, wrist_prior=wrist_prior)
     n = int(dm.struct.n_joints_out)
     if targets.dim() != 3 or tuple(targets.shape[1:]) != (n, 3) or targets.shape[0] < 1:
         raise ValueError(f"targets must be (T, {n}, 3), got {tuple(targets.shape)}")
     T = int(targets.shape[0])
-    if tuple(betas.shape) not in ((10,), (T, 10)):
-        raise ValueError(f"betas must be (10,) or ({T}, 10), got {tuple(betas.shape)}")
-    for name, t, shape in (("in_pose", in_pose, (T, 17, 3)), ("trans", trans, (T, 3)), ("weights", weights, (T, n)), ("prior", prior, (T, 45)),
-                           ("wrist_prior", wrist_prior, (T, 3))):
-        if t is not None and tuple(t.shape) != shape:
-            raise ValueError(f"{name} must be {shape}, got {tuple(t.shape)}")
+    _lm_shapes(("betas", betas, [(10,), (T, 10)]), ("in_pose", in_pose, (T, 17, 3)), ("trans", trans, (T, 3)), ("weights", weights, (T, n)),
+               ("prior", prior, (T, 45)), ("wrist_prior", wrist_prior, (T, 3)))
     iters, lambda0, pose_prior_weight, wrist_prior_weight = int(iters), float(lambda0), float(pose_prior_weight), float(wrist_prior_weight)
-    if iters < 0 or any(not (0.0 <= v < float("inf")) for v in (lambda0, pose_prior_weight, wrist_prior_weight)):
-        raise ValueError(f"iters >= 0 and finite lambda0, pose_prior_weight, wrist_prior_weight >= 0, got {iters}, {lambda0}, "
-                         f"{pose_prior_weight}, {wrist_prior_weight}")
-    if dm.v_template.device != targets.device:
-        raise ValueError(f"the model is on {dm.v_template.device}, the targets on {targets.device}")
-    dev = targets.device
-    want = ((T, 17, 3), (T, 3), (T, 2), (T,), (T, n, 3) if joints else None, (T, 3 * n, 54) if jac else None)
-    if out is None:
-        out = ArmIkResult(*[None if shape is None else torch.empty(shape, dtype=torch.int32 if name == "status" else torch.float32, device=dev)
-                            for name, shape in zip(ArmIkResult._fields, want)])
-    else:
-        for name, t, shape in zip(ArmIkResult._fields, out, want):
-            if (t is None) != (shape is None) or (t is not None and (tuple(t.shape) != shape or t.device != dev or not t.is_contiguous()
-                                                                      or t.dtype != (torch.int32 if name == "status" else torch.float32))):
-                raise ValueError(f"out.{name} does not fit this call")
-    out.in_pose.copy_(in_pose.detach())
-    out.trans.copy_(trans.detach())
-    c = lambda t: None if t is None else t.detach().contiguous()
-    betas, targets, weights, prior, wrist_prior = c(betas), c(targets), c(weights), c(prior), c(wrist_prior)
+    _lm_scalars(iters, lambda0=lambda0, pose_prior_weight=pose_prior_weight, wrist_prior_weight=wrist_prior_weight)
+    _lm_model_device(dm, targets)
+    out = _lm_result(ArmIkResult, ((T, 17, 3), (T, 3), (T, 2), (T,), (T, n, 3) if joints else None, (T, 3 * n, 54) if jac else None), out,
+                     targets.device)
+    _lm_start(out, in_pose=in_pose, trans=trans)
+    betas, targets, weights, prior, wrist_prior = map(_lm_input, (betas, targets, weights, prior, wrist_prior))
     opt = _lib.ArmIkOptions(iters, lambda0, pose_prior_weight, wrist_prior_weight, int(bool(solve_wrist)), int(betas.dim() == 2))
-    with torch.cuda.device(dev):
+    with torch.cuda.device(targets.device):
         rc = _lib.lib().harp_arm_ik(ctypes.byref(dm.struct), _lib.ptr(betas), _lib.ptr(targets), _lib.ptr(weights), _lib.ptr(prior),
                                     _lib.ptr(wrist_prior), T, ctypes.byref(opt), _lib.ptr(out.in_pose), _lib.ptr(out.trans), _lib.ptr(out.cost),
                                     _lib.ptr(out.status), _lib.ptr(out.joints), _lib.ptr(out.jac), _lib.stream())
@@ -1806,49 +1787,26 @@ def mano_reproj_ik(dm, betas, targets, pose48, trans, cam, focal, S, weights=Non
     ReprojIkResult of the same shapes whose tensors are written instead of new ones — the call then allocates nothing and can be
     captured into a graph."""
     _playback_input("mano_reproj_ik", betas, targets, pose48, trans, cam, weights, depth_weights, prior, z_prior)
-    named = (("betas", betas), ("targets", targets), ("pose48", pose48), ("trans", trans), ("cam", cam), ("weights", weights),
-             ("depth_weights", depth_weights), ("prior", prior), ("z_prior", z_prior))
-    for name, t in named:
-        if t is not None and t.dtype != torch.float32:
-            raise TypeError(f"mano_reproj_ik takes float32 tensors, {name} is {t.dtype}")
+    _lm_float32("mano_reproj_ik", betas=betas, targets=targets, pose48=pose48, trans=trans, cam=cam, weights=weights,
+                depth_weights=depth_weights, prior=prior, z_prior=z_prior)
     if targets.dim() != 3 or tuple(targets.shape[1:]) != (21, 3) or targets.shape[0] < 1:
         raise ValueError(f"targets must be (N, 21, 3), got {tuple(targets.shape)}")
     N = targets.shape[0]
-    if tuple(betas.shape) not in ((10,), (N, 10)):
-        raise ValueError(f"betas must be (10,) or ({N}, 10), got {tuple(betas.shape)}")
-    if tuple(cam.shape) not in ((3,), (N, 3)):
-        raise ValueError(f"cam must be (3,) or ({N}, 3), got {tuple(cam.shape)}")
-    for name, t, shape in (("pose48", pose48, (N, 48)), ("trans", trans, (N, 3)), ("weights", weights, (N, 21)),
-                           ("depth_weights", depth_weights, (N, 21)), ("prior", prior, (N, 45)), ("z_prior", z_prior, (N,))):
-        if t is not None and tuple(t.shape) != shape:
-            raise ValueError(f"{name} must be {shape}, got {tuple(t.shape)}")
+    _lm_shapes(("betas", betas, [(10,), (N, 10)]), ("cam", cam, [(3,), (N, 3)]), ("pose48", pose48, (N, 48)), ("trans", trans, (N, 3)),
+               ("weights", weights, (N, 21)), ("depth_weights", depth_weights, (N, 21)), ("prior", prior, (N, 45)), ("z_prior", z_prior, (N,)))
     iters, lambda0, pose_prior_weight, z_prior_weight, focal = int(iters), float(lambda0), float(pose_prior_weight), float(z_prior_weight), float(focal)
-    inf = float("inf")
-    if iters < 0 or not (0.0 <= lambda0 < inf) or not (0.0 <= pose_prior_weight < inf) or not (0.0 <= z_prior_weight < inf):
-        raise ValueError(f"iters >= 0 and finite lambda0, pose_prior_weight, z_prior_weight >= 0, got {iters}, {lambda0}, {pose_prior_weight}, "
-                         f"{z_prior_weight}")
-    if not (0.0 < focal < inf) or int(S) != S or int(S) <= 0:
+    _lm_scalars(iters, lambda0=lambda0, pose_prior_weight=pose_prior_weight, z_prior_weight=z_prior_weight)
+    if not (0.0 < focal < float("inf")) or int(S) != S or int(S) <= 0:
         raise ValueError(f"focal > 0 and an image size S >= 1, got {focal}, {S}")
     if z_prior is None and z_prior_weight != 0.0:
         raise ValueError("z_prior_weight needs z_prior")
-    if dm.v_template.device != targets.device:
-        raise ValueError(f"the model is on {dm.v_template.device}, the targets on {targets.device}")
-    dev = targets.device
-    want = ((N, 48), (N, 3), (N, 2), (N,), (N, 21, 3) if proj else None, (N, 63, 51) if jac else None)
-    if out is None:
-        out = ReprojIkResult(*[None if shape is None else torch.empty(shape, dtype=torch.int32 if name == "status" else torch.float32, device=dev)
-                               for name, shape in zip(ReprojIkResult._fields, want)])
-    else:
-        for name, t, shape in zip(ReprojIkResult._fields, out, want):
-            if (t is None) != (shape is None) or (t is not None and (tuple(t.shape) != shape or t.device != dev or not t.is_contiguous()
-                                                                      or t.dtype != (torch.int32 if name == "status" else torch.float32))):
-                raise ValueError(f"out.{name} does not fit this call")
-    out.pose48.copy_(pose48.detach())
-    out.trans.copy_(trans.detach())
-    c = lambda t: None if t is None else t.detach().contiguous()
-    betas, targets, cam, weights, depth_weights, prior, z_prior = c(betas), c(targets), c(cam), c(weights), c(depth_weights), c(prior), c(z_prior)
+    _lm_model_device(dm, targets)
+    out = _lm_result(ReprojIkResult, ((N, 48), (N, 3), (N, 2), (N,), (N, 21, 3) if proj else None, (N, 63, 51) if jac else None), out,
+                     targets.device)
+    _lm_start(out, pose48=pose48, trans=trans)
+    betas, targets, cam, weights, depth_weights, prior, z_prior = map(_lm_input, (betas, targets, cam, weights, depth_weights, prior, z_prior))
     opt = _lib.ReprojIkOptions(iters, lambda0, pose_prior_weight, z_prior_weight, int(betas.dim() == 2), int(cam.dim() == 2), focal, int(S))
-    with torch.cuda.device(dev):
+    with torch.cuda.device(targets.device):
         rc = _lib.lib().harp_mano_reproj_ik(ctypes.byref(dm.struct), _lib.ptr(betas), _lib.ptr(cam), _lib.ptr(targets), _lib.ptr(weights),
                                             _lib.ptr(depth_weights), _lib.ptr(prior), _lib.ptr(z_prior), N, ctypes.byref(opt),
                                             _lib.ptr(out.pose48), _lib.ptr(out.trans), _lib.ptr(out.cost), _lib.ptr(out.status),

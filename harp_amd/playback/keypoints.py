@@ -1,7 +1,11 @@
 """The host side of Motion.from_keypoints, numpy float64 and no device: the model's rest joints, the bone-length scale, the
 Kabsch start of the root (T problems of six points each), and `ik_inputs`, which checks what a caller passed and returns the arrays that
 ops.mano_ik is fed.  `checked` is the package's one coercion and check of a tensor or array-like that a caller passed.  The SMPL-X arm's
-counterparts (Motion.from_arm_keypoints): `rest_arm_joints`, `match_arm_lengths`, `arm_palm_start`."""
+counterparts (Motion.from_arm_keypoints): `rest_arm_joints`, `match_arm_lengths`, `arm_palm_start`.  Image keypoints
+(Motion.from_image_keypoints): `camera_tz` and `project_pixels` (the player's camera), `planar_palm_starts` (the two
+starts that a plane's pixels allow) and `image_ik_inputs` for ops.mano_reproj_ik.  What the five Motion.from_* constructors set up
+alike stands once, below `checked`: `frame_cam`, `avatar_shape`, `check_init`, `init_rows`, `held_wrist`, `arm_start_rows`,
+`smoothed`."""
 import numpy as np
 import torch
 
@@ -33,6 +37,57 @@ def checked(name, x, *shapes, kind=None, split=False, tensor=False):
         raise TypeError(f"{name} must be floating point, got {a.dtype}")
     want = {None: want, "f": f"floating point {want}", "i": f"{want} integers"}[kind]
     raise ValueError(f"{name} must be {want}, got {tuple(a.shape)}" if kind is None else f"{name} must be {want}, got {a.dtype} {tuple(a.shape)}")
+
+
+def frame_cam(cam, params, T):
+    """the per-frame cam (T,3) float32 of a solved motion: `cam` (3,) or (T,3), or row 0 of the fit's when it is None"""
+    return np.broadcast_to(checked("cam", params["cam"][0] if cam is None else cam, (3,), (T, 3)).astype(np.float32), (T, 3)).copy()
+
+
+def avatar_shape(params):
+    """the avatar's shape (10,) float64 from the fit's parameter dict: given to the solve, not solved"""
+    return params["shape"].detach().cpu().numpy().astype(np.float64).reshape(10)
+
+
+def check_init(init, T, wrist=False):
+    """a warm start is None or anything with a length of T and rot / trans / pose rows (wrist=True: and wrist_pose), else a ValueError"""
+    fields = ("rot", "trans", "pose") + ("wrist_pose",) * wrist
+    if init is not None and (not all(getattr(init, k, None) is not None for k in fields) or len(init) != T):
+        raise ValueError(f"init must be a Motion of {T} frames" + " with wrist_pose" * wrist)
+
+
+def init_rows(init):
+    """(rot (T,3), trans (T,3), pose (T,45)) of a warm start, on the host as the Motion stores them"""
+    return init.rot.cpu().numpy(), init.trans.cpu().numpy(), init.pose.cpu().numpy()
+
+
+def held_wrist(wrist_pose, init, T):
+    """the arm's wrist (T,3) float64 that a solve holds, or the centre of its prior: wrist_pose (3,) or (T,3), else init's, else zeros"""
+    if init is not None and wrist_pose is None:
+        return init.wrist_pose.cpu().numpy().astype(np.float64)
+    return np.broadcast_to(np.zeros(3) if wrist_pose is None else checked("wrist_pose", wrist_pose, (3,), (T, 3)).astype(np.float64), (T, 3))
+
+
+def arm_start_rows(T, wrist, init=None):
+    """the arm's start (in_pose (T,17,3) = [rot | wrist | pose(15)], trans (T,3)), float64: init's rot, pose and trans around `wrist`, or
+    without init the model at the origin with that wrist — where the solver's own forward is evaluated for the rigid start, whose rot
+    and trans the caller then writes in"""
+    rows, trans = np.zeros((T, 17, 3)), np.zeros((T, 3))
+    rows[:, 1] = wrist
+    if init is not None:
+        rows[:, 0], trans, pose = init_rows(init)
+        rows[:, 2:] = pose.reshape(T, 15, 3)
+    return rows, trans
+
+
+def smoothed(smooth, points, w):
+    """(points (T,n,3), weights (T,n) or None) after the window filter.  smooth: None (both as they came) or a function (points, weights)
+    -> (points, used (T,n)); a joint it filled (used > 0) whose weight was <= 0 then counts as used, with weight 1; a joint with nothing
+    in its window comes back as it went in."""
+    if smooth is None:
+        return points, w
+    out, filled = smooth(points, w)
+    return np.asarray(out, np.float64), None if w is None else np.where((np.asarray(filled) > 0) & ~(w > 0), 1.0, w)
 
 
 def rest_chain_joints(model, shape):
@@ -155,14 +210,9 @@ def ik_inputs(keypoints, weights, cam, init, params, model, match_bone_lengths=T
     kp = checked("keypoints", keypoints, (None, 21, 3), kind="f", split=True).astype(np.float64)
     T = kp.shape[0]
     w = None if weights is None else checked("weights", weights, (T, 21), kind="f", split=True).astype(np.float64)
-    if init is not None and (not all(hasattr(init, k) for k in ("rot", "trans", "pose")) or len(init) != T):
-        raise ValueError(f"init must be a Motion of {T} frames")
-    if smooth is not None:
-        kp, filled = smooth(kp, w)                      # (a joint with nothing in its window comes back as it went in)
-        kp = np.asarray(kp, np.float64)
-        w = None if w is None else np.where((np.asarray(filled) > 0) & ~(w > 0), 1.0, w)
-    cam = np.broadcast_to(checked("cam", params["cam"][0] if cam is None else cam, (3,), (T, 3)).astype(np.float32), (T, 3)).copy()
-    shape = params["shape"].detach().cpu().numpy().astype(np.float64).reshape(10)
+    check_init(init, T)
+    kp, w = smoothed(smooth, kp, w)
+    cam, shape = frame_cam(cam, params, T), avatar_shape(params)
     used = np.isfinite(kp).all(-1) & (True if w is None else (w > 0))
     rest = rest_chain_joints(model, shape)
     if match_bone_lengths:
@@ -171,7 +221,7 @@ def ik_inputs(keypoints, weights, cam, init, params, model, match_bone_lengths=T
     if init is None:
         (rot, trans), pose = palm_start(kp, used, rest), np.zeros((T, 45))
     else:
-        rot, trans, pose = init.rot.cpu().numpy(), init.trans.cpu().numpy(), init.pose.cpu().numpy()
+        rot, trans, pose = init_rows(init)
     return dict(shape=shape, keypoints=kp, pose48=np.concatenate([rot, pose], 1), trans=trans, weights=w, cam=cam)
 
 
@@ -311,24 +361,21 @@ def image_ik_inputs(keypoints, weights, depth, cam, init, params, model, focal, 
     T = kp.shape[0]
     w = None if weights is None else checked("weights", weights, (T, 21), kind="f", split=True).astype(np.float64)
     d = None if depth is None else checked("depth", depth, (T, 21), kind="f", split=True).astype(np.float64)
-    if init is not None and (not all(hasattr(init, k) for k in ("rot", "trans", "pose")) or len(init) != T):
-        raise ValueError(f"init must be a Motion of {T} frames")
+    check_init(init, T)
     if smooth is not None:
-        p3, filled = smooth(np.concatenate([kp, np.zeros((T, 21, 1))], -1), w)
-        kp = np.asarray(p3, np.float64)[..., :2]
-        w = None if w is None else np.where((np.asarray(filled) > 0) & ~(w > 0), 1.0, w)
+        p3, w = smoothed(smooth, np.concatenate([kp, np.zeros((T, 21, 1))], -1), w)
+        kp = p3[..., :2]
         if d is not None:
-            d = np.asarray(smooth(np.concatenate([d[..., None], np.zeros((T, 21, 2))], -1), None)[0], np.float64)[..., 0]
-    cam = np.broadcast_to(checked("cam", params["cam"][0] if cam is None else cam, (3,), (T, 3)).astype(np.float32), (T, 3)).copy()
-    shape = params["shape"].detach().cpu().numpy().astype(np.float64).reshape(10)
+            d = smoothed(smooth, np.concatenate([d[..., None], np.zeros((T, 21, 2))], -1), None)[0][..., 0]
+    cam, shape = frame_cam(cam, params, T), avatar_shape(params)
     used = np.isfinite(kp).all(-1) & (True if w is None else (w > 0))
     rest = rest_chain_joints(model, shape)
     rot, trans, zbar = planar_palm_starts(kp, used, rest, cam, focal, S)
     if init is None:
         pose48 = np.concatenate([rot, np.zeros((T, 2, 45))], -1)
     else:
-        pose48 = np.concatenate([init.rot.cpu().numpy(), init.pose.cpu().numpy()], 1).astype(np.float64)[:, None]
-        trans = init.trans.cpu().numpy().astype(np.float64)[:, None]
+        rot, trans, pose = init_rows(init)
+        pose48, trans = np.concatenate([rot, pose], 1).astype(np.float64)[:, None], trans.astype(np.float64)[:, None]
         palm = np.array(PALM)
         # the warm start's own palm depth: the palm joints are rigid under the root rotation
         for t in range(T):

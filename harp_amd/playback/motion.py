@@ -1,8 +1,9 @@
 """The rows of a motion and what is done to them on the device: `Motion`, its retiming (ops.motion_resample), its solve
-from keypoints (ops.mano_ik, §24; the SMPL-X arm: ops.arm_ik, §29) or from mesh vertices (ops.mano_vertex_fit, §27; the SMPL-X arm:
-ops.arm_vertex_fit, §28) and the
-window filter of a motion or of keypoints (ops.motion_filter, §25).  `RowLayout` is the one description of the packed table that the
-resampler and the filter read."""
+from 3-D keypoints (ops.mano_ik, §24; the SMPL-X arm: ops.arm_ik, §29), from image keypoints (ops.mano_reproj_ik, §30) or from mesh
+vertices (ops.mano_vertex_fit, §27; the SMPL-X arm: ops.arm_vertex_fit, §28) and the window filter of a motion or of keypoints
+(ops.motion_filter, §25).  `RowLayout` is the one description of the packed table that the resampler and the filter read.  What the five
+solving constructors set up alike stands once (§34): on the host in keypoints.py, where a device is involved in the private functions
+below."""
 import numpy as np
 import torch
 
@@ -13,6 +14,31 @@ from .keypoints import checked
 
 def _rows_f32(name, a, width, T=None):
     return checked(name, a, (T, width), tensor=True).to(torch.float32).contiguous()
+
+
+def _solve_on(device, params):
+    """(the device a Motion.from_* solve runs on: `device`, by default that of params["shape"] when it is a HIP device, else "cuda"; the
+    float32 upload of a host array to it, None staying None)"""
+    dev = torch.device(device if device is not None else (params["shape"].device if params["shape"].is_cuda else "cuda"))
+    return dev, lambda x: None if x is None else torch.as_tensor(np.ascontiguousarray(x, dtype=np.float32)).to(dev)
+
+
+def _hand_device_model(hand_layer, dev):
+    from ..manopth.manolayer import ManoDeviceModel
+    return ManoDeviceModel(hand_layer._model_np, dev)
+
+
+def _arm_device_model(arm_layer, dev):
+    """the layer's own TreeDeviceModel when it lives on `dev`, else one made there"""
+    if arm_layer._dev == dev:
+        return arm_layer.device_model
+    from ..hand_models_harp.body_models import TreeDeviceModel
+    return TreeDeviceModel(arm_layer._model_np, dev)
+
+
+def _window(smooth, dev, joints=21):
+    """smooth=sigma as the function K.smoothed takes: smooth_keypoints on `dev`, its two results brought to the host; None for None"""
+    return None if smooth is None else lambda kp, w: tuple(t.cpu().numpy() for t in smooth_keypoints(kp, weights=w, sigma=smooth, device=dev, joints=joints))
 
 
 class RowLayout:
@@ -63,6 +89,11 @@ class Motion:
         return self.pose.shape[0]
 
     @classmethod
+    def _from_arm_result(cls, res, cam):
+        """a solved arm result's in_pose (T,17,3) = [rot | wrist | pose(15)] and trans -> the Motion with wrist_pose"""
+        return cls(res.in_pose[:, 2:].reshape(-1, 45), res.in_pose[:, 0], res.trans, cam, wrist_pose=res.in_pose[:, 1])
+
+    @classmethod
     def from_params(cls, params, rows=None, per_frame_light=False):
         """The fit's own frames (all of them, or `rows` of its tables, in that order): the replay case.  The motion carries no light
         unless per_frame_light=True: a fit with share_light_position (the default) reads and updates row 0 of its light table only, the
@@ -94,13 +125,9 @@ class Motion:
         if "pose_mean" in hand_layer._model_np:
             raise NotImplementedError("Motion.from_keypoints solves the MANO hand; the SMPL-X arm needs a kinematic-tree solver: "
                                       "Motion.from_arm_keypoints")
-        dev = torch.device(device if device is not None else (params["shape"].device if params["shape"].is_cuda else "cuda"))
-        host = lambda pair: tuple(t.cpu().numpy() for t in pair)      # noqa: E731
-        a = K.ik_inputs(keypoints, weights, cam, init, params, hand_layer._model_np, match_bone_lengths,
-                        None if smooth is None else lambda kp, w: host(smooth_keypoints(kp, weights=w, sigma=smooth, device=dev)))
-        from ..manopth.manolayer import ManoDeviceModel
-        up = lambda x: None if x is None else torch.as_tensor(np.ascontiguousarray(x, dtype=np.float32)).to(dev)
-        res = ops.mano_ik(ManoDeviceModel(hand_layer._model_np, dev), up(a["shape"]), up(a["keypoints"]), up(a["pose48"]), up(a["trans"]),
+        dev, up = _solve_on(device, params)
+        a = K.ik_inputs(keypoints, weights, cam, init, params, hand_layer._model_np, match_bone_lengths, _window(smooth, dev))
+        res = ops.mano_ik(_hand_device_model(hand_layer, dev), up(a["shape"]), up(a["keypoints"]), up(a["pose48"]), up(a["trans"]),
                           weights=up(a["weights"]), iters=iters, prior_weight=prior_weight)
         return cls(res.pose48[:, 3:], res.pose48[:, :3], res.trans, a["cam"])
 
@@ -141,16 +168,12 @@ class Motion:
         for name, v in (("depth_weight", depth_weight), ("prior_weight", prior_weight), ("depth_prior_weight", depth_prior_weight)):
             if not (0.0 <= float(v) < float("inf")):
                 raise ValueError(f"{name} must be finite and >= 0, got {v}")
-        dev = torch.device(device if device is not None else (params["shape"].device if params["shape"].is_cuda else "cuda"))
-        host = lambda pair: tuple(t.cpu().numpy() for t in pair)      # noqa: E731
-        a = K.image_ik_inputs(keypoints, weights, depth, cam, init, params, hand_layer._model_np, focal, S,
-                              None if smooth is None else lambda kp, w: host(smooth_keypoints(kp, weights=w, sigma=smooth, device=dev)))
+        dev, up = _solve_on(device, params)
+        a = K.image_ik_inputs(keypoints, weights, depth, cam, init, params, hand_layer._model_np, focal, S, _window(smooth, dev))
         T, C = a["pose48"].shape[:2]
-        from ..manopth.manolayer import ManoDeviceModel
-        up = lambda x: None if x is None else torch.as_tensor(np.ascontiguousarray(x, dtype=np.float32)).to(dev)
-        rep = lambda x: None if x is None else np.repeat(x, C, axis=0)      # frame-major: problem t * C + c
+        rep =lambda x: None if x is None else np.repeat(x, C, axis=0)      # frame-major: problem t * C + c
         scale = (focal / a["depth"]) ** 2                               # (T,) px^2 per squared metre (radian) at the start's palm depth
-        res = ops.mano_reproj_ik(ManoDeviceModel(hand_layer._model_np, dev), up(a["shape"]), up(rep(a["targets"])),
+        res = ops.mano_reproj_ik(_hand_device_model(hand_layer, dev), up(a["shape"]), up(rep(a["targets"])),
                                  up(a["pose48"].reshape(T * C, 48)), up(a["trans"].reshape(T * C, 3)), up(rep(a["cam"])), focal, S,
                                  weights=up(rep(a["weights"])),
                                  depth_weights=None if depth is None else up(rep(np.broadcast_to((depth_weight * scale)[:, None], (T, 21)))),
@@ -177,17 +200,13 @@ class Motion:
         if "pose_mean" in hand_layer._model_np:
             raise NotImplementedError("Motion.from_vertices fits the MANO hand; the SMPL-X arm needs a fit over its kinematic tree: "
                                       "Motion.from_arm_vertices")
-        dev = torch.device(device if device is not None else (params["shape"].device if params["shape"].is_cuda else "cuda"))
+        dev, up = _solve_on(device, params)
         v = checked("vertices", vertices, (None, 778, 3), kind="f", split=True).astype(np.float64)
         T = v.shape[0]
         w = None if weights is None else checked("weights", weights, (T, 778), kind="f", split=True).astype(np.float64)
-        if init is not None and (not all(hasattr(init, k) for k in ("rot", "trans", "pose")) or len(init) != T):
-            raise ValueError(f"init must be a Motion of {T} frames")
-        cam = np.broadcast_to(checked("cam", params["cam"][0] if cam is None else cam, (3,), (T, 3)).astype(np.float32), (T, 3)).copy()
-        shape = params["shape"].detach().cpu().numpy().astype(np.float64).reshape(10)
-        from ..manopth.manolayer import ManoDeviceModel
-        dm = ManoDeviceModel(hand_layer._model_np, dev)
-        up = lambda x: None if x is None else torch.as_tensor(np.ascontiguousarray(x, dtype=np.float32)).to(dev)
+        K.check_init(init, T)
+        cam, shape = K.frame_cam(cam, params, T), K.avatar_shape(params)
+        dm = _hand_device_model(hand_layer, dev)
         targets, betas = up(v), up(shape)
         if init is None:
             # the model's vertices at this shape and zero stored pose: the solver's own forward, evaluated at the origin
@@ -196,7 +215,7 @@ class Motion:
                                         K.rest_chain_joints(hand_layer._model_np, shape)[0])
             pose = np.zeros((T, 45))
         else:
-            rot, trans, pose = init.rot.cpu().numpy(), init.trans.cpu().numpy(), init.pose.cpu().numpy()
+            rot, trans, pose = K.init_rows(init)
         res = ops.mano_vertex_fit(dm, targets, up(np.concatenate([rot, pose], 1)), betas, up(trans), weights=up(w), solve_shape=False, iters=iters,
                                   pose_prior_weight=pose_prior_weight)
         return cls(res.pose48[:, 3:], res.pose48[:, :3], res.trans, cam)
@@ -218,11 +237,8 @@ class Motion:
         carries no light: AvatarPlayer.load_motion then uses the fit's row 0."""
         if "pose_mean" not in arm_layer._model_np:
             raise ValueError("Motion.from_arm_vertices fits the SMPL-X arm layer; Motion.from_vertices fits the MANO hand")
-        dev = torch.device(device if device is not None else (params["shape"].device if params["shape"].is_cuda else "cuda"))
-        dm = arm_layer.device_model if arm_layer._dev == dev else None
-        if dm is None:
-            from ..hand_models_harp.body_models import TreeDeviceModel
-            dm = TreeDeviceModel(arm_layer._model_np, dev)
+        dev, up = _solve_on(device, params)
+        dm = _arm_device_model(arm_layer, dev)
         NV = int(dm.NV)
         n = int(np.shape(vertices)[1]) if np.ndim(vertices) == 3 else -1
         if n not in (NV, 778):
@@ -231,33 +247,21 @@ class Motion:
         v = checked("vertices", vertices, (None, n, 3), kind="f", split=True).astype(np.float64)
         T = v.shape[0]
         w = None if weights is None else checked("weights", weights, (T, n), kind="f", split=True).astype(np.float64)
-        if init is not None and (not all(getattr(init, k, None) is not None for k in ("rot", "trans", "pose", "wrist_pose")) or len(init) != T):
-            raise ValueError(f"init must be a Motion of {T} frames with wrist_pose")
+        K.check_init(init, T, wrist=True)
         if arm_topology and wrist_pose is not None:
             raise ValueError("wrist_pose is what a fit to MANO-topology vertices holds the wrist at; arm-topology vertices solve it")
-        cam = np.broadcast_to(checked("cam", params["cam"][0] if cam is None else cam, (3,), (T, 3)).astype(np.float32), (T, 3)).copy()
-        shape = params["shape"].detach().cpu().numpy().astype(np.float64).reshape(10)
-        if init is not None and wrist_pose is None:
-            wrist = init.wrist_pose.cpu().numpy().astype(np.float64)
-        else:
-            wrist = np.broadcast_to(np.zeros(3) if wrist_pose is None else checked("wrist_pose", wrist_pose, (3,), (T, 3)).astype(np.float64), (T, 3))
-        up = lambda x: None if x is None else torch.as_tensor(np.ascontiguousarray(x, dtype=np.float32)).to(dev)
+        cam, shape = K.frame_cam(cam, params, T), K.avatar_shape(params)
         idx = None if arm_topology else arm_layer.right_mano_idx.to(dev)
         targets, betas = up(v), up(shape)
-        rows = np.zeros((T, 17, 3))
-        rows[:, 1] = wrist
+        rows, trans = K.arm_start_rows(T, K.held_wrist(wrist_pose, init, T), init)
         if init is None:
             # the model's vertices at this shape and wrist with zero stored pose: the solver's own forward, evaluated at the origin
-            zero = ops.arm_vertex_fit(dm, targets, up(rows), betas, up(np.zeros((T, 3))), vert_idx=idx, solve_shape=False, iters=0, verts=True).verts
+            zero = ops.arm_vertex_fit(dm, targets, up(rows), betas, up(trans), vert_idx=idx, solve_shape=False, iters=0, verts=True).verts
             rest = (zero if idx is None else zero[:, idx]).cpu().numpy().astype(np.float64) / 1000.0
-            rot, trans = K.vertex_start(v, np.ones((T, n)) if w is None else w, rest, np.zeros(3))
-            rows[:, 0] = rot
-        else:
-            rows[:, 0], trans = init.rot.cpu().numpy(), init.trans.cpu().numpy()
-            rows[:, 2:] = init.pose.cpu().numpy().reshape(T, 15, 3)
+            rows[:, 0], trans = K.vertex_start(v, np.ones((T, n)) if w is None else w, rest, np.zeros(3))
         res = ops.arm_vertex_fit(dm, targets, up(rows), betas, up(trans), vert_idx=idx, weights=up(w), solve_shape=False, solve_wrist=arm_topology,
                                  iters=iters, pose_prior_weight=pose_prior_weight, wrist_prior_weight=wrist_prior_weight)
-        return cls(res.in_pose[:, 2:].reshape(T, 45), res.in_pose[:, 0], res.trans, cam, wrist_pose=res.in_pose[:, 1])
+        return cls._from_arm_result(res, cam)
 
     @classmethod
     def from_arm_keypoints(cls, keypoints, params, arm_layer, cam=None, weights=None, match_bone_lengths=True, iters=15, prior_weight=1e-5,
@@ -291,45 +295,29 @@ class Motion:
         kp = checked("keypoints", keypoints, (None, n, 3), kind="f", split=True).astype(np.float64)
         T = kp.shape[0]
         w = None if weights is None else checked("weights", weights, (T, n), kind="f", split=True).astype(np.float64)
-        if init is not None and (not all(getattr(init, k, None) is not None for k in ("rot", "trans", "pose", "wrist_pose")) or len(init) != T):
-            raise ValueError(f"init must be a Motion of {T} frames with wrist_pose")
-        cam = np.broadcast_to(checked("cam", params["cam"][0] if cam is None else cam, (3,), (T, 3)).astype(np.float32), (T, 3)).copy()
-        shape = params["shape"].detach().cpu().numpy().astype(np.float64).reshape(10)
-        if init is not None and wrist_pose is None:
-            wrist = init.wrist_pose.cpu().numpy().astype(np.float64)
-        else:
-            wrist = np.broadcast_to(np.zeros(3) if wrist_pose is None else checked("wrist_pose", wrist_pose, (3,), (T, 3)).astype(np.float64), (T, 3))
-        dev = torch.device(device if device is not None else (params["shape"].device if params["shape"].is_cuda else "cuda"))
-        if smooth is not None:
-            kp_s, filled = smooth_keypoints(kp, weights=w, sigma=smooth, device=dev, joints=n)
-            kp = kp_s.cpu().numpy().astype(np.float64)              # (a joint with nothing in its window comes back as it went in)
-            w = None if w is None else np.where((filled.cpu().numpy() > 0) & ~(w > 0), 1.0, w)
+        K.check_init(init, T, wrist=True)
+        cam, shape = K.frame_cam(cam, params, T), K.avatar_shape(params)
+        wrist = K.held_wrist(wrist_pose, init, T)
+        dev, up = _solve_on(device, params)
+        kp, w = K.smoothed(_window(smooth, dev, n), kp, w)
         used = np.isfinite(kp).all(-1) & (True if w is None else (w > 0))
         if match_bone_lengths:
             kp, _ = K.match_arm_lengths(kp, used, K.rest_arm_joints(arm_layer._model_np, shape))
-        dm = arm_layer.device_model if arm_layer._dev == dev else None
-        if dm is None:
-            from ..hand_models_harp.body_models import TreeDeviceModel
-            dm = TreeDeviceModel(arm_layer._model_np, dev)
-        up = lambda x: None if x is None else torch.as_tensor(np.ascontiguousarray(x, dtype=np.float32)).to(dev)
+        dm = _arm_device_model(arm_layer, dev)
         # the hand alone is the 22-wide problem with the elbow unused and the wrist held
         tg = kp if n == 22 else np.concatenate([kp, np.full((T, 1, 3), np.nan)], 1)
         wt = used.astype(np.float64) if w is None else np.where(used, w, 0.0)
         wt = wt if n == 22 else np.concatenate([wt, np.zeros((T, 1))], 1)
         targets, betas = up(tg), up(shape)
-        rows = np.zeros((T, 17, 3))
-        rows[:, 1] = wrist if init is None or n == 21 else init.wrist_pose.cpu().numpy()      # (a solved wrist starts where init has it)
+        # (a solved wrist starts where init has it, whatever the centre of its prior)
+        rows, trans = K.arm_start_rows(T, wrist if init is None or n == 21 else init.wrist_pose.cpu().numpy(), init)
         if init is None:
             # the model's joints at this shape and wrist with zero stored pose: the solver's own forward, evaluated at the origin
-            zero = ops.arm_ik(dm, betas, targets, up(rows), up(np.zeros((T, 3))), iters=0, joints=True).joints
-            rot, trans = K.arm_palm_start(kp, used, zero.cpu().numpy().astype(np.float64) / 1000.0)
-            rows[:, 0] = rot
-        else:
-            rows[:, 0], trans = init.rot.cpu().numpy(), init.trans.cpu().numpy()
-            rows[:, 2:] = init.pose.cpu().numpy().reshape(T, 15, 3)
+            zero = ops.arm_ik(dm, betas, targets, up(rows), up(trans), iters=0, joints=True).joints
+            rows[:, 0], trans = K.arm_palm_start(kp, used, zero.cpu().numpy().astype(np.float64) / 1000.0)
         res = ops.arm_ik(dm, betas, targets, up(rows), up(trans), weights=up(wt), wrist_prior=up(wrist), solve_wrist=n == 22, iters=iters,
                          pose_prior_weight=prior_weight, wrist_prior_weight=wrist_prior_weight)
-        return cls(res.in_pose[:, 2:].reshape(T, 45), res.in_pose[:, 0], res.trans, cam, wrist_pose=res.in_pose[:, 1])
+        return cls._from_arm_result(res, cam)
 
     def save(self, path):
         np.savez(path, **{k: getattr(self, k).cpu().numpy() for k in self.FIELDS if getattr(self, k) is not None})
@@ -387,9 +375,10 @@ def _segment_ids(segments, T):
 
 def smooth_keypoints(keypoints, weights=None, sigma=2.0, radius=None, trim=None, segments=None, device="cuda", joints=21):
     """(T,21,3) keypoints through the window filter as 21 vector channels (ops.motion_filter) -> (keypoints (T,21,3) float32,
-    used (T,21) int32), both on `device`.  joints=22: the SMPL-X arm's layout, the elbow as one more point row of the same call.  weights: None or (T,21) confidences.  A joint with a non-finite coordinate or a weight <= 0 has
+    used (T,21) int32), both on `device`.  weights: None or (T,21) confidences.  A joint with a non-finite coordinate or a weight <= 0 has
     weight 0: it does not pull on its neighbours and is FILLED from them when any lie in the window (used > 0); with none it comes back as
-    it went in (used == 0).  trim: None or a distance in the keypoints' unit for the trimmed second pass; segments: as Motion.smooth."""
+    it went in (used == 0).  trim: None or a distance in the keypoints' unit for the trimmed second pass; segments: as Motion.smooth.
+    joints=22: the SMPL-X arm's layout, the elbow as one more point row of the same call."""
     n = int(joints)
     kp = checked("keypoints", keypoints, (None, n, 3), kind="f", tensor=True).to(torch.float32)
     T = kp.shape[0]

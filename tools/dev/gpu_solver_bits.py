@@ -7,7 +7,11 @@ Each batch: 4 problems from a start near the truth (the targets are the solver's
 every optional output; problem 3 has fewer used targets than the solver asks for (status -1), one unused target is NaN, and problem 2 of
 the reprojection solve starts with its used joints behind the camera (status -2).
 
-    python tools/dev/gpu_solver_bits.py [--out profiles/lm_core_bits_new.json]"""
+The second part does the same for the layer above: every field of the Motion that each of the five Motion.from_*
+constructors returns for 4 frames, once from the rigid start, once with init= and, for the three keypoint constructors, once with
+smooth=1.0 (a dropped joint is filled); the arm's two in both of their input layouts.  Public API only, as the first part.
+
+    python tools/dev/gpu_solver_bits.py [--out profiles/solver_front_bits_new.json]"""
 import argparse
 import hashlib
 import json
@@ -141,6 +145,104 @@ def arm(res):
                    args + (kw["weights"], prior))
 
 
+def record_motion(res, name, m):
+    for f in m.FIELDS:
+        if getattr(m, f) is not None:
+            res[f"Motion.{name}/{f}"] = digest(getattr(m, f))
+
+
+def hand_motions(res):
+    """Motion.from_keypoints, from_image_keypoints and from_vertices: from the rigid start, with init=, and (keypoints) with smooth=1.0"""
+    from harp_amd import ops, synth
+    from harp_amd.manopth.manolayer import ManoLayer
+    from harp_amd.playback import Motion
+    layer = ManoLayer(flat_hand_mean=False, use_pca=False, model=synth.make_mano_model(), device=DEV)
+    dm = layer.device_model
+    rng = np.random.default_rng(41)
+    pose = np.concatenate([rng.normal(size=(T, 3)) * 0.5, rng.normal(size=(T, 45)) * 0.2], 1)
+    trans = rng.uniform(-0.03, 0.03, size=(T, 3))
+    shape = rng.normal(size=10) * 0.5
+    cam = np.array(CAM) + rng.uniform(-0.01, 0.01, size=(T, 3))
+    params = dict(shape=up(shape), cam=up(cam))
+    init = Motion(pose[:, 3:] + rng.normal(size=(T, 45)) * 0.05, pose[:, :3] + rng.normal(size=(T, 3)) * 0.05,
+                  trans + rng.normal(size=(T, 3)) * 0.005, cam)
+    w = rng.uniform(0.5, 1.5, size=(T, 21))
+    w[1, 7] = 0.0                                          # a joint that the window fills under smooth=
+
+    kp = (ops.mano_ik(dm, up(shape), torch.zeros(T, 21, 3, device=DEV), up(pose), up(trans), iters=0, joints=True).joints / 1000.0).cpu().double().numpy()
+    noisy = kp * 1.07 + rng.normal(size=kp.shape) * 1e-3   # another hand's size: the bone-length scale has work to do
+    noisy[2, 11] = np.nan
+    record_motion(res, "from_keypoints/rigid", Motion.from_keypoints(noisy, params, layer, weights=w, device=DEV))
+    record_motion(res, "from_keypoints/init", Motion.from_keypoints(noisy, params, layer, cam=cam[0], init=init, device=DEV))
+    record_motion(res, "from_keypoints/smooth", Motion.from_keypoints(noisy, params, layer, weights=w, smooth=1.0, device=DEV))
+
+    Z = kp[..., 2] + 2.0 * FOCAL / (S * cam[:, :1] + 1e-9)
+    px = np.stack([S / 2 + FOCAL * (kp[..., 0] + cam[:, 1:2]) / Z, S / 2 + FOCAL * (kp[..., 1] + cam[:, 2:3]) / Z], -1)
+    px = px + rng.normal(size=px.shape) * 0.3
+    px[2, 11] = np.nan
+    depth = kp[..., 2] - kp[:, :1, 2]
+    cfg = dict(focal_length=FOCAL, img_size=S)
+    record_motion(res, "from_image_keypoints/rigid", Motion.from_image_keypoints(px, params, layer, cam=cam, weights=w, depth=depth, configs=cfg, device=DEV))
+    record_motion(res, "from_image_keypoints/init", Motion.from_image_keypoints(px, params, layer, cam=cam, init=init, configs=cfg, device=DEV))
+    record_motion(res, "from_image_keypoints/smooth",
+                  Motion.from_image_keypoints(px, params, layer, cam=cam, weights=w, depth=depth, smooth=1.0, configs=cfg, device=DEV))
+
+    verts = (ops.mano_vertex_fit(dm, torch.zeros(T, 778, 3, device=DEV), up(pose), up(shape), up(trans), solve_shape=False, iters=0,
+                                 verts=True).verts / 1000.0).cpu().double().numpy()
+    verts = verts + rng.normal(size=verts.shape) * 1e-3
+    verts[0, 5] = np.nan
+    wv = rng.uniform(0.5, 1.5, size=(T, 778))
+    record_motion(res, "from_vertices/rigid", Motion.from_vertices(verts, params, layer, weights=wv, pose_prior_weight=1e-4, device=DEV))
+    record_motion(res, "from_vertices/init", Motion.from_vertices(verts, params, layer, init=init, device=DEV))
+
+
+def arm_motions(res):
+    """Motion.from_arm_vertices (arm and MANO topology) and from_arm_keypoints (with and without the elbow): rigid start, init=, smooth=1.0"""
+    from harp_amd import ops, synth
+    from harp_amd.hand_models_harp.body_models import SMPLXARM
+    from harp_amd.playback import Motion
+    import harp_amd
+    model = synth.make_smplx_arm_model(seed=0)
+    corr = np.load(os.path.join(os.path.dirname(os.path.abspath(harp_amd.__file__)), "assets", "arm_corr.npz"))
+    layer = SMPLXARM(model, model["faces"], corr["mano_vert_from_arm"], device=DEV)
+    dm = layer.device_model
+    rng = np.random.default_rng(43)
+    rows = np.concatenate([rng.normal(size=(T, 1, 3)) * 0.5, rng.normal(size=(T, 1, 3)) * 0.1, rng.normal(size=(T, 15, 3)) * 0.2], 1)
+    trans = rng.uniform(-0.2, 0.2, size=(T, 3))
+    shape = rng.normal(size=10) * 0.5
+    cam = np.array(CAM) + rng.uniform(-0.01, 0.01, size=(T, 3))
+    params = dict(shape=up(shape), cam=up(cam))
+    init = Motion(rows[:, 2:].reshape(T, 45) + rng.normal(size=(T, 45)) * 0.05, rows[:, 0] + rng.normal(size=(T, 3)) * 0.05,
+                  trans + rng.normal(size=(T, 3)) * 0.005, cam, wrist_pose=rows[:, 1] + rng.normal(size=(T, 3)) * 0.02)
+
+    n = int(dm.struct.n_joints_out)
+    kp = (ops.arm_ik(dm, up(shape), torch.zeros(T, n, 3, device=DEV), up(rows), up(trans), iters=0, joints=True).joints / 1000.0).cpu().double().numpy()
+    noisy = trans[:, None] + (kp - trans[:, None]) * 1.05 + rng.normal(size=kp.shape) * 1e-3
+    noisy[2, 11] = np.nan
+    w = rng.uniform(0.5, 1.5, size=(T, n))
+    w[1, 7] = 0.0
+    record_motion(res, "from_arm_keypoints/rigid", Motion.from_arm_keypoints(noisy, params, layer, weights=w, device=DEV))
+    record_motion(res, "from_arm_keypoints/init", Motion.from_arm_keypoints(noisy, params, layer, cam=cam[0], init=init, wrist_pose=rows[0, 1], device=DEV))
+    record_motion(res, "from_arm_keypoints/smooth", Motion.from_arm_keypoints(noisy, params, layer, weights=w, smooth=1.0, device=DEV))
+    record_motion(res, "from_arm_keypoints/hand_rigid",
+                  Motion.from_arm_keypoints(noisy[:, :21], params, layer, weights=w[:, :21], wrist_pose=rows[:, 1], device=DEV))
+    record_motion(res, "from_arm_keypoints/hand_init", Motion.from_arm_keypoints(noisy[:, :21], params, layer, init=init, device=DEV))
+    record_motion(res, "from_arm_keypoints/hand_smooth", Motion.from_arm_keypoints(noisy[:, :21], params, layer, smooth=1.0, device=DEV))
+
+    NV = int(model["v_template"].shape[0])
+    verts = (ops.arm_vertex_fit(dm, torch.zeros(T, NV, 3, device=DEV), up(rows), up(shape), up(trans), solve_shape=False, iters=0,
+                                verts=True).verts / 1000.0).cpu().double().numpy()
+    verts = verts + rng.normal(size=verts.shape) * 1e-3
+    verts[0, 5] = np.nan
+    wv = rng.uniform(0.5, 1.5, size=(T, NV))
+    idx = np.asarray(corr["mano_vert_from_arm"]).reshape(-1)
+    record_motion(res, "from_arm_vertices/rigid", Motion.from_arm_vertices(verts, params, layer, weights=wv, pose_prior_weight=1e-4, device=DEV))
+    record_motion(res, "from_arm_vertices/init", Motion.from_arm_vertices(verts, params, layer, init=init, device=DEV))
+    record_motion(res, "from_arm_vertices/mano_rigid",
+                  Motion.from_arm_vertices(verts[:, idx], params, layer, weights=wv[:, idx], wrist_pose=rows[:, 1], device=DEV))
+    record_motion(res, "from_arm_vertices/mano_init", Motion.from_arm_vertices(verts[:, idx], params, layer, cam=cam, init=init, device=DEV))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -148,6 +250,8 @@ def main():
     res = {}
     hand(res)
     arm(res)
+    hand_motions(res)
+    arm_motions(res)
     torch.cuda.synchronize()
     print(json.dumps(res, indent=1))
     if a.out:
