@@ -418,3 +418,15 @@ class ReprojIkOptions(ctypes.Structure):
 SIGNATURES["harp_mano_reproj_ik_frames_per_block"] = (_i, [])
 SIGNATURES["harp_mano_reproj_ik"] = (_i, [_mp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, ctypes.POINTER(ReprojIkOptions), _vp, _vp, _vp, _vp, _vp, _vp,
                                           _vp])
+
+
+class ArmReprojIkOptions(ctypes.Structure):
+    """mirror of `harp_arm_reproj_ik_options` (include/harp_hip.h)"""
+    _fields_ = [("iters", _i), ("lambda0", _f), ("pose_prior_weight", _f), ("wrist_prior_weight", _f), ("z_prior_weight", _f), ("solve_wrist", _i),
+                ("betas_per_frame", _i), ("cam_per_frame", _i), ("focal", _f), ("S", _i)]
+
+
+# batched 2.5-D reprojection inverse kinematics of the SMPL-X arm (csrc/arm_reproj_ik.hip)
+SIGNATURES["harp_arm_reproj_ik_frames_per_block"] = (_i, [])
+SIGNATURES["harp_arm_reproj_ik"] = (_i, [_trp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, ctypes.POINTER(ArmReprojIkOptions), _vp, _vp, _vp, _vp,
+                                         _vp, _vp, _vp])

@@ -1511,7 +1511,7 @@ def flow_layers(layers, to, ss=1, scene_depth=None, scene_rows=None, scene_depth
     return o
 
 
-# ---- the front that the five batched Levenberg-Marquardt solvers below share --------------------------------------------
+# ---- the front that the six batched Levenberg-Marquardt solvers below share ---------------------------------------------
 # A wrapper runs, in this order: _playback_input (device tensors, forward only), _lm_float32, its own check of `targets`, _lm_shapes,
 # _lm_scalars, its own checks, _lm_model_device, _lm_result, _lm_start, _lm_input, then its options struct and its one call.
 def _lm_float32(fn, **named):
@@ -1812,4 +1812,64 @@ def mano_reproj_ik(dm, betas, targets, pose48, trans, cam, focal, S, weights=Non
                                             _lib.ptr(out.pose48), _lib.ptr(out.trans), _lib.ptr(out.cost), _lib.ptr(out.status),
                                             _lib.ptr(out.proj), _lib.ptr(out.jac), _lib.stream())
     _lib.check(rc, "harp_mano_reproj_ik")
+    return out
+
+
+# ---- batched 2.5-D reprojection inverse kinematics of the SMPL-X arm (csrc/arm_reproj_ik.hip) -------------------------
+ArmReprojIkResult = collections.namedtuple("ArmReprojIkResult", "in_pose trans cost status proj jac")
+
+
+def arm_reproj_ik_frames_per_block():
+    """the problems one workgroup of harp_arm_reproj_ik solves"""
+    return int(_lib.lib().harp_arm_reproj_ik_frames_per_block())
+
+
+def arm_reproj_ik(dm, betas, targets, in_pose, trans, cam, focal, S, weights=None, depth_weights=None, prior=None, wrist_prior=None, z_prior=None,
+                  solve_wrist=True, iters=20, lambda0=1e-3, pose_prior_weight=0.0, wrist_prior_weight=0.0, z_prior_weight=0.0, proj=False,
+                  jac=False, out=None):
+    """Image keypoints -> SMPL-X arm rows: N Levenberg-Marquardt solves in one launch (csrc/arm_reproj_ik.hip: harp_arm_reproj_ik, whose
+    contract include/harp_hip.h states), forward only.  dm: a TreeDeviceModel (hand_models_harp.body_models) with n = n_joints_out output
+    joints (the arm: 22 = the wrist, the five fingers root to tip, the elbow); betas (10,) for all problems or (N,10); targets (N,n,3) =
+    (u, v, d): continuous pixels (the centre of column i at i + 0.5) and the depth relative to the wrist in metres, in the order of the
+    model's joints; in_pose (N,17,3) = [rot | wrist | pose(15)] and trans (N,3): the start, left untouched; solve_wrist=False holds the
+    wrist row at what in_pose gives; cam (3,) or (N,3), focal (pixels) and S (the image size): the player's camera; weights (N,n) or None
+    (ones) on the pixel rows and depth_weights (N,n) or None (no depth rows), both in px^2 per squared unit of the residual — an entry with
+    weight <= 0 or a non-finite target is unused; prior (N,45) or None (the mean pose) with pose_prior_weight on sum (pose - prior)^2;
+    wrist_prior (N,3) or None (zeros) with wrist_prior_weight on sum (wrist - wrist_prior)^2; z_prior (N,) with z_prior_weight on
+    (trans_z - z_prior)^2 (None: the weight must be 0).  Returns ArmReprojIkResult(in_pose, trans, cost (N,2) = at the start and at the
+    result, status (N,) int32 = accepted steps, -1 for a problem with fewer than 4 used pixel joints, -2 for a tree the kernel's tables do
+    not hold or -3 for one with a used joint behind the camera at the start (all returned as they came), proj (N,n,3) = (u, v, d) or None,
+    jac (N,3 n,54) or None), the optional ones at the result.  iters = 0 evaluates at the start.  out: an earlier ArmReprojIkResult of the
+    same shapes whose tensors are written instead of new ones — the call then allocates nothing and can be captured into a graph."""
+    _playback_input("arm_reproj_ik", betas, targets, in_pose, trans, cam, weights, depth_weights, prior, wrist_prior, z_prior)
+    _lm_float32("arm_reproj_ik", betas=betas, targets=targets, in_pose=in_pose, trans=trans, cam=cam, weights=weights, depth_weights=depth_weights,
+                prior=prior, wrist_prior=wrist_prior, z_prior=z_prior)
+    n = int(dm.struct.n_joints_out)
+    if targets.dim() != 3 or tuple(targets.shape[1:]) != (n, 3) or targets.shape[0] < 1:
+        raise ValueError(f"targets must be (N, {n}, 3), got {tuple(targets.shape)}")
+    N = int(targets.shape[0])
+    _lm_shapes(("betas", betas, [(10,), (N, 10)]), ("cam", cam, [(3,), (N, 3)]), ("in_pose", in_pose, (N, 17, 3)), ("trans", trans, (N, 3)),
+               ("weights", weights, (N, n)), ("depth_weights", depth_weights, (N, n)), ("prior", prior, (N, 45)),
+               ("wrist_prior", wrist_prior, (N, 3)), ("z_prior", z_prior, (N,)))
+    iters, lambda0, focal = int(iters), float(lambda0), float(focal)
+    pose_prior_weight, wrist_prior_weight, z_prior_weight = float(pose_prior_weight), float(wrist_prior_weight), float(z_prior_weight)
+    _lm_scalars(iters, lambda0=lambda0, pose_prior_weight=pose_prior_weight, wrist_prior_weight=wrist_prior_weight, z_prior_weight=z_prior_weight)
+    if not (0.0 < focal < float("inf")) or int(S) != S or int(S) <= 0:
+        raise ValueError(f"focal > 0 and an image size S >= 1, got {focal}, {S}")
+    if z_prior is None and z_prior_weight != 0.0:
+        raise ValueError("z_prior_weight needs z_prior")
+    _lm_model_device(dm, targets)
+    out = _lm_result(ArmReprojIkResult, ((N, 17, 3), (N, 3), (N, 2), (N,), (N, n, 3) if proj else None, (N, 3 * n, 54) if jac else None), out,
+                     targets.device)
+    _lm_start(out, in_pose=in_pose, trans=trans)
+    betas, targets, cam, weights, depth_weights, prior, wrist_prior, z_prior = map(
+        _lm_input, (betas, targets, cam, weights, depth_weights, prior, wrist_prior, z_prior))
+    opt = _lib.ArmReprojIkOptions(iters, lambda0, pose_prior_weight, wrist_prior_weight, z_prior_weight, int(bool(solve_wrist)),
+                                  int(betas.dim() == 2), int(cam.dim() == 2), focal, int(S))
+    with torch.cuda.device(targets.device):
+        rc = _lib.lib().harp_arm_reproj_ik(ctypes.byref(dm.struct), _lib.ptr(betas), _lib.ptr(cam), _lib.ptr(targets), _lib.ptr(weights),
+                                           _lib.ptr(depth_weights), _lib.ptr(prior), _lib.ptr(wrist_prior), _lib.ptr(z_prior), N,
+                                           ctypes.byref(opt), _lib.ptr(out.in_pose), _lib.ptr(out.trans), _lib.ptr(out.cost),
+                                           _lib.ptr(out.status), _lib.ptr(out.proj), _lib.ptr(out.jac), _lib.stream())
+    _lib.check(rc, "harp_arm_reproj_ik")
     return out

@@ -5,9 +5,9 @@ it over a video or a plain background as finished 8-bit frames (DESIGN.md Â§22-Â
 The package in five modules, each importing only those before it:
 
   keypoints  the float64 host side of the keypoint solve: rest joints, bone-length scale, Kabsch start, `ik_inputs`; `vertex_start`, the
-             batched rigid start of the vertex fit; `rest_arm_joints`, `match_arm_lengths`, `arm_palm_start` for the SMPL-X arm's keypoints; `planar_palm_starts`, `project_pixels`, `image_ik_inputs` for image keypoints; and `checked`, the one coercion of a caller's tensor or array-like
+             batched rigid start of the vertex fit; `rest_arm_joints`, `match_arm_lengths`, `arm_palm_start` for the SMPL-X arm's keypoints; `planar_palm_starts`, `project_pixels`, `image_ik_inputs` for image keypoints, `arm_image_ik_inputs`, `arm_image_starts` for the arm's; and `checked`, the one coercion of a caller's tensor or array-like
   motion     `Motion` (the per-frame rows), `RowLayout` (their one packed table), `Motion.resample` (ops.motion_resample),
-             `Motion.from_keypoints` (ops.mano_ik), `Motion.from_image_keypoints` (ops.mano_reproj_ik), `Motion.from_vertices` (ops.mano_vertex_fit), `Motion.from_arm_vertices` (ops.arm_vertex_fit), `Motion.from_arm_keypoints` (ops.arm_ik), `Motion.smooth` / `smooth_keypoints` (ops.motion_filter), `motion_jitter`
+             `Motion.from_keypoints` (ops.mano_ik), `Motion.from_image_keypoints` (ops.mano_reproj_ik), `Motion.from_arm_image_keypoints` (ops.arm_reproj_ik), `Motion.from_vertices` (ops.mano_vertex_fit), `Motion.from_arm_vertices` (ops.arm_vertex_fit), `Motion.from_arm_keypoints` (ops.arm_ik), `Motion.smooth` / `smooth_keypoints` (ops.motion_filter), `motion_jitter`
   labels     `face_part_labels`, `part_names`: the part of the hand every face belongs to, from the skinning weights (host integers)
   player     `AvatarPlayer`, the forward-only renderer â€” the fit's own fused front, rasterisers and shader without a backward, then
              harp_resolve_u8: six calls of the C ABI per batch of frames, in order on one stream, captured into a graph â€” and `ScenePlayer`,
@@ -24,7 +24,7 @@ The package in five modules, each importing only those before it:
 Importing the package needs neither the built library nor a device.
 """
 from .cli import main
-from .keypoints import (ARM_JOINT_IDX, CHAIN_BONES, ELBOW, JOINT_REORDER, PALM, arm_palm_start, axis_angle_of, bone_length_scale,
+from .keypoints import (ARM_JOINT_IDX, CHAIN_BONES, ELBOW, JOINT_REORDER, PALM, arm_image_ik_inputs, arm_image_starts, arm_palm_start, axis_angle_of, bone_length_scale,
                         kabsch_rotation, match_arm_lengths, palm_start, planar_palm_starts, project_pixels, rest_arm_joints, rest_chain_joints,
                         vertex_start)
 from .labels import face_part_labels, part_names
@@ -34,4 +34,5 @@ from .player import BG_WHITE, FLOW_TOL, LABEL_TOL, Annotation, Flow, AvatarPlaye
 __all__ = ["Motion", "AvatarPlayer", "ScenePlayer", "smooth_keypoints", "motion_jitter", "pose_mean_rows", "rest_chain_joints",
            "bone_length_scale", "kabsch_rotation", "axis_angle_of", "palm_start", "JOINT_REORDER", "PALM", "CHAIN_BONES", "load_backgrounds",
            "load_scene_depth", "main", "BG_WHITE", "vertex_start", "arm_palm_start", "rest_arm_joints", "match_arm_lengths", "ARM_JOINT_IDX", "ELBOW",
-           "planar_palm_starts", "project_pixels", "face_part_labels", "part_names", "Annotation", "LABEL_TOL", "Flow", "FLOW_TOL"]
+           "planar_palm_starts", "project_pixels", "face_part_labels", "part_names", "Annotation", "LABEL_TOL", "Flow", "FLOW_TOL", "arm_image_ik_inputs",
+           "arm_image_starts"]

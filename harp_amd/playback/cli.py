@@ -20,7 +20,10 @@ def parse_args(argv=None):
                                                       "(Motion.from_arm_keypoints)")
     ap.add_argument("--keypoints2d", default=None, help=".npz of keypoints (T,21,2) in pixels of the fit's img_size [, weights (T,21), depth (T,21) "
                                                         "metres relative to the wrist, cam (3,) or (T,3)] instead of --motion: the motion is "
-                                                        "solved from them by reprojection (Motion.from_image_keypoints; the MANO hand only)")
+                                                        "solved from them by reprojection (Motion.from_image_keypoints); with a use_arm config "
+                                                        "(T,22,2) = the 21 hand keypoints plus the elbow as row 21 (the wrist is solved) or "
+                                                        "(T,21,2) (the wrist is held) [, weights and depth of that width, wrist_pose (3,) or "
+                                                        "(T,3)] (Motion.from_arm_image_keypoints): what --labels writes for either avatar")
     ap.add_argument("--vertices", default=None, help=".npz of vertices (T,778,3) in metres, MANO topology [, weights (T,778), cam (3,) or (T,3)] "
                                                      "instead of --motion: the motion is fitted to them (Motion.from_vertices); with a use_arm "
                                                      "config (T,778,3) or the arm's (T,1026,3) [, wrist_pose (3,) or (T,3) for 778] "
@@ -107,8 +110,13 @@ def main(argv=None):
         elif keypoints2d_path is not None:
             with np.load(keypoints2d_path) as z:
                 opt = lambda k: z[k] if k in z.files else None            # noqa: E731
-                motion = Motion.from_image_keypoints(z["keypoints"], params, hand_layer, cam=opt("cam"), weights=opt("weights"),
-                                                     depth=opt("depth"), device=args.device, configs=configs)
+                if "pose_mean" in hand_layer._model_np:                     # the SMPL-X arm (use_arm)
+                    motion = Motion.from_arm_image_keypoints(z["keypoints"], params, hand_layer, cam=opt("cam"), weights=opt("weights"),
+                                                             depth=opt("depth"), wrist_pose=opt("wrist_pose"), device=args.device,
+                                                             configs=configs)
+                else:
+                    motion = Motion.from_image_keypoints(z["keypoints"], params, hand_layer, cam=opt("cam"), weights=opt("weights"),
+                                                         depth=opt("depth"), device=args.device, configs=configs)
         elif vertices_path is not None:
             with np.load(vertices_path) as z:
                 opt = lambda k: z[k] if k in z.files else None            # noqa: E731

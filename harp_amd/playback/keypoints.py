@@ -3,7 +3,8 @@ Kabsch start of the root (T problems of six points each), and `ik_inputs`, which
 ops.mano_ik is fed.  `checked` is the package's one coercion and check of a tensor or array-like that a caller passed.  The SMPL-X arm's
 counterparts (Motion.from_arm_keypoints): `rest_arm_joints`, `match_arm_lengths`, `arm_palm_start`.  Image keypoints
 (Motion.from_image_keypoints): `camera_tz` and `project_pixels` (the player's camera), `planar_palm_starts` (the two
-starts that a plane's pixels allow) and `image_ik_inputs` for ops.mano_reproj_ik.  What the five Motion.from_* constructors set up
+starts that a plane's pixels allow) and `image_ik_inputs` for ops.mano_reproj_ik; the SMPL-X arm's (Motion.from_arm_image_keypoints,
+DESIGN.md §35): `arm_image_ik_inputs` and `arm_image_starts` for ops.arm_reproj_ik.  What the Motion.from_* constructors set up
 alike stands once, below `checked`: `frame_cam`, `avatar_shape`, `check_init`, `init_rows`, `held_wrist`, `arm_start_rows`,
 `smoothed`."""
 import numpy as np
@@ -289,9 +290,10 @@ def camera_tz(cam, focal, S):
 
 
 def project_pixels(joints, cam, focal, S):
-    """joints (..., 21, 3) metres in the frame of the fit's `joints` -> (..., 21, 3) = (u, v, d) as csrc/reproj_ik.hip states them: the
-    player's camera (view = (-x - cam1, -y - cam2, z + t_z)) read at the rasteriser's pixel centres, so that the centre of column i is at
-    u = i + 0.5 and of row i at v = i + 0.5, and the depth relative to the wrist.  cam (3,) or (..., 3).  numpy float64."""
+    """joints (..., n, 3) metres in the frame of the fit's `joints` — the hand's 21 rows, or the SMPL-X arm's 22 with the elbow as row 21 —
+    -> (..., n, 3) = (u, v, d) as csrc/reproj_ik.hip and csrc/arm_reproj_ik.hip state them: the player's camera (view = (-x - cam1,
+    -y - cam2, z + t_z)) read at the rasteriser's pixel centres, so that the centre of column i is at u = i + 0.5 and of row i at
+    v = i + 0.5, and the depth relative to the wrist (row 0).  cam (3,) or (..., 3).  numpy float64."""
     j = np.asarray(joints, np.float64)
     cam = np.asarray(cam, np.float64)
     Z = j[..., 2] + camera_tz(cam, focal, S)[..., None]
@@ -383,6 +385,72 @@ def image_ik_inputs(keypoints, weights, depth, cam, init, params, model, focal, 
             zbar[t] = ((rest[palm] - rest[0]) @ R.T + rest[0] + trans[t, 0]).mean(0)[2] + camera_tz(cam[t], focal, S)
     targets = np.concatenate([kp, np.full((T, 21, 1), np.nan) if d is None else d[..., None]], -1)
     return dict(shape=shape, targets=targets, weights=w, pose48=pose48, trans=trans, depth=zbar, cam=cam)
+
+
+def arm_image_ik_inputs(keypoints, weights, depth, cam, init, wrist_pose, params, smooth=None):
+    """What Motion.from_arm_image_keypoints passes to ops.arm_reproj_ik before the start is known, checked and prepared on the host:
+    dict(shape (10,), targets (T,22,3) = (u, v, d) with NaN where there is no pixel or depth, weights (T,22) (0 for an unused joint),
+    wrist (T,3) = what the wrist is held at or the centre of its prior, solve_wrist, in_pose (T,17,3) and trans (T,3) = the point at which
+    the solver's own forward gives the joints for the rigid start (init's rows with init), cam (T,3) float32), the others float64.
+    keypoints (T,22,2) with the elbow as row 21: the wrist is solved; (T,21,2): the same 22-wide problem with the elbow unused and the
+    wrist held.  depth None or of the keypoints' width.  smooth: None or a function (points (T,22,3), weights) -> (points, used (T,22)),
+    which the pixels (as (u, v, 0)) and the depths (as (d, 0, 0)) go through; a joint it filled then counts as used."""
+    n = int(np.shape(keypoints)[1]) if np.ndim(keypoints) == 3 else -1
+    if n not in (21, 22):
+        raise ValueError(f"keypoints must be (T, 22, 2) with the elbow or (T, 21, 2) without, got {tuple(np.shape(keypoints))}")
+    kp = checked("keypoints", keypoints, (None, n, 2), kind="f", split=True).astype(np.float64)
+    T = kp.shape[0]
+    w = None if weights is None else checked("weights", weights, (T, n), kind="f", split=True).astype(np.float64)
+    d = None if depth is None else checked("depth", depth, (T, n), kind="f", split=True).astype(np.float64)
+    check_init(init, T, wrist=True)
+    if n == 21:                                             # the hand alone: the elbow's row is there and unused
+        kp = np.concatenate([kp, np.full((T, 1, 2), np.nan)], 1)
+        w = np.concatenate([np.ones((T, 21)) if w is None else w, np.zeros((T, 1))], 1)
+        d = None if d is None else np.concatenate([d, np.full((T, 1), np.nan)], 1)
+    if smooth is not None:
+        p3, w = smoothed(smooth, np.concatenate([kp, np.zeros((T, 22, 1))], -1), w)
+        kp = p3[..., :2]
+        if d is not None:
+            d = smoothed(smooth, np.concatenate([d[..., None], np.zeros((T, 22, 2))], -1), None)[0][..., 0]
+        if n == 21:
+            kp[:, ELBOW], w[:, ELBOW] = np.nan, 0.0
+    cam, shape = frame_cam(cam, params, T), avatar_shape(params)
+    used = np.isfinite(kp).all(-1) & (True if w is None else (w > 0))
+    wt = used.astype(np.float64) if w is None else np.where(used, w, 0.0)
+    wrist = held_wrist(wrist_pose, init, T)
+    # (a solved wrist starts where init has it, whatever the centre of its prior)
+    rows, trans = arm_start_rows(T, wrist if init is None or n == 21 else init.wrist_pose.cpu().numpy(), init)
+    targets = np.concatenate([kp, np.full((T, 22, 1), np.nan) if d is None else d[..., None]], -1)
+    return dict(shape=shape, targets=targets, weights=wt, wrist=np.array(wrist), solve_wrist=n == 22, in_pose=rows,
+                trans=np.asarray(trans, np.float64), cam=cam)
+
+
+def arm_image_starts(a, joints0, init, focal, S):
+    """The candidate starts of the arm's reprojection solve: (in_pose (T,C,17,3), trans (T,C,3), depth (T,) = the start's palm depth along
+    the view axis), float64.  a: arm_image_ik_inputs' dict; joints0 (T,22,3) metres: the solver's own joints at a's in_pose / trans.
+    Without init C = 2: rows 0..20 of joints0 (the avatar's shape, the held or prior wrist, zero pose, zero root and trans; row 0 is the
+    origin: the arm is wrist-centred) go to planar_palm_starts unchanged, frame by frame where the wrist differs between frames.  With
+    init C = 1: its rows, and the depth of its own palm."""
+    T = a["in_pose"].shape[0]
+    j0 = np.asarray(joints0, np.float64)
+    cam = a["cam"].astype(np.float64)
+    if init is not None:
+        depth = j0[:, np.array(PALM), 2].mean(1) + camera_tz(cam, focal, S)
+        return a["in_pose"][:, None].copy(), a["trans"][:, None].copy(), depth
+    px, used = a["targets"][:, :21, :2], a["weights"][:, :21] > 0
+    if np.all(j0 == j0[:1]):
+        rot, trans, depth = planar_palm_starts(px, used, j0[0, :21], cam, focal, S)
+    else:
+        rot, trans, depth = np.zeros((T, 2, 3)), np.zeros((T, 2, 3)), camera_tz(cam, focal, S)
+        for t in range(T):                                  # (a frame without its six palm pixels: the starts of the last that had them)
+            if used[t, np.array(PALM)].all():
+                r, tr, z = planar_palm_starts(px[t:t + 1], used[t:t + 1], j0[t, :21], cam[t:t + 1], focal, S)
+                rot[t], trans[t], depth[t] = r[0], tr[0], z[0]
+            elif t > 0:
+                rot[t], trans[t], depth[t] = rot[t - 1], trans[t - 1], depth[t - 1]
+    in_pose = np.repeat(a["in_pose"][:, None], 2, axis=1)
+    in_pose[:, :, 0] = rot
+    return in_pose, trans, depth
 
 
 def _rotation_of(aa):

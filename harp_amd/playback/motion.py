@@ -1,7 +1,8 @@
 """The rows of a motion and what is done to them on the device: `Motion`, its retiming (ops.motion_resample), its solve
-from 3-D keypoints (ops.mano_ik, §24; the SMPL-X arm: ops.arm_ik, §29), from image keypoints (ops.mano_reproj_ik, §30) or from mesh
+from 3-D keypoints (ops.mano_ik, §24; the SMPL-X arm: ops.arm_ik, §29), from image keypoints (ops.mano_reproj_ik, §30; the SMPL-X arm:
+ops.arm_reproj_ik, §35) or from mesh
 vertices (ops.mano_vertex_fit, §27; the SMPL-X arm: ops.arm_vertex_fit, §28) and the window filter of a motion or of keypoints
-(ops.motion_filter, §25).  `RowLayout` is the one description of the packed table that the resampler and the filter read.  What the five
+(ops.motion_filter, §25).  `RowLayout` is the one description of the packed table that the resampler and the filter read.  What the
 solving constructors set up alike stands once (§34): on the host in keypoints.py, where a device is involved in the private functions
 below."""
 import numpy as np
@@ -158,10 +159,10 @@ class Motion:
         smooth: None, or the sigma in frames of a Gaussian window that the pixels (and depths) go through first (smooth_keypoints, with
         `weights` as the confidences); Motion.smooth filters the solved rows instead.  The result carries no light.  device: where the
         solve runs (default: the device of params["shape"] when that is a HIP device, else "cuda").  The SMPL-X arm needs a solver for
-        its kinematic tree and raises NotImplementedError."""
+        its kinematic tree and raises NotImplementedError: Motion.from_arm_image_keypoints is that solver."""
         if "pose_mean" in hand_layer._model_np:
-            raise NotImplementedError("Motion.from_image_keypoints solves the MANO hand; the SMPL-X arm needs a kinematic-tree solver, and "
-                                      "there is none for image keypoints yet")
+            raise NotImplementedError("Motion.from_image_keypoints solves the MANO hand; the SMPL-X arm needs a kinematic-tree solver: "
+                                      "Motion.from_arm_image_keypoints")
         if configs is None or "focal_length" not in configs or "img_size" not in configs:
             raise ValueError("Motion.from_image_keypoints needs configs= with the fit's focal_length and img_size")
         focal, S = float(configs["focal_length"]), int(configs["img_size"])
@@ -318,6 +319,67 @@ class Motion:
         res = ops.arm_ik(dm, betas, targets, up(rows), up(trans), weights=up(wt), wrist_prior=up(wrist), solve_wrist=n == 22, iters=iters,
                          pose_prior_weight=prior_weight, wrist_prior_weight=wrist_prior_weight)
         return cls._from_arm_result(res, cam)
+
+    @classmethod
+    def from_arm_image_keypoints(cls, keypoints, params, arm_layer, cam=None, weights=None, depth=None, depth_weight=1.0, prior_weight=1e-5,
+                                 wrist_prior_weight=1e-4, depth_prior_weight=2.5e-5, wrist_pose=None, iters=20, init=None, smooth=None,
+                                 device=None, configs=None):
+        """A motion WITH wrist_pose for an SMPL-X arm avatar from IMAGE keypoints (a 2-D hand or body tracker run on a video) by batched
+        reprojection inverse kinematics over the arm's joint tree on the device (ops.arm_reproj_ik, csrc/arm_reproj_ik.hip, DESIGN.md
+        §35).  keypoints in pixels of the fit's img_size, with the centre of column i at i + 0.5 and of row i at i + 0.5 of the frames the
+        player renders:
+        (T,22,2) — the 21 hand keypoints in the model's order (wrist, then thumb, index, middle, ring and little, each from root to tip)
+        plus the ELBOW as row 21: the wrist is SOLVED, and wrist_pose ((3,) or (T,3); default zeros, or init.wrist_pose) is the centre
+        of its prior (wrist_prior_weight); a frame whose elbow is missing is still solved, and the prior then decides its wrist;
+        (T,21,2) — the hand only: the same launch with the elbow's weight 0 and the wrist HELD at wrist_pose.
+        A joint with a non-finite coordinate or a weight <= 0 (weights (T,n), default ones) is ignored.  depth: None or (T,n) metres
+        relative to the wrist along the view axis ("2.5-D"; NaN where there is none; the wrist's own entry is not read) — what a labelled
+        arm playback writes into keypoints.npz beside the pixels.  params, cam, configs (required, by keyword): as
+        Motion.from_image_keypoints takes them.
+        The start: wrist as held (or the prior's centre) and pose zero; the model's joints there come from the solver's own forward, and
+        rows 0..20 of them go to planar_palm_starts, which gives the TWO root rotations and translations that the palm's pixels allow; both
+        go through ONE solve of 2 T problems and the one with the lower final cost is taken per frame on the device.  init= takes a Motion
+        of equal length with wrist_pose as the only candidate.
+        The four weights are dimensionless and multiplied by (focal / Z_t)^2 with Z_t the start's palm depth, as in
+        from_image_keypoints: depth_weight on the depth rows (their own frame's factor), prior_weight on the pull of the finger pose to
+        the model's mean pose, wrist_prior_weight on the pull of a solved wrist to wrist_pose, depth_prior_weight on the pull of trans_z
+        to the start's (the three priors take the median of the frames' factors).  There is no bone-length matching in 2-D.
+        THE LIMIT is from_image_keypoints': without `depth` the reprojection is right and the 3-D pose is not unique (on the
+        seeded scenes the joints are off by 8 .. 13 mm in the median and up to 227 mm at under 3.2 px; with depth rows 1.2 .. 1.4 mm in
+        the median and 7.1 mm at most).
+        smooth: None, or the sigma in frames of a Gaussian window that the pixels (and depths) go through first (smooth_keypoints with
+        joints=22).  The result carries no light.  A MANO layer raises ValueError: Motion.from_image_keypoints solves that model."""
+        if "pose_mean" not in arm_layer._model_np:
+            raise ValueError("Motion.from_arm_image_keypoints solves the SMPL-X arm layer; Motion.from_image_keypoints solves the MANO hand")
+        if configs is None or "focal_length" not in configs or "img_size" not in configs:
+            raise ValueError("Motion.from_arm_image_keypoints needs configs= with the fit's focal_length and img_size")
+        focal, S = float(configs["focal_length"]), int(configs["img_size"])
+        for name, v in (("depth_weight", depth_weight), ("prior_weight", prior_weight), ("wrist_prior_weight", wrist_prior_weight),
+                        ("depth_prior_weight", depth_prior_weight)):
+            if not (0.0 <= float(v) < float("inf")):
+                raise ValueError(f"{name} must be finite and >= 0, got {v}")
+        dev, up = _solve_on(device, params)
+        a = K.arm_image_ik_inputs(keypoints, weights, depth, cam, init, wrist_pose, params, _window(smooth, dev, 22))
+        dm = _arm_device_model(arm_layer, dev)
+        T = a["in_pose"].shape[0]
+        betas = up(a["shape"])
+        # the model's joints at this shape and wrist with zero stored pose (or at init): the solver's own forward, nothing solved
+        zero = ops.arm_ik(dm, betas, up(np.zeros((T, 22, 3))), up(a["in_pose"]), up(a["trans"]), iters=0, joints=True).joints
+        in_pose, trans, zbar = K.arm_image_starts(a, zero.cpu().numpy().astype(np.float64) / 1000.0, init, focal, S)
+        C = in_pose.shape[1]
+        rep = lambda x: np.repeat(x, C, axis=0)                          # frame-major: problem t * C + c
+        scale = (focal / zbar) ** 2                                     # (T,) px^2 per squared metre (radian) at the start's palm depth
+        med = float(np.median(scale))
+        res = ops.arm_reproj_ik(dm, betas, up(rep(a["targets"])), up(in_pose.reshape(T * C, 17, 3)), up(trans.reshape(T * C, 3)),
+                                up(rep(a["cam"])), focal, S, weights=up(rep(a["weights"])),
+                                depth_weights=None if depth is None else up(rep(np.broadcast_to((depth_weight * scale)[:, None], (T, 22)))),
+                                wrist_prior=up(rep(a["wrist"])), z_prior=up(trans.reshape(T * C, 3)[:, 2]), solve_wrist=a["solve_wrist"],
+                                iters=iters, pose_prior_weight=prior_weight * med, wrist_prior_weight=wrist_prior_weight * med,
+                                z_prior_weight=depth_prior_weight * med)
+        pick = res.cost[:, 1].reshape(T, C).argmin(1, keepdim=True)      # the candidate with the lower final cost, on the device
+        take = lambda rows, n: rows.reshape(T, C, n).gather(1, pick[:, :, None].expand(T, 1, n))[:, 0]      # noqa: E731
+        return cls._from_arm_result(ops.ArmReprojIkResult(take(res.in_pose, 51).reshape(T, 17, 3), take(res.trans, 3), None, None, None, None),
+                                    a["cam"])
 
     def save(self, path):
         np.savez(path, **{k: getattr(self, k).cpu().numpy() for k in self.FIELDS if getattr(self, k) is not None})

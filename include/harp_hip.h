@@ -1434,6 +1434,61 @@ int harp_mano_reproj_ik(const harp_mano_model* m, const float* betas, const floa
                         const float* depth_weights, const float* prior, const float* z_prior, int N, const harp_reproj_ik_options* opt,
                         float* pose48, float* trans, float* cost, int32_t* status, float* proj, float* jac, hipStream_t stream);
 
+/* ---- batched 2.5-D reprojection IK on the joint tree: image keypoints -> SMPL-X arm rows (csrc/arm_reproj_ik.hip; playback
+ * Motion.from_arm_image_keypoints) ----
+ * Nothing in the reference does this.  The model inverted is harp_lbs_tree_fwd's, seen through the camera and pixel centres of
+ * harp_mano_reproj_ik.  N independent Levenberg-Marquardt solves in one launch (one kernel node), forward only, no workspace, no
+ * allocation, no synchronisation, no atomics, fixed summation order (capturable; a repeated call gives the same bits).  Unknowns per
+ * problem x = [rot 3 | wrist 3 | pose 45 | trans 3]: x[0..51) is the problem's row of in_pose (N,17,3) and x[51..54) its trans, exactly as
+ * harp_arm_ik takes them.  Given: betas (10,) for all problems, or (N,10) with betas_per_frame != 0 (the model's other NB - 10
+ * coefficients are zero); cam (3,), or (N,3) with cam_per_frame != 0; focal and S (the image is S x S pixels).
+ *   j(x) (n_out,3) metres = harp_arm_ik's joints, n_out = n_joints_out <= 22 (the arm: the wrist, the five fingers root to tip, the elbow
+ *   as row 21), rows from the model's joint_src.
+ *   Z_k = j_k.z + t_z, t_z = 2 focal / (S cam0 + 1e-9);   u_k = S/2 + focal (j_k.x + cam1) / Z_k;   v_k = S/2 + focal (j_k.y + cam2) / Z_k;
+ *   d_k = j_k.z - j_0.z: harp_mano_reproj_ik's convention (the centre of column i at u = i + 0.5), over n_out rows, the elbow's d included.
+ *   C(x) = sum_k w_k [(u_k - U_k)^2 + (v_k - V_k)^2] + sum_{k>=1} wz_k (d_k - D_k)^2 + pose_prior_weight sum_i (pose_i - prior_i)^2
+ *          + wrist_prior_weight sum_i (wrist_i - wrist_prior_i)^2 + z_prior_weight (trans_z - z_prior)^2;
+ *   targets (N,n_out,3) = (U, V, D): pixels, pixels, metres; weights (N,n_out) or NULL (ones); depth_weights (N,n_out) or NULL (no depth
+ *   rows; the wrist's own entry is never used); prior (N,45) or NULL (zeros: the model's mean pose); wrist_prior (N,3) or NULL (zeros);
+ *   z_prior (N) or NULL (then z_prior_weight must be 0).  The weights are in px^2 per squared unit of their residual.  A joint's PIXEL rows
+ *   are used when w_k > 0 and U_k, V_k are finite; its DEPTH row when k >= 1, wz_k > 0 and D_k is finite; an unused entry never enters
+ *   arithmetic.
+ *   solve_wrist == 0: the wrist row of in_pose is read and never written; its three columns are FROZEN as in harp_arm_ik (A_ii = 1, zeros
+ *   elsewhere in its row and column, g_i = 0: its step is exactly 0).
+ *   Iteration, exactly `iters` times, harp_mano_ik's: J = the exact 3 n_out x 54 derivative of the rows (u, v, d) at x; A = J^T W J + P,
+ *   g = J^T W r + P (x - x_prior), P = the three prior weights on the 45 pose, 3 wrist and trans_z diagonals; (A + lambda diag A) d = -g by
+ *   a Cholesky factorisation of the matrix scaled from both sides by 1 / sqrt(A_ii (1 + lambda)); x' = x + d; C(x') < C(x): accept,
+ *   lambda = max(0.1 lambda, 1e-9); otherwise (a NaN included, a non-positive or non-finite pivot or diagonal, and a candidate with a used
+ *   pixel joint at Z_k <= 1e-3) keep x, lambda = min(10 lambda, 1e6).  lambda starts at lambda0.
+ * In/out: in_pose (N,17,3) (the wrist row only when solve_wrist), trans (N,3).  Out: cost (N,2) = C at the input and at the result; status
+ * (N) int32 = accepted steps; -1 for a problem with fewer than 4 used pixel joints; -2 (cost 0, nothing else written) when the model's tree
+ * is not one the kernel's tables hold, by harp_arm_ik's rule; -3 for a problem with a used pixel joint at Z_k <= 1e-3 at its input (cost is
+ * C as evaluated there).  None of the three is solved: their in_pose / trans rows are not written.  Optional out (NULL allowed), at the
+ * final x: proj (N,n_out,3) = (u, v, d) and jac (N,3 n_out,54), always all 54 columns; a joint that is neither pixel-used nor in front
+ * (Z_k <= 1e-3) has u = v = 0 and zero u / v rows.  The elbow's rows in the 48 wrist and finger columns, and d d_k / d trans, are exactly 0.
+ * iters == 0 evaluates cost, proj and jac at the input and writes neither in_pose nor trans.
+ * HARP_ERR_ARG before any launch: m, opt, betas, cam, targets, in_pose, trans, cost or status NULL; N <= 0; iters < 0; lambda0 or a prior
+ * weight negative or not finite; focal not positive and finite; S <= 0; z_prior NULL with z_prior_weight != 0; n_joints_out outside
+ * 1..HARP_ARM_IK_MAX_JOINTS; center_joint outside [0, NJ); n_pose_in != 17; NB < 10, NB > 32 or NJ > 64.
+ * harp_arm_reproj_ik_frames_per_block: the problems one workgroup solves (tests size their batches around it). */
+typedef struct harp_arm_reproj_ik_options {
+  int iters;
+  float lambda0;            /* 1e-3 */
+  float pose_prior_weight;  /* px^2 / rad^2 */
+  float wrist_prior_weight; /* px^2 / rad^2 */
+  float z_prior_weight;     /* px^2 / m^2 */
+  int solve_wrist;          /* 0: the wrist row of in_pose given and frozen */
+  int betas_per_frame;      /* 0: betas (10,); otherwise betas (N,10) */
+  int cam_per_frame;        /* 0: cam (3,); otherwise cam (N,3) */
+  float focal;              /* pixels */
+  int S;                    /* image size, pixels */
+} harp_arm_reproj_ik_options;
+int harp_arm_reproj_ik_frames_per_block(void);
+int harp_arm_reproj_ik(const harp_tree_model* m, const float* betas, const float* cam, const float* targets, const float* weights,
+                       const float* depth_weights, const float* prior, const float* wrist_prior, const float* z_prior, int N,
+                       const harp_arm_reproj_ik_options* opt, float* in_pose, float* trans, float* cost, int32_t* status, float* proj,
+                       float* jac, hipStream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,11 +1,13 @@
-"""The bits of the five batched Levenberg-Marquardt solvers (csrc/ik.hip, reproj_ik.hip, arm_ik.hip, vertex_fit.hip, arm_vertex_fit.hip;
-DESIGN.md §31): a SHA-256 of the raw bytes of every output tensor of one small deterministic batch per solver and per setting of
+"""The bits of the six batched Levenberg-Marquardt solvers (csrc/ik.hip, reproj_ik.hip, arm_ik.hip, vertex_fit.hip, arm_vertex_fit.hip,
+arm_reproj_ik.hip): a SHA-256 of the raw bytes of every output tensor of one small deterministic batch per solver and per setting of
 solve_shape / solve_wrist.  Two builds of the library that print the same digests compute the same thing; the file touches nothing but
 harp_amd.ops and the synthetic hand and arm models, so it runs unchanged against an older checkout.
 
 Each batch: 4 problems from a start near the truth (the targets are the solver's own forward at iters = 0 of a true point), 3 iterations,
 every optional output; problem 3 has fewer used targets than the solver asks for (status -1), one unused target is NaN, and problem 2 of
-the reprojection solve starts with its used joints behind the camera (status -2).
+the reprojection solves starts with its used joints behind the camera (status -2; the arm's: -3).  The arm's reprojection solve and its
+constructor (§35) come last in their parts, with random streams of their own, and are left out against a checkout that has neither: the
+digests of the five older solvers stay comparable across that commit.
 
 The second part does the same for the layer above: every field of the Motion that each of the five Motion.from_*
 constructors returns for 4 frames, once from the rigid start, once with init= and, for the three keypoint constructors, once with
@@ -144,6 +146,26 @@ def arm(res):
             record(res, f"arm_vertex_fit/shape{int(solve_shape)}_wrist{int(solve_wrist)}", ops.arm_vertex_fit(dm, *args, **kw),
                    args + (kw["weights"], prior))
 
+    # image keypoints (csrc/arm_reproj_ik.hip): a stream of its own, so that what stands above does not move
+    if not hasattr(ops, "arm_reproj_ik"):
+        return
+    rng = np.random.default_rng(39)
+    tr = rng.uniform(-0.05, 0.05, size=(T, 3))
+    j = (ops.arm_ik(dm, up(betas), torch.zeros(T, n, 3, device=DEV), up(rows), up(tr), iters=0, joints=True).joints / 1000.0).cpu().double().numpy()
+    Z = j[..., 2] + 2.0 * FOCAL / (S * CAM[0] + 1e-9)
+    px = np.stack([S / 2 + FOCAL * (j[..., 0] + CAM[1]) / Z, S / 2 + FOCAL * (j[..., 1] + CAM[2]) / Z, j[..., 2] - j[:, :1, 2]], -1)
+    px[0, 1] = np.nan
+    w = weights_with_few(n, 3, rng)
+    wz = rng.uniform(0.5, 1.5, size=(T, n)) * 1e6
+    t0r = up(tr + rng.normal(size=tr.shape) * 0.01)
+    t0r[2, 2] = -2.0                                       # every joint of problem 2 behind the camera at the input
+    for solve_wrist in (True, False):
+        args = (up(betas), up(px), x0, t0r, up(CAM), FOCAL, S)
+        kw = dict(weights=up(w), depth_weights=up(wz), prior=prior, wrist_prior=wprior, z_prior=up(tr[:, 2]), solve_wrist=solve_wrist,
+                  pose_prior_weight=40.0, wrist_prior_weight=400.0, z_prior_weight=100.0, iters=ITERS, proj=True, jac=True)
+        record(res, f"arm_reproj_ik/wrist{int(solve_wrist)}", ops.arm_reproj_ik(dm, *args, **kw),
+               (args[0], args[1], x0, t0r, args[4], kw["weights"], kw["depth_weights"], prior, wprior, kw["z_prior"]))
+
 
 def record_motion(res, name, m):
     for f in m.FIELDS:
@@ -241,6 +263,28 @@ def arm_motions(res):
     record_motion(res, "from_arm_vertices/mano_rigid",
                   Motion.from_arm_vertices(verts[:, idx], params, layer, weights=wv[:, idx], wrist_pose=rows[:, 1], device=DEV))
     record_motion(res, "from_arm_vertices/mano_init", Motion.from_arm_vertices(verts[:, idx], params, layer, cam=cam, init=init, device=DEV))
+
+    # image keypoints (§35), both widths: rigid starts, init=, smooth=1.0; a stream of its own
+    if not hasattr(Motion, "from_arm_image_keypoints"):
+        return
+    rng = np.random.default_rng(47)
+    tr = rng.uniform(-0.03, 0.03, size=(T, 3))
+    j = (ops.arm_ik(dm, up(shape), torch.zeros(T, n, 3, device=DEV), up(rows), up(tr), iters=0, joints=True).joints / 1000.0).cpu().double().numpy()
+    Z = j[..., 2] + 2.0 * FOCAL / (S * cam[:, :1] + 1e-9)
+    px = np.stack([S / 2 + FOCAL * (j[..., 0] + cam[:, 1:2]) / Z, S / 2 + FOCAL * (j[..., 1] + cam[:, 2:3]) / Z], -1)
+    px = px + rng.normal(size=px.shape) * 0.3
+    px[2, 11] = np.nan
+    depth = j[..., 2] - j[:, :1, 2]
+    cfg = dict(focal_length=FOCAL, img_size=S)
+    init2 = Motion(init.pose, init.rot, tr + rng.normal(size=(T, 3)) * 0.005, cam, wrist_pose=init.wrist_pose)
+    f = Motion.from_arm_image_keypoints
+    record_motion(res, "from_arm_image_keypoints/rigid", f(px, params, layer, cam=cam, weights=w, depth=depth, configs=cfg, device=DEV))
+    record_motion(res, "from_arm_image_keypoints/init", f(px, params, layer, cam=cam, init=init2, configs=cfg, device=DEV))
+    record_motion(res, "from_arm_image_keypoints/smooth", f(px, params, layer, cam=cam, weights=w, depth=depth, smooth=1.0, configs=cfg, device=DEV))
+    record_motion(res, "from_arm_image_keypoints/hand_rigid",
+                  f(px[:, :21], params, layer, cam=cam, weights=w[:, :21], depth=depth[:, :21], wrist_pose=rows[:, 1], configs=cfg, device=DEV))
+    record_motion(res, "from_arm_image_keypoints/hand_init", f(px[:, :21], params, layer, cam=cam, init=init2, configs=cfg, device=DEV))
+    record_motion(res, "from_arm_image_keypoints/hand_smooth", f(px[:, :21], params, layer, cam=cam, smooth=1.0, configs=cfg, device=DEV))
 
 
 def main():
