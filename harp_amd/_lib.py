@@ -360,6 +360,16 @@ class FlowLayer(ctypes.Structure):
 SIGNATURES["harp_flow_layers"] = (_i, [ctypes.POINTER(FlowLayer), _i, _i, _i, _i, _vp, _i, _vp, _vp, _i, _vp, _f, _vp, _vp, _vp, _vp])
 
 
+class ContactMesh(ctypes.Structure):
+    """mirror of `harp_contact_mesh` (include/harp_hip.h)"""
+    _fields_ = ([(n, _vp) for n in ("verts", "cam_R", "cam_T", "faces")] + [(n, ctypes.c_int32) for n in ("V", "F", "flip_x", "reserved")])
+
+
+# per-vertex distance, nearest face and winding number between two meshes (csrc/contact.hip)
+SIGNATURES["harp_mesh_contact_ws_floats"] = (_sz, [_i, _i])
+SIGNATURES["harp_mesh_contact"] = (_i, [ctypes.POINTER(ContactMesh), ctypes.POINTER(ContactMesh), _i, _f, _vp, _vp, _vp, _vp, _vp])
+
+
 class IkOptions(ctypes.Structure):
     """mirror of `harp_ik_options` (include/harp_hip.h)"""
     _fields_ = [("iters", _i), ("lambda0", _f), ("prior_weight", _f), ("betas_per_frame", _i)]

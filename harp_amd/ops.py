@@ -1511,6 +1511,74 @@ def flow_layers(layers, to, ss=1, scene_depth=None, scene_rows=None, scene_depth
     return o
 
 
+# ---- contact labels: distance, nearest face and winding number between two meshes (csrc/contact.hip) ---------------------
+# one side of mesh_contact: verts (B,V,3), cam_R (B,9), cam_T (B,3) float32 as the fused front leaves vd, cam_R and cam_T; faces (F,3)
+# int32 (the target's; the query's is not read); flip: the mesh is shown mirrored in x
+ContactMesh = collections.namedtuple("ContactMesh", "verts cam_R cam_T faces flip", defaults=(None, False))
+MeshContact = collections.namedtuple("MeshContact", "dist face wind")
+_CONTACT_OUTPUTS = ("dist", "face", "wind")
+
+
+def _contact_side(name, side, B, target):
+    """one ContactMesh (or a dict of its fields) checked -> (the C struct, the tensors it points at)"""
+    if isinstance(side, dict):
+        if set(side) - set(ContactMesh._fields):
+            raise ValueError(f"mesh_contact: {name} takes the keys {ContactMesh._fields}, got {sorted(side)}")
+        side = ContactMesh(**side)
+    if not isinstance(side, ContactMesh):
+        raise TypeError(f"mesh_contact: {name} is an ops.ContactMesh or a dict of its fields")
+    v, R, T, faces = side.verts, side.cam_R, side.cam_T, side.faces
+    _playback_input("mesh_contact", v, R, T, faces)
+    if any(t is None or t.dtype != torch.float32 for t in (v, R, T)):
+        raise TypeError(f"mesh_contact: {name} takes float32 verts, cam_R and cam_T")
+    if v.dim() != 3 or v.shape[0] < 1 or v.shape[1] < 1 or v.shape[2] != 3:
+        raise ValueError(f"mesh_contact: {name}.verts is (B, V, 3), got {tuple(v.shape)}")
+    B = v.shape[0] if B is None else B
+    if v.shape[0] != B or tuple(R.shape) != (B, 9) or tuple(T.shape) != (B, 3):
+        raise ValueError(f"mesh_contact: {name} takes verts ({B}, V, 3), cam_R ({B}, 9) and cam_T ({B}, 3), got {tuple(v.shape)}, "
+                         f"{tuple(R.shape)}, {tuple(T.shape)}")
+    keep = [v.detach().contiguous(), R.detach().contiguous(), T.detach().contiguous()]
+    m = _lib.ContactMesh(verts=_lib.ptr(keep[0]), cam_R=_lib.ptr(keep[1]), cam_T=_lib.ptr(keep[2]), V=v.shape[1], F=0,
+                         flip_x=int(bool(side.flip)), reserved=0)
+    if target:
+        if faces is None or faces.dtype != torch.int32:
+            raise TypeError(f"mesh_contact: {name}.faces must be int32, got {None if faces is None else faces.dtype}")
+        if faces.dim() != 2 or faces.shape[0] < 1 or faces.shape[1] != 3:
+            raise ValueError(f"mesh_contact: {name}.faces is (F, 3), got {tuple(faces.shape)}")
+        keep.append(faces.detach().contiguous())
+        m.faces, m.F = _lib.ptr(keep[3]), faces.shape[0]
+    return m, keep
+
+
+def mesh_contact(query, target, max_dist=math.inf, want=_CONTACT_OUTPUTS):
+    """For every vertex of `query` its relation to the surface of `target`, frame by frame (csrc/contact.hip: harp_mesh_contact, whose
+    contract include/harp_hip.h states), forward only: a label, no gradient.  query, target: ops.ContactMesh (or dicts of its fields) of
+    device tensors over the same B frames; the target needs faces.  max_dist metres, >= 0, inf for no limit.  want: which of "dist",
+    "face", "wind" to compute.  Returns MeshContact(dist (B,Vq) float32: the unsigned distance to the target's nearest triangle, +inf
+    beyond max_dist; face (B,Vq) int32: a face that attains it, -1 for none; wind (B,Vq) float32: the generalised winding number of the
+    target about the vertex (about 1 inside, 0 outside; > 0.5 is the playback's "inside"), 0 where dist is +inf), None for an output that
+    was not asked for."""
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or set(want) - set(_CONTACT_OUTPUTS):
+        raise ValueError(f"mesh_contact: want is a non-empty selection of {_CONTACT_OUTPUTS}, got {want}")
+    max_dist = float(max_dist)
+    if not max_dist >= 0:
+        raise ValueError(f"mesh_contact: max_dist must not be negative or NaN, got {max_dist}")
+    q, keep_q = _contact_side("query", query, None, False)
+    B = keep_q[0].shape[0]
+    t, keep_t = _contact_side("target", target, B, True)
+    _playback_input("mesh_contact", keep_q[0], keep_t[0])
+    dev, Vq = keep_q[0].device, keep_q[0].shape[1]
+    L = _lib.lib()
+    ws = torch.empty(L.harp_mesh_contact_ws_floats(B, t.F), dtype=torch.float32, device=dev)
+    new = lambda k, dt: torch.empty(B, Vq, dtype=dt, device=dev) if k in want else None      # noqa: E731
+    o = MeshContact(new("dist", torch.float32), new("face", torch.int32), new("wind", torch.float32))
+    with torch.cuda.device(dev):
+        rc = L.harp_mesh_contact(ctypes.byref(q), ctypes.byref(t), B, max_dist, _lib.ptr(ws), *[_lib.ptr(x) for x in o], _lib.stream())
+    _lib.check(rc, "harp_mesh_contact")
+    return o
+
+
 # ---- the front that the six batched Levenberg-Marquardt solvers below share (DESIGN.md §34) ---------------------------------------------
 # A wrapper runs, in this order: _playback_input (device tensors, forward only), _lm_float32, its own check of `targets`, _lm_shapes,
 # _lm_scalars, its own checks, _lm_model_device, _lm_result, _lm_start, _lm_input, then its options struct and its one call.

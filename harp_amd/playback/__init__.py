@@ -13,13 +13,14 @@ The package in five modules, each importing only those before it:
              harp_resolve_u8: six calls of the C ABI per batch of frames, in order on one stream, captured into a graph — and `ScenePlayer`,
              several such avatars in one frame through ONE harp_composite_layers_u8 per batch; both on `_Player`, which owns staging,
              graphs and the way to disk; `annotate` of either says what the frames show (harp_annotate_layers, harp_keypoint_visibility),
-             `flow` where each pixel's surface point lies in another frame (harp_flow_layers)
+             `flow` where each pixel's surface point lies in another frame (harp_flow_layers); `ScenePlayer.contact` where the avatars
+             touch: per vertex the signed distance to the nearest other avatar, its face and part (harp_mesh_contact)
   cli        `main`:
 
     python -m harp_amd.playback --config CFG (--motion MOTION.npz | --keypoints KP.npz | --keypoints2d KP.npz | --vertices V.npz) --out DIR [--fps-scale X] [--ss 2] [--background DIR] [--alpha]
                                 [--flip] [--also CFG:MOTION[:flip]]... [--scene-depth DIR] [--masks]
                                 [--smooth SIGMA [--smooth-trim RAD]] [--smooth-keypoints SIGMA] [--labels [--label-tol M]]
-                                [--flow {fw,bw,both} [--flow-tol M]]
+                                [--flow {fw,bw,both} [--flow-tol M]] [--contacts [--contact-dist M]]
 
 Importing the package needs neither the built library nor a device.
 """
@@ -29,10 +30,10 @@ from .keypoints import (ARM_JOINT_IDX, CHAIN_BONES, ELBOW, JOINT_REORDER, PALM, 
                         vertex_start)
 from .labels import face_part_labels, part_names
 from .motion import Motion, motion_jitter, pose_mean_rows, smooth_keypoints
-from .player import BG_WHITE, FLOW_TOL, LABEL_TOL, Annotation, Flow, AvatarPlayer, ScenePlayer, load_backgrounds, load_scene_depth
+from .player import BG_WHITE, CONTACT_DIST, FLOW_TOL, LABEL_TOL, Annotation, Contact, Flow, AvatarPlayer, ScenePlayer, load_backgrounds, load_scene_depth
 
 __all__ = ["Motion", "AvatarPlayer", "ScenePlayer", "smooth_keypoints", "motion_jitter", "pose_mean_rows", "rest_chain_joints",
            "bone_length_scale", "kabsch_rotation", "axis_angle_of", "palm_start", "JOINT_REORDER", "PALM", "CHAIN_BONES", "load_backgrounds",
            "load_scene_depth", "main", "BG_WHITE", "vertex_start", "arm_palm_start", "rest_arm_joints", "match_arm_lengths", "ARM_JOINT_IDX", "ELBOW",
            "planar_palm_starts", "project_pixels", "face_part_labels", "part_names", "Annotation", "LABEL_TOL", "Flow", "FLOW_TOL", "arm_image_ik_inputs",
-           "arm_image_starts"]
+           "arm_image_starts", "Contact", "CONTACT_DIST"]

@@ -3,7 +3,7 @@ import numpy as np
 
 from .. import ops
 from .motion import Motion, motion_jitter
-from .player import FLOW_TOL, LABEL_TOL, AvatarPlayer, ScenePlayer
+from .player import CONTACT_DIST, FLOW_TOL, LABEL_TOL, AvatarPlayer, ScenePlayer
 
 
 def parse_args(argv=None):
@@ -54,6 +54,12 @@ def parse_args(argv=None):
     ap.add_argument("--flow-tol", type=float, default=FLOW_TOL, metavar="M",
                     help="with --flow: a point counts as visible in the other frame when the nearest surface where it lands is no nearer than "
                          "its depth minus M metres")
+    ap.add_argument("--contacts", action="store_true",
+                    help="with --also: also write contacts.npz, per avatar and vertex the signed distance to the nearest other avatar's "
+                         "surface (negative inside it), which avatar, face and part that is, and per frame the smallest distance and the "
+                         "deepest penetration")
+    ap.add_argument("--contact-dist", type=float, default=CONTACT_DIST, metavar="M",
+                    help="with --contacts: a vertex farther than M metres from every other avatar has no contact")
     ap.add_argument("--smooth", type=float, default=None, metavar="SIGMA",
                     help="filter the loaded or solved motion with a Gaussian window of SIGMA frames before --fps-scale (Motion.smooth); prints the "
                          "joint jitter before and after")
@@ -70,6 +76,10 @@ def parse_args(argv=None):
         raise SystemExit("--label-tol must not be negative")
     if not (args.flow_tol >= 0 and np.isfinite(args.flow_tol)):
         raise SystemExit("--flow-tol must not be negative and must be finite")
+    if not args.contact_dist >= 0:
+        raise SystemExit("--contact-dist must not be negative")
+    if args.contacts and not args.also:
+        raise SystemExit("--contacts needs a second avatar: give --also CFG:MOTION[:flip]")
     if args.smooth_trim is not None and args.smooth is None:
         raise SystemExit("--smooth-trim needs --smooth")
     if args.smooth_keypoints is not None and args.keypoints is None:
@@ -159,6 +169,7 @@ def main(argv=None):
             motions.append(motion)
         scene = ScenePlayer(players, flip=[spec[2] for spec in specs])
         paths = scene.play(motions, args.out, backgrounds=args.background, scene_depth=args.scene_depth, fmt=fmt, alpha=args.alpha, masks=args.masks,
-                           labels=args.labels, label_tol=args.label_tol, flow=args.flow, flow_tol=args.flow_tol)
+                           labels=args.labels, label_tol=args.label_tol, flow=args.flow, flow_tol=args.flow_tol, contacts=args.contacts,
+                           contact_dist=args.contact_dist)
     print(f"wrote {len(paths)} frames to {args.out}")
     return paths

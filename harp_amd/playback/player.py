@@ -25,6 +25,15 @@ FLOW_TOL = ops.FLOW_TOL                                # metres: how far under t
 # (x, y); dz (n,S,S) float32: its view depth there minus its depth here, metres; status (n,S,S,2) uint8 = (0 nothing | 1 not trackable |
 # 2 lands outside the image | 3 hidden at the target | 4 visible there, what hides it: 0 nothing, 1 + the player, 255 the scene depth)
 Flow = collections.namedtuple("Flow", "flow dz status")
+CONTACT_DIST = 0.02                                    # metres: how near another avatar's surface counts as contact; about a finger's thickness
+# what ScenePlayer.contact returns: per player k a device tensor over the rows asked for and its V_k vertices, in tuples
+# with one entry per player.  dist (n,V_k) float32, SIGNED: the distance to the nearest other player's surface, negative where the vertex
+# is inside it (wind > 0.5), +inf beyond max_dist; other (n,V_k) uint8: 0 none, 1 + that nearest player; face (n,V_k) int32: the face of
+# it that is touched, -1 none; part (n,V_k) uint8: that face's part (face_part_labels), 0 none; wind (n,V_k) float32: the winding number
+# of that player's surface about the vertex.  Per frame: min_dist (n,) float32, the smallest signed distance of any vertex (+inf: no
+# contact), and max_penetration (n,) float32, the largest -dist over the inside vertices, or 0.  Unlike Annotation and Flow, every tensor
+# is new (compose_contact): a later contact() does not change an earlier result
+Contact = collections.namedtuple("Contact", "dist other face part wind min_dist max_penetration")
 
 
 def _ck(rc, what):
@@ -386,14 +395,17 @@ class AvatarPlayer(_Player):
         a.rgb, a.texnm = _lib.ptr(s["rgb"]), _lib.ptr(self.texnm)
         return a
 
-    def _render_batch(self, fid, shade=True):
+    def _render_batch(self, fid, shade=True, front_only=False):
         """front, rasterisers and shader of one batch of B frames, in order on the current stream: s["rgb"], s["face_c"] (and s["z_c"]
-        with keep_depth) at S * ss, everything in front of the resolve; shade=False stops before the shader (labels need no colour)"""
+        with keep_depth) at S * ss, everything in front of the resolve; shade=False stops before the shader (labels need no colour),
+        front_only=True after the front (contacts need the vertices s["vd"] and the camera only)"""
         L, s, p, tp, st = _lib.lib(), self.s, _lib.ptr, self.topo, _lib.stream()
         B, V, F, Sh = self.B, tp.V, tp.F, self.Sh
         z_c = p(s["z_c"]) if self.keep_depth else None
         h = self._front_struct(fid)
         _ck((L.harp_arm_front_fwd if self.use_arm else L.harp_hand_front_fwd)(ctypes.byref(h), st), "front_fwd")
+        if front_only:
+            return
         if self.self_shadow:
             _ck(L.harp_raster_setup_pair(p(s["ndc_c"]), 0.0, p(s["ws_c"]), p(s["ndc_l"]), 0.0, p(s["ws_l"]), p(tp.faces), B, V, F, Sh, st),
                 "raster_setup_pair")
@@ -440,6 +452,12 @@ class AvatarPlayer(_Player):
         """the batch just rendered is the flow's target: device copies of its ndc_c and z_c, in stream order"""
         self.s_to["ndc"].copy_(self.s["ndc_c"])
         self.s_to["z"].copy_(self.s["z_c"])
+
+    def _contact_mesh(self, flip):
+        """this player's side of a harp_mesh_contact over its batch buffers"""
+        s, p, tp = self.s, _lib.ptr, self.topo
+        return _lib.ContactMesh(verts=p(s["vd"]), cam_R=p(s["cam_R"]), cam_T=p(s["cam_T"]), faces=p(tp.faces), V=tp.V, F=tp.F, flip_x=int(flip),
+                                reserved=0)
 
     def _keypoint_buffers(self, n):
         """(uvz, vis) for n frames of this player's joints; whoever runs the launches owns them (the player itself, or its scene)"""
@@ -584,6 +602,7 @@ class ScenePlayer(_Player):
         super().__init__(p0.dev, p0.S, p0.ss, p0.B, all(p.use_graph for p in players),
                          (("background", (p0.S, p0.S, 3), torch.uint8), ("scene_depth", (p0.S, p0.S), torch.float32)))
         self._labels_wanted, self.lab, self.kp = False, None, None
+        self._contacts_wanted, self._contact = False, None      # what contact() adds, allocated on its first call (_grow)
 
     def load_motions(self, motions):
         """one motion per player, of equal length: scene row i is row i of every motion (AvatarPlayer.load_motion each)"""
@@ -607,14 +626,34 @@ class ScenePlayer(_Player):
         if self._labels_wanted and self.lab is None:
             self.lab = _label_buffers(self._n_cap, self.S, len(self.players), self.dev)
             self.kp = [pl._keypoint_buffers(self._n_cap) for pl in self.players]
+        if self._contacts_wanted and (self._contact is None or self._contact["cap"] != self._n_cap):
+            # per ordered pair (query k, target j) the three outputs of harp_mesh_contact over every padded row; one workspace, for the
+            # target with the most faces (the calls follow each other on one stream)
+            n, P = self._n_cap, len(self.players)
+            new = lambda dt, V: torch.empty(n, V, dtype=dt, device=self.dev)      # noqa: E731
+            pairs = {(k, j): (new(torch.float32, q.topo.V), new(torch.int32, q.topo.V), new(torch.float32, q.topo.V))
+                     for k, q in enumerate(self.players) for j in range(P) if j != k}
+            ws = torch.empty(max(_lib.lib().harp_mesh_contact_ws_floats(self.B, pl.topo.F) for pl in self.players), dtype=torch.float32, device=self.dev)
+            self._contact = dict(cap=n, pairs=pairs, ws=ws)
 
-    def _enqueue(self, n_pad, channels, with_bg, with_depth, with_owner, labels=None, flow=None):
+    def _enqueue(self, n_pad, channels, with_bg, with_depth, with_owner, labels=None, flow=None, contact=None):
         """per batch: every player's front / rasterisers / shader, then one composite; with labels = (part, depth, uv, keypoints, tol)
         every player's front / rasterisers, then the labels of the batch and every player's keypoints; with flow = ("flow", tol)
         every player's front / rasterisers of the TARGET rows and copies of their ndc_c and z_c, the same of the source rows, then
-        the flow of the batch"""
+        the flow of the batch; with contact = ("contact", max_dist) every player's front only, then one harp_mesh_contact per ordered
+        pair of players into the pair's rows of self._contact.  max_dist is part of the graph key, as flow's and the labels' tol are: every
+        distinct value captures a graph of its own, kept until the scene grows or new tables are loaded"""
         L, p, B = _lib.lib(), _lib.ptr, self.B
         per = self.S * self.S
+        if contact is not None:                          # ("contact", max_dist): every player's front, then one call per ordered pair
+            meshes = [pl._contact_mesh(f) for pl, f in zip(self.players, self.flip)]
+            for lo in range(0, n_pad, B):
+                for pl in self.players:
+                    pl._render_batch(self.idx_dev[0, lo:lo + B], front_only=True)
+                for (k, j), (d, f, w) in self._contact["pairs"].items():
+                    _ck(L.harp_mesh_contact(ctypes.byref(meshes[k]), ctypes.byref(meshes[j]), B, contact[1], p(self._contact["ws"]),
+                                            d[lo:].data_ptr(), f[lo:].data_ptr(), w[lo:].data_ptr(), _lib.stream()), "mesh_contact")
+            return
         if flow is not None:
             P = len(self.players)
             layers = (_lib.FlowLayer * P)(*[pl._flow_layer(f) for pl, f in zip(self.players, self.flip)])
@@ -692,14 +731,42 @@ class ScenePlayer(_Player):
                          to=(to_rows, [(scene_depth, depth_to_rows)]))[1]
         return self._flow_view(n)
 
+    @torch.no_grad()
+    def contact(self, rows, max_dist=CONTACT_DIST):
+        """Where the avatars of the scene's frames `rows` touch -> Contact (above): per player and vertex the signed distance to the nearest
+        OTHER player's surface, which player, face and part that is, and the winding number about it; per frame the smallest distance and
+        the deepest penetration.  Needs at least two players.  Per batch every player's front only (no rasteriser runs) and one
+        harp_mesh_contact per ordered pair of players, under a graph key of its own; the minimum over the others is taken afterwards
+        with torch ops on the device (the lower player wins a tie).  max_dist metres: beyond it a vertex has no contact (+inf, 0, -1, 0,
+        0); CONTACT_DIST = 0.02 is about a finger's thickness, a convention, not a tuned value.  A vertex is INSIDE another avatar when
+        the winding number of that avatar's surface about it exceeds 0.5; the hand and arm meshes are open at the wrist or shoulder, so
+        near that opening the value is fractional."""
+        if len(self.players) < 2:
+            raise ValueError("contact needs a scene of at least two players")
+        if self.T < 1 or any(p.tables is None for p in self.players):
+            raise RuntimeError("load_motions() first")
+        max_dist = float(max_dist)
+        if not max_dist >= 0:
+            raise ValueError(f"max_dist must not be negative or NaN, got {max_dist}")
+        tabs = [pl._part_table() for pl in self.players]
+        self._contacts_wanted = True
+        n = self._render(rows, False, [(None, None), (None, None)], False, None, None, ("contact", max_dist))[1]
+        return compose_contact([{j: tuple(t[:n] for t in self._contact["pairs"][k, j]) for j in range(len(self.players)) if j != k}
+                                for k in range(len(self.players))], tabs)
+
     def play(self, motions, out_dir, backgrounds=None, scene_depth=None, fmt="jpg", alpha=False, masks=False, labels=False, label_tol=LABEL_TOL,
-             flow=None, flow_tol=FLOW_TOL):
+             flow=None, flow_tol=FLOW_TOL, contacts=False, contact_dist=CONTACT_DIST):
         """load_motions(motions), render the scene batch by batch and write out_dir/%04d.<fmt> as AvatarPlayer.play does; with masks=True
         also out_dir/mask_%04d.png, the owner map (8-bit grey: 0 background, 1 + the player).  backgrounds: as AvatarPlayer.play;
         scene_depth: None, a float32 (N,S,S) tensor or a directory (load_scene_depth), frame i tested against depth i mod N.  labels=True
         also writes the label files (write_labels), one keypoints_<k>.npz per player k when there are several.  Returns the list of the
-        frames' paths.  flow="fw" | "bw" | "both" also writes the flow files (write_flow)."""
+        frames' paths.  flow="fw" | "bw" | "both" also writes the flow files (write_flow).  contacts=True (at least two players) also
+        writes contacts.npz (write_contacts) with contact(rows, contact_dist) of every frame."""
         _flow_mode(flow), _flow_tol(flow_tol)
+        if contacts and len(self.players) < 2:
+            raise ValueError("contacts need a scene of at least two players")
+        if contacts and not float(contact_dist) >= 0:
+            raise ValueError(f"contact_dist must not be negative or NaN, got {contact_dist}")
 
         def prepare():
             self.load_motions(motions)
@@ -718,6 +785,9 @@ class ScenePlayer(_Player):
             dr = lambda rows: None if d is None else rows % d.shape[0]      # noqa: E731
             write_flow(out_dir, self.T, self.B, lambda rows, to: self.flow(rows, to, tol=flow_tol, scene_depth=d, depth_rows=dr(rows),
                                                                           depth_to_rows=dr(to)), flow)
+        if contacts:
+            write_contacts(out_dir, self.T, self.B, lambda rows: self.contact(rows, contact_dist), [part_names_of(pl) for pl in self.players],
+                           float(contact_dist))
         return paths
 
 
@@ -747,6 +817,53 @@ def _enqueue_labels(lab, lo, layers, n_layers, B, S, ss, scene, labels):
     lab["bbox"][lo:lo + B].zero_()                       # (inside the captured sequence: the boxes are accumulated by atomic max)
     _ck(_lib.lib().harp_annotate_layers(layers, n_layers, B, S, ss, *scene, at("owner"), at("part", labels[0]), at("depth", labels[1]), at("face"),
                                         at("uv", labels[2]), at("bbox"), _lib.stream()), "annotate_layers")
+
+
+def compose_contact(pairs, part_tables):
+    """The documented rule from the pairwise results to Contact, in torch ops on the device.  pairs: per player k a dict {other player j:
+    (dist, face, wind) of harp_mesh_contact with k as the query and j as the target}; part_tables: per player its (F,) uint8 part of every
+    face.  Per vertex the other with the smallest unsigned distance wins, the lower player a tie; the distance is negated where that
+    player's winding number exceeds 0.5.  A pair beyond max_dist brings (+inf, -1, 0) and never wins over a finite one.  A player's part
+    table is indexed by ITS faces only (the players of a scene may have meshes of different sizes), and every tensor returned is new:
+    none is a view of `pairs`."""
+    dist, other, face, part, wind = [], [], [], [], []
+    for mine in pairs:
+        d = f = w = o = pt = None
+        for j in sorted(mine):
+            dj, fj, wj = mine[j]
+            hit = fj >= 0
+            oj = torch.where(hit, torch.full_like(fj, j + 1, dtype=torch.uint8), torch.zeros_like(fj, dtype=torch.uint8))
+            pj = torch.where(hit, part_tables[j][fj.clamp(min=0).long()], torch.zeros_like(oj))
+            if d is None:
+                d, f, w, o, pt = dj, fj.clone(), wj.clone(), oj, pj
+            else:
+                m = dj < d
+                d, f, w, o, pt = (torch.where(m, new, old) for new, old in ((dj, d), (fj, f), (wj, w), (oj, o), (pj, pt)))
+        dist.append(torch.where(w > 0.5, -d, d)); other.append(o); face.append(f); part.append(pt); wind.append(w)
+    min_dist = torch.stack([d.amin(1) for d in dist]).amin(0)
+    deep = torch.stack([torch.where(w > 0.5, -d, torch.zeros_like(d)).amax(1) for d, w in zip(dist, wind)]).amax(0)
+    return Contact(tuple(dist), tuple(other), tuple(face), tuple(part), tuple(wind), min_dist, deep.clamp(min=0))
+
+
+def write_contacts(out_dir, T, B, contact, names, max_dist):
+    """contacts.npz of a played scene beside its frames, batch by batch: per player k dist_k (T,V_k) float32 signed metres (+inf: none),
+    other_k (T,V_k) uint8, face_k (T,V_k) int32, part_k (T,V_k) uint8, wind_k (T,V_k) float32 and part_names_k; min_dist (T,),
+    max_penetration (T,) float32; max_dist, the contact distance used.  contact(rows) -> Contact; names: one list of part names per player."""
+    P = len(names)
+    keys = ("dist", "other", "face", "part", "wind")
+    got = {f"{key}_{k}": [] for key in keys for k in range(P)}
+    per_frame = dict(min_dist=[], max_penetration=[])
+    for lo in range(0, T, B):
+        c = contact(np.arange(lo, min(T, lo + B)))
+        for key in keys:
+            for k in range(P):
+                got[f"{key}_{k}"].append(getattr(c, key)[k].cpu().numpy())
+        for key in per_frame:
+            per_frame[key].append(getattr(c, key).cpu().numpy())
+    path = os.path.join(out_dir, "contacts.npz")
+    np.savez(path, max_dist=np.float32(max_dist), **{k: np.concatenate(v) for k, v in {**got, **per_frame}.items()},
+             **{f"part_names_{k}": np.array(names[k]) for k in range(P)})
+    return path
 
 
 def _flow_tol(tol):

@@ -1187,6 +1187,46 @@ int harp_flow_layers(const harp_flow_layer* layers, int n_layers, int B, int S, 
                      const int32_t* scene_rows, const float* scene_z_to, int n_scene_to, const int32_t* scene_rows_to, float tol, float* flow,
                      float* dz, unsigned char* status, hipStream_t stream);
 
+/* ---- contact labels: per-vertex distance and penetration between two meshes (csrc/contact.hip; playback/player.py ScenePlayer.contact;
+ * DESIGN.md §36) ----
+ * Nothing in the reference does this.  The entry is pairwise: for every vertex of a QUERY mesh its relation to the surface of a TARGET
+ * mesh, over the B frames of a batch.  It uses no atomics, allocates nothing, only enqueues on `stream` (a set-up launch and the main
+ * launch) and is capturable; a repeated call gives the same bits.  Both structs are HOST structs read during the call. */
+typedef struct harp_contact_mesh {
+  const float* verts;     /* (B,V,3) model-space vertices as the fused front leaves `vd` */
+  const float* cam_R;     /* (B,9)  \ view = harp_project_fwd's transform: X = p.r[0,3,6] + T[0], Y = p.r[1,4,7] + T[1],    */
+  const float* cam_T;     /* (B,3)  / Z = p.r[2,5,8] + T[2]                                                                  */
+  const int32_t* faces;   /* (F,3); read for the target only, may be NULL for the query (whose F is not read either) */
+  int32_t V, F;
+  int32_t flip_x;         /* != 0: the mesh is shown mirrored, view.x -> -view.x */
+  int32_t reserved;       /* 0 */
+} harp_contact_mesh;
+/* floats of workspace for B frames of a target of F_target faces (0 for B <= 0 or F_target <= 0): per frame one box of 8 floats per
+ * chunk of 128 faces and 12 floats per face (its view-space corners), written by the set-up launch and read by the main one */
+size_t harp_mesh_contact_ws_floats(int B, int F_target);
+/* harp_mesh_contact: max_dist metres, ws of harp_mesh_contact_ws_floats(B, target->F) floats, 16-byte aligned -> dist (B,Vq) f32,
+ * face (B,Vq) i32, wind (B,Vq) f32.  All geometry is in view space after the flip.  For query vertex (b, i) with view position p:
+ *   dist: the unsigned Euclidean distance from p to the nearest point of the target's triangles of frame b when that distance is
+ *     <= max_dist, otherwise +inf.  max_dist = +inf is allowed: no limit.
+ *   face: a target face that attains that distance, the lowest index among exactly equal float32 values; -1 when dist is +inf.
+ *   wind: the generalised winding number of the target surface about p = the sum over the target's faces of the signed solid angle
+ *     over 4 pi, in van Oosterom-Strackee form: 2 atan2(det[a,b,c], |a||b||c| + (a.b)|c| + (b.c)|a| + (c.a)|b|) with a, b, c the corners
+ *     minus p.  It is negated when target->flip_x is set (mirroring reverses the orientation).  It is computed only where dist is
+ *     finite and is 0 elsewhere.  About 1 inside a closed outward-oriented mesh and about 0 outside; MANO and the arm mesh are open at
+ *     the wrist or shoulder, so the value is fractional near the opening.  "Inside" as wind > 0.5 is the Python layer's convention.
+ *   A target face with a non-finite corner (in view space) or an index outside [0, target->V) is skipped by both sums; nothing is read
+ *     out of bounds.  A zero-area face (its normal (b - a) x (c - a) exactly zero in float32, as for repeated indices) counts as its
+ *     segment or point for the distance and adds 0 to wind; no input gives a NaN.  A non-finite query vertex gives +inf, -1, 0.
+ *   dist, face and wind may each be NULL, but not all three; a missing output changes nothing in the others.
+ * The distance is computed in float32 from the float32 view positions: within 32 * 2^-24 M of the exact one, M the largest absolute view
+ * coordinate.  The result does not depend on how the faces are chunked: chunks are skipped by bounding boxes only where no face of
+ * theirs could replace or tie a result.
+ * HARP_ERR_ARG before any launch: a NULL query, target, ws, verts, cam_R or cam_T; a NULL target->faces; V of either, target->F or B <= 0;
+ * a non-zero reserved; max_dist negative or NaN; all outputs NULL; ws not 16-byte aligned; more than 2^31 - 1 tiles of 64 query vertices
+ * or chunks over the batch. */
+int harp_mesh_contact(const harp_contact_mesh* query, const harp_contact_mesh* target, int B, float max_dist, float* ws, float* dist,
+                      int32_t* face, float* wind, hipStream_t stream);
+
 /* ---- batched MANO inverse kinematics: 3-D keypoints -> pose rows (csrc/ik.hip; playback.py Motion.from_keypoints) ----
  * Nothing in the reference does this: its change_pose takes another sequence's parameters.  The model inverted is harp_lbs_mano_fwd's.
  * T independent Levenberg-Marquardt solves in one launch, forward only, no workspace, no allocation, no synchronisation, no atomics
