@@ -7,6 +7,8 @@ hardware happens to interleave them badly."""
 import contextlib
 import os
 import re
+import sys
+import threading
 
 import torch
 
@@ -113,3 +115,86 @@ def delayed(eng, where):
         for name, fn in saved.items():
             setattr(L, name, fn)
         eng._graphs = {}
+
+
+# ---- host / device hand-offs (tests/test_gpu_handoffs.py) ------------------------------------------------------------------------------
+# Where the HOST can run ahead of the device — a pinned buffer rewritten before its copy has run, a pinned buffer read before its copy
+# has landed — the device is made late by whole milliseconds, and the host-side waits are watched: a run proves something only if one
+# of its waits really found its event incomplete.
+_EVENT_BASE = torch._C._CudaEventBase                   # the methods under torch.cuda.Event's wrappers: what the spies call through to
+_waits_checked = {}
+
+
+def busy_wait(ms):
+    """Enqueue a busy wait of about `ms` milliseconds on the current stream: calibrate()'s busy wait, scaled by the time per unit it
+    measured.  The first call per process and length times one such wait with events (and waits for it) and asserts that it took
+    between 0.5 x and 2 x the request; every call then enqueues the wait and returns at once."""
+    sleep, n, us = calibrate()
+    units = max(1, int(round(n * (float(ms) * 1e3 / us))))
+    if units not in _waits_checked:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        sleep(units)
+        e1.record()
+        _EVENT_BASE.synchronize(e1)                      # (not through torch.cuda.Event.synchronize: a wait_spy may have it)
+        took = e0.elapsed_time(e1)
+        print(f"[delay] busy_wait({ms:.1f} ms): {units} {_cal['unit']} took {took:.1f} ms")
+        assert 0.5 * ms <= took <= 2.0 * ms, (ms, units, took)
+        _waits_checked[units] = took
+    sleep(units)
+
+
+@contextlib.contextmanager
+def late_calls(obj, name, ms):
+    """Inside the context every call of the Python attribute `obj.name` (a function of a module, a method of an instance) first enqueues
+    busy_wait(ms) on the stream current at that moment: the device work of every such call starts `ms` late.  The attribute is restored
+    on exit (an instance's own attribute that hid its class's method is deleted again)."""
+    own = name in vars(obj)
+    fn = getattr(obj, name)
+
+    def call(*args, **kw):
+        busy_wait(ms)
+        return fn(*args, **kw)
+
+    setattr(obj, name, call)
+    try:
+        yield
+    finally:
+        if own:
+            setattr(obj, name, fn)
+        else:
+            delattr(obj, name)
+
+
+@contextlib.contextmanager
+def wait_spy(bypass=False, method="synchronize"):
+    """Wrap torch.cuda.Event.synchronize (or, with method="query", torch.cuda.Event.query) and yield the list of records, one dict per
+    call: `complete` — for synchronize: self.query() as it was on entry; for query: what it returned — `thread`, the calling thread's
+    name, and `where`, the name of the calling function.  synchronize calls through unless `bypass` is true (the positive controls: the
+    host then does not wait).  The method is restored on exit.  A record with complete == False is the proof that the host reached a
+    wait before the device had got there: without one a delayed run has not opened the window it claims to test."""
+    assert method in ("synchronize", "query") and not (bypass and method == "query"), (method, bypass)
+    records = []
+    saved = getattr(torch.cuda.Event, method)
+
+    def spy(self):
+        rec = dict(complete=None, thread=threading.current_thread().name, where=sys._getframe(1).f_code.co_name)
+        if method == "query":
+            rec["complete"] = bool(saved(self))
+            records.append(rec)
+            return rec["complete"]
+        rec["complete"] = bool(_EVENT_BASE.query(self))
+        records.append(rec)
+        if not bypass:
+            saved(self)
+
+    setattr(torch.cuda.Event, method, spy)
+    try:
+        yield records
+    finally:
+        setattr(torch.cuda.Event, method, saved)
+
+
+def incomplete(records, where=None, thread=None):
+    """how many of wait_spy's records found their event incomplete, of those made in function `where` / on thread `thread`"""
+    return sum(1 for r in records if not r["complete"] and where in (None, r["where"]) and thread in (None, r["thread"]))
