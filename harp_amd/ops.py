@@ -1078,6 +1078,55 @@ def _playback_input(name, *ts):
     check_forward_only(*[t for t in ts if t is not None and t.is_floating_point()])
 
 
+def _background_input(background, bg_rows, bg_color, B, S, device):
+    """resolve_u8's checks of (background, bg_rows, bg_color) -> (background, n_bg, bg_rows, the colour as a (3,) float32 device tensor)"""
+    n_bg = 0
+    if background is not None:
+        if background.dtype != torch.uint8 or background.dim() != 4 or tuple(background.shape[1:]) != (S, S, 3) or background.shape[0] < 1:
+            raise TypeError(f"background must be uint8 (n_bg, {S}, {S}, 3), got {background.dtype} {tuple(background.shape)}")
+        n_bg = background.shape[0]
+        if bg_rows is None and n_bg not in (1, B):
+            raise ValueError(f"{n_bg} backgrounds for {B} frames: pass bg_rows")
+        background = background.contiguous()
+    if bg_rows is not None:
+        if bg_rows.dtype != torch.int32 or tuple(bg_rows.shape) != (B,):
+            raise TypeError(f"bg_rows must be int32 ({B},), got {bg_rows.dtype} {tuple(bg_rows.shape)}")
+        bg_rows = bg_rows.contiguous()
+    if torch.is_tensor(bg_color):
+        if bg_color.dtype != torch.float32 or tuple(bg_color.shape) != (3,):
+            raise TypeError(f"bg_color must be three numbers or a float32 (3,) tensor, got {bg_color.dtype} {tuple(bg_color.shape)}")
+        return background, n_bg, bg_rows, bg_color.detach().contiguous()
+    return background, n_bg, bg_rows, torch.tensor([float(c) for c in bg_color], dtype=torch.float32).reshape(3).to(device)
+
+
+def _frames_out(out, B, S, C, device):
+    """the (B,S,S,C) uint8 frames to write into: the caller's `out` checked, or new ones"""
+    if out is None:
+        return torch.empty(B, S, S, C, dtype=torch.uint8, device=device)
+    if out.dtype != torch.uint8 or tuple(out.shape) != (B, S, S, C) or not out.is_contiguous():
+        raise ValueError(f"out must be a contiguous uint8 tensor {(B, S, S, C)}")
+    return out
+
+
+def _scene_depth_input(name, scene_depth, scene_rows, B, S):
+    """the checks of (scene_depth, scene_rows) of composite_layers_u8 and the label ops -> (scene_depth, scene_rows, n_scene), contiguous"""
+    n_scene = 0
+    if scene_depth is not None:
+        if scene_depth.dtype != torch.float32 or scene_depth.dim() != 3 or tuple(scene_depth.shape[1:]) != (S, S) or scene_depth.shape[0] < 1:
+            raise TypeError(f"scene_depth must be float32 (n_scene, {S}, {S}), got {scene_depth.dtype} {tuple(scene_depth.shape)}")
+        n_scene = scene_depth.shape[0]
+        if scene_rows is None and n_scene not in (1, B):
+            raise ValueError(f"{n_scene} scene depths for {B} frames: pass scene_rows")
+        scene_depth = scene_depth.detach().contiguous()
+    if scene_rows is not None:
+        if scene_depth is None:
+            raise ValueError("scene_rows without a scene_depth")
+        if scene_rows.dtype != torch.int32 or tuple(scene_rows.shape) != (B,):
+            raise TypeError(f"scene_rows must be int32 ({B},), got {scene_rows.dtype} {tuple(scene_rows.shape)}")
+        scene_rows = scene_rows.contiguous()
+    return scene_depth, scene_rows, n_scene
+
+
 def motion_resample(keys, times, n_rot, rot_offset=None):
     """Key-frame rows at fractional times (csrc/playback.hip: harp_motion_resample), forward only: keys (Tk, 3 n_rot + n_lin) float32 =
     n_rot axis-angle triples then n_lin linear channels, times (Tn,) float32 in key-frame units (clamped to [0, Tk - 1]) ->
@@ -1196,29 +1245,9 @@ def resolve_u8(rgb, face_id, ss=1, background=None, bg_rows=None, bg_color=(1, 1
     B, S = rgb.shape[0], rgb.shape[1] // ss
     if face_id.dtype != torch.int32 or tuple(face_id.shape) != tuple(rgb.shape[:3]):
         raise TypeError(f"face_id must be int32 {tuple(rgb.shape[:3])}, got {face_id.dtype} {tuple(face_id.shape)}")
-    n_bg = 0
-    if background is not None:
-        if background.dtype != torch.uint8 or background.dim() != 4 or tuple(background.shape[1:]) != (S, S, 3) or background.shape[0] < 1:
-            raise TypeError(f"background must be uint8 (n_bg, {S}, {S}, 3), got {background.dtype} {tuple(background.shape)}")
-        n_bg = background.shape[0]
-        if bg_rows is None and n_bg not in (1, B):
-            raise ValueError(f"{n_bg} backgrounds for {B} frames: pass bg_rows")
-        background = background.contiguous()
-    if bg_rows is not None:
-        if bg_rows.dtype != torch.int32 or tuple(bg_rows.shape) != (B,):
-            raise TypeError(f"bg_rows must be int32 ({B},), got {bg_rows.dtype} {tuple(bg_rows.shape)}")
-        bg_rows = bg_rows.contiguous()
-    if torch.is_tensor(bg_color):
-        if bg_color.dtype != torch.float32 or tuple(bg_color.shape) != (3,):
-            raise TypeError(f"bg_color must be three numbers or a float32 (3,) tensor, got {bg_color.dtype} {tuple(bg_color.shape)}")
-        color = bg_color.detach().contiguous()
-    else:
-        color = torch.tensor([float(c) for c in bg_color], dtype=torch.float32).reshape(3).to(rgb.device)
+    background, n_bg, bg_rows, color = _background_input(background, bg_rows, bg_color, B, S, rgb.device)
     C = 4 if alpha else 3
-    if out is None:
-        out = torch.empty(B, S, S, C, dtype=torch.uint8, device=rgb.device)
-    elif out.dtype != torch.uint8 or tuple(out.shape) != (B, S, S, C) or not out.is_contiguous():
-        raise ValueError(f"out must be a contiguous uint8 tensor {(B, S, S, C)}")
+    out = _frames_out(out, B, S, C, rgb.device)
     with torch.cuda.device(rgb.device):
         rc = _lib.lib().harp_resolve_u8(_lib.ptr(rgb.detach().contiguous()), _lib.ptr(face_id.contiguous()), B, S, ss, _lib.ptr(background), n_bg,
                                         _lib.ptr(bg_rows), _lib.ptr(color), C, _lib.ptr(out), _lib.stream())
@@ -1255,43 +1284,10 @@ def composite_layers_u8(layers, ss=1, scene_depth=None, scene_rows=None, backgro
             raise TypeError(f"layer {i}: rgb and zbuf must be float32, got {c.dtype} and {z.dtype}")
         if tuple(c.shape) != tuple(rgb.shape) or tuple(z.shape) != tuple(rgb.shape[:3]):
             raise ValueError(f"layer {i}: rgb {tuple(c.shape)} and zbuf {tuple(z.shape)} must be {tuple(rgb.shape)} and {tuple(rgb.shape[:3])}")
-    n_scene = 0
-    if scene_depth is not None:
-        if scene_depth.dtype != torch.float32 or scene_depth.dim() != 3 or tuple(scene_depth.shape[1:]) != (S, S) or scene_depth.shape[0] < 1:
-            raise TypeError(f"scene_depth must be float32 (n_scene, {S}, {S}), got {scene_depth.dtype} {tuple(scene_depth.shape)}")
-        n_scene = scene_depth.shape[0]
-        if scene_rows is None and n_scene not in (1, B):
-            raise ValueError(f"{n_scene} scene depths for {B} frames: pass scene_rows")
-        scene_depth = scene_depth.detach().contiguous()
-    if scene_rows is not None:
-        if scene_depth is None:
-            raise ValueError("scene_rows without a scene_depth")
-        if scene_rows.dtype != torch.int32 or tuple(scene_rows.shape) != (B,):
-            raise TypeError(f"scene_rows must be int32 ({B},), got {scene_rows.dtype} {tuple(scene_rows.shape)}")
-        scene_rows = scene_rows.contiguous()
-    n_bg = 0
-    if background is not None:
-        if background.dtype != torch.uint8 or background.dim() != 4 or tuple(background.shape[1:]) != (S, S, 3) or background.shape[0] < 1:
-            raise TypeError(f"background must be uint8 (n_bg, {S}, {S}, 3), got {background.dtype} {tuple(background.shape)}")
-        n_bg = background.shape[0]
-        if bg_rows is None and n_bg not in (1, B):
-            raise ValueError(f"{n_bg} backgrounds for {B} frames: pass bg_rows")
-        background = background.contiguous()
-    if bg_rows is not None:
-        if bg_rows.dtype != torch.int32 or tuple(bg_rows.shape) != (B,):
-            raise TypeError(f"bg_rows must be int32 ({B},), got {bg_rows.dtype} {tuple(bg_rows.shape)}")
-        bg_rows = bg_rows.contiguous()
-    if torch.is_tensor(bg_color):
-        if bg_color.dtype != torch.float32 or tuple(bg_color.shape) != (3,):
-            raise TypeError(f"bg_color must be three numbers or a float32 (3,) tensor, got {bg_color.dtype} {tuple(bg_color.shape)}")
-        color = bg_color.detach().contiguous()
-    else:
-        color = torch.tensor([float(c) for c in bg_color], dtype=torch.float32).reshape(3).to(rgb.device)
+    scene_depth, scene_rows, n_scene = _scene_depth_input("composite_layers_u8", scene_depth, scene_rows, B, S)
+    background, n_bg, bg_rows, color = _background_input(background, bg_rows, bg_color, B, S, rgb.device)
     C = 4 if alpha else 3
-    if out is None:
-        out = torch.empty(B, S, S, C, dtype=torch.uint8, device=rgb.device)
-    elif out.dtype != torch.uint8 or tuple(out.shape) != (B, S, S, C) or not out.is_contiguous():
-        raise ValueError(f"out must be a contiguous uint8 tensor {(B, S, S, C)}")
+    out = _frames_out(out, B, S, C, rgb.device)
     own = torch.empty(B, S, S, dtype=torch.uint8, device=rgb.device) if owner else None
     keep = [(c.detach().contiguous(), z.detach().contiguous()) for c, z, _ in layers]      # (alive until the launch is enqueued)
     arr = (_lib.Layer * len(layers))(*[_lib.Layer(_lib.ptr(c), _lib.ptr(z), int(bool(l[2])), 0) for (c, z), l in zip(keep, layers)])
@@ -1307,27 +1303,6 @@ def composite_layers_u8(layers, ss=1, scene_depth=None, scene_rows=None, backgro
 LayerLabels = collections.namedtuple("LayerLabels", "owner part depth face uv bbox")
 KeypointVisibility = collections.namedtuple("KeypointVisibility", "uvz vis")
 LABEL_OCCLUDER_SCENE = 255                             # vis[..., 1] of a joint hidden by the scene depth
-
-
-def _scene_depth_input(name, scene_depth, scene_rows, B, S):
-    """composite_layers_u8's checks of (scene_depth, scene_rows) -> (scene_depth, scene_rows, n_scene), contiguous"""
-    n_scene = 0
-    if scene_depth is not None:
-        if scene_depth.dtype != torch.float32 or scene_depth.dim() != 3 or tuple(scene_depth.shape[1:]) != (S, S) or scene_depth.shape[0] < 1:
-            raise TypeError(f"scene_depth must be float32 (n_scene, {S}, {S}), got {scene_depth.dtype} {tuple(scene_depth.shape)}")
-        n_scene = scene_depth.shape[0]
-        if scene_rows is None and n_scene not in (1, B):
-            raise ValueError(f"{n_scene} scene depths for {B} frames: pass scene_rows")
-        scene_depth = scene_depth.detach().contiguous()
-    if scene_rows is not None:
-        if scene_depth is None:
-            raise ValueError("scene_rows without a scene_depth")
-        if scene_rows.dtype != torch.int32 or tuple(scene_rows.shape) != (B,):
-            raise TypeError(f"scene_rows must be int32 ({B},), got {scene_rows.dtype} {tuple(scene_rows.shape)}")
-        scene_rows = scene_rows.contiguous()
-    return scene_depth, scene_rows, n_scene
-
-
 _LABEL_LAYER_KEYS = ("face_id", "zbuf", "face_label", "flip", "ndc", "faces", "verts_uvs", "faces_uvs")
 
 

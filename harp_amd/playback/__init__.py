@@ -11,10 +11,12 @@ The package in five modules, each importing only those before it:
   labels     `face_part_labels`, `part_names`: the part of the hand every face belongs to, from the skinning weights (host integers)
   player     `AvatarPlayer`, the forward-only renderer — the fit's own fused front, rasterisers and shader without a backward, then
              harp_resolve_u8: six calls of the C ABI per batch of frames, in order on one stream, captured into a graph — and `ScenePlayer`,
-             several such avatars in one frame through ONE harp_composite_layers_u8 per batch; both on `_Player`, which owns staging,
-             graphs and the way to disk; `annotate` of either says what the frames show (harp_annotate_layers, harp_keypoint_visibility),
-             `flow` where each pixel's surface point lies in another frame (harp_flow_layers); `ScenePlayer.contact` where the avatars
-             touch: per vertex the signed distance to the nearest other avatar, its face and part (harp_mesh_contact)
+             several such avatars in one frame through ONE harp_composite_layers_u8 per batch; both on `_Player`, which owns the
+             staging table (`_Stage`), the graphs, each pass's buffers and the way to disk.  A call is one pass — frames, labels, flow
+             or contact — under a graph of its own: `annotate` of either says what the frames show (harp_annotate_layers,
+             harp_keypoint_visibility), `flow` where each pixel's surface point lies in another frame (harp_flow_layers), both written
+             once over the player's layers (an avatar is a scene of one); `ScenePlayer.contact` where the avatars touch: per vertex
+             the signed distance to the nearest other avatar, its face and part (harp_mesh_contact)
   cli        `main`:
 
     python -m harp_amd.playback --config CFG (--motion MOTION.npz | --keypoints KP.npz | --keypoints2d KP.npz | --vertices V.npz) --out DIR [--fps-scale X] [--ss 2] [--background DIR] [--alpha]

@@ -1,6 +1,7 @@
-"""The two forward-only renderers on one base.  `_Player` owns what a render call and a play loop need whatever is drawn:
-the index stage, the copies of the caller's tensors, the output buffer, the graphs and the double-buffered way to disk.  `AvatarPlayer`
-adds one avatar's launches and the resolve (§22), `ScenePlayer` several avatars and the composite (§23)."""
+"""The two forward-only renderers on one base.  `_Player` owns what a call and a play loop need whatever is drawn: the
+index stage (`_Stage`) with the copies of the caller's tensors, the buffers of each kind of pass, the graphs, the labels and flow passes
+over the player's layers, and the double-buffered way to disk.  `AvatarPlayer` adds one avatar's launches and the resolve (§22),
+`ScenePlayer` several avatars, the composite (§23) and the contact pass (§36)."""
 import collections
 import ctypes
 import os
@@ -36,11 +37,6 @@ CONTACT_DIST = 0.02                                    # metres: how near anothe
 Contact = collections.namedtuple("Contact", "dist other face part wind min_dist max_penetration")
 
 
-def _ck(rc, what):
-    if rc != 0:
-        raise RuntimeError(f"{what} failed with status {rc}")
-
-
 def _host_rows(name, rows, n=None):
     r = checked(name, rows).astype(np.int64).reshape(-1)
     if n is not None and r.shape[0] != n:
@@ -64,19 +60,64 @@ def stage_table(rows, n_pad, inputs=()):
     return tab
 
 
-class _Player:
-    """What AvatarPlayer and ScenePlayer share.  A subclass declares the caller tensors it stages (`_inputs`: name, per-row shape, dtype)
-    and supplies `_enqueue(n_pad, channels, *flags)`, the launches of a whole call in order on the current stream; `flags` begins with one
-    bool per staged input.  Nothing is allocated after the constructor except when a longer `rows` is first seen (`_grow`)."""
+class _Stage:
+    """One index table of a render call (stage_table's layout over `inputs`, a player's declared (name, per-row shape, dtype)) on the
+    device, its pinned host copy, and the player's own copy of every staged input the calls have used so far."""
 
-    _holds = "the motion holds"
+    def __init__(self, inputs, dev, B):
+        self.inputs, self.dev, self.B, self.cap, self.bufs = inputs, dev, B, 0, {}
+
+    def alloc(self, n, used):
+        """the tables for n padded rows when that is not their length, and a copy of every input of `used` (one bool per input) that
+        has none yet (no graph reads it: the key of a graph says which inputs it uses)"""
+        if n != self.cap:
+            rows = 1 + 2 * len(self.inputs)
+            self.idx_dev = torch.zeros(rows, n, dtype=torch.int32, device=self.dev)
+            self.idx_pin = torch.zeros(rows, n, dtype=torch.int32).pin_memory()
+            self.cap, self.bufs = n, {}
+        for (name, shape, dtype), u in zip(self.inputs, used):
+            if u and name not in self.bufs:
+                self.bufs[name] = torch.empty(n, *shape, dtype=dtype, device=self.dev)
+
+    def upload(self, table, tensors, n, done=None):
+        """the host table into the pinned copy and from there to the device in one copy (`done`, an event, is recorded behind it), then
+        the rows in use of every caller tensor into the player's copy, in stream order.  The caller has waited for the previous upload."""
+        self.idx_pin.numpy()[:, :table.shape[1]] = table
+        self.idx_dev.copy_(self.idx_pin, non_blocking=True)
+        if done is not None:
+            done.record()
+        for k, ((name, _, _), t) in enumerate(zip(self.inputs, tensors)):
+            if t is not None:
+                torch.index_select(t, 0, self.idx_dev[2 + 2 * k, :n], out=self.bufs[name][:n])
+
+    def rows(self, lo):
+        """the motion's rows of the batch at `lo`, on the device"""
+        return self.idx_dev[0, lo:lo + self.B]
+
+    def args(self, name, lo, used):
+        """what a kernel takes of staged input `name` for the batch at `lo`: (the player's copy, its rows, the batch's slots), or
+        (None, 0, None) when the call does not use it (used: {name: bool}) or the player declares no such input"""
+        if not used.get(name):
+            return None, 0, None
+        k = [i[0] for i in self.inputs].index(name)
+        return self.bufs[name].data_ptr(), self.cap, self.idx_dev[1 + 2 * k, lo:lo + self.B].data_ptr()
+
+
+class _Player:
+    """What AvatarPlayer and ScenePlayer share.  A subclass declares the caller tensors it stages (`_inputs`: name, per-row shape, dtype),
+    says what it draws (`_layers`) and supplies `_enqueue_frames`.  A call is one PASS, a hashable (kind, *what it carries): ("frames",
+    channels, owner), ("labels", _label_flags' tuple), ("flow", tol) or ("contact", max_dist).  Per kind there is one `_enqueue_<kind>`,
+    the launches of a whole call in order on the current stream, and one `_alloc_<kind>`, its output buffers.  Nothing is allocated
+    after the constructor except when a pass is first used or a longer `rows` is first seen (`_grow`)."""
+
+    _holds, _load = "the motion holds", "load_motion"
 
     def __init__(self, device, S, ss, B, use_graph, inputs):
         self.dev, self.S, self.ss, self.B, self.use_graph = torch.device(device), S, ss, B, bool(use_graph)
         self._inputs = inputs
         self.T = self._n_cap = 0
-        self.idx_done, self._bufs, self._graphs = None, {}, {}
-        self._flow = None                                # what flow() adds, allocated on its first call (_grow_flow)
+        self._stage, self._stage_to = _Stage(inputs, self.dev, B), None      # the source rows'; the target rows' of flow(), made on its first call
+        self.idx_done, self._out, self._graphs = None, {}, {}
         self.bg_color_dev = torch.empty(3, dtype=torch.float32, device=self.dev)
         self.bg_color = BG_WHITE
 
@@ -95,19 +136,30 @@ class _Player:
     def _device(self):
         return self.dev if self.dev.index is not None else torch.device(self.dev.type, torch.cuda.current_device())
 
-    def _grow(self, n_pad, used):
+    def _ready(self, need_depth=False):
+        """the preconditions of a call; need_depth: the name of a call that reads the layers' depth maps"""
+        layers = [pl for pl, _ in self._layers()]
+        if need_depth and not all(pl.keep_depth for pl in layers):
+            raise ValueError(f"{need_depth} needs a player built with keep_depth=True")
+        if any(pl.tables is None for pl in layers) or (self.T < 1 and self not in layers):      # (a scene's own T is 0 until ITS motions are loaded)
+            raise RuntimeError(f"{self._load}() first")
+
+    def _grow(self, n_pad, used, decl_to=None, used_to=None):
+        """A longer call than any before drops every graph and every pass's buffers with the capacity they were made for; then the
+        index table(s) are made for the capacity (decl_to, used_to: the inputs of flow's target rows; their table is made on first use)"""
         if n_pad > self._n_cap:
-            # per rendered frame: its row of the motion, then per staged input its row of the player's copy (-1: none) and the row of the
-            # caller's tensor that is copied there (stage_table); staged in pinned memory and uploaded in one copy per call
-            rows = 1 + 2 * len(self._inputs)
-            self.idx_dev = torch.zeros(rows, n_pad, dtype=torch.int32, device=self.dev)
-            self.idx_pin = torch.zeros(rows, n_pad, dtype=torch.int32).pin_memory()
-            self.idx_done = None
-            self.out = torch.empty(n_pad * self.S * self.S * 4, dtype=torch.uint8, device=self.dev)
-            self._n_cap, self._bufs, self._graphs = n_pad, {}, {}
-        for (name, shape, dtype), u in zip(self._inputs, used):
-            if u and name not in self._bufs:             # (no graph reads it yet)
-                self._bufs[name] = torch.empty(self._n_cap, *shape, dtype=dtype, device=self.dev)
+            self._n_cap, self._out, self._graphs = n_pad, {}, {}
+        self._stage.alloc(self._n_cap, used)
+        if decl_to is not None:
+            self._stage_to = self._stage_to or _Stage(decl_to, self.dev, self.B)
+            self._stage_to.alloc(self._n_cap, used_to)
+
+    def _buffers(self, kind):
+        """The output buffers of a pass, the one rule for every kind: made by `_alloc_<kind>(capacity)` on the pass's first use, and again
+        after _grow has dropped them — together with the graphs, so no graph outlives a buffer it points at"""
+        if kind not in self._out:
+            self._out[kind] = getattr(self, "_alloc_" + kind)(self._n_cap)
+        return self._out[kind]
 
     def _staged(self, name, t, rows, n, shape, dtype):
         """a (N, *shape) device tensor of the caller's and its rows -> (the rows checked, N), or (None, 0) without the tensor"""
@@ -125,51 +177,16 @@ class _Player:
             return (np.arange(n, dtype=np.int64) if N == n else np.zeros(n, dtype=np.int64)), N
         return _host_rows(f"the rows of {name}", rows, n), N
 
-    def _upload(self, table, tensors, n):
-        """the index table to the device in one copy, then the rows in use of every caller tensor into the player's copy, in stream order"""
-        if self.idx_done is not None:
-            self.idx_done.synchronize()                  # the previous call's upload has read the staging buffer
-        self.idx_pin.numpy()[:, :table.shape[1]] = table
-        self.idx_dev.copy_(self.idx_pin, non_blocking=True)
-        self.idx_done = torch.cuda.Event()
-        self.idx_done.record()
-        for k, ((name, _, _), t) in enumerate(zip(self._inputs, tensors)):
-            if t is not None:
-                torch.index_select(t, 0, self.idx_dev[2 + 2 * k, :n], out=self._bufs[name][:n])
-
-    def _grow_flow(self, n_inputs, used):
-        """What flow() needs beside render's buffers, allocated on its first call and again when a longer `rows` has grown the player: the
-        index table of the TARGET rows (stage_table's layout over n_inputs staged inputs, beside idx_dev, which keeps its own) with its
-        pinned stage, the three outputs, and a copy of its own for every staged input the target rows use"""
-        if self._flow is None or self._flow["cap"] != self._n_cap:
-            n, S, rows = self._n_cap, self.S, 1 + 2 * n_inputs
-            new = lambda dt, *shape: torch.empty(n, *shape, dtype=dt, device=self.dev)      # noqa: E731
-            self._flow = dict(cap=n, idx_dev=torch.zeros(rows, n, dtype=torch.int32, device=self.dev),
-                              idx_pin=torch.zeros(rows, n, dtype=torch.int32).pin_memory(), flow=new(torch.float32, S, S, 2),
-                              dz=new(torch.float32, S, S), status=new(torch.uint8, S, S, 2), bufs={})
-        for (name, shape, dtype), u in zip(self._inputs[len(self._inputs) - n_inputs:], used):
-            if u and name not in self._flow["bufs"]:     # (no graph reads it yet)
-                self._flow["bufs"][name] = torch.empty(self._n_cap, *shape, dtype=dtype, device=self.dev)
-
-    def _upload_to(self, table, tensors, n):
-        """_upload for the target rows' table, enqueued in front of it: the event that _upload records covers both copies"""
-        fl = self._flow
+    def _upload(self, table, tensors, n, to=None):
+        """The one host wait and the one event of a call: the previous call's upload has read the pinned table(s) before either is
+        written again; then the target rows' table (to: its (table, tensors), flow only) and the source rows', each with its gathers,
+        the event behind the source table's copy and so behind both"""
         if self.idx_done is not None:
             self.idx_done.synchronize()
-        fl["idx_pin"].numpy()[:, :table.shape[1]] = table
-        fl["idx_dev"].copy_(fl["idx_pin"], non_blocking=True)
-        for k, ((name, _, _), t) in enumerate(zip(self._inputs[len(self._inputs) - len(tensors):], tensors)):
-            if t is not None:
-                torch.index_select(t, 0, fl["idx_dev"][2 + 2 * k, :n], out=fl["bufs"][name][:n])
-
-    def _staged_to_args(self, k, name, lo, used):
-        """_staged_args of the target rows' copy of staged input `name`, k-th of the target table"""
-        if not used:
-            return None, 0, None
-        return self._flow["bufs"][name].data_ptr(), self._n_cap, self._flow["idx_dev"][1 + 2 * k, lo:lo + self.B].data_ptr()
-
-    def _flow_view(self, n):
-        return Flow(self._flow["flow"][:n], self._flow["dz"][:n], self._flow["status"][:n])
+        if to is not None:
+            self._stage_to.upload(*to, n)
+        self.idx_done = torch.cuda.Event()
+        self._stage.upload(table, tensors, n, self.idx_done)
 
     def _run(self, key):
         """_enqueue(*key) as it is, or as the replay of its graph, captured when the key is first seen"""
@@ -187,41 +204,129 @@ class _Player:
             self._graphs[key] = g
         g.replay()
 
-    def _staged_args(self, k, lo, used):
-        """what a kernel takes of staged input k for the batch at `lo`: (the player's copy, its rows, the batch's slots), or (None, 0, None)"""
-        if not used:
-            return None, 0, None
-        return self._bufs[self._inputs[k][0]].data_ptr(), self._n_cap, self.idx_dev[1 + 2 * k, lo:lo + self.B].data_ptr()
-
-    def _render(self, rows, alpha, inputs, *flags, to=None):
-        """The render path of both players: `rows` checked on the host, padded to whole batches, staged with `inputs` (per declared input
-        the caller's (tensor, rows)), and enqueued or replayed under the key (padded length, channels, input used?..., *flags)
-        -> (frames (n, S, S, channels), n).  to (flow only): (the target rows, [the caller's (tensor, rows) of the staged inputs the target
-        frames use, the last of the declared ones]); they travel in a table of their own (_grow_flow)."""
-        r = _host_rows("rows", rows)
-        n = r.shape[0]
-        if n < 1:
+    def _checked_rows(self, name, rows, n=None):
+        r = _host_rows(name, rows, n)
+        if r.shape[0] < 1:
             raise ValueError("no rows to render")
         if r.min() < 0 or r.max() >= self.T:             # (on the host, before anything is enqueued: the kernels gather rows unchecked)
-            raise IndexError(f"rows span [{r.min()}, {r.max()}] but {self._holds} {self.T} frames")
-        C = 4 if alpha else 3
-        staged = [self._staged(name, t, rr, n, shape, dtype) for (name, shape, dtype), (t, rr) in zip(self._inputs, inputs)]
-        used = tuple(rr is not None for rr, _ in staged)
+            raise IndexError(f"{name} span [{r.min()}, {r.max()}] but {self._holds} {self.T} frames")
+        return r
+
+    def _render(self, rows, inputs, pass_, to=None):
+        """The path of every call of both players: `rows` checked on the host, padded to whole batches, staged with `inputs` ({name of a
+        declared input: the caller's (tensor, rows)}; one that is not named is not used), and `pass_` enqueued or replayed under the key
+        (padded length, input used?..., pass_) into its buffers -> n, the rows asked for.  to (flow only): (the target rows, the
+        `inputs` of the target frames); they travel in a table of their own, over the inputs named there."""
+        r = self._checked_rows("rows", rows)
+        n = r.shape[0]
         n_pad = -(-n // self.B) * self.B
-        if to is not None:
-            r_to = _host_rows("to_rows", to[0], n)
-            if r_to.min() < 0 or r_to.max() >= self.T:
-                raise IndexError(f"to_rows span [{r_to.min()}, {r_to.max()}] but {self._holds} {self.T} frames")
-            decl = self._inputs[len(self._inputs) - len(to[1]):]
-            staged_to = [self._staged(name, t, rr, n, shape, dtype) for (name, shape, dtype), (t, rr) in zip(decl, to[1])]
+        tensors, staged = self._staged_all(self._inputs, inputs, n)
+        used = tuple(rr is not None for rr, _ in staged)
         with torch.cuda.device(self.dev):
-            self._grow(n_pad, used)
-            if to is not None:
-                self._grow_flow(len(staged_to), [rr is not None for rr, _ in staged_to])
-                self._upload_to(stage_table(r_to, n_pad, staged_to), [t for t, _ in to[1]], n)
-            self._upload(stage_table(r, n_pad, staged), [t for t, _ in inputs], n)
-            self._run((n_pad, C) + used + flags)
-        return self.out[:n * self.S * self.S * C].view(n, self.S, self.S, C), n
+            if to is None:
+                self._grow(n_pad, used)
+            else:
+                r_to = self._checked_rows("to_rows", to[0], n)
+                decl = [i for i in self._inputs if i[0] in to[1]]
+                tensors_to, staged_to = self._staged_all(decl, to[1], n)
+                self._grow(n_pad, used, decl, [rr is not None for rr, _ in staged_to])
+                to = stage_table(r_to, n_pad, staged_to), tensors_to
+            self._buffers(pass_[0])
+            self._upload(stage_table(r, n_pad, staged), tensors, n, to)
+            self._run((n_pad,) + used + (pass_,))
+        return n
+
+    def _staged_all(self, decl, inputs, n):
+        """_staged of every declared input of `decl` -> (the caller's tensors, [(rows, N)]), in the order of the declaration"""
+        given = [inputs.get(name, (None, None)) for name, _, _ in decl]
+        return [t for t, _ in given], [self._staged(name, t, rr, n, shape, dtype) for (name, shape, dtype), (t, rr) in zip(decl, given)]
+
+    def _enqueue(self, n_pad, *key):
+        """the launches of a whole call: the pass's own method, told which staged inputs the call uses"""
+        kind, *carried = key[-1]
+        getattr(self, "_enqueue_" + kind)(n_pad, dict(zip((i[0] for i in self._inputs), key[:-1])), *carried)
+
+    def _frames(self, rows, inputs, alpha, owner=False):
+        """the frames pass -> (frames (n, S, S, channels), n)"""
+        C = 4 if alpha else 3
+        n = self._render(rows, inputs, ("frames", C, bool(owner)))
+        return self._out["frames"]["out"][:n * self.S * self.S * C].view(n, self.S, self.S, C), n
+
+    def _alloc_frames(self, n):
+        return dict(out=torch.empty(n * self.S * self.S * 4, dtype=torch.uint8, device=self.dev))
+
+    def _scene_depth_args(self, lo, used, to=False):
+        """the scene depth arguments of the batch at `lo`, of the source frames or (to=True) of the flow's target frames; (None, 0, None)
+        for a call without a scene depth and for a player that declares none"""
+        return (self._stage_to if to else self._stage).args("scene_depth", lo, used)
+
+    # ---- labels and flow, over the layers (DESIGN.md §32, §33): an avatar is a scene of one unflipped layer without a scene depth ------
+    def _alloc_labels(self, n):
+        """the maps over every padded row, the boxes per layer, and per layer the (uvz, vis) of its joints"""
+        S, layers = self.S, self._layers()
+        new = lambda dt, *shape: torch.empty(n, *shape, dtype=dt, device=self.dev)      # noqa: E731
+        return dict(owner=new(torch.uint8, S, S), part=new(torch.uint8, S, S), depth=new(torch.float32, S, S), face=new(torch.int32, S, S),
+                    uv=new(torch.float32, S, S, 2), bbox=new(torch.int32, len(layers), 4),
+                    kp=[dict(uvz=new(torch.float32, pl.n_joints, 3), vis=new(torch.uint8, pl.n_joints, 2)) for pl, _ in layers])
+
+    def _enqueue_labels(self, n_pad, used, flags):
+        """per batch every layer's front / rasterisers (no shader: labels need no colour), the clear of the batch's boxes and
+        harp_annotate_layers, then with keypoints every layer's harp_keypoint_visibility; flags = (part, depth, uv, keypoints, tol)"""
+        lab, layers, B = self._out["labels"], self._layers(), self.B
+        P = len(layers)
+        arr = (_lib.LabelLayer * P)(*[pl._label_layer(f, flags[2]) for pl, f in layers])
+        for lo in range(0, n_pad, B):
+            at = lambda k, on=True: lab[k][lo:].data_ptr() if on else None      # noqa: E731
+            scene = self._scene_depth_args(lo, used)
+            for pl, _ in layers:
+                pl._render_batch(self._stage.rows(lo), shade=False)
+            lab["bbox"][lo:lo + B].zero_()                # (inside the captured sequence: the boxes are accumulated by atomic max)
+            _lib.check(_lib.lib().harp_annotate_layers(arr, P, B, self.S, self.ss, *scene, at("owner"), at("part", flags[0]), at("depth", flags[1]),
+                                                       at("face"), at("uv", flags[2]), at("bbox"), _lib.stream()), "annotate_layers")
+            if flags[3]:
+                for k, (pl, _) in enumerate(layers):
+                    pl._keypoints_batch(lab["kp"][k], lo, arr, P, k, scene, flags[4])
+
+    def _annotate(self, rows, inputs, flags):
+        """the labels pass -> Annotation in the scene's form: bbox (n, layers, 4), uvz and vis tuples with one tensor per layer"""
+        for pl, _ in self._layers():
+            pl._part_table()
+        n = self._render(rows, inputs, ("labels", flags))
+        lab = self._out["labels"]
+        view = lambda k, on=True: lab[k][:n] if on else None      # noqa: E731
+        kp = lambda key: tuple(b[key][:n] for b in lab["kp"]) if flags[3] else None      # noqa: E731
+        return Annotation(view("owner"), view("part", flags[0]), view("depth", flags[1]), view("face"), view("uv", flags[2]),
+                          ops.bbox_from_extents(lab["bbox"][:n], self.S), kp("uvz"), kp("vis"))
+
+    def _alloc_flow(self, n):
+        S = self.S
+        new = lambda dt, *shape: torch.empty(n, *shape, dtype=dt, device=self.dev)      # noqa: E731
+        return dict(flow=new(torch.float32, S, S, 2), dz=new(torch.float32, S, S), status=new(torch.uint8, S, S, 2))
+
+    def _enqueue_flow(self, n_pad, used, tol):
+        """per batch every layer's front / rasterisers of the TARGET rows and copies of their ndc_c and z_c, the same of the source rows,
+        then one harp_flow_layers"""
+        fl, layers, B = self._out["flow"], self._layers(), self.B
+        P = len(layers)
+        arr = (_lib.FlowLayer * P)(*[pl._flow_layer(f) for pl, f in layers])
+        for lo in range(0, n_pad, B):
+            for pl, _ in layers:
+                pl._render_batch(self._stage_to.rows(lo), shade=False)
+                pl._keep_targets()
+            for pl, _ in layers:
+                pl._render_batch(self._stage.rows(lo), shade=False)
+            _lib.check(_lib.lib().harp_flow_layers(arr, P, B, self.S, self.ss, *self._scene_depth_args(lo, used), *self._scene_depth_args(lo, used, to=True),
+                                                   tol, fl["flow"][lo:].data_ptr(), fl["dz"][lo:].data_ptr(), fl["status"][lo:].data_ptr(),
+                                                   _lib.stream()), "flow_layers")
+
+    def _flow(self, rows, inputs, to, tol):
+        """the flow pass -> Flow"""
+        tol = _tol(tol)
+        for pl, _ in self._layers():
+            pl._flow_targets()
+        n = self._render(rows, inputs, ("flow", tol), to=to)
+        fl = self._out["flow"]
+        return Flow(fl["flow"][:n], fl["dz"][:n], fl["status"][:n])
 
     def _play(self, out_dir, fmt, alpha, prepare, masks=False):
         """The way to disk of both players: the format checked, out_dir made, then render = prepare() (which loads the motion and the
@@ -299,12 +404,12 @@ class AvatarPlayer(_Player):
                         light_positions=own("light_positions", (-1, 3)))
         self._alloc_scratch()
         with torch.cuda.device(self.dev):
-            _ck(_lib.lib().harp_normalize3_pack(_lib.ptr(self.fit["texture"]), _lib.ptr(self.fit["normal_map"]), self.Ht * self.Wt,
+            _lib.check(_lib.lib().harp_normalize3_pack(_lib.ptr(self.fit["texture"]), _lib.ptr(self.fit["normal_map"]), self.Ht * self.Wt,
                                                 _lib.ptr(self.nmap_n), _lib.ptr(self.texnm), _lib.stream()), "normalize3_pack")
         self._cap = 0
         self.tab = self.tables = None
         self._skin_weights = np.asarray(hand_layer._model_np["weights"])      # (V0, NJ): the part table is made from it on first use
-        self._face_label, self._labels_wanted, self.lab, self.kp = None, False, None, None
+        self._face_label = None
         self.s_to = None                                 # the target frames' ndc_c and z_c of a batch, allocated on the first flow()
 
     def _alloc_scratch(self):
@@ -403,19 +508,19 @@ class AvatarPlayer(_Player):
         B, V, F, Sh = self.B, tp.V, tp.F, self.Sh
         z_c = p(s["z_c"]) if self.keep_depth else None
         h = self._front_struct(fid)
-        _ck((L.harp_arm_front_fwd if self.use_arm else L.harp_hand_front_fwd)(ctypes.byref(h), st), "front_fwd")
+        _lib.check((L.harp_arm_front_fwd if self.use_arm else L.harp_hand_front_fwd)(ctypes.byref(h), st), "front_fwd")
         if front_only:
             return
         if self.self_shadow:
-            _ck(L.harp_raster_setup_pair(p(s["ndc_c"]), 0.0, p(s["ws_c"]), p(s["ndc_l"]), 0.0, p(s["ws_l"]), p(tp.faces), B, V, F, Sh, st),
+            _lib.check(L.harp_raster_setup_pair(p(s["ndc_c"]), 0.0, p(s["ws_c"]), p(s["ndc_l"]), 0.0, p(s["ws_l"]), p(tp.faces), B, V, F, Sh, st),
                 "raster_setup_pair")
-            _ck(L.harp_rasterize_fwd(p(s["ndc_c"]), p(tp.faces), B, V, F, Sh, 4, 0.0, 1.0, p(s["ws_c"]), p(s["face_c"]), z_c, None, st), "raster_cam")
-            _ck(L.harp_rasterize_fwd_keep(p(s["ndc_l"]), p(tp.faces), B, V, F, Sh, 4, p(s["ws_l"]), p(s["face_l"]), p(s["zl"]), p(s["zl_state"]), st),
+            _lib.check(L.harp_rasterize_fwd(p(s["ndc_c"]), p(tp.faces), B, V, F, Sh, 4, 0.0, 1.0, p(s["ws_c"]), p(s["face_c"]), z_c, None, st), "raster_cam")
+            _lib.check(L.harp_rasterize_fwd_keep(p(s["ndc_l"]), p(tp.faces), B, V, F, Sh, 4, p(s["ws_l"]), p(s["face_l"]), p(s["zl"]), p(s["zl_state"]), st),
                 "raster_light")
         else:                                            # one view: the rasteriser's own set-up
-            _ck(L.harp_rasterize_fwd(p(s["ndc_c"]), p(tp.faces), B, V, F, Sh, 0, 0.0, 1.0, p(s["ws_c"]), p(s["face_c"]), z_c, None, st), "raster_cam")
+            _lib.check(L.harp_rasterize_fwd(p(s["ndc_c"]), p(tp.faces), B, V, F, Sh, 0, 0.0, 1.0, p(s["ws_c"]), p(s["face_c"]), z_c, None, st), "raster_cam")
         if shade:
-            _ck(L.harp_shade_fwd(ctypes.byref(self._shade_struct()), st), "shade_fwd")
+            _lib.check(L.harp_shade_fwd(ctypes.byref(self._shade_struct()), st), "shade_fwd")
 
     # ---- labels ---------------------------------------------------------------------------------------------------
     def _part_table(self):
@@ -459,53 +564,24 @@ class AvatarPlayer(_Player):
         return _lib.ContactMesh(verts=p(s["vd"]), cam_R=p(s["cam_R"]), cam_T=p(s["cam_T"]), faces=p(tp.faces), V=tp.V, F=tp.F, flip_x=int(flip),
                                 reserved=0)
 
-    def _keypoint_buffers(self, n):
-        """(uvz, vis) for n frames of this player's joints; whoever runs the launches owns them (the player itself, or its scene)"""
-        return dict(uvz=torch.empty(n, self.n_joints, 3, dtype=torch.float32, device=self.dev),
-                    vis=torch.empty(n, self.n_joints, 2, dtype=torch.uint8, device=self.dev))
-
-    def _enqueue_keypoints(self, kp, lo, layers, n_layers, self_layer, scene, tol):
-        """harp_keypoint_visibility of this player's batch into rows lo.. of the buffers kp; scene: _staged_args of the scene depth"""
+    def _keypoints_batch(self, kp, lo, layers, n_layers, self_layer, scene, tol):
+        """harp_keypoint_visibility of this player's batch into rows lo.. of the buffers kp; scene: the scene depth arguments of the batch"""
         s, p = self.s, _lib.ptr
-        _ck(_lib.lib().harp_keypoint_visibility(p(s["joints_m"]), p(s["cam_R"]), p(s["cam_T"]), self.B, self.n_joints, self.focal_h / self.ss, self.S,
-                                                self.ss, self_layer, layers, n_layers, *scene, tol, kp["uvz"][lo:].data_ptr(),
-                                                kp["vis"][lo:].data_ptr(), _lib.stream()), "keypoint_visibility")
+        _lib.check(_lib.lib().harp_keypoint_visibility(p(s["joints_m"]), p(s["cam_R"]), p(s["cam_T"]), self.B, self.n_joints, self.focal_h / self.ss,
+                                                       self.S, self.ss, self_layer, layers, n_layers, *scene, tol, kp["uvz"][lo:].data_ptr(),
+                                                       kp["vis"][lo:].data_ptr(), _lib.stream()), "keypoint_visibility")
 
-    def _grow(self, n_pad, used):
-        grew = n_pad > self._n_cap
-        super()._grow(n_pad, used)
-        if grew:
-            self.lab = None
-        if self._labels_wanted and self.lab is None:
-            self.lab = _label_buffers(self._n_cap, self.S, 1, self.dev)
-            self.kp = self._keypoint_buffers(self._n_cap)
+    def _layers(self):
+        return [(self, False)]
 
-    def _enqueue(self, n_pad, channels, with_bg, labels=None, flow=None):
-        """per batch of B frames: its launches up to the shader, then the resolve; with labels = (part, depth, uv, keypoints, tol) the
-        launches up to the rasterisers, then the labels of the batch; with flow = ("flow", tol) the launches up to the rasterisers of the
-        TARGET rows, copies of their ndc_c and z_c, the same of the source rows, then the flow of the batch"""
-        L, s, p = _lib.lib(), self.s, _lib.ptr
+    def _enqueue_frames(self, n_pad, used, channels, owner):
+        """per batch of B frames: its launches up to the shader, then the resolve"""
+        s, p, out = self.s, _lib.ptr, self._out["frames"]["out"]
         per = self.S * self.S * channels
-        if flow is not None:
-            layer = (_lib.FlowLayer * 1)(self._flow_layer(False))
-            for lo in range(0, n_pad, self.B):
-                self._render_batch(self._flow["idx_dev"][0, lo:lo + self.B], shade=False)
-                self._keep_targets()
-                self._render_batch(self.idx_dev[0, lo:lo + self.B], shade=False)
-                _enqueue_flow(self._flow, lo, layer, 1, self.B, self.S, self.ss, (None, 0, None), (None, 0, None), flow[1])
-            return
-        if labels is not None:
-            layer = (_lib.LabelLayer * 1)(self._label_layer(False, labels[2]))
-            for lo in range(0, n_pad, self.B):
-                self._render_batch(self.idx_dev[0, lo:lo + self.B], shade=False)
-                _enqueue_labels(self.lab, lo, layer, 1, self.B, self.S, self.ss, (None, 0, None), labels)
-                if labels[3]:
-                    self._enqueue_keypoints(self.kp, lo, layer, 1, 0, (None, 0, None), labels[4])
-            return
         for lo in range(0, n_pad, self.B):
-            self._render_batch(self.idx_dev[0, lo:lo + self.B])
-            _ck(L.harp_resolve_u8(p(s["rgb"]), p(s["face_c"]), self.B, self.S, self.ss, *self._staged_args(0, lo, with_bg), p(self.bg_color_dev),
-                                  channels, self.out[lo * per:].data_ptr(), _lib.stream()), "resolve_u8")
+            self._render_batch(self._stage.rows(lo))
+            _lib.check(_lib.lib().harp_resolve_u8(p(s["rgb"]), p(s["face_c"]), self.B, self.S, self.ss, *self._stage.args("background", lo, used),
+                                                  p(self.bg_color_dev), channels, out[lo * per:].data_ptr(), _lib.stream()), "resolve_u8")
 
     @torch.no_grad()
     def render(self, rows, background=None, bg_rows=None, alpha=False):
@@ -514,9 +590,8 @@ class AvatarPlayer(_Player):
         a (N,S,S,3) uint8 device tensor; frame i is composited over its row bg_rows[i], without bg_rows over row i (N == len(rows)) or row
         0 (N == 1); a row outside [0, N) takes bg_color.  The rows in use are copied into a buffer of the player's in stream order, so
         one captured graph serves every background tensor and the caller's tensor is free again once the call has returned."""
-        if self.tables is None:
-            raise RuntimeError("load_motion() first")
-        return self._render(rows, alpha, [(background, bg_rows)])[0]
+        self._ready()
+        return self._frames(rows, dict(background=(background, bg_rows)), alpha)[0]
 
     @torch.no_grad()
     def annotate(self, rows, parts=True, depth=True, uv=False, keypoints=True, tol=LABEL_TOL):
@@ -526,15 +601,9 @@ class AvatarPlayer(_Player):
         harp_annotate_layers and harp_keypoint_visibility, under the same graph path.  tol: a joint lies INSIDE the hand, a finger's
         radius or half the palm's thickness under the skin, so a joint counts as visible when the nearest surface at its pixel is no
         nearer than its own depth minus tol metres; 0.02 is that convention, not a tuned value."""
-        if not self.keep_depth:
-            raise ValueError("annotate needs a player built with keep_depth=True")
-        if self.tables is None:
-            raise RuntimeError("load_motion() first")
-        labels = _label_flags(parts, depth, uv, keypoints, tol)
-        self._part_table()
-        self._labels_wanted = True
-        n = self._render(rows, False, [(None, None)], labels)[1]
-        return _annotation(self.lab, n, self.S, labels, self.kp["uvz"][:n] if labels[3] else None, self.kp["vis"][:n] if labels[3] else None, one=True)
+        self._ready(need_depth="annotate")
+        a = self._annotate(rows, {}, _label_flags(parts, depth, uv, keypoints, tol))
+        return a._replace(bbox=a.bbox[:, 0], uvz=a.uvz and a.uvz[0], vis=a.vis and a.vis[0])      # the one layer's, bare
 
     @torch.no_grad()
     def flow(self, rows, to_rows, tol=FLOW_TOL):
@@ -543,14 +612,8 @@ class AvatarPlayer(_Player):
         and z_c, the front and the rasterisers of the source rows and one harp_flow_layers, under a graph key of its own.  tol: the point
         lies on the surface, so the tolerance only absorbs the depth difference between where it lands and the centre of the sub-pixel
         it is tested at; 0.005 is that convention, not a tuned value."""
-        if not self.keep_depth:
-            raise ValueError("flow needs a player built with keep_depth=True")
-        if self.tables is None:
-            raise RuntimeError("load_motion() first")
-        tol = _flow_tol(tol)
-        self._flow_targets()
-        n = self._render(rows, False, [(None, None)], None, ("flow", tol), to=(to_rows, []))[1]
-        return self._flow_view(n)
+        self._ready(need_depth="flow")
+        return self._flow(rows, {}, (to_rows, {}), tol)
 
     # ---- a whole motion to files ------------------------------------------------------------------------------------------------
     def play(self, motion, out_dir, backgrounds=None, fmt="jpg", alpha=False, labels=False, label_tol=LABEL_TOL, flow=None, flow_tol=FLOW_TOL):
@@ -560,7 +623,7 @@ class AvatarPlayer(_Player):
         a thread pool while the next batch renders.  labels=True (needs keep_depth=True) also writes part_%04d.png, depth_%04d.png,
         iuv_%04d.png and keypoints.npz (write_labels).  flow="fw" | "bw" | "both" (needs keep_depth=True) also writes flow_%04d.flo and /
         or flow_bw_%04d.flo with their status PNGs (write_flow).  Returns the list of paths."""
-        _flow_mode(flow), _flow_tol(flow_tol)
+        _flow_mode(flow), _tol(flow_tol)
 
         def prepare():
             self.load_motion(motion)
@@ -568,7 +631,9 @@ class AvatarPlayer(_Player):
             return lambda rows: self.render(rows, bgs, None if bgs is None else rows % bgs.shape[0], alpha)
         paths = self._play(out_dir, fmt, alpha, prepare)
         if labels:
-            write_labels(out_dir, self.T, self.B, lambda rows: self.annotate(rows, uv=True, tol=label_tol), [part_names_of(self)])
+            self._ready(need_depth="annotate")
+            flags = _label_flags(True, True, True, True, label_tol)
+            write_labels(out_dir, self.T, self.B, lambda rows: self._annotate(rows, {}, flags), [part_names_of(self)])
         if flow:
             write_flow(out_dir, self.T, self.B, lambda rows, to: self.flow(rows, to, tol=flow_tol), flow)
         return paths
@@ -582,7 +647,7 @@ class ScenePlayer(_Player):
     included — a LEFT hand is a right-hand fit of horizontally mirrored frames shown with flip.  The avatars cast no shadows on each
     other.  The launches are captured into a graph when every player was built with use_graph=True."""
 
-    _holds = "the motions hold"
+    _holds, _load = "the motions hold", "load_motions"
 
     def __init__(self, players, flip=None):
         players = list(players)
@@ -601,8 +666,6 @@ class ScenePlayer(_Player):
         self.players = players
         super().__init__(p0.dev, p0.S, p0.ss, p0.B, all(p.use_graph for p in players),
                          (("background", (p0.S, p0.S, 3), torch.uint8), ("scene_depth", (p0.S, p0.S), torch.float32)))
-        self._labels_wanted, self.lab, self.kp = False, None, None
-        self._contacts_wanted, self._contact = False, None      # what contact() adds, allocated on its first call (_grow)
 
     def load_motions(self, motions):
         """one motion per player, of equal length: scene row i is row i of every motion (AvatarPlayer.load_motion each)"""
@@ -618,74 +681,46 @@ class ScenePlayer(_Player):
             self._graphs = {}
         self.T = len(motions[0])
 
-    def _grow(self, n_pad, used):
-        if n_pad > self._n_cap:
-            self.owner = torch.empty(n_pad, self.S, self.S, dtype=torch.uint8, device=self.dev)
-            self.lab = None
-        super()._grow(n_pad, used)
-        if self._labels_wanted and self.lab is None:
-            self.lab = _label_buffers(self._n_cap, self.S, len(self.players), self.dev)
-            self.kp = [pl._keypoint_buffers(self._n_cap) for pl in self.players]
-        if self._contacts_wanted and (self._contact is None or self._contact["cap"] != self._n_cap):
-            # per ordered pair (query k, target j) the three outputs of harp_mesh_contact over every padded row; one workspace, for the
-            # target with the most faces (the calls follow each other on one stream)
-            n, P = self._n_cap, len(self.players)
-            new = lambda dt, V: torch.empty(n, V, dtype=dt, device=self.dev)      # noqa: E731
-            pairs = {(k, j): (new(torch.float32, q.topo.V), new(torch.int32, q.topo.V), new(torch.float32, q.topo.V))
-                     for k, q in enumerate(self.players) for j in range(P) if j != k}
-            ws = torch.empty(max(_lib.lib().harp_mesh_contact_ws_floats(self.B, pl.topo.F) for pl in self.players), dtype=torch.float32, device=self.dev)
-            self._contact = dict(cap=n, pairs=pairs, ws=ws)
+    def _layers(self):
+        return list(zip(self.players, self.flip))
 
-    def _enqueue(self, n_pad, channels, with_bg, with_depth, with_owner, labels=None, flow=None, contact=None):
-        """per batch: every player's front / rasterisers / shader, then one composite; with labels = (part, depth, uv, keypoints, tol)
-        every player's front / rasterisers, then the labels of the batch and every player's keypoints; with flow = ("flow", tol)
-        every player's front / rasterisers of the TARGET rows and copies of their ndc_c and z_c, the same of the source rows, then
-        the flow of the batch; with contact = ("contact", max_dist) every player's front only, then one harp_mesh_contact per ordered
-        pair of players into the pair's rows of self._contact.  max_dist is part of the graph key, as flow's and the labels' tol are: every
-        distinct value captures a graph of its own, kept until the scene grows or new tables are loaded"""
-        L, p, B = _lib.lib(), _lib.ptr, self.B
-        per = self.S * self.S
-        if contact is not None:                          # ("contact", max_dist): every player's front, then one call per ordered pair
-            meshes = [pl._contact_mesh(f) for pl, f in zip(self.players, self.flip)]
-            for lo in range(0, n_pad, B):
-                for pl in self.players:
-                    pl._render_batch(self.idx_dev[0, lo:lo + B], front_only=True)
-                for (k, j), (d, f, w) in self._contact["pairs"].items():
-                    _ck(L.harp_mesh_contact(ctypes.byref(meshes[k]), ctypes.byref(meshes[j]), B, contact[1], p(self._contact["ws"]),
-                                            d[lo:].data_ptr(), f[lo:].data_ptr(), w[lo:].data_ptr(), _lib.stream()), "mesh_contact")
-            return
-        if flow is not None:
-            P = len(self.players)
-            layers = (_lib.FlowLayer * P)(*[pl._flow_layer(f) for pl, f in zip(self.players, self.flip)])
-            for lo in range(0, n_pad, B):
-                for pl in self.players:
-                    pl._render_batch(self._flow["idx_dev"][0, lo:lo + B], shade=False)
-                    pl._keep_targets()
-                for pl in self.players:
-                    pl._render_batch(self.idx_dev[0, lo:lo + B], shade=False)
-                _enqueue_flow(self._flow, lo, layers, P, B, self.S, self.ss, self._staged_args(1, lo, with_depth),
-                              self._staged_to_args(0, "scene_depth", lo, with_depth), flow[1])
-            return
-        if labels is not None:
-            P = len(self.players)
-            layers = (_lib.LabelLayer * P)(*[pl._label_layer(f, labels[2]) for pl, f in zip(self.players, self.flip)])
-            for lo in range(0, n_pad, B):
-                scene = self._staged_args(1, lo, with_depth)
-                for pl in self.players:
-                    pl._render_batch(self.idx_dev[0, lo:lo + B], shade=False)
-                _enqueue_labels(self.lab, lo, layers, P, B, self.S, self.ss, scene, labels)
-                if labels[3]:
-                    for k, pl in enumerate(self.players):
-                        pl._enqueue_keypoints(self.kp[k], lo, layers, P, k, scene, labels[4])
-            return
-        layers = (_lib.Layer * len(self.players))(*[_lib.Layer(p(pl.s["rgb"]), p(pl.s["z_c"]), int(f), 0) for pl, f in zip(self.players, self.flip)])
+    def _alloc_frames(self, n):
+        return dict(super()._alloc_frames(n), owner=torch.empty(n, self.S, self.S, dtype=torch.uint8, device=self.dev))
+
+    def _enqueue_frames(self, n_pad, used, channels, owner):
+        """per batch: every player's front / rasterisers / shader, then one composite"""
+        p, B, bufs = _lib.ptr, self.B, self._out["frames"]
+        per = self.S * self.S * channels
+        layers = (_lib.Layer * len(self.players))(*[_lib.Layer(p(pl.s["rgb"]), p(pl.s["z_c"]), int(f), 0) for pl, f in self._layers()])
         for lo in range(0, n_pad, B):
             for pl in self.players:
-                pl._render_batch(self.idx_dev[0, lo:lo + B])
-            _ck(L.harp_composite_layers_u8(layers, len(self.players), B, self.S, self.ss, *self._staged_args(1, lo, with_depth),
-                                           *self._staged_args(0, lo, with_bg), p(self.bg_color_dev), channels,
-                                           self.out[lo * per * channels:].data_ptr(), self.owner[lo:].data_ptr() if with_owner else None,
-                                           _lib.stream()), "composite_layers_u8")
+                pl._render_batch(self._stage.rows(lo))
+            _lib.check(_lib.lib().harp_composite_layers_u8(layers, len(self.players), B, self.S, self.ss, *self._scene_depth_args(lo, used),
+                                                           *self._stage.args("background", lo, used), p(self.bg_color_dev), channels,
+                                                           bufs["out"][lo * per:].data_ptr(), bufs["owner"][lo:].data_ptr() if owner else None,
+                                                           _lib.stream()), "composite_layers_u8")
+
+    def _alloc_contact(self, n):
+        """per ordered pair (query k, target j) the three outputs of harp_mesh_contact over every padded row; one workspace, for the
+        target with the most faces (the calls follow each other on one stream)"""
+        new = lambda dt, V: torch.empty(n, V, dtype=dt, device=self.dev)      # noqa: E731
+        pairs = {(k, j): (new(torch.float32, q.topo.V), new(torch.int32, q.topo.V), new(torch.float32, q.topo.V))
+                 for k, q in enumerate(self.players) for j in range(len(self.players)) if j != k}
+        ws = torch.empty(max(_lib.lib().harp_mesh_contact_ws_floats(self.B, pl.topo.F) for pl in self.players), dtype=torch.float32, device=self.dev)
+        return dict(pairs=pairs, ws=ws)
+
+    def _enqueue_contact(self, n_pad, used, max_dist):
+        """per batch every player's front only, then one harp_mesh_contact per ordered pair of players into the pair's rows.  max_dist is
+        part of the pass and so of the graph key, as flow's and the labels' tol are: every distinct value captures a graph of its own,
+        kept until the scene grows or new tables are loaded"""
+        p, B, bufs = _lib.ptr, self.B, self._out["contact"]
+        meshes = [pl._contact_mesh(f) for pl, f in self._layers()]
+        for lo in range(0, n_pad, B):
+            for pl in self.players:
+                pl._render_batch(self._stage.rows(lo), front_only=True)
+            for (k, j), (d, f, w) in bufs["pairs"].items():
+                _lib.check(_lib.lib().harp_mesh_contact(ctypes.byref(meshes[k]), ctypes.byref(meshes[j]), B, max_dist, p(bufs["ws"]),
+                                                        d[lo:].data_ptr(), f[lo:].data_ptr(), w[lo:].data_ptr(), _lib.stream()), "mesh_contact")
 
     @torch.no_grad()
     def render(self, rows, background=None, bg_rows=None, alpha=False, scene_depth=None, depth_rows=None, owner=False):
@@ -695,26 +730,18 @@ class ScenePlayer(_Player):
         resolution in the unit of the avatars' view depth (a value > 0 is a measurement and hides what lies behind it); frame i is tested
         against its row depth_rows[i], without depth_rows against row i (N == len(rows)) or row 0 (N == 1); a row outside [0, N) means no
         scene depth.  Backgrounds and depths in use are copied into buffers of the scene's, so one captured graph per (padded length,
-        channels, background?, depth?, owner?) serves every tensor."""
-        if self.T < 1 or any(p.tables is None for p in self.players):
-            raise RuntimeError("load_motions() first")
-        frames, n = self._render(rows, alpha, [(background, bg_rows), (scene_depth, depth_rows)], bool(owner))
-        return (frames, self.owner[:n]) if owner else frames
+        background?, depth?, channels, owner?) serves every tensor."""
+        self._ready()
+        frames, n = self._frames(rows, dict(background=(background, bg_rows), scene_depth=(scene_depth, depth_rows)), alpha, owner)
+        return (frames, self._out["frames"]["owner"][:n]) if owner else frames
 
     @torch.no_grad()
     def annotate(self, rows, parts=True, depth=True, uv=False, keypoints=True, tol=LABEL_TOL, scene_depth=None, depth_rows=None):
         """What the scene's frames `rows` show -> Annotation, as AvatarPlayer.annotate: owner is bit for bit render(owner=True)'s, bbox is
         (n, players, 4), and uvz and vis are tuples with one tensor per player (its own joints; the occluder 1 + k is player k, 255 the
         scene depth).  scene_depth, depth_rows: as render."""
-        if self.T < 1 or any(p.tables is None for p in self.players):
-            raise RuntimeError("load_motions() first")
-        labels = _label_flags(parts, depth, uv, keypoints, tol)
-        for pl in self.players:
-            pl._part_table()
-        self._labels_wanted = True
-        n = self._render(rows, False, [(None, None), (scene_depth, depth_rows)], False, labels)[1]
-        kp = lambda key: tuple(b[key][:n] for b in self.kp) if labels[3] else None      # noqa: E731
-        return _annotation(self.lab, n, self.S, labels, kp("uvz"), kp("vis"), one=False)
+        self._ready()
+        return self._annotate(rows, dict(scene_depth=(scene_depth, depth_rows)), _label_flags(parts, depth, uv, keypoints, tol))
 
     @torch.no_grad()
     def flow(self, rows, to_rows, tol=FLOW_TOL, scene_depth=None, depth_rows=None, depth_to_rows=None):
@@ -722,14 +749,8 @@ class ScenePlayer(_Player):
         AvatarPlayer.flow: the source point is annotate's (the same owner, face and uv), the occluder 1 + k is player k, 255 the scene
         depth.  scene_depth: as render; frame rows[i] is composited against its row depth_rows[i] and the point is tested at the target
         against its row depth_to_rows[i] (each without its rows: row i when N == len(rows), row 0 when N == 1)."""
-        if self.T < 1 or any(p.tables is None for p in self.players):
-            raise RuntimeError("load_motions() first")
-        tol = _flow_tol(tol)
-        for pl in self.players:
-            pl._flow_targets()
-        n = self._render(rows, False, [(None, None), (scene_depth, depth_rows)], False, None, ("flow", tol),
-                         to=(to_rows, [(scene_depth, depth_to_rows)]))[1]
-        return self._flow_view(n)
+        self._ready()
+        return self._flow(rows, dict(scene_depth=(scene_depth, depth_rows)), (to_rows, dict(scene_depth=(scene_depth, depth_to_rows))), tol)
 
     @torch.no_grad()
     def contact(self, rows, max_dist=CONTACT_DIST):
@@ -743,15 +764,14 @@ class ScenePlayer(_Player):
         near that opening the value is fractional."""
         if len(self.players) < 2:
             raise ValueError("contact needs a scene of at least two players")
-        if self.T < 1 or any(p.tables is None for p in self.players):
-            raise RuntimeError("load_motions() first")
+        self._ready()
         max_dist = float(max_dist)
         if not max_dist >= 0:
             raise ValueError(f"max_dist must not be negative or NaN, got {max_dist}")
         tabs = [pl._part_table() for pl in self.players]
-        self._contacts_wanted = True
-        n = self._render(rows, False, [(None, None), (None, None)], False, None, None, ("contact", max_dist))[1]
-        return compose_contact([{j: tuple(t[:n] for t in self._contact["pairs"][k, j]) for j in range(len(self.players)) if j != k}
+        n = self._render(rows, {}, ("contact", max_dist))
+        pairs = self._out["contact"]["pairs"]
+        return compose_contact([{j: tuple(t[:n] for t in pairs[k, j]) for j in range(len(self.players)) if j != k}
                                 for k in range(len(self.players))], tabs)
 
     def play(self, motions, out_dir, backgrounds=None, scene_depth=None, fmt="jpg", alpha=False, masks=False, labels=False, label_tol=LABEL_TOL,
@@ -762,7 +782,7 @@ class ScenePlayer(_Player):
         also writes the label files (write_labels), one keypoints_<k>.npz per player k when there are several.  Returns the list of the
         frames' paths.  flow="fw" | "bw" | "both" also writes the flow files (write_flow).  contacts=True (at least two players) also
         writes contacts.npz (write_contacts) with contact(rows, contact_dist) of every frame."""
-        _flow_mode(flow), _flow_tol(flow_tol)
+        _flow_mode(flow), _tol(flow_tol)
         if contacts and len(self.players) < 2:
             raise ValueError("contacts need a scene of at least two players")
         if contacts and not float(contact_dist) >= 0:
@@ -797,26 +817,16 @@ def part_names_of(player):
     return joint_part_names(player._skin_weights.shape[1])
 
 
-def _label_flags(parts, depth, uv, keypoints, tol):
+def _tol(tol):
     import math
     tol = float(tol)
     if not (tol >= 0 and math.isfinite(tol)):
         raise ValueError(f"tol must be non-negative and finite, got {tol}")
-    return (bool(parts), bool(depth), bool(uv), bool(keypoints), tol)
+    return tol
 
 
-def _label_buffers(n, S, P, dev):
-    new = lambda dt, *shape: torch.empty(n, *shape, dtype=dt, device=dev)      # noqa: E731
-    return dict(owner=new(torch.uint8, S, S), part=new(torch.uint8, S, S), depth=new(torch.float32, S, S), face=new(torch.int32, S, S),
-                uv=new(torch.float32, S, S, 2), bbox=new(torch.int32, P, 4))
-
-
-def _enqueue_labels(lab, lo, layers, n_layers, B, S, ss, scene, labels):
-    """the clear of the batch's boxes and harp_annotate_layers into rows lo.. of the label buffers, on the current stream"""
-    at = lambda k, on=True: lab[k][lo:].data_ptr() if on else None      # noqa: E731
-    lab["bbox"][lo:lo + B].zero_()                       # (inside the captured sequence: the boxes are accumulated by atomic max)
-    _ck(_lib.lib().harp_annotate_layers(layers, n_layers, B, S, ss, *scene, at("owner"), at("part", labels[0]), at("depth", labels[1]), at("face"),
-                                        at("uv", labels[2]), at("bbox"), _lib.stream()), "annotate_layers")
+def _label_flags(parts, depth, uv, keypoints, tol):
+    return (bool(parts), bool(depth), bool(uv), bool(keypoints), _tol(tol))
 
 
 def compose_contact(pairs, part_tables):
@@ -866,31 +876,10 @@ def write_contacts(out_dir, T, B, contact, names, max_dist):
     return path
 
 
-def _flow_tol(tol):
-    import math
-    tol = float(tol)
-    if not (tol >= 0 and math.isfinite(tol)):
-        raise ValueError(f"tol must be non-negative and finite, got {tol}")
-    return tol
-
-
 def _flow_mode(flow):
     if flow not in (None, "fw", "bw", "both"):
         raise ValueError(f'flow is None, "fw", "bw" or "both", got {flow!r}')
     return flow
-
-
-def _enqueue_flow(fl, lo, layers, n_layers, B, S, ss, scene, scene_to, tol):
-    """harp_flow_layers into rows lo.. of the flow buffers, on the current stream"""
-    _ck(_lib.lib().harp_flow_layers(layers, n_layers, B, S, ss, *scene, *scene_to, tol, fl["flow"][lo:].data_ptr(), fl["dz"][lo:].data_ptr(),
-                                    fl["status"][lo:].data_ptr(), _lib.stream()), "flow_layers")
-
-
-def _annotation(lab, n, S, labels, uvz, vis, one):
-    bbox = ops.bbox_from_extents(lab["bbox"][:n], S)
-    view = lambda k, on=True: lab[k][:n] if on else None      # noqa: E731
-    return Annotation(view("owner"), view("part", labels[0]), view("depth", labels[1]), view("face"), view("uv", labels[2]),
-                      bbox[:, 0] if one else bbox, uvz, vis)
 
 
 def write_labels(out_dir, T, B, annotate, names):
@@ -909,10 +898,8 @@ def write_labels(out_dir, T, B, annotate, names):
         rows = np.arange(lo, min(T, lo + B))
         a = annotate(rows)
         part, depth, uv = a.part.cpu().numpy(), a.depth.cpu().numpy(), a.uv.cpu().numpy()
-        single = torch.is_tensor(a.uvz)                   # an AvatarPlayer's: one player, bbox (n,4)
-        uvz, vis, bbox = ((a.uvz,), (a.vis,), a.bbox[:, None]) if single else (a.uvz, a.vis, a.bbox)
         for k in range(P):
-            kp[k]["uvz"].append(uvz[k].cpu().numpy()); kp[k]["vis"].append(vis[k].cpu().numpy()); kp[k]["bbox"].append(bbox[:, k].cpu().numpy())
+            kp[k]["uvz"].append(a.uvz[k].cpu().numpy()); kp[k]["vis"].append(a.vis[k].cpu().numpy()); kp[k]["bbox"].append(a.bbox[:, k].cpu().numpy())
         mm = np.clip((1000.0 * depth.astype(np.float64) + 0.5).astype(np.int64), 0, 65535).astype(np.uint16)
         q = np.clip(np.floor(255.0 * uv.astype(np.float64) + 0.5), 0, 255).astype(np.uint8)
         for i, r in enumerate(rows):                     # (host copies of this batch: encoded while the next batch is labelled)

@@ -177,10 +177,10 @@ def test_a1_avatar_render_back_to_back(tmp_path_factory, use_graph):
 
 @pytest.mark.parametrize("use_graph", [True, False], ids=["graph", "eager"])
 def test_a2_avatar_flow_back_to_back(tmp_path_factory, use_graph):
-    """AvatarPlayer.flow: the only path through _upload_to, whose table of the target rows has no event of its own — the wait in
-    _upload_to is on the event the previous call's _upload recorded behind both copies"""
+    """AvatarPlayer.flow: the only path with a second table, that of the target rows, which has no event of its own — the one wait in
+    _upload, in front of both tables, is on the event the previous call's _upload recorded behind both copies"""
     player = _avatar(_hands(tmp_path_factory)[0], use_graph, keep_depth=True)
-    _under_delay(f"A2 flow, graph={use_graph}", [lambda r=r, t=t: player.flow(r, t) for r, t in zip(ROWS, TO_ROWS)], "_upload_to")
+    _under_delay(f"A2 flow, graph={use_graph}", [lambda r=r, t=t: player.flow(r, t) for r, t in zip(ROWS, TO_ROWS)], "_upload")
 
 
 @pytest.mark.parametrize("use_graph", [True, False], ids=["graph", "eager"])

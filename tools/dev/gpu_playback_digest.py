@@ -6,6 +6,9 @@ The scene: the synthetic hand of bench.py at 64 x 64, 5 frames, batches of 2 (2,
 at linspace(0, 4, 9); Motion.smooth(sigma 1, trim_rot 0.5); Motion.from_keypoints of the fit's own joints; AvatarPlayer.render for ss 1, 2 x
 self shadow on / off, each plain, over a background with bg_rows reversed, and with alpha; ScenePlayer.render of two players, one flipped,
 at ss 2 with background, scene depth, alpha and owner; every file AvatarPlayer.play (jpg) and ScenePlayer.play(masks, alpha) (png) write.
+The label passes: AvatarPlayer.annotate(uv=True) and .flow of a keep_depth player; ScenePlayer.annotate(uv=True) and .flow with the scene
+depth under distinct depth_rows / depth_to_rows; ScenePlayer.contact; every file AvatarPlayer.play(labels, flow="both") and
+ScenePlayer.play(labels, flow="both", contacts, masks) write (of an .npz its arrays: the archive itself carries the time of writing).
 
     python tools/dev/gpu_playback_digest.py [--tree DIR] [--out digests.json]      (--tree: the tree whose harp_amd is imported)"""
 import argparse
@@ -34,9 +37,19 @@ def motion_sha(m):
 def files_sha(d):
     out = {}
     for f in sorted(os.listdir(d)):
+        if f.endswith(".npz"):
+            with np.load(os.path.join(d, f)) as z:
+                out[f] = {k: sha(z[k]) for k in sorted(z.files)}
+            continue
         with open(os.path.join(d, f), "rb") as h:
             out[f] = sha(h.read())
     return out
+
+
+def fields_sha(t):
+    """a namedtuple of tensors, tuples of tensors and Nones -> {field: sha, list of shas, or None}"""
+    one = lambda x: None if x is None else sha(x) if torch.is_tensor(x) else [sha(y) for y in x]      # noqa: E731
+    return {k: one(getattr(t, k)) for k in t._fields}
 
 
 def main():
@@ -46,6 +59,8 @@ def main():
     a = ap.parse_args()
     sys.path.insert(0, HERE)
     sys.path.insert(0, os.path.abspath(a.tree))
+    import harp_amd                                        # noqa: F401  (this tree's, before gpu_playback_time puts its own tree in front)
+    print("harp_amd of", os.path.dirname(os.path.abspath(harp_amd.__file__)), file=sys.stderr)
     from gpu_playback_time import scene
     from harp_amd.playback import AvatarPlayer, Motion, ScenePlayer
     T, S, B, dev = 5, 64, 2, "cuda"
@@ -86,6 +101,18 @@ def main():
         res["avatar_play_jpg"] = files_sha(os.path.join(d, "avatar"))
         sc.play([motion, m1], os.path.join(d, "scene"), backgrounds=bg, scene_depth=depth, fmt="png", alpha=True, masks=True)
         res["scene_play_png"] = files_sha(os.path.join(d, "scene"))
+        to = (rows + 2) % T
+        p = AvatarPlayer(cfg, params, layer, batch_size=B, ss=2, device=dev, keep_depth=True)
+        p.load_motion(motion)
+        res["avatar_annotate_uv"], res["avatar_flow"] = fields_sha(p.annotate(rows, uv=True)), fields_sha(p.flow(rows, to))
+        res["scene_annotate_uv"] = fields_sha(sc.annotate(rows, uv=True, scene_depth=depth, depth_rows=rows[::-1].copy()))
+        res["scene_flow"] = fields_sha(sc.flow(rows, to, scene_depth=depth, depth_rows=rows[::-1].copy(), depth_to_rows=(rows + 1) % T))
+        res["scene_contact"] = fields_sha(sc.contact(rows, 1.0))
+        p.play(motion, os.path.join(d, "avatar_labels"), backgrounds=bg, fmt="png", labels=True, flow="both")
+        res["avatar_play_labels"] = files_sha(os.path.join(d, "avatar_labels"))
+        sc.play([motion, m1], os.path.join(d, "scene_labels"), backgrounds=bg, scene_depth=depth, fmt="png", masks=True, labels=True, flow="both",
+                contacts=True, contact_dist=1.0)
+        res["scene_play_labels"] = files_sha(os.path.join(d, "scene_labels"))
     print(json.dumps(res))
     if a.out:
         with open(a.out, "w") as f:
