@@ -368,6 +368,9 @@ class ContactMesh(ctypes.Structure):
 # per-vertex distance, nearest face and winding number between two meshes (csrc/contact.hip)
 SIGNATURES["harp_mesh_contact_ws_floats"] = (_sz, [_i, _i])
 SIGNATURES["harp_mesh_contact"] = (_i, [ctypes.POINTER(ContactMesh), ctypes.POINTER(ContactMesh), _i, _f, _vp, _vp, _vp, _vp, _vp])
+# the same with a per-(query vertex, target face) exclusion table (self-contact)
+SIGNATURES["harp_contact_excl_words"] = (_sz, [_i, _i])
+SIGNATURES["harp_mesh_contact_excl"] = (_i, [ctypes.POINTER(ContactMesh), ctypes.POINTER(ContactMesh), _vp, _i, _f, _vp, _vp, _vp, _vp, _vp])
 
 
 class IkOptions(ctypes.Structure):

@@ -22,6 +22,8 @@
 // The cull is conservative: the boxes are exact float32 bounds of the very coordinates the distances are computed from, and the margin
 //   (kCullMargin times the largest absolute box coordinate) is above the rounding of the gap and of a computed distance together, so a
 //   skipped chunk holds no face that could have replaced, or tied with, any lane's result.  The outputs do not depend on the chunking.
+// harp_mesh_contact_excl (self-contact) is the same two launches with contact_kernel<true>: a per-(query vertex, face) bit
+//   table removes faces from a vertex's distance minimum; the winding sum stays over all faces.  The comment at the kernel says how.
 // No atomics, no scratch, no allocation; every index is checked before it is used and all stores are per-lane vector stores.
 #include "harp_common.h"
 
@@ -185,12 +187,20 @@ __device__ __forceinline__ void stage_chunk(float4* __restrict__ lds, const floa
   __builtin_amdgcn_wave_barrier();
 }
 
+// kMask (harp_mesh_contact_excl): excl holds, chunk-major, one uint4 = 128 bits per (chunk, query vertex); bit k of it set
+//   means face c * kFaces + k does not count for that vertex's distance minimum.  A lane loads its word after the cull decision (a culled
+//   chunk's words are never read) and before the chunk is staged, so the load is in flight during the copy; the 64 lanes of a tile read
+//   64 consecutive 16-byte words.  The inner loop picks one of the four 32-bit words and one bit by the loop counter, which is
+//   wave-uniform: selects and a shift by a scalar, no indexed register, no scratch.  The test only removes candidates: a lane with every
+//   face of its chunks excluded keeps best = inf, which leaves the cull by `worst` at inf for the wave, so max_dist alone culls — the
+//   cull stays conservative with no change.  Pass 2, the winding sum, is not masked.  Without kMask the kernel is the one before.
+template <bool kMask>
 __global__ void __launch_bounds__(kLanes* kWaves) contact_kernel(const float* __restrict__ verts, const float* __restrict__ cam_R,
                                                                  const float* __restrict__ cam_T, int V, int q_flip,
                                                                  const float* __restrict__ boxes, const float* __restrict__ recs, int F,
                                                                  int n_chunks, int n_tiles, int t_flip, float max_dist,
-                                                                 float* __restrict__ dist, int32_t* __restrict__ face,
-                                                                 float* __restrict__ wind) {
+                                                                 const uint4* __restrict__ excl, float* __restrict__ dist,
+                                                                 int32_t* __restrict__ face, float* __restrict__ wind) {
   __shared__ float4 stage[kWaves][kFaces * (kRec / 4)];
   __shared__ float part_d[kWaves][kLanes], part_w[kWaves][kLanes];
   __shared__ int part_f[kWaves][kLanes];
@@ -223,12 +233,20 @@ __global__ void __launch_bounds__(kLanes* kWaves) contact_kernel(const float* __
       const float gap = uniform(sqrtf(gx * gx + gy * gy + gz * gz) - kCullMargin * m);
       if (gap > fminf(max_dist, worst)) continue;                     // (an empty box gives inf - inf = NaN or an infinite gap: the chunk has no valid face either way)
       const int n = min(kFaces, F - c * kFaces);
+      uint4 ex = make_uint4(0u, 0u, 0u, 0u);
+      if (kMask && live) ex = excl[(size_t)c * V + i];                // (c < n_chunks, i < V: inside the table of n_chunks * V words)
       stage_chunk(lds, rb + (size_t)c * kFaces * kRec, n, lane);
       for (int k = 0; k < n; ++k) {
         const float4 r0 = lds[3 * k], r1 = lds[3 * k + 1], r2 = lds[3 * k + 2];
         if (r2.y != 0.0f) {                                           // (the same record in every lane: wave-uniform)
           const float d2 = tri_dist2(px, py, pz, r0, r1, r2);
-          if (d2 < best2) {                                           // a candidate; it replaces only on a strictly smaller float32 DISTANCE
+          bool counts = true;
+          if (kMask) {                                                // (k is wave-uniform: the word by selects, the bit by a scalar shift)
+            const int wsel = k >> 5;
+            const uint32_t word = wsel == 0 ? ex.x : wsel == 1 ? ex.y : wsel == 2 ? ex.z : ex.w;
+            counts = ((word >> (k & 31)) & 1u) == 0u;
+          }
+          if (d2 < best2 && counts) {                                 // a candidate; it replaces only on a strictly smaller float32 DISTANCE
             const float d = sqrtf(d2);
             if (d < best) { best = d; best2 = d2; bf = c * kFaces + k; }
           }
@@ -247,7 +265,8 @@ __global__ void __launch_bounds__(kLanes* kWaves) contact_kernel(const float* __
       const int f = part_f[k][lane];
       if (f >= 0 && (d < best || (d == best && f < bf))) { best = d; bf = f; }
     }
-    const bool near = ok && best <= max_dist;
+    // (with the mask a lane can be left without a face although the target has valid ones: at max_dist = inf its best = inf is no contact)
+    const bool near = ok && best <= max_dist && (!kMask || bf >= 0);
     if (wind && __ballot(near) != 0ull) {                             // (the same in the four waves)
       for (int c = wave; c < n_chunks; c += kWaves) {
         const int n = min(kFaces, F - c * kFaces);
@@ -277,16 +296,12 @@ bool mesh_ok(const harp_contact_mesh* m, bool target) {
   return m && m->verts && m->cam_R && m->cam_T && m->V > 0 && m->reserved == 0 && (!target || (m->faces && m->F > 0));
 }
 
-}  // namespace
-
-extern "C" size_t harp_mesh_contact_ws_floats(int B, int F_target) {
-  if (B <= 0 || F_target <= 0) return 0;
-  return (size_t)B * (chunks_of(F_target) * kBox + (size_t)F_target * kRec);
-}
-
-extern "C" int harp_mesh_contact(const harp_contact_mesh* query, const harp_contact_mesh* target, int B, float max_dist, float* ws,
-                                 float* dist, int32_t* face, float* wind, hipStream_t stream) {
+// the checks and the two launches of both entries; kMask: with the exclusion table
+template <bool kMask>
+int launch_contact(const harp_contact_mesh* query, const harp_contact_mesh* target, const uint32_t* excl, int B, float max_dist, float* ws,
+                   float* dist, int32_t* face, float* wind, hipStream_t stream) {
   if (!mesh_ok(query, false) || !mesh_ok(target, true) || !ws || B <= 0) return HARP_ERR_ARG;
+  if (kMask && (!excl || ((uintptr_t)excl & 15) != 0)) return HARP_ERR_ARG;
   if (!(max_dist >= 0.0f)) return HARP_ERR_ARG;                       // (a NaN is not)
   if (!dist && !face && !wind) return HARP_ERR_ARG;
   if (((uintptr_t)ws & 15) != 0) return HARP_ERR_ARG;
@@ -298,9 +313,31 @@ extern "C" int harp_mesh_contact(const harp_contact_mesh* query, const harp_cont
   hipLaunchKernelGGL(contact_setup_kernel, dim3((unsigned)(n_chunks * B)), dim3(kFaces), 0, stream, target->verts, target->cam_R,
                      target->cam_T, target->faces, target->V, F, (int)n_chunks, target->flip_x != 0 ? 1 : 0, boxes, recs);
   HARP_CHECK_LAUNCH();
-  hipLaunchKernelGGL(contact_kernel, dim3((unsigned)(n_tiles * B)), dim3(kLanes * kWaves), 0, stream, query->verts, query->cam_R, query->cam_T, V,
-                     query->flip_x != 0 ? 1 : 0, (const float*)boxes, (const float*)recs, F, (int)n_chunks, (int)n_tiles,
-                     target->flip_x != 0 ? 1 : 0, max_dist, dist, face, wind);
+  hipLaunchKernelGGL(contact_kernel<kMask>, dim3((unsigned)(n_tiles * B)), dim3(kLanes * kWaves), 0, stream, query->verts, query->cam_R,
+                     query->cam_T, V, query->flip_x != 0 ? 1 : 0, (const float*)boxes, (const float*)recs, F, (int)n_chunks, (int)n_tiles,
+                     target->flip_x != 0 ? 1 : 0, max_dist, (const uint4*)excl, dist, face, wind);
   HARP_CHECK_LAUNCH();
   return HARP_OK;
+}
+
+}  // namespace
+
+extern "C" size_t harp_mesh_contact_ws_floats(int B, int F_target) {
+  if (B <= 0 || F_target <= 0) return 0;
+  return (size_t)B * (chunks_of(F_target) * kBox + (size_t)F_target * kRec);
+}
+
+extern "C" int harp_mesh_contact(const harp_contact_mesh* query, const harp_contact_mesh* target, int B, float max_dist, float* ws,
+                                 float* dist, int32_t* face, float* wind, hipStream_t stream) {
+  return launch_contact<false>(query, target, nullptr, B, max_dist, ws, dist, face, wind, stream);
+}
+
+extern "C" size_t harp_contact_excl_words(int V_query, int F_target) {
+  if (V_query <= 0 || F_target <= 0) return 0;
+  return chunks_of(F_target) * (size_t)V_query * 4;
+}
+
+extern "C" int harp_mesh_contact_excl(const harp_contact_mesh* query, const harp_contact_mesh* target, const uint32_t* excl, int B,
+                                      float max_dist, float* ws, float* dist, int32_t* face, float* wind, hipStream_t stream) {
+  return launch_contact<true>(query, target, excl, B, max_dist, ws, dist, face, wind, stream);
 }

@@ -1492,6 +1492,7 @@ def flow_layers(layers, to, ss=1, scene_depth=None, scene_rows=None, scene_depth
 ContactMesh = collections.namedtuple("ContactMesh", "verts cam_R cam_T faces flip", defaults=(None, False))
 MeshContact = collections.namedtuple("MeshContact", "dist face wind")
 _CONTACT_OUTPUTS = ("dist", "face", "wind")
+CONTACT_EXCL_FACES = 128                               # HARP_CONTACT_EXCL_FACES: the faces one 16-byte word of an exclusion table covers
 
 
 def _contact_side(name, side, B, target):
@@ -1525,14 +1526,16 @@ def _contact_side(name, side, B, target):
     return m, keep
 
 
-def mesh_contact(query, target, max_dist=math.inf, want=_CONTACT_OUTPUTS):
+def mesh_contact(query, target, max_dist=math.inf, want=_CONTACT_OUTPUTS, exclude=None):
     """For every vertex of `query` its relation to the surface of `target`, frame by frame (csrc/contact.hip: harp_mesh_contact, whose
     contract include/harp_hip.h states), forward only: a label, no gradient.  query, target: ops.ContactMesh (or dicts of its fields) of
     device tensors over the same B frames; the target needs faces.  max_dist metres, >= 0, inf for no limit.  want: which of "dist",
     "face", "wind" to compute.  Returns MeshContact(dist (B,Vq) float32: the unsigned distance to the target's nearest triangle, +inf
     beyond max_dist; face (B,Vq) int32: a face that attains it, -1 for none; wind (B,Vq) float32: the generalised winding number of the
     target about the vertex (about 1 inside, 0 outside; > 0.5 is the playback's "inside"), 0 where dist is +inf), None for an output that
-    was not asked for."""
+    was not asked for.  exclude: None, or the faces that do not count for a vertex's distance minimum (harp_mesh_contact_excl, DESIGN.md
+    §37): an int32 or uint32 contiguous device tensor (ceil(F / 128), Vq, 4), bit k & 31 of exclude[c, i, k >> 5] for face 128 c + k and
+    query vertex i, the same for every frame (playback.selfcontact.pack_exclusion makes it from a (Vq, F) bool); wind is not masked."""
     want = (want,) if isinstance(want, str) else tuple(want)
     if not want or set(want) - set(_CONTACT_OUTPUTS):
         raise ValueError(f"mesh_contact: want is a non-empty selection of {_CONTACT_OUTPUTS}, got {want}")
@@ -1544,13 +1547,27 @@ def mesh_contact(query, target, max_dist=math.inf, want=_CONTACT_OUTPUTS):
     t, keep_t = _contact_side("target", target, B, True)
     _playback_input("mesh_contact", keep_q[0], keep_t[0])
     dev, Vq = keep_q[0].device, keep_q[0].shape[1]
+    if exclude is not None:
+        shape = (-(-t.F // CONTACT_EXCL_FACES), Vq, 4)
+        if not torch.is_tensor(exclude) or exclude.dtype not in (torch.int32, torch.uint32):
+            raise TypeError(f"mesh_contact: exclude must be an int32 or uint32 tensor, got {exclude.dtype if torch.is_tensor(exclude) else type(exclude)}")
+        if exclude.device != dev:
+            raise ValueError(f"mesh_contact: exclude is on {exclude.device}, the meshes on {dev}")
+        if tuple(exclude.shape) != shape:
+            raise ValueError(f"mesh_contact: exclude must be {shape} = (chunks of {CONTACT_EXCL_FACES} faces, Vq, 4), got {tuple(exclude.shape)}")
+        if not exclude.is_contiguous():
+            raise ValueError("mesh_contact: exclude must be contiguous")
     L = _lib.lib()
     ws = torch.empty(L.harp_mesh_contact_ws_floats(B, t.F), dtype=torch.float32, device=dev)
     new = lambda k, dt: torch.empty(B, Vq, dtype=dt, device=dev) if k in want else None      # noqa: E731
     o = MeshContact(new("dist", torch.float32), new("face", torch.int32), new("wind", torch.float32))
     with torch.cuda.device(dev):
-        rc = L.harp_mesh_contact(ctypes.byref(q), ctypes.byref(t), B, max_dist, _lib.ptr(ws), *[_lib.ptr(x) for x in o], _lib.stream())
-    _lib.check(rc, "harp_mesh_contact")
+        if exclude is None:
+            rc = L.harp_mesh_contact(ctypes.byref(q), ctypes.byref(t), B, max_dist, _lib.ptr(ws), *[_lib.ptr(x) for x in o], _lib.stream())
+        else:
+            rc = L.harp_mesh_contact_excl(ctypes.byref(q), ctypes.byref(t), _lib.ptr(exclude), B, max_dist, _lib.ptr(ws),
+                                          *[_lib.ptr(x) for x in o], _lib.stream())
+    _lib.check(rc, "harp_mesh_contact" if exclude is None else "harp_mesh_contact_excl")
     return o
 
 

@@ -3,7 +3,7 @@ import numpy as np
 
 from .. import ops
 from .motion import Motion, motion_jitter
-from .player import CONTACT_DIST, FLOW_TOL, LABEL_TOL, AvatarPlayer, ScenePlayer
+from .player import CONTACT_DIST, FLOW_TOL, LABEL_TOL, SELF_CONTACT_DIST, SELF_GEODESIC, AvatarPlayer, ScenePlayer
 
 
 def parse_args(argv=None):
@@ -60,6 +60,16 @@ def parse_args(argv=None):
                          "deepest penetration")
     ap.add_argument("--contact-dist", type=float, default=CONTACT_DIST, metavar="M",
                     help="with --contacts: a vertex farther than M metres from every other avatar has no contact")
+    ap.add_argument("--self-contacts", action="store_true",
+                    help="also write self_contacts.npz, per avatar and vertex the signed distance to the nearest face of the avatar's OWN "
+                         "surface that lies beyond a geodesic radius of it (negative inside another part of the avatar), that face and its "
+                         "part, which parts touch which (a pinch: thumb3 and index3) and per frame the smallest distance and the deepest "
+                         "penetration; one avatar is enough")
+    ap.add_argument("--self-contact-dist", type=float, default=SELF_CONTACT_DIST, metavar="M",
+                    help="with --self-contacts: a vertex farther than M metres from every counting face of its avatar has no contact")
+    ap.add_argument("--self-geodesic", type=float, default=SELF_GEODESIC, metavar="M",
+                    help="with --self-contacts: the faces within M metres of a vertex along the mesh's edges do not count for it; above "
+                         "--self-contact-dist")
     ap.add_argument("--smooth", type=float, default=None, metavar="SIGMA",
                     help="filter the loaded or solved motion with a Gaussian window of SIGMA frames before --fps-scale (Motion.smooth); prints the "
                          "joint jitter before and after")
@@ -80,6 +90,10 @@ def parse_args(argv=None):
         raise SystemExit("--contact-dist must not be negative")
     if args.contacts and not args.also:
         raise SystemExit("--contacts needs a second avatar: give --also CFG:MOTION[:flip]")
+    if args.self_contacts and not (args.self_contact_dist >= 0 and np.isfinite(args.self_contact_dist)):
+        raise SystemExit("--self-contact-dist must not be negative and must be finite")
+    if args.self_contacts and not args.self_geodesic > args.self_contact_dist:
+        raise SystemExit("--self-geodesic must exceed --self-contact-dist")
     if args.smooth_trim is not None and args.smooth is None:
         raise SystemExit("--smooth-trim needs --smooth")
     if args.smooth_keypoints is not None and args.keypoints is None:
@@ -154,7 +168,8 @@ def main(argv=None):
         configs, params, hand_layer, motion = load(args.config, args.motion, args.keypoints, args.vertices, args.keypoints2d)
         player = AvatarPlayer(configs, params, hand_layer, batch_size=args.batch_size, ss=args.ss, device=args.device, keep_depth=args.labels or args.flow is not None)
         paths = player.play(motion, args.out, backgrounds=args.background, fmt=fmt, alpha=args.alpha, labels=args.labels, label_tol=args.label_tol,
-                            flow=args.flow, flow_tol=args.flow_tol)
+                            flow=args.flow, flow_tol=args.flow_tol, self_contacts=args.self_contacts, self_contact_dist=args.self_contact_dist,
+                            self_geodesic=args.self_geodesic)
     else:
         specs = [(args.config, args.motion, args.flip, args.keypoints, args.vertices, args.keypoints2d)]
         for spec in args.also:
@@ -170,6 +185,7 @@ def main(argv=None):
         scene = ScenePlayer(players, flip=[spec[2] for spec in specs])
         paths = scene.play(motions, args.out, backgrounds=args.background, scene_depth=args.scene_depth, fmt=fmt, alpha=args.alpha, masks=args.masks,
                            labels=args.labels, label_tol=args.label_tol, flow=args.flow, flow_tol=args.flow_tol, contacts=args.contacts,
-                           contact_dist=args.contact_dist)
+                           contact_dist=args.contact_dist, self_contacts=args.self_contacts, self_contact_dist=args.self_contact_dist,
+                           self_geodesic=args.self_geodesic)
     print(f"wrote {len(paths)} frames to {args.out}")
     return paths

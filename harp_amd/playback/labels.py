@@ -20,6 +20,19 @@ def vertex_part_labels(weights):
     return (1 + np.argmax(w, axis=1)).astype(np.uint8)          # (argmax: the first of equal weights)
 
 
+def subdivided_vertex_part_labels(weights, edges0):
+    """The part of every VERTEX of the once-subdivided mesh: weights (V0, NJ), edges0 (E0, 2) the base edges in the order of their
+    midpoints (topology.subdivide_topology) -> (V0 + E0,) uint8.  A base vertex by vertex_part_labels, the rule face_part_labels votes
+    with; midpoint V0 + e by the same rule on the mean of its two ends' weights, which is how the subdivision skins it."""
+    w, e = np.asarray(weights), np.asarray(edges0).reshape(-1, 2).astype(np.int64)
+    base = vertex_part_labels(w)
+    if e.shape[0] == 0:
+        return base
+    if e.min() < 0 or e.max() >= w.shape[0]:
+        raise ValueError(f"edges0 must index the {w.shape[0]} base vertices")
+    return np.concatenate([base, vertex_part_labels(0.5 * (w[e[:, 0]].astype(np.float64) + w[e[:, 1]].astype(np.float64)))])
+
+
 def face_part_labels(weights, faces0, V0):
     """The part of every face of the once-subdivided mesh: weights (V0, NJ) skinning weights, faces0 (F0, 3) the base faces -> (4 F0,)
     uint8 in 1..NJ, in the face order [f0; f1; f2; f3] of topology.subdivide_topology.  A base vertex's part is 1 + the argmax of its

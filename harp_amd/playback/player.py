@@ -1,9 +1,10 @@
 """The two forward-only renderers on one base.  `_Player` owns what a call and a play loop need whatever is drawn: the
 index stage (`_Stage`) with the copies of the caller's tensors, the buffers of each kind of pass, the graphs, the labels and flow passes
 over the player's layers, and the double-buffered way to disk.  `AvatarPlayer` adds one avatar's launches and the resolve (§22),
-`ScenePlayer` several avatars, the composite (§23) and the contact pass (§36)."""
+`ScenePlayer` several avatars, the composite (§23) and the contact pass (§36); the self-contact pass (§37) is the base's, over the layers."""
 import collections
 import ctypes
+import math
 import os
 
 import numpy as np
@@ -35,6 +36,20 @@ CONTACT_DIST = 0.02                                    # metres: how near anothe
 # contact), and max_penetration (n,) float32, the largest -dist over the inside vertices, or 0.  Unlike Annotation and Flow, every tensor
 # is new (compose_contact): a later contact() does not change an earlier result
 Contact = collections.namedtuple("Contact", "dist other face part wind min_dist max_penetration")
+# self-contact within ONE avatar.  Both are conventions, not tuned values.  SELF_GEODESIC: the faces within 3 cm of a vertex
+# along the mesh's edges (about a finger's segment and a half) do not count for it — its own neighbourhood is always near.
+# SELF_CONTACT_DIST: 4 mm; on the hand template at rest with that exclusion no vertex has a counting face within 4 mm (the nearest is at
+# 4.56 mm), while 336 of 778 lie within 2 cm (the facing sides of neighbouring fingers): CONTACT_DIST is not usable within one hand
+SELF_GEODESIC = 0.03
+SELF_CONTACT_DIST = 0.004
+# what self_contact returns per avatar: device tensors over the rows asked for and the avatar's V vertices, every one new.
+# dist (n,V) float32, SIGNED: the distance to the nearest face of the avatar's own surface that is not excluded for the vertex, negative
+# where the vertex is inside another part of the avatar (wind > 1.0), +inf beyond max_dist; face (n,V) int32: that face, -1 none; part
+# (n,V) uint8: that face's part, 0 none; own_part (V,) uint8: the vertex's own part (labels.subdivided_vertex_part_labels); wind (n,V)
+# float32: the winding number of the WHOLE surface about the vertex (not masked), 0 where dist is +inf; touch (n,P,P) bool, P = 1 + the
+# skinning joints: touch[t, p, q] = some vertex of part p is within max_dist of a face of part q (a pinch: touch[t, thumb3, index3]);
+# min_dist (n,) float32: the smallest signed distance (+inf: no contact); max_penetration (n,) float32: the largest -dist, or 0
+SelfContact = collections.namedtuple("SelfContact", "dist face part own_part wind touch min_dist max_penetration")
 
 
 def _host_rows(name, rows, n=None):
@@ -106,7 +121,7 @@ class _Stage:
 class _Player:
     """What AvatarPlayer and ScenePlayer share.  A subclass declares the caller tensors it stages (`_inputs`: name, per-row shape, dtype),
     says what it draws (`_layers`) and supplies `_enqueue_frames`.  A call is one PASS, a hashable (kind, *what it carries): ("frames",
-    channels, owner), ("labels", _label_flags' tuple), ("flow", tol) or ("contact", max_dist).  Per kind there is one `_enqueue_<kind>`,
+    channels, owner), ("labels", _label_flags' tuple), ("flow", tol), ("contact", max_dist) or ("selfcontact", max_dist, geodesic).  Per kind there is one `_enqueue_<kind>`,
     the launches of a whole call in order on the current stream, and one `_alloc_<kind>`, its output buffers.  Nothing is allocated
     after the constructor except when a pass is first used or a longer `rows` is first seen (`_grow`)."""
 
@@ -328,6 +343,40 @@ class _Player:
         fl = self._out["flow"]
         return Flow(fl["flow"][:n], fl["dz"][:n], fl["status"][:n])
 
+    # ---- self-contact, over the layers: every layer against itself, an avatar is a scene of one ------------------------
+    def _alloc_selfcontact(self, n):
+        """per layer the three outputs of harp_mesh_contact_excl over every padded row; one workspace, for the layer with the most faces
+        (the calls follow each other on one stream)"""
+        layers = [pl for pl, _ in self._layers()]
+        new = lambda dt, V: torch.empty(n, V, dtype=dt, device=self.dev)      # noqa: E731
+        ws = torch.empty(max(_lib.lib().harp_mesh_contact_ws_floats(self.B, pl.topo.F) for pl in layers), dtype=torch.float32, device=self.dev)
+        return dict(out=[(new(torch.float32, pl.topo.V), new(torch.int32, pl.topo.V), new(torch.float32, pl.topo.V)) for pl in layers], ws=ws)
+
+    def _enqueue_selfcontact(self, n_pad, used, max_dist, geodesic):
+        """per batch every layer's front only, then one harp_mesh_contact_excl per layer with the layer as query AND target (its own flip
+        on both sides) under its exclusion table of `geodesic` (made by _self_contact before: nothing is built inside a capture).
+        max_dist and geodesic are part of the pass and so of the graph key"""
+        p, B, bufs, layers = _lib.ptr, self.B, self._out["selfcontact"], self._layers()
+        meshes = [pl._contact_mesh(f) for pl, f in layers]
+        tables = [pl._exclusion_table(geodesic) for pl, _ in layers]
+        for lo in range(0, n_pad, B):
+            for pl, _ in layers:
+                pl._render_batch(self._stage.rows(lo), front_only=True)
+            for m, tab, (d, f, w) in zip(meshes, tables, bufs["out"]):
+                _lib.check(_lib.lib().harp_mesh_contact_excl(ctypes.byref(m), ctypes.byref(m), p(tab), B, max_dist, p(bufs["ws"]),
+                                                             d[lo:].data_ptr(), f[lo:].data_ptr(), w[lo:].data_ptr(), _lib.stream()),
+                           "mesh_contact_excl")
+
+    def _self_contact(self, rows, max_dist, geodesic):
+        """the self-contact pass -> one SelfContact per layer"""
+        max_dist, geodesic = _self_contact_args(max_dist, geodesic)
+        layers = [pl for pl, _ in self._layers()]
+        with torch.cuda.device(self.dev):
+            static = [(pl._part_table(), pl._own_part_table(), pl._exclusion_table(geodesic)) for pl in layers]
+        n = self._render(rows, {}, ("selfcontact", max_dist, geodesic))
+        return tuple(compose_self_contact(*(t[:n] for t in out), part, own, 1 + pl._skin_weights.shape[1])
+                     for pl, out, (part, own, _) in zip(layers, self._out["selfcontact"]["out"], static))
+
     def _play(self, out_dir, fmt, alpha, prepare, masks=False):
         """The way to disk of both players: the format checked, out_dir made, then render = prepare() (which loads the motion and the
         caller's inputs) called batch by batch: render(rows) -> frames, or (frames, owner) with masks.  Each leaves through a pinned host
@@ -410,6 +459,7 @@ class AvatarPlayer(_Player):
         self.tab = self.tables = None
         self._skin_weights = np.asarray(hand_layer._model_np["weights"])      # (V0, NJ): the part table is made from it on first use
         self._face_label = None
+        self._own_part, self._excl = None, {}            # self-contact (§37): the vertices' own parts, the exclusion table per geodesic radius
         self.s_to = None                                 # the target frames' ndc_c and z_c of a batch, allocated on the first flow()
 
     def _alloc_scratch(self):
@@ -564,6 +614,38 @@ class AvatarPlayer(_Player):
         return _lib.ContactMesh(verts=p(s["vd"]), cam_R=p(s["cam_R"]), cam_T=p(s["cam_T"]), faces=p(tp.faces), V=tp.V, F=tp.F, flip_x=int(flip),
                                 reserved=0)
 
+    # ---- self-contact: what belongs to the topology and the fit's shape, made on first use -----------------------------
+    def _rest_vertices(self):
+        """(V,3) float64 metres, the rest geometry the exclusion is measured on: the model's template shaped by the fit's betas and
+        subdivided by the topology's midpoints; not posed (the mean pose is not added either) and not displaced — the displacements
+        and the pose change an edge path by far less than the radius"""
+        dm, tp = self.dm, self.topo
+        nb = min(int(self.fit["shape"].shape[0]), int(dm.shapedirs_T.shape[0]))
+        v = dm.v_template.double().reshape(-1, 3) + (self.fit["shape"][:nb].double() @ dm.shapedirs_T[:nb].double()).view(-1, 3)
+        if v.shape[0] != tp.V0:
+            raise RuntimeError(f"the model's template has {v.shape[0]} vertices, the topology {tp.V0}")
+        if tp.E0 == 0:
+            return v
+        e = tp.edges0.long()
+        return torch.cat([v, 0.5 * (v[e[:, 0]] + v[e[:, 1]])])
+
+    def _exclusion_table(self, geodesic):
+        """the exclusion table of harp_mesh_contact_excl for this avatar against itself at the radius `geodesic`, on the device"""
+        if geodesic not in self._excl:
+            from .selfcontact import geodesic_exclusion, pack_exclusion
+            self._excl[geodesic] = pack_exclusion(geodesic_exclusion(self._rest_vertices(), self.topo.faces, geodesic))
+        return self._excl[geodesic]
+
+    def _own_part_table(self):
+        """the part of every vertex of the subdivided mesh on the device (labels.subdivided_vertex_part_labels)"""
+        if self._own_part is None:
+            from .labels import subdivided_vertex_part_labels
+            tab = subdivided_vertex_part_labels(self._skin_weights, self.topo.edges0.cpu().numpy()[:self.topo.E0])
+            if tab.shape[0] != self.topo.V:
+                raise RuntimeError(f"{tab.shape[0]} vertex parts for {self.topo.V} vertices")
+            self._own_part = torch.from_numpy(tab).to(self.dev)
+        return self._own_part
+
     def _keypoints_batch(self, kp, lo, layers, n_layers, self_layer, scene, tol):
         """harp_keypoint_visibility of this player's batch into rows lo.. of the buffers kp; scene: the scene depth arguments of the batch"""
         s, p = self.s, _lib.ptr
@@ -615,15 +697,32 @@ class AvatarPlayer(_Player):
         self._ready(need_depth="flow")
         return self._flow(rows, {}, (to_rows, {}), tol)
 
+    @torch.no_grad()
+    def self_contact(self, rows, max_dist=SELF_CONTACT_DIST, geodesic=SELF_GEODESIC):
+        """Where the avatar of the frames `rows` touches ITSELF (a pinch, a fist, crossed fingers) -> SelfContact (above): per vertex the
+        signed distance to the nearest face of its own surface that does not lie within `geodesic` metres of it along the mesh's edges
+        (selfcontact.geodesic_exclusion on the rest geometry, built on first use per radius), that face and its part, the winding
+        number of the whole surface, which parts touch which, and per frame the smallest distance and the deepest penetration.  Per
+        batch the front only and one harp_mesh_contact_excl, under a graph key of its own.  A vertex ON a closed surface sees it under
+        its exterior-angle share, 0.14 .. 0.82 on the hand at rest, and 1 more when it is inside another part: INSIDE is wind > 1.0.
+        max_dist is finite, >= 0 and below geodesic: otherwise the vertex's own neighbourhood just beyond the radius would always be
+        "in contact".  SELF_CONTACT_DIST = 0.004 and SELF_GEODESIC = 0.03 are conventions, not tuned values."""
+        self._ready()
+        return self._self_contact(rows, max_dist, geodesic)[0]
+
     # ---- a whole motion to files ------------------------------------------------------------------------------------------------
-    def play(self, motion, out_dir, backgrounds=None, fmt="jpg", alpha=False, labels=False, label_tol=LABEL_TOL, flow=None, flow_tol=FLOW_TOL):
+    def play(self, motion, out_dir, backgrounds=None, fmt="jpg", alpha=False, labels=False, label_tol=LABEL_TOL, flow=None, flow_tol=FLOW_TOL,
+             self_contacts=False, self_contact_dist=SELF_CONTACT_DIST, self_geodesic=SELF_GEODESIC):
         """load_motion(motion), render it batch by batch and write out_dir/%04d.<fmt> (fmt "jpg" or "png"; alpha=True needs "png" and
         writes RGBA).  backgrounds: None, a (N,S,S,3) uint8 tensor or a directory of images of that size (sorted by name); frame i is
         composited over background i mod N.  The frames leave through two pinned host buffers, one per batch in flight, and are encoded on
         a thread pool while the next batch renders.  labels=True (needs keep_depth=True) also writes part_%04d.png, depth_%04d.png,
         iuv_%04d.png and keypoints.npz (write_labels).  flow="fw" | "bw" | "both" (needs keep_depth=True) also writes flow_%04d.flo and /
-        or flow_bw_%04d.flo with their status PNGs (write_flow).  Returns the list of paths."""
+        or flow_bw_%04d.flo with their status PNGs (write_flow).  self_contacts=True also writes self_contacts.npz (write_self_contacts)
+        with self_contact(rows, self_contact_dist, self_geodesic) of every frame.  Returns the list of paths."""
         _flow_mode(flow), _tol(flow_tol)
+        if self_contacts:
+            _self_contact_args(self_contact_dist, self_geodesic)
 
         def prepare():
             self.load_motion(motion)
@@ -636,6 +735,9 @@ class AvatarPlayer(_Player):
             write_labels(out_dir, self.T, self.B, lambda rows: self._annotate(rows, {}, flags), [part_names_of(self)])
         if flow:
             write_flow(out_dir, self.T, self.B, lambda rows, to: self.flow(rows, to, tol=flow_tol), flow)
+        if self_contacts:
+            write_self_contacts(out_dir, self.T, self.B, lambda rows: self._self_contact(rows, self_contact_dist, self_geodesic),
+                                [part_names_of(self)], self_contact_dist, self_geodesic)
         return paths
 
 
@@ -774,15 +876,27 @@ class ScenePlayer(_Player):
         return compose_contact([{j: tuple(t[:n] for t in pairs[k, j]) for j in range(len(self.players)) if j != k}
                                 for k in range(len(self.players))], tabs)
 
+    @torch.no_grad()
+    def self_contact(self, rows, max_dist=SELF_CONTACT_DIST, geodesic=SELF_GEODESIC):
+        """Where every avatar of the scene's frames `rows` touches itself -> a tuple of SelfContact, one per player, each what that
+        player's own AvatarPlayer.self_contact gives for its motion (a flipped player is mirrored on both sides: the same distances,
+        faces and parts).  One player is enough.  Contact BETWEEN the avatars is contact()."""
+        self._ready()
+        return self._self_contact(rows, max_dist, geodesic)
+
     def play(self, motions, out_dir, backgrounds=None, scene_depth=None, fmt="jpg", alpha=False, masks=False, labels=False, label_tol=LABEL_TOL,
-             flow=None, flow_tol=FLOW_TOL, contacts=False, contact_dist=CONTACT_DIST):
+             flow=None, flow_tol=FLOW_TOL, contacts=False, contact_dist=CONTACT_DIST, self_contacts=False, self_contact_dist=SELF_CONTACT_DIST,
+             self_geodesic=SELF_GEODESIC):
         """load_motions(motions), render the scene batch by batch and write out_dir/%04d.<fmt> as AvatarPlayer.play does; with masks=True
         also out_dir/mask_%04d.png, the owner map (8-bit grey: 0 background, 1 + the player).  backgrounds: as AvatarPlayer.play;
         scene_depth: None, a float32 (N,S,S) tensor or a directory (load_scene_depth), frame i tested against depth i mod N.  labels=True
         also writes the label files (write_labels), one keypoints_<k>.npz per player k when there are several.  Returns the list of the
         frames' paths.  flow="fw" | "bw" | "both" also writes the flow files (write_flow).  contacts=True (at least two players) also
-        writes contacts.npz (write_contacts) with contact(rows, contact_dist) of every frame."""
+        writes contacts.npz (write_contacts) with contact(rows, contact_dist) of every frame.  self_contacts=True also writes
+        self_contacts.npz (write_self_contacts) with self_contact(rows, self_contact_dist, self_geodesic) of every frame."""
         _flow_mode(flow), _tol(flow_tol)
+        if self_contacts:
+            _self_contact_args(self_contact_dist, self_geodesic)
         if contacts and len(self.players) < 2:
             raise ValueError("contacts need a scene of at least two players")
         if contacts and not float(contact_dist) >= 0:
@@ -808,6 +922,9 @@ class ScenePlayer(_Player):
         if contacts:
             write_contacts(out_dir, self.T, self.B, lambda rows: self.contact(rows, contact_dist), [part_names_of(pl) for pl in self.players],
                            float(contact_dist))
+        if self_contacts:
+            write_self_contacts(out_dir, self.T, self.B, lambda rows: self.self_contact(rows, self_contact_dist, self_geodesic),
+                                [part_names_of(pl) for pl in self.players], self_contact_dist, self_geodesic)
         return paths
 
 
@@ -873,6 +990,57 @@ def write_contacts(out_dir, T, B, contact, names, max_dist):
     path = os.path.join(out_dir, "contacts.npz")
     np.savez(path, max_dist=np.float32(max_dist), **{k: np.concatenate(v) for k, v in {**got, **per_frame}.items()},
              **{f"part_names_{k}": np.array(names[k]) for k in range(P)})
+    return path
+
+
+def _self_contact_args(max_dist, geodesic):
+    """max_dist finite and >= 0, geodesic > max_dist (inf allowed: every face the vertex is connected to is excluded) -> both as floats"""
+    max_dist, geodesic = float(max_dist), float(geodesic)
+    if not (max_dist >= 0 and math.isfinite(max_dist)):
+        raise ValueError(f"max_dist must be finite and not negative, got {max_dist}")
+    if not geodesic > max_dist:
+        raise ValueError(f"geodesic must exceed max_dist = {max_dist} (a vertex's own neighbourhood just beyond the radius would always be "
+                         f"in contact), got {geodesic}")
+    return max_dist, geodesic
+
+
+def compose_self_contact(dist, face, wind, part_table, own_part, n_parts):
+    """The documented rule from harp_mesh_contact_excl's outputs of a mesh against itself to SelfContact, in torch ops on the device.
+    dist, face, wind (n,V); part_table (F,) uint8 the part of every face; own_part (V,) uint8 the part of every vertex; n_parts = P.
+    The distance is negated where the (unmasked) winding number exceeds 1.0; touch[t, p, q] is set by every vertex of part p whose
+    nearest counting face within max_dist is of part q.  Every tensor returned is new."""
+    hit = face >= 0
+    part = torch.where(hit, part_table[face.clamp(min=0).long()], torch.zeros_like(face, dtype=torch.uint8))
+    inside = wind > 1.0
+    pair = own_part.long()[None, :] * n_parts + part.long()
+    touch = torch.zeros(dist.shape[0], n_parts * n_parts, dtype=torch.int32, device=dist.device)
+    touch.scatter_reduce_(1, pair, hit.to(torch.int32), "amax", include_self=True)
+    signed = torch.where(inside, -dist, dist)
+    deep = torch.where(inside, dist, torch.zeros_like(dist)).amax(1).clamp(min=0)
+    return SelfContact(signed, face.clone(), part, own_part.clone(), wind.clone(), touch.bool().view(-1, n_parts, n_parts), signed.amin(1), deep)
+
+
+def write_self_contacts(out_dir, T, B, self_contact, names, max_dist, geodesic):
+    """self_contacts.npz of a played motion beside its frames, batch by batch: per player k dist_k (T,V_k) float32 signed metres (+inf:
+    none), face_k (T,V_k) int32, part_k (T,V_k) uint8, wind_k (T,V_k) float32, touch_k (T,P_k,P_k) bool, own_part_k (V_k,) uint8 and
+    part_names_k; min_dist (T,) and max_penetration (T,) float32 over all players; max_dist and geodesic, the two distances used.
+    self_contact(rows) -> one SelfContact per player; names: one list of part names per player."""
+    P = len(names)
+    keys = ("dist", "face", "part", "wind", "touch")
+    got = {f"{key}_{k}": [] for key in keys for k in range(P)}
+    per_frame = dict(min_dist=[], max_penetration=[])
+    own = {}
+    for lo in range(0, T, B):
+        cs = self_contact(np.arange(lo, min(T, lo + B)))
+        for k, c in enumerate(cs):
+            for key in keys:
+                got[f"{key}_{k}"].append(getattr(c, key).cpu().numpy())
+            own[f"own_part_{k}"] = c.own_part.cpu().numpy()
+        per_frame["min_dist"].append(torch.stack([c.min_dist for c in cs]).amin(0).cpu().numpy())
+        per_frame["max_penetration"].append(torch.stack([c.max_penetration for c in cs]).amax(0).cpu().numpy())
+    path = os.path.join(out_dir, "self_contacts.npz")
+    np.savez(path, max_dist=np.float32(max_dist), geodesic=np.float32(geodesic), **own,
+             **{k: np.concatenate(v) for k, v in {**got, **per_frame}.items()}, **{f"part_names_{k}": np.array(names[k]) for k in range(P)})
     return path
 
 

@@ -1227,6 +1227,31 @@ size_t harp_mesh_contact_ws_floats(int B, int F_target);
 int harp_mesh_contact(const harp_contact_mesh* query, const harp_contact_mesh* target, int B, float max_dist, float* ws, float* dist,
                       int32_t* face, float* wind, hipStream_t stream);
 
+/* ---- the same with a per-(query vertex, target face) exclusion: self-contact within one mesh (csrc/contact.hip; playback/player.py
+ * self_contact) ----
+ * A vertex of a mesh is at distance 0 from its own faces, so a mesh queried against itself needs to be told which faces do not count
+ * for which vertex (playback/selfcontact.py builds the table from a geodesic radius).
+ * Table: excl[(c * V_query + i) * 4 + (k >> 5)] bit (k & 31) stands for target face c * HARP_CONTACT_EXCL_FACES + k and query vertex i:
+ * chunk-major, one 16-byte word of 128 bits per (chunk of 128 faces, vertex), so that the 64 lanes of a tile read 64 consecutive words
+ * per chunk.  harp_contact_excl_words(V_query, F_target) = ceil(F_target / 128) * V_query * 4 uint32 words (0 for a non-positive
+ * argument).  The table is the same for every frame of the batch: it belongs to a topology, not to a pose.  Bits past F are ignored. */
+#define HARP_CONTACT_EXCL_FACES 128
+size_t harp_contact_excl_words(int V_query, int F_target);
+/* harp_mesh_contact_excl: harp_mesh_contact's contract word for word (the same ws of harp_mesh_contact_ws_floats floats, the same two
+ * launches, no atomics, no allocation, capturable, a repeated call gives the same bits), with one addition: a face whose bit is set for
+ * a query vertex is skipped by that vertex's distance MINIMUM.  That decides dist, face (the lowest index among the faces that count
+ * and attain the minimum), and whether the vertex is within max_dist; a vertex with every valid face excluded gives +inf, -1, 0.
+ *   wind is NOT masked: it is the sum over ALL valid faces of the target, computed only where the masked dist is within max_dist.  For
+ *     a vertex ON the surface of its own closed mesh that sum is the vertex's exterior-angle share (the faces that meet at it add
+ *     exactly 0, the rest of the surface is seen under less than a half space from a convex place, more from a concave one): 0.14 .. 0.82
+ *     on the hand template at rest, no vertex above 0.95, and it rises by about 1 when the vertex is inside ANOTHER part of the mesh
+ *     (two overlapping 320-face icospheres as one mesh: 0.415 .. 0.421 outside, 1.415 .. 1.421 inside) — so "inside" is wind > 1.0 here,
+ *     the Python layer's convention.  A MASKED winding sum has no such reading: from a convex patch its own neighbourhood is seen
+ *     edge-on, so what removing it takes from the sum depends on the radius of the exclusion.
+ * HARP_ERR_ARG before any launch: harp_mesh_contact's, and a NULL excl or one that is not 16-byte aligned. */
+int harp_mesh_contact_excl(const harp_contact_mesh* query, const harp_contact_mesh* target, const uint32_t* excl, int B, float max_dist,
+                           float* ws, float* dist, int32_t* face, float* wind, hipStream_t stream);
+
 /* ---- batched MANO inverse kinematics: 3-D keypoints -> pose rows (csrc/ik.hip; playback.py Motion.from_keypoints) ----
  * Nothing in the reference does this: its change_pose takes another sequence's parameters.  The model inverted is harp_lbs_mano_fwd's.
  * T independent Levenberg-Marquardt solves in one launch, forward only, no workspace, no allocation, no synchronisation, no atomics
